@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X PHY DSP engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts N ranks ITSELF (one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their
 environment) from a parent that never touches the GPU, waits for them and relays rank 0's JSON line; a failing rank fails
@@ -17,15 +17,24 @@ A step is one pass of that hot path over the batch.  `value` = decoded bits of a
 srslte_amd.sharding.shard_range(total, r, world) of a global unit list that grows with the world size (weak scaling);
 the only collective of the job is one broadcast of the cell / decoder configuration at start-up (RCCL on GPUs).
 
-The other single-GPU configurations of BASELINE.json ride in the same JSON line under `extra` (tools/bench_legs.py), each
-with its own `roofline` and `cpu_baseline`: `ldpc` (configs[2]: NR 100 MHz, LDPC BG1 Z=384 at 20 iterations + OFDM N=4096),
-`cellsearch` (configs[4]: PSS/SSS over 10 ms captures, 504 PCI hypotheses), `uplink` (configs[3]: the per-GPU shard of the
-multi-UE PUSCH receive chain).  `--no-extras` runs the headline alone.
+A plain run sets up, warms up, times the steps and prints the JSON line of the headline, nothing else.  `--full` adds the
+other measurements and checks to the same line:
+  * the other single-GPU configurations of BASELINE.json, under `extra` (tools/bench_legs.py), each with its own `roofline`
+    and `cpu_baseline`: `ldpc` (configs[2]: NR 100 MHz, LDPC BG1 Z=384 at 20 iterations + OFDM N=4096), `cellsearch`
+    (configs[4]: PSS/SSS over 10 ms captures, 504 PCI hypotheses), `uplink` (configs[3]: the per-GPU shard of the multi-UE
+    PUSCH receive chain), ...; `--only` picks some of them, `--no-extras` none;
+  * `pcie_inclusive` / `pcie_inclusive_8bit`: the turbo decoder fed from pinned host memory (N = 1 only, not with `--no-extras`);
+  * `cpu_baseline` (not with `--no-cpu`): the reference's own turbo decoder (oracle/_ref, AVX2 host) or our scalar port
+    (oracle/) on ONE host core over a bounded sample of the same code blocks, which doubles as the in-bench parity check,
+    with `bler` and the OFDM CPU port (rank 0, N = 1 only).
 
 `roofline` describes the dominant kernel of the step (the turbo decoder), `roofline_ofdm` the OFDM demodulator (the HBM-bound
-kernel of the path).  Kernel durations are measured live with HIP events on the launch stream.  `cpu_baseline` times the
-reference's own turbo decoder (oracle/_ref, AVX2 host) or our scalar port (oracle/) on ONE host core over a bounded sample
-of the same code blocks, and doubles as the in-bench parity check (rank 0, N = 1 only).
+kernel of the path).  Kernel durations are measured live with HIP events on the launch stream of the timed steps.
+
+`--dump-outputs DIR` writes, after the timed steps, what rank 0's last step computed as float32 .npy files: `turbo_bits.npy`
+(the hard decisions of a fixed, seeded sample of the code blocks, one 0 / 1 value per bit, [blocks, K]) and `ofdm_re.npy` (the
+resource grids of a fixed, seeded sample of the subframes, [subframes, REs, re / im]).  The inputs depend on the arguments
+only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -59,15 +68,21 @@ def parse(argv=None):
     # The CUs do not finish their rounds together, so the end of a launch runs on a part of the chip: 4096 subframes (3.25 rounds) 30.2 Gbit/s,
     # 5040 (4 rounds) 33.5, 10,080 (8 rounds) 34.5, 20,160 (16 rounds) 35.2 on one box (DESIGN.md par. 3.2)
     ap.add_argument("--sf", type=int, default=10080, help="subframes per rank per step")
-    ap.add_argument("--cpu-sample", type=int, default=48, help="code blocks decoded on the CPU for baseline + parity")
-    ap.add_argument("--no-cpu", action="store_true", help="skip every cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (no extra.ldpc / cellsearch / uplink)")
-    ap.add_argument("--only", default="", help="comma list of extras to run (default: all of %s)" % ",".join(EXTRAS))
-    ap.add_argument("--extra-steps", type=int, default=8, help="timed steps of each extra leg (a cell-search step is 1.4 ms: three of them are mostly launch latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baselines, host-fed rates and extra legs (default: headline only)")
+    ap.add_argument("--cpu-sample", type=int, default=48, help="code blocks decoded on the CPU for baseline + parity (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip every cpu_baseline leg (--full)")
+    ap.add_argument("--no-extras", action="store_true", help="no extra.ldpc / cellsearch / uplink ... and no pcie_inclusive (--full)")
+    ap.add_argument("--only", default="", help="comma list of extras to run (--full; default: all of %s)" % ",".join(EXTRAS))
+    ap.add_argument("--extra-steps", type=int, default=8, help="timed steps of each extra leg (--full; a cell-search step is 1.4 ms: three of them are mostly launch latency)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="CPU rehearsal of the N-rank launch path (gloo): launcher, rendezvous, config broadcast, sharding, "
                          "barrier + max-over-ranks timing; no kernels run and `value` is null")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.only and not a.full:
+        ap.error("--only picks legs of a --full run")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ launcher (GPU free)
@@ -226,6 +241,23 @@ def make_turbo_pool(S, capi, torch, dev, stream, k_cb, pool_n, seed):
     return torch.clamp(torch.round(100.0 * y), -32768, 32767).to(torch.int16), msgs
 
 
+DUMP_SEED = 20240  # the sample of rows dump_outputs writes depends on this and the shapes only
+DUMP_CODE_BLOCKS = 512  # 512 x 6144 bits as float32: 12.6 MB
+DUMP_SUBFRAMES = 128  # 128 x 16800 REs x (re, im) as float32: 17.2 MB
+
+
+def dump_outputs(out_dir, torch, np, d_bits, d_re):
+    """what the last timed step left in the output buffers, for a seeded sample of rows (the full outputs are > 1 GB):
+    turbo_bits.npy [blocks, K] hard decisions unpacked MSB first (the order of the transmitted message bits), ofdm_re.npy [subframes, REs, 2]"""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, d, n_keep in (("turbo_bits", d_bits, DUMP_CODE_BLOCKS), ("ofdm_re", d_re, DUMP_SUBFRAMES)):
+        rows = np.sort(rng.choice(d.shape[0], size=min(n_keep, d.shape[0]), replace=False))
+        x = d[torch.as_tensor(rows, device=d.device)].cpu()
+        x = np.unpackbits(x.numpy(), axis=1) if name == "turbo_bits" else torch.view_as_real(x).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
 def plumbing_only(a, rank, world):
     """the N-rank path without a GPU: same launcher, rendezvous, broadcast, sharding and timing protocol, gloo backend"""
     import torch
@@ -365,6 +397,8 @@ def worker(a):
     t_ofdm = sum(e[0].elapsed_time(e[1]) for e in evs) / a.steps * 1e-3
     t_tdec = sum(e[1].elapsed_time(e[2]) for e in evs) / a.steps * 1e-3
     dt, t_ofdm, t_tdec = ctx.max_over_ranks([dt, t_ofdm, t_tdec])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, torch, np, d_bits, d_re)
 
     res = None
     if rank == 0:
@@ -405,7 +439,7 @@ def worker(a):
                               "avg_launch_ms": t_ofdm * 1e3, "algorithmic_bytes_per_launch": n_sf * sf_bytes,
                               "traffic_rate_gbs": (traffic_o / t_ofdm / 1e9) if traffic_o else None},
         }
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             pool = d_pool.cpu().numpy()
             cpu_bits, info = cpu_baseline(pool, a.cpu_sample)
             gpu_bits = d_bits[:pool_n].cpu().numpy()[:cpu_bits.shape[0]]
@@ -428,7 +462,7 @@ def worker(a):
     # ---- PCIe-inclusive rates (never `value`): inputs start in pinned HOST memory, results end there.  Chunks alternate between two streams
     # (each: H2D -> decode -> D2H), so the upload of one chunk runs under the decode of the other; the H2D rate of the same bytes alone and
     # the device-resident kernel rate bound it from above.
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         import bench_legs as L
 
         res["pcie_inclusive"] = L.host_fed_turbo(S, capi, torch, dev, d_llr, in_stride, k_cb, nit, llr8=False, chunk=16380)
@@ -437,7 +471,7 @@ def worker(a):
     # ---- the other single-GPU configurations of BASELINE.json
     del tdec, d_llr, d_bits, d_time, d_re
     torch.cuda.empty_cache()
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         import bench_legs as L
 
         which = [w for w in (a.only.split(",") if a.only else EXTRAS) if w]

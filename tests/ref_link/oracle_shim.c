@@ -9,7 +9,7 @@
  * and PDSCH CRC of signal.1.92M.amar.dat, the PMCH CRC of the 100-PRB MBSFN subframe): the reference's channel
  * estimator, PBCH / PCFICH / PDCCH / PDSCH decoders consume what the oracle's OFDM demodulator produces.
  *
- * The product never sees this file: it is linked only into tests/ref_link/_build/bin_oracle/.
+ * The product never sees this file: it is linked only into oracle/_ref/ref_link/bin_oracle/.
  * Struct layouts come from include/srsran_amd/phy_abi.h (checked against the reference headers by
  * tests/test_host_cpu.py); handle state that the oracle does not need is left zero.
  */

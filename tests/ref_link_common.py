@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "ref_link", "_build")
+# built by tests/ref_link/Makefile next to the reference's compiled library (oracle/_ref): built products travel with that directory
+BUILD = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "ref_link")
 GOLD = os.path.join(HERE, "golden")
 
 
@@ -15,7 +16,7 @@ def program(kind, name):
     """kind: "bin" (linked against libsrsran_phy_hip.so) or "bin_oracle" (linked against the oracle shim)"""
     p = os.path.join(BUILD, kind, name)
     if not os.path.exists(p):
-        pytest.skip("tests/ref_link/_build/%s/%s not built (make -C tests/ref_link needs the reference tree: dev container)" % (kind, name))
+        pytest.skip("oracle/_ref/ref_link/%s/%s not built (make -C tests/ref_link needs the reference tree)" % (kind, name))
     return p
 
 

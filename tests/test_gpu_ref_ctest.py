@@ -15,7 +15,7 @@ import json
 import os
 
 import pytest
-from ref_link_common import HERE, add_ctest_data, make_data_dir, run_program
+from ref_link_common import HERE, add_ctest_data, make_data_dir, program, run_program
 
 pytestmark = pytest.mark.gpu
 
@@ -166,7 +166,7 @@ def _selected_rmlut():
 def test_ctest_line_on_the_librarys_lut_rate_matchers(entry, data_dir):
     import subprocess
 
-    exe = os.path.join(HERE, "ref_link", "_build", "bin_rmlut", entry["program"])
+    exe = program("bin_rmlut", entry["program"])
     syms = subprocess.run(["nm", "-D", "--undefined-only", exe], stdout=subprocess.PIPE, text=True).stdout
     assert "srsran_rm_turbo_gentables" in syms, "bin_rmlut/%s does not take its LUT rate matchers from the library" % entry["program"]
     args = [str(data_dir / a[1:]) if a.startswith("@") else a for a in entry["args"]]

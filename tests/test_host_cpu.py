@@ -271,11 +271,11 @@ def test_product_never_touches_the_oracle():
 def test_transport_block_seams_are_bound_in_the_reference_programs():
     """tests/ref_link `make tb`: in the reference's unmodified sch.o / sch_nr.o the seam symbols are WEAK definitions, and the linked programs call the
     library's entry points through the bindings (static facts of the build, no GPU needed; the programs themselves run in tests/test_gpu_ref_ctest.py)"""
-    build = os.path.join(ROOT, "tests", "ref_link", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "ref_link")
     weak = {"sch_weak.o": {"decode_tb_cb", "srsran_dlsch_encode2"},
             "sch_nr_weak.o": {"srsran_dlsch_nr_decode", "srsran_ulsch_nr_decode", "srsran_dlsch_nr_encode", "srsran_ulsch_nr_encode"}}
     if not os.path.exists(os.path.join(build, "bin_tb", "pusch_test")):
-        pytest.skip("tests/ref_link/_build/bin_tb not built (needs the reference tree: dev container)")
+        pytest.skip("oracle/_ref/ref_link/bin_tb not built (needs the reference tree)")
     for obj, names in weak.items():
         p = os.path.join(build, "obj", "tb", obj)
         if os.path.exists(p):  # (objects stay in the dev container's tree; the programs travel)

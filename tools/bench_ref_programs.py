@@ -19,7 +19,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "ref_link", "_build")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "ref_link")
 
 CASES = [
     # (program, args, label).  pusch_test decodes a fresh subframe per iteration; pdsch_test -X n decodes ONCE and skips the n - 1 repetitions

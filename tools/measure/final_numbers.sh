@@ -3,7 +3,7 @@
 # programs as stopwatch, the TTI probe, the latency kernels' tables, the seam and handle benches.  usage: bash tools/measure/final_numbers.sh [out dir]
 O=${1:-gpurun_out/final}
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err && tail -c 400 $O/bench.json &&
+python bench.py --full > $O/bench.json 2> $O/bench.err && tail -c 400 $O/bench.json &&
 python tools/bench_ref_programs.py > $O/ref_programs.json 2> $O/ref_programs.err &&
 ./tools/probe/tti_probe > $O/tti_probe.txt 2>&1 &&
 ( python tools/measure/es_time.py 1; python tools/measure/es_time.py 64 ) 2> /dev/null | grep "n_tb" > $O/es_time.txt &&

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/round4
 mkdir -p $OUT
-C="python bench.py --steps 3 --warmup 1 --only cellsearch --no-cpu"
+C="python bench.py --full --steps 3 --warmup 1 --only cellsearch --no-cpu"
 : > $OUT/pss_wall.txt
 for V in wave recompute; do
   export SRSRAN_HIP_PSS_VARIANT=$V

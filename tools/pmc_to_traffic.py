@@ -30,7 +30,7 @@ def mean_counter(d, counter):
 
 def main():
     fetch, write = mean_counter(sys.argv[1], "FETCH_SIZE"), mean_counter(sys.argv[2], "WRITE_SIZE")
-    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/profile_round.sh) on `python bench.py --steps 2 --warmup 1 "
+    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/profile_round.sh) on `python bench.py --full --steps 2 --warmup 1 "
                      "--extra-steps 2 --no-cpu`; FETCH_SIZE (KB) doubled for 16-byte-per-lane reads on gfx950 as MI355X_MICROARCH.md prescribes, "
                      "WRITE_SIZE (KB) taken as is; largest dispatch of each kernel (= the bench-sized launch)"}
     for frag, (key, ukey, units) in UNITS.items():

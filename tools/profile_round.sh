@@ -7,12 +7,12 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/round4}
 mkdir -p $OUT
-B="python bench.py --steps 2 --warmup 1 --extra-steps 2 --no-cpu"
+B="python bench.py --full --steps 2 --warmup 1 --extra-steps 2 --no-cpu"
 if [ "$SKIP_PYTEST" != "1" ]; then
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
 tail -3 $OUT/pytest_gpu.log
 fi
-python bench.py > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json | cut -c1-300 &&
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json | cut -c1-300 &&
 python tools/bench_handle.py > $OUT/bench_handle.json 2> $OUT/bench_handle.err &&
 python tools/bench_tti.py --out $OUT/tti.json > /dev/null 2> $OUT/tti.err &&
 ( rocprofv3 --kernel-trace --stats -d $OUT/trace_tti -o t -- python tools/bench_tti.py --calls 100 --snrs 6.0 --ntb 1,64 > /dev/null 2> $OUT/trace_tti.err; python tools/rocpd_summary.py $OUT/trace_tti > $OUT/tti_kernel_stats.txt; rm -rf $OUT/trace_tti ) &&
@@ -30,7 +30,7 @@ python tools/bench_sch.py > $OUT/bench_sch.json 2> $OUT/bench_sch.err &&
 python tools/bench_pusch_rx.py > $OUT/bench_pusch_rx.json 2> $OUT/bench_pusch_rx.err &&
 python tools/bench_nr_rx.py > $OUT/bench_nr_rx.json 2> $OUT/bench_nr_rx.err &&
 python tools/bench_sch_nr.py > $OUT/bench_sch_nr.json 2> $OUT/bench_sch_nr.err &&
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python bench.py --steps 5 --warmup 1 --no-cpu > $OUT/bench_under_rocprof.json 2> $OUT/trace.err &&
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python bench.py --full --steps 5 --warmup 1 --no-cpu > $OUT/bench_under_rocprof.json 2> $OUT/trace.err &&
 python tools/rocpd_summary.py $OUT/trace > $OUT/kernel_stats.txt &&
 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o p -- $B > /dev/null 2> $OUT/pmc_fetch.err &&
 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o p -- $B > /dev/null 2> $OUT/pmc_write.err &&
@@ -65,7 +65,7 @@ for C in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ
   rm -rf $OUT/t8
 done
 # ---- PSS correlation kernels (DESIGN.md par. 3.4): the product (one wave per block), two waves per block, round 1's workgroup per block
-C="python bench.py --steps 3 --warmup 1 --only cellsearch --no-cpu"
+C="python bench.py --full --steps 3 --warmup 1 --only cellsearch --no-cpu"
 : > $OUT/pss_variants.txt
 export SRSRAN_HIP_LIB=$PWD/tools/probe/lib/libsrsran_phy_hip_variants.so
 for V in wave recompute pair block; do

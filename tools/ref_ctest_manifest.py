@@ -5,7 +5,7 @@
 
 For every add_test / add_lte_test / add_nr_test / add_nbiot_test line with literal arguments in lib/src/phy/**/test/CMakeLists.txt the
 manifest keeps: ctest name, program, argument list, the data files it names (by base name) and -- read from the linked program in
-tests/ref_link/_build/bin_full with nm -- which product symbols it binds.  Lines whose program binds none are dropped (they would not
+oracle/_ref/ref_link/bin_full with nm -- which product symbols it binds.  Lines whose program binds none are dropped (they would not
 exercise the product), so are programs that need a radio.  The looped LDPC / PUSCH lines of the CMake files are represented by a
 hand-picked literal subset at the end.  tests/test_gpu_ref_ctest.py runs every entry on the GPU box and expects exit code 0, which is
 what ctest itself checks.
@@ -18,7 +18,7 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PHY = "/root/reference/lib/src/phy"
-BIN = os.path.join(ROOT, "tests", "ref_link", "_build", "bin_full")
+BIN = os.path.join(ROOT, "oracle", "_ref", "ref_link", "bin_full")
 LIB = os.path.join(ROOT, "srslte_amd", "lib", "libsrsran_phy_hip.so")
 MAX_DATA = 320 * 1024  # bytes per data file kept as a fixture
 

@@ -15,8 +15,13 @@
  * (the kernels read them from the pinned staging image), the payload and the verdict come down.  Soft-buffer handling (HARQ combining
  * across calls, stored code blocks) is srsran_hip_decode_tb_cb's (phy_sch_abi.h).
  *
+ * A PUSCH grant that carries control information (HARQ-ACK, RI, CQI multiplexed into it by TS 36.212 5.2.2.8) is taken by srsran_hip_pusch_decode_uci:
+ * the de-multiplexer is part of the demodulator's store, the few soft bits of the control fields come down with the payload, and the caller runs the
+ * reference's own small decoders (uci.c) on them.
+ *
  * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, MIMO layer mapping /
- * precoding (more than one port), UCI multiplexing (a grant with ACK / RI / CQI bits goes down the reference's own path), EVM measurement.
+ * precoding (more than one port), a PUSCH without a transport block (tbs == 0: CQI only), 8-bit soft bits on a grant with control information,
+ * the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the control bits themselves, EVM measurement.
  */
 #ifndef SRSRAN_AMD_PHY_CHAN_ABI_H
 #define SRSRAN_AMD_PHY_CHAN_ABI_H
@@ -65,6 +70,40 @@ SRSRAN_API int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_
  * decoded in separate passes.  Returns SRSRAN_SUCCESS when every grant was processed (res[i].crc_ok tells its outcome). */
 SRSRAN_API int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const cf_t* const* sf_symbols, const cf_t* const* ce,
                                              srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res);
+
+/* ---- PUSCH receive with control information (srsran_pusch_decode -> srsran_ulsch_decode, sch.c:1121-1192, with HARQ-ACK / RI / CQI configured).
+ * With H' = tb.nof_re, cols = SC-FDMA symbols of the grant, rows = H' / cols: ACK symbol n sits in row rows - 1 - n / 4, column {2,3,8,9}[(3 n) % 4]
+ * (cols > 10) or {1,2,6,7}; RI symbol n in the same row, column {1,4,7,10} or {0,3,5,8} (uci.c:364-416); soft bit k of the symbol at (row, col) has
+ * position row Qm + rows col Qm + k in the reference's q_bits.  The data stream g is every symbol that is not an RI symbol, row by row, with zeros at
+ * ACK symbols; its first Q_prime_cqi Qm soft bits are the CQI code word, the transport block is decoded from the G Qm behind it, G = H' - Q_prime_ri -
+ * Q_prime_cqi.  (As in the reference, with Q_prime_ri > 0 g[0] holds the soft bit of the highest RI position: vector.c:141-146 on the table of
+ * sch.c:660-681.)  Taken: 16-bit soft bits, Q_prime_ack and Q_prime_ri <= 4 * 12 * L_prb, Q_prime_ri + Q_prime_cqi < H'. */
+typedef struct SRSRAN_API {
+  uint32_t Q_prime_ack; /* modulation symbols punctured by HARQ-ACK (uci.c:418 Q_prime_ri_ack), 0 = none */
+  uint32_t Q_prime_ri;  /* modulation symbols taken by RI, 0 = none */
+  uint32_t Q_prime_cqi; /* modulation symbols of the CQI code word in front of the data (uci.c:173), 0 = none */
+} srsran_hip_pusch_uci_t;
+/* caller's memory; a pointer may be NULL when its count is 0.  *_llr: the demodulated and descrambled soft bit of bit k of symbol n at [n Qm + k]
+ * (q_bits[position]); *_c: the scrambling chip c_seq[position] (the 1-bit decoder undoes the scrambling of the repeated bit with it, uci.c:678-682);
+ * *_pos: the position; cqi_llr: g[0 .. Q_prime_cqi Qm) */
+typedef struct SRSRAN_API {
+  int16_t*  ack_llr;
+  uint8_t*  ack_c;
+  uint32_t* ack_pos; /* Q_prime_ack * Qm entries each */
+  int16_t*  ri_llr;
+  uint8_t*  ri_c;
+  uint32_t* ri_pos;  /* Q_prime_ri * Qm entries each */
+  int16_t*  cqi_llr; /* Q_prime_cqi * Qm entries */
+} srsran_hip_pusch_uci_out_t;
+/* uci: the three counts; out: where the control soft bits go.  All three counts 0: exactly srsran_hip_pusch_decode.  Still ONE host wait. */
+SRSRAN_API int srsran_hip_pusch_decode_uci(const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* sf_symbols, const cf_t* ce,
+                                           srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_pusch_uci_out_t* out);
+/* the grants of one TTI, with and without control information, in ONE call: arrays of n entries (uci[i] all zero: a grant without; out[i] is then not
+ * looked at).  One equaliser launch, one transform launch per allocation size, one demodulator launch per soft-bit width.  Every res[i] is initialised
+ * before anything is checked; an invalid grant refuses the whole call (SRSRAN_ERROR_INVALID_INPUTS) before anything is enqueued. */
+SRSRAN_API int srsran_hip_pusch_decode_uci_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* const* sf_symbols,
+                                                 const cf_t* const* ce, srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data,
+                                                 srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out);
 
 /* ---- PDSCH receive, one codeword: `symbols` are the grant's nof_re extracted REs (srsran_pdsch_get) of HOST memory.  ce != NULL: single
  * port, single receive antenna -- the zero-forcing / MMSE equaliser srsran_predecoding_single(symbols, ce, ., NULL, nof_re, scaling,

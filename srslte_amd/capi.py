@@ -145,6 +145,15 @@ class HipPuschRx(C.Structure):
                 ("shortened", C.c_uint32), ("noise_estimate", C.c_float), ("meas_epre", C.c_uint32)]
 
 
+class HipPuschUci(C.Structure):  # srsran_hip_pusch_uci_t
+    _fields_ = [("Q_prime_ack", C.c_uint32), ("Q_prime_ri", C.c_uint32), ("Q_prime_cqi", C.c_uint32)]
+
+
+class HipPuschUciOut(C.Structure):  # srsran_hip_pusch_uci_out_t
+    _fields_ = [("ack_llr", C.c_void_p), ("ack_c", C.c_void_p), ("ack_pos", C.c_void_p), ("ri_llr", C.c_void_p), ("ri_c", C.c_void_p), ("ri_pos", C.c_void_p),
+                ("cqi_llr", C.c_void_p)]
+
+
 class HipPdschRx(C.Structure):
     _fields_ = [("tb", HipGrantTb), ("scaling", C.c_float), ("noise_estimate", C.c_float)]
 
@@ -498,6 +507,10 @@ def lib():
             "srsran_hip_pusch_decode": (i32, [C.POINTER(HipPuschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
             "srsran_hip_pusch_decode_multi": (i32, [u32, C.POINTER(HipPuschRx), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.POINTER(SoftbufferRx)),
                                                     C.POINTER(vp), C.POINTER(HipGrantRes)]),
+            "srsran_hip_pusch_decode_uci": (i32, [C.POINTER(HipPuschRx), C.POINTER(HipPuschUci), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes),
+                                                  C.POINTER(HipPuschUciOut)]),
+            "srsran_hip_pusch_decode_uci_multi": (i32, [u32, C.POINTER(HipPuschRx), C.POINTER(HipPuschUci), C.POINTER(vp), C.POINTER(vp),
+                                                        C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(HipPuschUciOut)]),
             "srsran_hip_pdsch_decode": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
             "srsran_hip_pdsch_encode": (i32, [C.POINTER(HipPdschTx), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pdsch_decode_dbg": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp]),

@@ -152,14 +152,22 @@ struct PuschPlan { // one grant of a (multi-)call
   srsran_hip_sch_head_t   head;
   srsran_hip_dft_batch_t* plan = nullptr;
   sch::FrontEnd           front;
+  size_t                  o_uci = 0; // the grant's control image in the pinned image (modem_device.h: uci_image_*)
 };
+
+inline bool has_uci(const srsran_hip_pusch_uci_t& u)
+{
+  return (u.Q_prime_ack | u.Q_prime_ri | u.Q_prime_cqi) != 0;
+}
 
 } // namespace
 
 // ------------------------------------------------------------------------------------------------ PUSCH receive
 
-extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const cf_t* const* sf_symbols, const cf_t* const* ce,
-                                             srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res)
+// the grants of a call.  uci == nullptr: srsran_hip_pusch_decode{,_multi}; else uci[i] / out[i] are grant i's control-information counts and outputs
+// (srsran_hip_pusch_decode_uci{,_multi}) and the 16-bit grants' demodulator launch is the de-multiplexing one (modem::launch_uci).
+static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* const* sf_symbols, const cf_t* const* ce,
+                               srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out)
 {
   TraceRange trace_("srsran_hip_pusch_decode");
   if (n == 0) {
@@ -189,6 +197,26 @@ extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_
                 x.n_prb_tilde[1], x.cell_nof_prb, x.tb.nof_re, x.tb.mod);
       fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
       return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (uci && has_uci(uci[i])) {
+      const srsran_hip_pusch_uci_t& u = uci[i];
+      const srsran_hip_pusch_uci_out_t* o = out ? &out[i] : nullptr;
+      const char* why = nullptr;
+      if (x.tb.llr_is_8bit) {
+        why = "control information is taken with 16-bit soft bits only";
+      } else if (u.Q_prime_ack > 4 * 12 * x.L_prb || u.Q_prime_ri > 4 * 12 * x.L_prb) {
+        why = "more ACK / RI symbols than four columns hold";
+      } else if ((uint64_t)u.Q_prime_ri + u.Q_prime_cqi >= x.tb.nof_re) {
+        why = "RI and CQI leave no symbol for the transport block";
+      } else if (!o || (u.Q_prime_ack && (!o->ack_llr || !o->ack_c || !o->ack_pos)) || (u.Q_prime_ri && (!o->ri_llr || !o->ri_c || !o->ri_pos)) ||
+                 (u.Q_prime_cqi && !o->cqi_llr)) {
+        why = "no output for a non-zero count";
+      }
+      if (why) {
+        set_error("srsran_hip_pusch_decode_uci: grant %u (Q'ack %u, Q'ri %u, Q'cqi %u, %u PRB): %s", i, u.Q_prime_ack, u.Q_prime_ri, u.Q_prime_cqi, x.L_prb, why);
+        fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
     }
     PuschPlan& p = pl[i];
     p.nof_symb   = nsymb;
@@ -224,6 +252,16 @@ extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_
   const size_t o_eqj = 2 * region, o_mj = al256(o_eqj + n * sizeof(modem::EqJob)), o_tj = al256(o_mj + n * sizeof(modem::Job));
   pin_need = al256(o_tj + tiles * sizeof(uint32_t));
   dev_need = 2 * region;
+  // with control information: the de-multiplexing demodulator's job list behind the others, then every grant's control image (the kernel stores the
+  // control soft bits and chips straight into the pinned image: they are there after the call's one host wait)
+  const size_t o_uj = pin_need;
+  if (uci) {
+    pin_need = al256(o_uj + n * sizeof(modem::UciJob));
+    for (uint32_t i = 0; i < n; i++) {
+      pl[i].o_uci = pin_need;
+      pin_need    = al256(pin_need + modem::uci_image_bytes(uci[i].Q_prime_ack, uci[i].Q_prime_ri, uci[i].Q_prime_cqi, qm_of(g[i].tb.mod)));
+    }
+  }
   if (!s.grow(pin_need, dev_need)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_hip_pusch_decode: staging allocation failed\n");
     return SRSRAN_ERROR;
@@ -259,7 +297,12 @@ extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_
     const uint32_t L_prb = x.L_prb, nsymb = p.nof_symb;
     auto*          plan  = p.plan;
     p.front = [=](hipStream_t st, void* d_e) { return enqueue_rx_front(st, tb, psym, pce, 1.0f, noise, L_prb, nsymb, dx, dz, plan, d_e); };
-    items[i] = {&p.head, softbuffers[i], &p.seg, qm_rm(x.tb), x.tb.rv, x.tb.nof_re * qm_of(x.tb.mod), nullptr, &p.front, data[i], false};
+    // (with control information the transport block's e bits are what RI and CQI leave: G = H' - Q'ri - Q'cqi symbols, sch.c:1184-1190)
+    const uint32_t G = uci ? x.tb.nof_re - uci[i].Q_prime_ri - uci[i].Q_prime_cqi : x.tb.nof_re;
+    items[i] = {&p.head, softbuffers[i], &p.seg, qm_rm(x.tb), x.tb.rv, G * qm_of(x.tb.mod), nullptr, &p.front, data[i], false};
+  }
+  if (uci) { // a grant that does not reach the launch (sch_host.cpp refuses its soft buffer) leaves zeros
+    memset(s.pin + pl[0].o_uci, 0, pin_need - pl[0].o_uci);
   }
   // the front end of all grants at once (n > 1)
   bool                     front_done = false;
@@ -299,6 +342,29 @@ extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_
     for (uint32_t k = 1; k < m; k++) {
       base = static_cast<uint8_t*>(d_e[k]) < base ? static_cast<uint8_t*>(d_e[k]) : base;
     }
+    if (uci && !llr8) { // the 16-bit grants of the call, with and without control information, in one de-multiplexing demodulator launch
+      auto*    uj = reinterpret_cast<modem::UciJob*>(s.pin + o_uj) + job_cur;
+      auto*    tj = reinterpret_cast<uint32_t*>(s.pin + o_tj) + tile_cur;
+      uint32_t nt = 0;
+      for (uint32_t k = 0; k < m; k++) {
+        const uint32_t               i   = which[k];
+        const srsran_hip_pusch_rx_t& x   = g[i];
+        const uint32_t               cnt = modem::tiles_of(x.tb.mod, x.tb.nof_re);
+        uj[k] = modem::UciJob{x.tb.mod, x.tb.nof_re, (uint32_t)(pl[i].o_x / sizeof(cf_t)), (uint32_t)((size_t)(static_cast<uint8_t*>(d_e[k]) - base) / es), x.tb.seed, nt, cnt,
+                              12 * x.L_prb, pl[i].nof_symb, uci[i].Q_prime_ack, uci[i].Q_prime_ri, uci[i].Q_prime_cqi, (uint32_t)pl[i].o_uci};
+        for (uint32_t t = 0; t < cnt; t++) {
+          tj[nt++] = k;
+        }
+      }
+      job_cur += m;
+      tile_cur += nt;
+      modem::UciParams up = {s.dev + region, base, s.pin, uj, tj, nt, p.x1_bits, p.x2_cols, p.k};
+      if (modem::launch_uci(up, st) != hipSuccess) {
+        set_error("grant front end: demodulator launch failed");
+        return false;
+      }
+      return true;
+    }
     auto*    mj  = reinterpret_cast<modem::Job*>(s.pin + o_mj) + job_cur;
     auto*    tj  = reinterpret_cast<uint32_t*>(s.pin + o_tj) + tile_cur;
     uint32_t nt  = 0;
@@ -325,12 +391,77 @@ extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_
     }
     return true;
   };
-  sch::decode_tbs_staged(items.data(), n, n > 1 ? &group : nullptr);
+  sch::decode_tbs_staged(items.data(), n, (n > 1 || uci) ? &group : nullptr);
   for (uint32_t i = 0; i < n; i++) {
     res[i].crc_ok               = items[i].ok ? 1 : 0;
     res[i].avg_iterations_block = pl[i].head.avg_iterations;
   }
+  for (uint32_t i = 0; uci && i < n; i++) {
+    const srsran_hip_pusch_uci_t& u = uci[i];
+    if (!has_uci(u)) {
+      continue;
+    }
+    // the control image -> the caller's arrays; the positions are the closed form of uci.c:364-416
+    const uint32_t Qm = qm_of(g[i].tb.mod), rows = 12 * g[i].L_prb;
+    const bool     normal = pl[i].nof_symb > 10;
+    const int16_t* llr = reinterpret_cast<const int16_t*>(s.pin + pl[i].o_uci);
+    const uint8_t* chips = s.pin + pl[i].o_uci + modem::uci_image_chips(u.Q_prime_ack, u.Q_prime_ri, u.Q_prime_cqi, Qm);
+    static const uint32_t ack_cols[2][4] = {{1, 2, 6, 7}, {2, 3, 8, 9}}, ri_cols[2][4] = {{0, 3, 5, 8}, {1, 4, 7, 10}};
+    const size_t na = (size_t)u.Q_prime_ack * Qm, nr = (size_t)u.Q_prime_ri * Qm, nc = (size_t)u.Q_prime_cqi * Qm;
+    if (na) {
+      memcpy(out[i].ack_llr, llr, na * sizeof(int16_t));
+      memcpy(out[i].ack_c, chips, na);
+    }
+    if (nr) {
+      memcpy(out[i].ri_llr, llr + na, nr * sizeof(int16_t));
+      memcpy(out[i].ri_c, chips + na, nr);
+    }
+    if (nc) {
+      memcpy(out[i].cqi_llr, llr + na + nr, nc * sizeof(int16_t));
+    }
+    for (uint32_t k = 0; k < u.Q_prime_ack; k++) {
+      for (uint32_t b = 0; b < Qm; b++) {
+        out[i].ack_pos[k * Qm + b] = (rows - 1 - k / 4) * Qm + rows * ack_cols[normal][(3 * k) % 4] * Qm + b;
+      }
+    }
+    for (uint32_t k = 0; k < u.Q_prime_ri; k++) {
+      for (uint32_t b = 0; b < Qm; b++) {
+        out[i].ri_pos[k * Qm + b] = (rows - 1 - k / 4) * Qm + rows * ri_cols[normal][(3 * k) % 4] * Qm + b;
+      }
+    }
+  }
   return SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_pusch_decode_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const cf_t* const* sf_symbols, const cf_t* const* ce,
+                                             srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res)
+{
+  return pusch_decode_grants(n, g, nullptr, sf_symbols, ce, softbuffers, data, res, nullptr);
+}
+
+extern "C" int srsran_hip_pusch_decode_uci_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* const* sf_symbols,
+                                                 const cf_t* const* ce, srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data,
+                                                 srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out)
+{
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!g || !uci || !res) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  bool any = false;
+  for (uint32_t i = 0; i < n; i++) {
+    res[i] = {0, 0.f, NAN}; // every result, before anything is checked
+    any    = any || has_uci(uci[i]);
+  }
+  // no control information anywhere: the call IS srsran_hip_pusch_decode_multi
+  return pusch_decode_grants(n, g, any ? uci : nullptr, sf_symbols, ce, softbuffers, data, res, out);
+}
+
+extern "C" int srsran_hip_pusch_decode_uci(const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* sf_symbols, const cf_t* ce,
+                                           srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_pusch_uci_out_t* out)
+{
+  return srsran_hip_pusch_decode_uci_multi(1, g, uci, &sf_symbols, &ce, &softbuffer, &data, res, out);
 }
 
 extern "C" int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_t* sf_symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,

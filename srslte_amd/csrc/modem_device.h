@@ -95,6 +95,45 @@ void          host_mod_table(uint32_t mod, float2* out);
 
 uint32_t   tiles_of(uint32_t mod, uint32_t n);
 hipError_t launch(const Params& p, hipStream_t stream);
+// ---- PUSCH with control information: demodulator + descrambler + the UL-SCH de-multiplexer of TS 36.212 5.2.2.8 in its store (int16 soft bits).
+// The job's symbols are a matrix of `cols` SC-FDMA symbols x `rows` sub-carriers read column by column, as the transform leaves them.  RI symbol n
+// (0 .. q_ri - 1) sits in row rows - 1 - n / 4, column {1,4,7,10}[(3 n) % 4] (cols > 10) or {0,3,5,8}; ACK symbol n in the same row, column {2,3,8,9} or
+// {1,2,6,7} (uci.c:364-416).  Every symbol that is not an RI symbol has a rank among those, row by row (ulsch_interleave_gen, sch.c:660-681); ACK symbols
+// keep their rank and leave zeros (sch.c:1077-1080).  Rank < q_cqi: the CQI code word, behind it the transport block's e bits.
+struct UciJob {
+  uint32_t mod;     // QPSK, 16-QAM, 64-QAM
+  uint32_t n;       // symbols = rows * cols
+  uint32_t in_off;  // first symbol (cf_t units)
+  uint32_t out_off; // first e bit of the transport block (int16 units): soft bit k of rank r goes to out_off + (r - q_cqi) Qm + k
+  uint32_t seed;    // c_init
+  uint32_t tile0;   // first workgroup of this job
+  uint32_t ntiles;
+  uint32_t rows, cols;
+  uint32_t q_ack, q_ri, q_cqi; // modulation symbols of each kind
+  uint32_t uci_off; // first byte of the job's control image in UciParams::uci (layout: uci_image_*)
+};
+// control image of one job: int16 soft bits [ACK q_ack Qm | RI q_ri Qm | CQI q_cqi Qm], then the scrambling chips as bytes [ACK q_ack Qm | RI q_ri Qm]
+__host__ __device__ inline uint32_t uci_image_chips(uint32_t q_ack, uint32_t q_ri, uint32_t q_cqi, uint32_t Qm) // byte offset of the chips
+{
+  return 2u * (q_ack + q_ri + q_cqi) * Qm;
+}
+__host__ __device__ inline uint32_t uci_image_bytes(uint32_t q_ack, uint32_t q_ri, uint32_t q_cqi, uint32_t Qm)
+{
+  return uci_image_chips(q_ack, q_ri, q_cqi, Qm) + (q_ack + q_ri) * Qm;
+}
+struct UciParams {
+  const void*     in;
+  void*           out;
+  uint8_t*        uci;      // control images of all jobs (the pinned image: they come down with the payload, no copy operation)
+  const UciJob*   jobs;     // device-readable
+  const uint32_t* tile_job; // job index of every workgroup
+  uint32_t        n_tiles;
+  const uint32_t* x1_bits;
+  const uint32_t* x2_cols;
+  Consts          k;
+};
+hipError_t launch_uci(const UciParams& p, hipStream_t stream);
+
 // srsran_predecoding_single on device buffers (y, h, x: cf_t, 16-byte aligned; csi optional)
 hipError_t launch_eq(const void* y, const void* h, void* x, float* csi, uint32_t n, float scaling, float noise, hipStream_t stream);
 

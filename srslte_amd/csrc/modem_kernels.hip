@@ -472,6 +472,145 @@ __global__ __launch_bounds__(256) void modem_kernel(const Params p)
   }
 }
 
+// ---- PUSCH with control information (modem_device.h: UciJob): demod_tile's loads, arithmetic and chips; the store decides per symbol from (row, column)
+// and the three counts where its soft bits go.  No table, no atomics: a symbol's rank among the non-RI symbols is a closed form.
+
+// one chip of the sequence at an arbitrary bit (make_chips' jump to the 128-chip boundary, then the shift register up to the bit)
+__device__ __forceinline__ uint32_t chip_single(const uint32_t* x1_bits, const uint32_t* x2_cols, uint32_t seed, uint32_t bit)
+{
+  const uint32_t  j = bit / MODEM_SEQ_CHUNK, o = bit % MODEM_SEQ_CHUNK;
+  const uint32_t* col = x2_cols + (size_t)j * 31;
+  uint32_t        s2  = 0;
+  for (int i = 0; i < 31; i++) {
+    s2 ^= ((seed >> i) & 1u) ? col[i] : 0u;
+  }
+  for (uint32_t k = 0; k < o / 16; k++) {
+    s2 = step16_x2(s2);
+  }
+  const uint32_t c1 = x1_bits[(size_t)j * (MODEM_SEQ_CHUNK / 32) + (o >> 5)] >> (o & 31u);
+  return ((s2 >> (o & 15u)) ^ c1) & 1u;
+}
+
+template <int MOD>
+__device__ __forceinline__ void uci_tile(const UciParams& p, const UciJob& job, uint32_t tile, uint32_t* cbw)
+{
+  using T             = int16_t;
+  constexpr int  QM   = 2 * MOD;
+  const float2*  sym  = (const float2*)p.in + job.in_off;
+  T*             out  = (T*)p.out + job.out_off;
+  T*             u_llr = (T*)(p.uci + job.uci_off);
+  uint8_t*       u_c  = p.uci + job.uci_off + uci_image_chips(job.q_ack, job.q_ri, job.q_cqi, QM);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w0   = tile * MODEM_TILE_SYMS + (threadIdx.x >> 6) * (MODEM_TILE_SYMS / 4); // first symbol of this wave
+  if (w0 >= job.n) {
+    return;
+  }
+  constexpr int R = MODEM_TILE_SYMS / 256;
+  float2        x[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const uint32_t s = w0 + r * 64u + lane;
+    x[r]             = s < job.n ? sym[s] : make_float2(0.f, 0.f);
+  }
+  make_chips(p.x1_bits, p.x2_cols, job.seed, w0 * QM, min((MODEM_TILE_SYMS / 4) * QM, (job.n - w0) * QM), cbw);
+  // the four columns of each kind, one per nibble (index j); the symbol number inside a row of four is {0,3,2,1}[j], the inverse of (3 n) % 4
+  const uint32_t ri_cols = job.cols > 10 ? 0xA741u : 0x8530u, ack_cols = job.cols > 10 ? 0x9832u : 0x7621u, n_of_j = 0x1230u;
+  const uint32_t rows = job.rows, q_ack = job.q_ack, q_ri = job.q_ri, q_cqi = job.q_cqi;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const uint32_t s = w0 + r * 64u + lane;
+    if (s >= job.n) {
+      continue;
+    }
+    T   v[QM];
+    int iv[QM];
+    demod_int<T, MOD>(x[r].x, x[r].y, s, job.n, p.k, iv);
+    const uint32_t c = chips_at(cbw, (r * 64u + lane) * QM);
+#pragma unroll
+    for (int i = 0; i < QM; i++) {
+      v[i] = flip<T>((T)iv[i], (c >> i) & 1u);
+    }
+    const uint32_t col = s / rows, row = s - col * rows, b = rows - 1 - row; // b: rows below this one
+    const int      m   = (int)q_ri - 4 * (int)b;                            // RI symbols of this row: those whose number in the row is < m
+    int            n_ri = -1, n_ack = -1;
+    uint32_t       inrow = 0; // RI symbols of this row left of this column
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t rc = (ri_cols >> (4 * j)) & 15u, ac = (ack_cols >> (4 * j)) & 15u, t = (n_of_j >> (4 * j)) & 15u;
+      n_ri  = rc == col ? (int)(4 * b + t) : n_ri;
+      n_ack = ac == col ? (int)(4 * b + t) : n_ack;
+      inrow += (rc < col && (int)t < m) ? 1u : 0u;
+    }
+    if (n_ri >= 0 && (uint32_t)n_ri < q_ri) { // an RI symbol: soft bits and chips to the control image, nothing to g
+#pragma unroll
+      for (int i = 0; i < QM; i++) {
+        u_llr[(q_ack + (uint32_t)n_ri) * QM + i] = v[i];
+        u_c[(q_ack + (uint32_t)n_ri) * QM + i]   = (uint8_t)((c >> i) & 1u);
+      }
+      continue;
+    }
+    const uint32_t above = q_ri - min(q_ri, 4 * (b + 1)); // RI symbols in the rows above
+    const uint32_t rank  = row * job.cols + col - above - inrow;
+    if (n_ack >= 0 && (uint32_t)n_ack < q_ack) { // an ACK symbol punctures the stream: it keeps its rank and leaves zeros
+#pragma unroll
+      for (int i = 0; i < QM; i++) {
+        u_llr[(uint32_t)n_ack * QM + i] = v[i];
+        u_c[(uint32_t)n_ack * QM + i]   = (uint8_t)((c >> i) & 1u);
+        v[i]                            = 0;
+      }
+    }
+    if (rank == 0 && q_ri > 0) {
+      // The reference's table holds 0 at every RI position and its in-order loop (srsran_vec_lut_sis) writes those soft bits to g[0]: the last one, the
+      // highest RI position, stays -- the last bit of RI symbol 1 (of symbol 0 when there is only one) in the bottom row.  The lane that owns rank 0
+      // fetches that one soft bit itself (its symbol, its chip) in place of its own bit 0: g[0] has one writer.
+      const uint32_t nq = q_ri >= 2 ? 1u : 0u;
+      const uint32_t sq = ((ri_cols >> (4 * ((3 * nq) & 3u))) & 15u) * rows + rows - 1;
+      const float2   xq = sym[sq];
+      int            qv[QM];
+      demod_int<T, MOD>(xq.x, xq.y, sq, job.n, p.k, qv);
+      v[0] = flip<T>((T)qv[QM - 1], chip_single(p.x1_bits, p.x2_cols, job.seed, sq * QM + QM - 1));
+    }
+    if (rank < q_cqi) {
+      store_bits<T, QM>(u_llr + (size_t)(q_ack + q_ri + rank) * QM, v, false);
+    } else {
+      store_bits<T, QM>(out + (size_t)(rank - q_cqi) * QM, v, false);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void uci_demod_kernel(const UciParams p)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t cb[4][MODEM_TILE_BITS / 128 + 4];
+  __shared__ UciJob sjob;
+  const uint32_t    lo = p.tile_job[blockIdx.x];
+  if (threadIdx.x < sizeof(UciJob) / 4) {
+    ((uint32_t*)&sjob)[threadIdx.x] = ((const uint32_t*)(p.jobs + lo))[threadIdx.x];
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    cb[threadIdx.x >> 6][MODEM_TILE_BITS / 128] = 0; // chips_at reads one word past the last one
+  }
+  __syncthreads();
+  const UciJob   job  = sjob;
+  const uint32_t tile = blockIdx.x - job.tile0;
+  if (tile >= job.ntiles) {
+    return;
+  }
+  uint32_t* cbw = cb[threadIdx.x >> 6];
+  switch (job.mod) {
+    case 1:
+      uci_tile<1>(p, job, tile, cbw);
+      break;
+    case 2:
+      uci_tile<2>(p, job, tile, cbw);
+      break;
+    case 3:
+      uci_tile<3>(p, job, tile, cbw);
+      break;
+    default:
+      break;
+  }
+}
+
 // ---- modulator: one workgroup = MODEM_TILE_SYMS symbols, a quarter per wave; the wave's chips as in demod_tile
 template <int MOD>
 __device__ __forceinline__ void mod_tile(const ModParams& p, uint32_t tile, uint32_t* cbw)
@@ -728,6 +867,15 @@ hipError_t launch(const Params& p, hipStream_t stream)
       hipLaunchKernelGGL(modem_kernel<float>, dim3(p.n_tiles), dim3(256), 0, stream, p);
       break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_uci(const UciParams& p, hipStream_t stream)
+{
+  if (p.n_tiles == 0 || !p.jobs || !p.tile_job || !p.uci) {
+    return p.n_tiles ? hipErrorInvalidValue : hipSuccess;
+  }
+  hipLaunchKernelGGL(uci_demod_kernel, dim3(p.n_tiles), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 

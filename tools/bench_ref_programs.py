@@ -8,8 +8,13 @@ srsran_pusch_decode took (pdsch_test.c:480-499, pusch_test.c:326-396).  Three li
   tb      the library bound at the reference's transport-block seam decode_tb_cb (sch.c:370; tests/ref_link/tb_bind.c): one call per block
   chan    the library bound at the grant level (tests/ref_link/chan_bind.c: srsran_pusch_decode / srsran_pdsch_decode / srsran_pdsch_encode /
           srsran_ulsch_encode): ONE device call per grant, everything between the resource grid and the transport block resident
+  uci     chan, and PUSCH grants with HARQ-ACK / RI / CQI multiplexed in taken by the device path too (tests/ref_link/uci_bind.c, pusch_test only);
+          in `chan` such a grant falls through to the reference's own srsran_pusch_decode
 
 Run on the GPU box:  python tools/bench_ref_programs.py > gpurun_out/ref_programs.json
+                     python tools/bench_ref_programs.py --uci --runs 5 > profiles/ref_programs_uci.json
+(--uci: only the PUSCH rows with control information and their twins without, on refcpu / chan / uci; --runs N: every cell N processes, the steady
+figure of each, their median and range)
 """
 import json
 import os
@@ -27,6 +32,9 @@ CASES = [
     ("pusch_test", ["-n", "100", "-L", "100", "-m", "28", "-p", "enable_64qam", "-s", "40"], "PUSCH 100 PRB, MCS 28, 64-QAM (TBS 75376: 13 code blocks), 40 subframes"),
     ("pusch_test", ["-n", "100", "-L", "50", "-m", "21", "-p", "uci_ack", "2", "-p", "cqi", "wideband", "-s", "40"], "PUSCH 50 of 100 PRB, MCS 21, ACK + CQI multiplexed"),
     ("pusch_test", ["-n", "100", "-L", "50", "-m", "21", "-s", "40"], "PUSCH 50 of 100 PRB, MCS 21"),
+    ("pusch_test", ["-n", "25", "-L", "25", "-m", "14", "-p", "uci_ack", "2", "-p", "cqi", "wideband", "-s", "40"], "PUSCH 25 PRB, MCS 14, ACK + CQI multiplexed"),
+    ("pusch_test", ["-n", "6", "-L", "6", "-m", "10", "-p", "uci_ack", "2", "-p", "cqi", "wideband", "-s", "40"], "PUSCH 6 PRB, MCS 10, ACK + CQI multiplexed"),
+    ("pusch_test", ["-n", "6", "-L", "6", "-m", "10", "-s", "40"], "PUSCH 6 PRB, MCS 10"),
     ("pusch_test", ["-n", "25", "-L", "25", "-m", "14", "-s", "40"], "PUSCH 25 PRB, MCS 14"),
     ("pusch_test", ["-n", "15", "-L", "12", "-m", "14", "-s", "40"], "PUSCH 12 of 15 PRB, MCS 14"),
     ("pusch_test", ["-n", "6", "-L", "6", "-m", "0", "-s", "40"], "PUSCH 6 PRB, MCS 0 (one small code block)"),
@@ -69,13 +77,38 @@ def run(kind, prog, args):
     return res
 
 
+def run_n(kind, prog, args, runs):
+    """`runs` processes of one cell: the steady figure of each (the median subframe of a process), their median and range"""
+    if runs <= 1:
+        return run(kind, prog, args)
+    rs = [run(kind, prog, args) for _ in range(runs)]
+    if rs[0] is None:
+        return None
+    res = dict(rs[-1])
+    us = sorted(r["us_per_decode_steady"] for r in rs if r.get("us_per_decode_steady"))
+    if us:
+        res.update(runs=runs, rc=max(r["rc"] for r in rs), us_per_decode_steady_runs=[round(v, 1) for v in us], us_per_decode_steady=us[len(us) // 2],
+                   us_per_decode_steady_min=us[0], us_per_decode_steady_max=us[-1])
+    return res
+
+
 def main():
     rows = []
+    uci_only = "--uci" in sys.argv
+    runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 1
+    kinds = (("bin_refcpu", "reference_cpu_1_core"), ("bin_full", "library_per_code_block"), ("bin_tb", "library_transport_block_seam"),
+             ("bin_chan", "library_grant_seam"), ("bin_uci", "library_grant_seam_with_uci"))
+    if uci_only:
+        kinds = tuple(k for k in kinds if k[0] in ("bin_refcpu", "bin_chan", "bin_uci"))
+    twins = {" ".join(a).replace(" -p uci_ack 2 -p cqi wideband", "") for _, a, _ in CASES if "uci_ack" in a}
     for prog, args, label in CASES:
+        if uci_only and not (prog == "pusch_test" and ("uci_ack" in args or " ".join(args) in twins)):
+            continue
         row = {"program": prog, "args": " ".join(args), "what": label}
-        for kind, key in (("bin_refcpu", "reference_cpu_1_core"), ("bin_full", "library_per_code_block"), ("bin_tb", "library_transport_block_seam"),
-                          ("bin_chan", "library_grant_seam")):
-            row[key] = run(kind, prog, args)
+        for kind, key in kinds:
+            if kind == "bin_uci" and prog != "pusch_test":
+                continue
+            row[key] = run_n(kind, prog, args, runs)
         rows.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
     print(json.dumps({"host_cpus": os.cpu_count(), "rows": rows}, indent=1))

@@ -5,6 +5,7 @@
 #include "hip_common.h"
 #include "modem_device.h"
 #include "sch_stage.h"
+#include "stage.h"
 #include "srsran_amd/phy_chan_abi.h"
 
 #include <algorithm>
@@ -28,41 +29,16 @@ inline uint32_t qm_rm(const srsran_hip_grant_tb_t& tb) // what decode_tb / encod
 // per calling thread: pinned images the kernels read the grant's symbols / channel estimates from and write transmit symbols into, device
 // scratch between the front-end kernels, the transform plans of the allocation sizes seen so far
 struct ChanStage {
-  uint8_t* pin     = nullptr;
-  size_t   pin_cap = 0;
-  uint8_t* dev     = nullptr;
-  size_t   dev_cap = 0;
+  HostImage pin;
+  DeviceBuf dev;
   std::map<uint32_t, srsran_hip_dft_batch_t*> idft; // L_prb -> backward, normalised plan of 12 L_prb points (srsran_dft_precoding_init_rx)
   ~ChanStage()
   {
     for (auto& kv : idft) {
       srsran_hip_dft_batch_free(kv.second);
     }
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
   }
-  bool grow(size_t need_pin, size_t need_dev)
-  {
-    if (need_pin > pin_cap) {
-      (void)hipHostFree(pin);
-      pin     = nullptr;
-      pin_cap = 0;
-      if (host_image_alloc(&pin, need_pin + need_pin / 2) != hipSuccess) {
-        return false;
-      }
-      pin_cap = need_pin + need_pin / 2;
-    }
-    if (need_dev > dev_cap) {
-      (void)hipFree(dev);
-      dev     = nullptr;
-      dev_cap = 0;
-      if (hipMalloc((void**)&dev, need_dev + need_dev / 2) != hipSuccess) {
-        return false;
-      }
-      dev_cap = need_dev + need_dev / 2;
-    }
-    return true;
-  }
+  bool grow(size_t need_pin, size_t need_dev) { return pin.grow(need_pin, need_pin / 2) && dev.grow(need_dev, need_dev / 2); }
   srsran_hip_dft_batch_t* plan(uint32_t L_prb)
   {
     auto it = idft.find(L_prb);
@@ -84,9 +60,24 @@ ChanStage& stage()
   return r.get();
 }
 
-inline size_t al256(size_t v)
+// the calling thread's stage; nullptr (one line on stderr) without a device
+ChanStage* stage_for(const char* who)
 {
-  return (v + 255) & ~(size_t)255;
+  if (!device_available()) {
+    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
+    return nullptr;
+  }
+  bind_thread();
+  return &stage();
+}
+
+bool segment(srsran_cbsegm_t* seg, uint32_t tbs)
+{
+  if (srsran_cbsegm(seg, tbs) != SRSRAN_SUCCESS) {
+    fprintf(stderr, "Error computing segmentation for TBS=%d\n", tbs); // sch.c:637-640, 1133-1136, 1224-1228
+    return false;
+  }
+  return true;
 }
 
 bool tb_valid(const srsran_hip_grant_tb_t& tb, const char* who)
@@ -176,12 +167,11 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
   if (!g || !sf_symbols || !ce || !softbuffers || !data || !res) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pusch_decode: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_pusch_decode");
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  bind_thread();
-  ChanStage&             s = stage();
+  ChanStage&             s = *sp;
   std::vector<PuschPlan> pl(n);
   size_t                 pin_need = 0, dev_need = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -220,8 +210,7 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
     }
     PuschPlan& p = pl[i];
     p.nof_symb   = nsymb;
-    if (srsran_cbsegm(&p.seg, x.tb.tbs) != SRSRAN_SUCCESS) {
-      fprintf(stderr, "Error computing segmentation for TBS=%d\n", x.tb.tbs); // sch.c:1133-1136
+    if (!segment(&p.seg, x.tb.tbs)) {
       return SRSRAN_ERROR;
     }
     p.plan = s.plan(x.L_prb);
@@ -489,15 +478,13 @@ extern "C" int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const
   if (!tb_valid(g->tb, "srsran_hip_pdsch_decode") || (ce && !(g->scaling != 0.f))) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_pdsch_decode");
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  bind_thread();
-  ChanStage&      s = stage();
+  ChanStage&      s = *sp;
   srsran_cbsegm_t seg;
-  if (srsran_cbsegm(&seg, g->tb.tbs) != SRSRAN_SUCCESS) {
-    fprintf(stderr, "Error computing segmentation for TBS=%d\n", g->tb.tbs);
+  if (!segment(&seg, g->tb.tbs)) {
     return SRSRAN_ERROR;
   }
   const size_t nb = al256((size_t)g->tb.nof_re * sizeof(cf_t));
@@ -587,15 +574,13 @@ extern "C" int srsran_hip_pdsch_encode_dbg(const srsran_hip_pdsch_tx_t* g, srsra
   if (!tb_valid(g->tb, "srsran_hip_pdsch_encode")) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_encode: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_pdsch_encode");
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  bind_thread();
-  ChanStage&      s = stage();
+  ChanStage&      s = *sp;
   srsran_cbsegm_t seg;
-  if (srsran_cbsegm(&seg, g->tb.tbs) != SRSRAN_SUCCESS) {
-    fprintf(stderr, "Error computing segmentation for TBS=%d\n", g->tb.tbs); // sch.c:637-640
+  if (!segment(&seg, g->tb.tbs)) {
     return SRSRAN_ERROR;
   }
   const size_t nb = (size_t)g->tb.nof_re * sizeof(cf_t);
@@ -649,12 +634,11 @@ extern "C" int srsran_hip_pdsch_encode_multi(uint32_t n, const srsran_hip_pdsch_
   if (n == 1) {
     return srsran_hip_pdsch_encode(&g[0], softbuffers[0], data[0], symbols[0]);
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_encode: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_pdsch_encode");
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  bind_thread();
-  ChanStage&                   s = stage();
+  ChanStage&                   s = *sp;
   std::vector<srsran_cbsegm_t> seg(n);
   std::vector<sch::TxItem>     items(n);
   std::vector<size_t>          o_out(n);
@@ -663,8 +647,7 @@ extern "C" int srsran_hip_pdsch_encode_multi(uint32_t n, const srsran_hip_pdsch_
     if (!softbuffers[i] || !symbols[i] || !tb_valid(g[i].tb, "srsran_hip_pdsch_encode")) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
-    if (srsran_cbsegm(&seg[i], g[i].tb.tbs) != SRSRAN_SUCCESS) {
-      fprintf(stderr, "Error computing segmentation for TBS=%d\n", g[i].tb.tbs); // sch.c:637-640
+    if (!segment(&seg[i], g[i].tb.tbs)) {
       return SRSRAN_ERROR;
     }
     items[i] = {softbuffers[i], &seg[i], qm_rm(g[i].tb), g[i].tb.rv, g[i].tb.nof_re * qm_of(g[i].tb.mod), data[i], 0};
@@ -694,7 +677,7 @@ extern "C" int srsran_hip_pdsch_encode_multi(uint32_t n, const srsran_hip_pdsch_
     }
     modem::ModParams p = {};
     p.bits     = d_e;
-    p.out      = reinterpret_cast<float2*>(s.pin);
+    p.out      = reinterpret_cast<float2*>(s.pin.get());
     p.table    = tab;
     p.x1_bits  = sp.x1_bits;
     p.x2_cols  = sp.x2_cols;
@@ -727,15 +710,13 @@ extern "C" int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tbp, uint32_
     fprintf(stderr, "Invalid input\n"); // sch.c:1213-1221
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_ulsch_encode: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_ulsch_encode");
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  bind_thread();
-  ChanStage&      s = stage();
+  ChanStage&      s = *sp;
   srsran_cbsegm_t seg;
-  if (srsran_cbsegm(&seg, tb.tbs) != SRSRAN_SUCCESS) {
-    fprintf(stderr, "Error computing segmentation for TBS=%d\n", tb.tbs); // sch.c:1224-1228
+  if (!segment(&seg, tb.tbs)) {
     return SRSRAN_ERROR;
   }
   const uint32_t Qm = qm_of(tb.mod);
@@ -776,13 +757,12 @@ extern "C" int srsran_hip_modulate_bytes(uint32_t mod, const uint8_t* bits, cf_t
   if (scramble && nbits > SRSRAN_HIP_SEQUENCE_MAX_LEN) {
     return -1;
   }
-  if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_modulate_bytes: %s (there is no CPU fallback)\n", get_error());
+  ChanStage* sp = stage_for("srsran_hip_modulate_bytes");
+  if (!sp) {
     return -1;
   }
-  bind_thread();
+  ChanStage&  s  = *sp;
   hipStream_t st = sch::stage_stream();
-  ChanStage&  s  = stage();
   const size_t o_out = al256((nbits + 7) / 8 + 1);
   if (!st || !s.grow(o_out + (size_t)n * sizeof(cf_t), 0)) {
     return -1;

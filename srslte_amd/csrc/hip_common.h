@@ -180,11 +180,6 @@ public:
     std::lock_guard<std::mutex> lk(mu_);
     idle_.push_back(s);
   }
-  size_t idle()
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    return idle_.size();
-  }
 
 private:
   std::mutex      mu_;

@@ -1,6 +1,7 @@
 // modem_host.cpp -- C ABI of the soft demodulator / descrambler (include/srsran_amd/phy_modem_abi.h).
 #include "hip_common.h"
 #include "modem_device.h"
+#include "stage.h"
 #include "srsran_amd/phy_modem_abi.h"
 
 #include <cmath>
@@ -187,47 +188,13 @@ namespace {
 
 // ---- host-pointer calls: one job, thread-local staging ----------------------------------------------------------------------
 struct Stage {
-  hipStream_t st       = nullptr;
-  void*       d_in     = nullptr;
-  void*       d_out    = nullptr;
-  size_t      cap_in   = 0;
-  size_t      cap_out  = 0;
-  bool        tried    = false;
-  ~Stage()
-  {
-    (void)hipHostFree(d_in);
-    (void)hipHostFree(d_out);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
-  bool ready()
-  {
-    if (!tried) {
-      tried = true;
-      if (device_available() && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        st = nullptr;
-      }
-    }
-    return st != nullptr;
-  }
-  static bool grow(void** p, size_t* cap, size_t need)
-  {
-    if (need <= *cap) {
-      return true;
-    }
-    // PINNED HOST memory, mapped into the device's address space: a single call's symbols are read once and its soft bits written once, so the
-    // kernel works on the staging images themselves -- no copy operation on either side of it (6-9 us each whatever the size, and from / to
-    // pageable memory a staged, blocking one: tools/probe/roundtrip_probe.hip)
-    (void)hipHostFree(*p);
-    *p   = nullptr;
-    *cap = 0;
-    if (host_image_alloc(p, need + need / 2 + 256) != hipSuccess) {
-      return false;
-    }
-    *cap = need + need / 2 + 256;
-    return true;
-  }
+  StageStream st;
+  // PINNED HOST memory, mapped into the device's address space: a single call's symbols are read once and its soft bits written once, so the
+  // kernel works on the staging images themselves -- no copy operation on either side of it (6-9 us each whatever the size, and from / to
+  // pageable memory a staged, blocking one: tools/probe/roundtrip_probe.hip)
+  HostImage   d_in, d_out;
+  bool        ready() { return st.open(); }
+  static bool grow(HostImage& b, size_t need) { return b.grow(need, need / 2 + 256); }
 };
 
 Stage& stage()
@@ -253,7 +220,7 @@ int run_host(uint32_t mod, const void* in, void* out, int llr_type, uint32_t n, 
     return SRSRAN_ERROR;
   }
   modem::Params p;
-  if (!fill_params(p, llr_type) || !Stage::grow(&s.d_in, &s.cap_in, in_bytes) || !Stage::grow(&s.d_out, &s.cap_out, n_llr * es)) {
+  if (!fill_params(p, llr_type) || !Stage::grow(s.d_in, in_bytes) || !Stage::grow(s.d_out, n_llr * es)) {
     fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
     return SRSRAN_ERROR;
   }
@@ -496,13 +463,13 @@ extern "C" int srsran_predecoding_single(cf_t* y, cf_t* h, cf_t* x, float* csi, 
     return SRSRAN_ERROR;
   }
   const size_t nb   = (size_t)nof_symbols * sizeof(cf_t);
-  const size_t slot = (nb + 255) & ~(size_t)255;
-  if (!Stage::grow(&s.d_in, &s.cap_in, 2 * slot) || !Stage::grow(&s.d_out, &s.cap_out, slot + (size_t)nof_symbols * sizeof(float))) {
+  const size_t slot = al256(nb);
+  if (!Stage::grow(s.d_in, 2 * slot) || !Stage::grow(s.d_out, slot + (size_t)nof_symbols * sizeof(float))) {
     return SRSRAN_ERROR;
   }
-  uint8_t* din  = (uint8_t*)s.d_in;
-  uint8_t* dout = (uint8_t*)s.d_out;
-  memcpy(din, y, nb); // (the staging images are pinned host memory the kernel works on directly, see Stage::grow)
+  uint8_t* din  = s.d_in;
+  uint8_t* dout = s.d_out;
+  memcpy(din, y, nb); // (the staging images are pinned host memory the kernel works on directly, see Stage)
   memcpy(din + slot, h, nb);
   PHY_HIP_CHECK(modem::launch_eq(din, din + slot, dout, csi ? (float*)(dout + slot) : nullptr, (uint32_t)nof_symbols, scaling, noise_estimate, s.st),
                 SRSRAN_ERROR);

@@ -6,6 +6,7 @@
 // both against the compiled reference.
 #include "hip_common.h"
 #include "rm_device.h"
+#include "stage.h"
 #include "srsran_amd/phy_sch_abi.h"
 
 #include <map>
@@ -159,43 +160,10 @@ int rx_batch(const void* d_in, uint32_t in_stride, uint32_t in_len, void* d_out,
 // host-pointer form: one code block.  Staging buffers and the stream are kept per calling thread (the reference's function
 // is stateless; allocating per call would dominate it).
 struct HostStage {
-  hipStream_t st   = nullptr;
-  void*       d_in = nullptr;
-  void*       d_out = nullptr;
-  size_t      cap_in = 0, cap_out = 0;
-  bool        tried = false;
-  ~HostStage()
-  {
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
-  bool ready()
-  {
-    if (!tried) {
-      tried = true;
-      if (device_available() && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        st = nullptr;
-      }
-    }
-    return st != nullptr;
-  }
-  static bool grow(void** p, size_t* cap, size_t need)
-  {
-    if (need <= *cap) {
-      return true;
-    }
-    (void)hipFree(*p);
-    *p   = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need + 256) != hipSuccess) {
-      return false;
-    }
-    *cap = need + 256;
-    return true;
-  }
+  StageStream st;
+  DeviceBuf   d_in, d_out;
+  bool        ready() { return st.open(); }
+  static bool grow(DeviceBuf& b, size_t need) { return b.grow(need, 256); }
 };
 
 template <typename T>
@@ -215,7 +183,7 @@ int rx_host(const T* input, T* output, uint32_t in_len, uint32_t cb_idx, uint32_
   }
   const uint32_t K = (uint32_t)srsran_cbsegm_cbsize(cb_idx);
   const size_t   n_out = nof_sb ? 3 * ((size_t)K + 32) + 12 : 3 * (size_t)K + 12;
-  if (!HostStage::grow(&s.d_in, &s.cap_in, in_len * sizeof(T)) || !HostStage::grow(&s.d_out, &s.cap_out, n_out * sizeof(T))) {
+  if (!HostStage::grow(s.d_in, in_len * sizeof(T)) || !HostStage::grow(s.d_out, n_out * sizeof(T))) {
     return SRSRAN_ERROR;
   }
   PHY_HIP_CHECK(hipMemcpyAsync(s.d_in, input, in_len * sizeof(T), hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);

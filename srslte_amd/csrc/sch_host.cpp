@@ -6,6 +6,7 @@
 #include "srsran_amd/phy_sch_abi.h"
 #include "turbo_device.h"
 #include "sch_stage.h"
+#include "stage.h"
 
 #include <algorithm>
 #include <map>
@@ -460,88 +461,25 @@ extern "C" int srsran_hip_sch_decode_8bit(srsran_hip_sch_t* h, const int8_t* d_e
 namespace {
 
 struct TbStage {
-  hipStream_t       st  = nullptr;
+  StageStream       st;
   srsran_hip_sch_t* sch = nullptr;
-  uint8_t*          pin = nullptr; // pinned image: [soft rows | e bits | data]
-  uint8_t*          dev = nullptr; // the same layout on the device
-  size_t            cap = 0;
+  HostImage         pin; // pinned image: [soft rows | e bits | data]
+  DeviceBuf         dev; // the same layout on the device
   bool              tried = false;
-  ~TbStage()
-  {
-    srsran_hip_sch_free(sch);
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
+  ~TbStage() { srsran_hip_sch_free(sch); }
   bool ready()
   {
     if (!tried) {
       tried = true;
-      if (device_available()) {
-        bind_thread();
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-          st = nullptr;
-        } else if (srsran_hip_sch_create(&sch) != SRSRAN_SUCCESS) {
-          (void)hipStreamDestroy(st);
-          st = nullptr;
-        }
+      if (st.open()) {
+        (void)srsran_hip_sch_create(&sch); // (leaves nullptr when it fails)
       }
     }
-    return st != nullptr;
+    return sch != nullptr;
   }
-  bool grow(size_t need)
-  {
-    if (need <= cap) {
-      return true;
-    }
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    dev = pin = nullptr;
-    cap = 0;
-    if (hipMalloc((void**)&dev, need) != hipSuccess || host_image_alloc(&pin, need) != hipSuccess) {
-      return false;
-    }
-    cap = need;
-    return true;
-  }
+  bool grow(size_t need) { return dev.grow(need) && pin.grow(need); }
 };
 
-// true when the n bytes at p (8-byte aligned, as the rows of a soft buffer are) are all zero: a row straight after srsran_softbuffer_rx_reset
-// is not worth a copy, let alone a transfer.  Read-only, four independent accumulators (vectorises), early exit per 4 KB.
-inline bool all_zero(const uint8_t* p, size_t n)
-{
-  size_t i = 0;
-  if ((reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
-    const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
-    const size_t    w = n / 8;
-    for (size_t j = 0; j < w;) {
-      const size_t e = j + 512 < w ? j + 512 : w;
-      uint64_t     a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-      for (; j + 4 <= e; j += 4) {
-        a0 |= q[j], a1 |= q[j + 1], a2 |= q[j + 2], a3 |= q[j + 3];
-      }
-      for (; j < e; j++) {
-        a0 |= q[j];
-      }
-      if (a0 | a1 | a2 | a3) {
-        return false;
-      }
-    }
-    i = w * 8;
-  }
-  for (; i < n; i++) {
-    if (p[i]) {
-      return false;
-    }
-  }
-  return true;
-}
-
-} // namespace
-
-namespace {
 TbStage& tb_stage()
 {
   static thread_local StageRef<TbStage> r;
@@ -555,7 +493,7 @@ namespace sch {
 hipStream_t stage_stream()
 {
   TbStage& s = tb_stage();
-  return s.ready() ? s.st : nullptr;
+  return s.ready() ? (hipStream_t)s.st : nullptr;
 }
 } // namespace sch
 } // namespace phyhip
@@ -583,7 +521,6 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
   const bool   dev_e = it[0].front != nullptr;
   const size_t es   = llr8 ? 1 : 2;
   const size_t row  = (size_t)SRSRAN_HIP_SOFTBUFFER_CB_SIZE * es;
-  auto         al   = [](size_t v) { return (v + 255) & ~(size_t)255; };
   struct Plan {
     uint32_t C = 0, slot0 = 0;        // code blocks, first soft-buffer row of this block in the image
     size_t   o_e = 0, o_data = 0, n_data = 0;
@@ -624,11 +561,11 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
     slots += C;
     p.live = true;
   }
-  size_t off = al((size_t)slots * row);
+  size_t off = al256((size_t)slots * row);
   for (uint32_t t = 0; t < n; t++) {
     if (pl[t].live) {
       pl[t].o_e = off;
-      off       = al(off + (size_t)it[t].nof_e_bits * es);
+      off       = al256(off + (size_t)it[t].nof_e_bits * es);
     }
   }
   const size_t o_data0 = off;
@@ -636,7 +573,7 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
     if (pl[t].live) {
       pl[t].o_data = off;
       pl[t].n_data = it[t].seg->tbs / 8 + 6; // the last block's K/8 bytes end 3 bytes behind the transport CRC (:424 writes whole blocks)
-      off          = al(off + pl[t].n_data);
+      off          = al256(off + pl[t].n_data);
     }
   }
   const size_t total = off;

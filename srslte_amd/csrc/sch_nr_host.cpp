@@ -9,6 +9,7 @@
 // srsran_ra_nr_tbs, the reference's resource-allocation code, which is outside this library).
 #include "hip_common.h"
 #include "nr_sch_device.h"
+#include "stage.h"
 #include "srsran_amd/phy_batch.h"
 #include "srsran_amd/phy_modem_abi.h"
 #include "srsran_amd/phy_nr_sch_abi.h"
@@ -524,37 +525,18 @@ extern "C" int srsran_hip_sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_
 namespace {
 
 struct NrTbStage {
-  hipStream_t                               st = nullptr;
+  StageStream                               st;
   std::map<uint64_t, srsran_hip_sch_nr_t*>  sch; // (scaling factor, iterations) -> decoder object
-  uint8_t*                                  pin = nullptr; // pinned image: [soft rows | data rows | e bits | payload]
-  uint8_t*                                  dev = nullptr;
-  size_t                                    cap = 0;
-  bool                                      tried = false;
+  HostImage                                 pin; // pinned image: [soft rows | data rows | e bits | payload]
+  DeviceBuf                                 dev;
   static const uint32_t                     MAX_CB = 160; // > SRSRAN_SCH_NR_MAX_NOF_CB_LDPC (sch_nr.h:41)
   ~NrTbStage()
   {
     for (auto& kv : sch) {
       srsran_hip_sch_nr_free(kv.second);
     }
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
   }
-  bool ready()
-  {
-    if (!tried) {
-      tried = true;
-      if (device_available()) {
-        bind_thread();
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-          st = nullptr;
-        }
-      }
-    }
-    return st != nullptr;
-  }
+  bool ready() { return st.open(); }
   srsran_hip_sch_nr_t* decoder(float scaling, uint32_t iters)
   {
     uint32_t sbits;
@@ -571,53 +553,8 @@ struct NrTbStage {
     sch[key] = h;
     return h;
   }
-  bool grow(size_t need)
-  {
-    if (need <= cap) {
-      return true;
-    }
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    dev = pin = nullptr;
-    cap = 0;
-    if (hipMalloc((void**)&dev, need) != hipSuccess || host_image_alloc(&pin, need) != hipSuccess) {
-      return false;
-    }
-    cap = need;
-    return true;
-  }
+  bool grow(size_t need) { return dev.grow(need) && pin.grow(need); }
 };
-
-// true when the n bytes at p (8-byte aligned, as the rows of a soft buffer are) are all zero: a row straight after srsran_softbuffer_rx_reset
-// is not worth a copy, let alone a transfer.  Read-only, four independent accumulators (vectorises), early exit per 4 KB.
-inline bool all_zero(const uint8_t* p, size_t n)
-{
-  size_t i = 0;
-  if ((reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
-    const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
-    const size_t    w = n / 8;
-    for (size_t j = 0; j < w;) {
-      const size_t e = j + 512 < w ? j + 512 : w;
-      uint64_t     a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-      for (; j + 4 <= e; j += 4) {
-        a0 |= q[j], a1 |= q[j + 1], a2 |= q[j + 2], a3 |= q[j + 3];
-      }
-      for (; j < e; j++) {
-        a0 |= q[j];
-      }
-      if (a0 | a1 | a2 | a3) {
-        return false;
-      }
-    }
-    i = w * 8;
-  }
-  for (; i < n; i++) {
-    if (p[i]) {
-      return false;
-    }
-  }
-  return true;
-}
 
 } // namespace
 
@@ -644,9 +581,8 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
   if (!h) {
     return SRSRAN_ERROR;
   }
-  auto           al         = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const uint32_t sb_stride  = (uint32_t)al(c.N);
-  const uint32_t data_stride = (uint32_t)al((c.Kr + 7) / 8);
+  const uint32_t sb_stride  = (uint32_t)al256(c.N);
+  const uint32_t data_stride = (uint32_t)al256((c.Kr + 7) / 8);
   const uint32_t cb_bytes   = (c.Kp - c.L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (:650-652)
   uint8_t        flags[NrTbStage::MAX_CB];
   size_t         n_e = 0;
@@ -660,8 +596,8 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
       return SRSRAN_ERROR;
     }
   }
-  const size_t o_soft = 0, o_data = al(o_soft + (size_t)c.C * sb_stride), o_e = al(o_data + (size_t)c.C * data_stride), o_pay = al(o_e + n_e);
-  if (!s.grow(al(o_pay + c.A / 8 + 8))) {
+  const size_t o_soft = 0, o_data = al256(o_soft + (size_t)c.C * sb_stride), o_e = al256(o_data + (size_t)c.C * data_stride), o_pay = al256(o_e + n_e);
+  if (!s.grow(al256(o_pay + c.A / 8 + 8))) {
     fprintf(stderr, "[srsran_phy_hip] sch_nr decode: staging allocation failed\n");
     return SRSRAN_ERROR;
   }
@@ -878,9 +814,8 @@ extern "C" int srsran_hip_sch_nr_encode_tb(const srsran_hip_nr_tb_t* tb_in, cons
   for (uint32_t r = 0; r < c.C; r++) {
     n_e += get_E(c, r);
   }
-  auto         al    = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_pay = 0, o_e = al(o_pay + c.A / 8 + 8);
-  if (!s.grow(al(o_e + n_e))) {
+  const size_t o_pay = 0, o_e = al256(o_pay + c.A / 8 + 8);
+  if (!s.grow(al256(o_e + n_e))) {
     fprintf(stderr, "[srsran_phy_hip] sch_nr encode: staging allocation failed\n");
     return SRSRAN_ERROR;
   }

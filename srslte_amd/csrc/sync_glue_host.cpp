@@ -7,6 +7,7 @@
 // srsran_hip_cellsearch_* (sync_host.cpp); this file is the per-frame control flow the reference's callers
 // (ue_sync.c, ue_cell_search.c) expect.
 #include "hip_common.h"
+#include "stage.h"
 #include "srsran_amd/phy_sync_abi.h"
 #include "sync_device.h"
 #include "sync_glue.h"
@@ -21,46 +22,23 @@ using namespace phyhip;
 namespace {
 
 struct Stage {
-  hipStream_t st   = nullptr;
-  float2*     d[3] = {nullptr, nullptr, nullptr};
-  size_t      cap[3] = {0, 0, 0};
-  float2*     d_small = nullptr; // 8 results + arg-max
-  ~Stage()
-  {
-    for (auto* p : d) {
-      (void)hipFree(p);
-    }
-    (void)hipFree(d_small);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
+  StageStream                        st;
+  StageBuf<StageMem::Device, float2> d[3];    // (capacities in samples)
+  StageBuf<StageMem::Device, float2> d_small; // 8 results + arg-max
   bool ready()
   {
-    if (st) {
+    if (st.open() && d_small.grow(16)) {
       return true;
     }
-    if (!device_available()) {
-      return false;
-    }
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&d_small, 16 * sizeof(float2)) != hipSuccess) {
+    if (device_available()) {
       set_error("sync glue: cannot create the staging stream");
-      st = nullptr;
-      return false;
     }
-    return true;
+    return false;
   }
   float2* buf(int i, size_t n)
   {
-    if (n > cap[i]) {
-      (void)hipFree(d[i]);
-      d[i]   = nullptr;
-      cap[i] = 0;
-      if (hipMalloc(&d[i], n * sizeof(float2)) != hipSuccess) {
-        set_error("sync glue: device allocation of %zu samples failed", n);
-        return nullptr;
-      }
-      cap[i] = n;
+    if (!d[i].grow(n)) {
+      set_error("sync glue: device allocation of %zu samples failed", n);
     }
     return d[i];
   }

@@ -5,6 +5,7 @@
 #include "tables/lte_qpp_table.h"
 #include "tcod_device.h"
 #include "sch_stage.h"
+#include "stage.h"
 
 #include <algorithm>
 #include <map>
@@ -183,29 +184,10 @@ extern "C" int srsran_tcod_encode_lut(srsran_tcod_t* h, srsran_crc_t* crc_tb, sr
 
 namespace {
 struct TxStage {
-  hipStream_t st   = nullptr;
-  uint8_t*    d_sp = nullptr; // systematic + parity streams
-  uint8_t*    d_out = nullptr;
-  size_t      cap_out = 0;
-  bool        tried = false;
-  ~TxStage()
-  {
-    (void)hipFree(d_sp);
-    (void)hipFree(d_out);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
-  bool ready()
-  {
-    if (!tried) {
-      tried = true;
-      if (device_available() && (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&d_sp, 4096) != hipSuccess)) {
-        st = nullptr;
-      }
-    }
-    return st != nullptr;
-  }
+  StageStream st;
+  DeviceBuf   d_sp; // systematic + parity streams
+  DeviceBuf   d_out;
+  bool        ready() { return st.open() && d_sp.grow(4096); }
 };
 
 // srsran_bit_copy (bit.c:685-698) of `len` bits from the packed array `src` (bit 0 first) to dst at bit offset `dst_off`.  With
@@ -250,12 +232,10 @@ extern "C" int srsran_rm_turbo_tx_lut(uint8_t* w_buff, uint8_t* systematic, uint
     return SRSRAN_SUCCESS;
   }
   const size_t out_bytes = (out_len + 7) / 8;
-  if (out_bytes > s.cap_out) {
-    (void)hipFree(s.d_out);
-    s.d_out   = nullptr;
-    s.cap_out = 0;
-    PHY_HIP_CHECK(hipMalloc(&s.d_out, out_bytes + 1024), SRSRAN_ERROR);
-    s.cap_out = out_bytes + 1024;
+  if (!s.d_out.grow(out_bytes, 1024)) {
+    set_error("srsran_rm_turbo_tx_lut: device allocation of %zu bytes failed", out_bytes + 1024);
+    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+    return SRSRAN_ERROR;
   }
   tcod::LutRmParams p{};
   p.table = rm::device_fwd_table(K, rv_idx, &p.table_len);
@@ -630,68 +610,43 @@ extern "C" int srsran_hip_sch_encode(srsran_hip_sch_enc_t* h, const uint8_t* d_d
 // to the encoder either way) and such a call encodes again from them.
 namespace {
 struct TxTbStage {
-  hipStream_t           st  = nullptr;
-  srsran_hip_sch_enc_t* enc = nullptr;
-  uint8_t*              pin = nullptr; // pinned, device-visible image: [payload | e bits]
-  uint8_t*              dev = nullptr; // e bits on the device (the code blocks OR their partial bytes into them: not a job for host memory)
-  size_t                cap = 0;
-  bool                  tried = false;
-  ~TxTbStage()
-  {
-    srsran_hip_sch_enc_free(enc);
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    if (st) {
-      (void)hipStreamDestroy(st);
-    }
-  }
+  StageStream                  st;
+  srsran_hip_sch_enc_t*        enc = nullptr;
+  HostImage                    pin; // pinned, device-visible image: [payloads | room for the e bits to come down into]
+  DeviceBuf                    dev; // [e bits | payloads] (the code blocks OR their partial bytes into the e bits: not a job for host memory)
+  std::vector<srsran_hip_tb_t> tbs; // the call's blocks as srsran_hip_sch_encode takes them, and every block's first e byte in `dev`
+  std::vector<uint32_t>        e_off;
+  bool                         tried = false;
+  ~TxTbStage() { srsran_hip_sch_enc_free(enc); }
   bool ready()
   {
     if (!tried) {
       tried = true;
-      if (device_available()) {
-        bind_thread();
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-          st = nullptr;
-        } else if (srsran_hip_sch_enc_create(&enc) != SRSRAN_SUCCESS) {
-          (void)hipStreamDestroy(st);
-          st = nullptr;
-        }
+      if (st.open()) {
+        (void)srsran_hip_sch_enc_create(&enc); // (leaves nullptr when it fails)
       }
     }
-    return st != nullptr;
+    return enc != nullptr;
   }
-  bool grow(size_t need)
-  {
-    if (need <= cap) {
-      return true;
-    }
-    (void)hipFree(dev);
-    (void)hipHostFree(pin);
-    dev = pin = nullptr;
-    cap = 0;
-    if (hipMalloc((void**)&dev, need) != hipSuccess || host_image_alloc(&pin, need) != hipSuccess) {
-      return false;
-    }
-    cap = need;
-    return true;
-  }
+  bool grow(size_t need) { return dev.grow(need) && pin.grow(need); }
 };
-} // namespace
 
-extern "C" int srsran_hip_encode_tb(srsran_softbuffer_tx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits,
-                                    uint8_t* data, uint8_t* e_bits)
+TxTbStage& tx_tb_stage() // the calling thread's: the one srsran_hip_warmup() prepared, whichever entry point comes first
 {
-  return phyhip::sch::encode_tb_staged(softbuffer, cb_segm, Qm, rv, nof_e_bits, data, e_bits, nullptr);
+  static thread_local StageRef<TxTbStage> r;
+  return r.get();
 }
 
-// n transport blocks, their e bits consumed on the device (sch_stage.h)
-int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* back)
+// What becomes of a call's e bits: enqueues its work on `st`.  d_e_bits: their device image, block t's from byte e_byte_off[t] on; h_e_bits: the pinned
+// image's room for a download (as many bytes as the device image holds e bits).
+using TxConsumer = std::function<bool(hipStream_t st, const uint8_t* d_e_bits, uint8_t* h_e_bits, const uint32_t* e_byte_off)>;
+
+// encode_tb for n transport blocks on the thread's stage: ONE coding launch over the code blocks of all of them, `consume` behind it, one host wait.
+// empty_ok: a block without code blocks or e bits ends the call with SRSRAN_SUCCESS before any device work, as the reference's loop over the code
+// blocks does not run (sch.c:269); otherwise it is refused.
+int encode_items(phyhip::sch::TxItem* it, uint32_t n, bool empty_ok, const TxConsumer& consume)
 {
-  if (!it || !back || n == 0) {
-    return SRSRAN_ERROR_INVALID_INPUTS;
-  }
-  auto   al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  using phyhip::sch::TxItem;
   size_t pay_bytes = 0, e_bytes = 0, n_cb = 0;
   for (uint32_t t = 0; t < n; t++) {
     TxItem& x = it[t];
@@ -707,27 +662,30 @@ int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* b
       fprintf(stderr, "Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", x.seg->C, x.sb->max_cb); // :259-262
       return SRSRAN_ERROR;
     }
-    if (x.Qm == 0 || x.rv > 3 || x.seg->C == 0 || x.seg->tbs == 0 || x.nof_e_bits == 0) {
+    const bool empty = x.seg->C == 0 || x.seg->tbs == 0 || x.nof_e_bits == 0;
+    if (x.Qm == 0 || x.rv > 3 || (empty && !empty_ok)) {
       fprintf(stderr, "Invalid Qm\n"); // :264-267
       return SRSRAN_ERROR;
     }
-    pay_bytes += al(x.seg->tbs / 8 + 8);
-    e_bytes += al((x.nof_e_bits + 7) / 8 + 8);
+    if (empty) {
+      return SRSRAN_SUCCESS;
+    }
+    pay_bytes += al256(x.seg->tbs / 8 + 8);
+    e_bytes += al256((x.nof_e_bits + 7) / 8 + 8);
     n_cb += x.seg->C;
   }
-  static thread_local StageRef<TxTbStage> ref;
-  TxTbStage&                             s = ref.get();
+  TxTbStage& s = tx_tb_stage();
   if (!s.ready()) {
     fprintf(stderr, "[srsran_phy_hip] encode_tb: %s (there is no CPU fallback)\n", get_error());
     return SRSRAN_ERROR;
   }
-  if (!s.grow(e_bytes + pay_bytes + 512)) { // pinned: [payloads]; device: [e bits | payloads]
+  if (!s.grow(e_bytes + pay_bytes + 512)) {
     fprintf(stderr, "[srsran_phy_hip] encode_tb: staging allocation failed\n");
     return SRSRAN_ERROR;
   }
-  std::vector<srsran_hip_tb_t> tbs(n);
-  std::vector<uint32_t>        e_off(n);
-  size_t                       po = 0, eo = 0;
+  s.tbs.resize(n);
+  s.e_off.resize(n);
+  size_t po = 0, eo = 0;
   for (uint32_t t = 0; t < n; t++) {
     TxItem&        x = it[t];
     const uint32_t C = x.seg->C;
@@ -735,7 +693,7 @@ int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* b
     for (uint32_t i = 0; i < C; i++) { // payload slices of the code blocks in the transmit side's order (the C2 smaller blocks first, sch.c:284-290)
       const uint32_t K    = i < x.seg->C2 ? x.seg->K2 : x.seg->K1;
       const uint32_t rlen = C > 1 ? K - 24 : K;
-      const uint32_t nb   = (i + 1 == C ? rlen - 24 : rlen) / 8;
+      const uint32_t nb   = (i + 1 == C ? rlen - 24 : rlen) / 8; // the last block ends with the transport-block CRC, which is not payload
       if (!x.sb->buffer_b[i]) {
         return SRSRAN_ERROR;
       }
@@ -749,22 +707,25 @@ int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* b
       fprintf(stderr, "[srsran_phy_hip] encode_tb: segmentation does not add up to the transport block size (%u != %u)\n", rp, x.seg->tbs);
       return SRSRAN_ERROR;
     }
-    tbs[t]       = {x.seg->tbs, x.Qm, x.rv, x.nof_e_bits, (uint32_t)(8 * eo), (uint32_t)po, 0};
-    e_off[t]     = (uint32_t)eo;
+    s.tbs[t]     = {x.seg->tbs, x.Qm, x.rv, x.nof_e_bits, (uint32_t)(8 * eo), (uint32_t)po, 0};
+    s.e_off[t]   = (uint32_t)eo;
     x.e_byte_off = (uint32_t)eo;
-    po += al(x.seg->tbs / 8 + 8);
-    eo += al((x.nof_e_bits + 7) / 8 + 8);
+    po += al256(x.seg->tbs / 8 + 8);
+    eo += al256((x.nof_e_bits + 7) / 8 + 8);
   }
-  const bool direct = n_cb <= 64 && knob(KNOB_TCOD_LAT) != 0; // (as encode_tb_staged: the one-launch kernel reads the payload from the pinned image)
+  // The one-launch kernel of a subframe's worth of code blocks reads the payload ONCE, a dword per lane: straight from the pinned image.  (The throughput
+  // kernels read it byte-wise and more than once, which is slow across the bus: for them -- more than 64 code blocks, or SRSRAN_HIP_TCOD_LAT=0 -- it goes up
+  // with a copy.)
+  const bool direct = n_cb <= 64 && knob(KNOB_TCOD_LAT) != 0;
   if (!direct) {
     PHY_HIP_CHECK(hipMemcpyAsync(s.dev + e_bytes, s.pin, pay_bytes, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
   }
-  if (srsran_hip_sch_encode(s.enc, direct ? s.pin : s.dev + e_bytes, tbs.data(), n, s.dev, s.st) != SRSRAN_SUCCESS) {
+  if (srsran_hip_sch_encode(s.enc, direct ? s.pin.get() : s.dev + e_bytes, s.tbs.data(), n, s.dev, s.st) != SRSRAN_SUCCESS) {
     (void)hipStreamSynchronize(s.st);
     fprintf(stderr, "[srsran_phy_hip] encode_tb: %s\n", get_error());
     return SRSRAN_ERROR;
   }
-  const bool ok = (*back)(s.st, s.dev, e_off.data(), n);
+  const bool ok = consume(s.st, s.dev, s.pin + pay_bytes, s.e_off.data());
   PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR); // (also after a failed enqueue: nothing may be in flight when the images are re-used)
   if (!ok) {
     fprintf(stderr, "[srsran_phy_hip] encode_tb: %s\n", get_error());
@@ -772,9 +733,26 @@ int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* b
   }
   return SRSRAN_SUCCESS;
 }
+} // namespace
+
+extern "C" int srsran_hip_encode_tb(srsran_softbuffer_tx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits,
+                                    uint8_t* data, uint8_t* e_bits)
+{
+  return phyhip::sch::encode_tb_staged(softbuffer, cb_segm, Qm, rv, nof_e_bits, data, e_bits, nullptr);
+}
+
+// n transport blocks, their e bits consumed on the device (sch_stage.h)
+int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* back)
+{
+  if (!it || !back || n == 0) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return encode_items(it, n, false, [&](hipStream_t st, const uint8_t* d_e, uint8_t*, const uint32_t* e_off) { return (*back)(st, d_e, e_off, n); });
+}
 
 // `back` given: the e bits stay on the device and the kernels back(stream, d_e_bits) enqueues consume them there (chan_host.cpp: scrambling +
-// modulation, or the UL channel interleaver) -- their results are the caller's to collect after this function's one host wait
+// modulation, or the UL channel interleaver) -- their results are the caller's to collect after this function's one host wait.  Otherwise they come
+// down to e_bits.
 int phyhip::sch::encode_tb_staged(srsran_softbuffer_tx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits, uint8_t* data,
                                   uint8_t* e_bits, const BackEnd* back)
 {
@@ -782,81 +760,31 @@ int phyhip::sch::encode_tb_staged(srsran_softbuffer_tx_t* softbuffer, srsran_cbs
     fprintf(stderr, "Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d\n", e_bits != 0, cb_segm != 0, softbuffer != 0); // sch.c:351
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (cb_segm->F) {
-    fprintf(stderr, "Error filler bits are not supported. Use standard TBS\n"); // :254-257
-    return SRSRAN_ERROR;
-  }
-  if (cb_segm->C > softbuffer->max_cb) {
-    fprintf(stderr, "Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", cb_segm->C, softbuffer->max_cb); // :259-262
-    return SRSRAN_ERROR;
-  }
-  if (Qm == 0 || rv > 3) {
-    fprintf(stderr, "Invalid Qm\n"); // :264-267
-    return SRSRAN_ERROR;
-  }
-  const uint32_t C = cb_segm->C, tbs = cb_segm->tbs;
-  if (C == 0 || tbs == 0 || nof_e_bits == 0) {
-    return SRSRAN_SUCCESS; // the loop over code blocks does not run
-  }
-  static thread_local StageRef<TxTbStage> ref;
-  TxTbStage&                             s = ref.get();
-  if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] encode_tb: %s (there is no CPU fallback)\n", get_error());
-    return SRSRAN_ERROR;
-  }
-  auto         al    = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  TxItem       x     = {softbuffer, cb_segm, Qm, rv, nof_e_bits, data, 0};
   const size_t n_out = (nof_e_bits + 7) / 8;
-  const size_t o_pay = 0, o_e = al(o_pay + tbs / 8 + 8);
-  const size_t d_pay = al(n_out + 8); // device image: [e bits | payload]
-  if (!s.grow(al(o_e + n_out + 8) + 512)) {
-    fprintf(stderr, "[srsran_phy_hip] encode_tb: staging allocation failed\n");
-    return SRSRAN_ERROR;
-  }
-  // payload slices of the code blocks in the transmit side's order (the C2 smaller blocks first, sch.c:284-290)
-  uint32_t rp = 0;
-  for (uint32_t i = 0; i < C; i++) {
-    const uint32_t K    = i < cb_segm->C2 ? cb_segm->K2 : cb_segm->K1;
-    const uint32_t rlen = C > 1 ? K - 24 : K;
-    const uint32_t nb   = (i + 1 == C ? rlen - 24 : rlen) / 8; // the last block ends with the transport-block CRC, which is not payload
-    if (!softbuffer->buffer_b[i]) {
-      return SRSRAN_ERROR;
+  struct {
+    const BackEnd* back;
+    size_t         n_out;
+    const uint8_t* h_e; // where the e bits came down to
+  } c = {back, n_out, nullptr};
+  const int rc = encode_items(&x, 1, true, [&c](hipStream_t st, const uint8_t* d_e, uint8_t* h_e, const uint32_t*) {
+    if (c.back) {
+      return (*c.back)(st, d_e);
     }
-    if (data) {
-      memcpy(softbuffer->buffer_b[i], data + rp / 8, nb);
+    c.h_e = h_e;
+    if (hipMemcpyAsync(h_e, d_e, c.n_out, hipMemcpyDeviceToHost, st) != hipSuccess) {
+      set_error("download of the e bits failed");
+      return false;
     }
-    memcpy(s.pin + o_pay + rp / 8, softbuffer->buffer_b[i], nb);
-    rp += 8 * nb;
+    return true;
+  });
+  if (rc != SRSRAN_SUCCESS || !c.h_e) {
+    return rc; // (no download: `back` has the e bits, or the block was empty)
   }
-  if (rp != tbs) {
-    fprintf(stderr, "[srsran_phy_hip] encode_tb: segmentation does not add up to the transport block size (%u != %u)\n", rp, tbs);
-    return SRSRAN_ERROR;
-  }
-  const srsran_hip_tb_t tb = {tbs, Qm, rv, nof_e_bits, 0, 0, 0};
-  // The one-launch kernel of a transport block reads the payload ONCE, a dword per lane: straight from the pinned image.  (The throughput kernels read it
-  // byte-wise and more than once, which is slow across the bus: for them -- more than 64 code blocks never happen here, SRSRAN_HIP_TCOD_LAT=0 does -- it goes up with a copy.)
-  const bool direct = C <= 64 && knob(KNOB_TCOD_LAT) != 0;
-  if (!direct) {
-    PHY_HIP_CHECK(hipMemcpyAsync(s.dev + d_pay, s.pin + o_pay, tbs / 8, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-  }
-  if (srsran_hip_sch_encode(s.enc, direct ? s.pin + o_pay : s.dev + d_pay, &tb, 1, s.dev, s.st) != SRSRAN_SUCCESS) {
-    (void)hipStreamSynchronize(s.st);
-    fprintf(stderr, "[srsran_phy_hip] encode_tb: %s\n", get_error());
-    return SRSRAN_ERROR;
-  }
-  if (back) {
-    const bool ok = (*back)(s.st, s.dev);
-    PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR); // (also after a failed enqueue: nothing may be in flight when the images are re-used)
-    if (!ok) {
-      fprintf(stderr, "[srsran_phy_hip] encode_tb: %s\n", get_error());
-      return SRSRAN_ERROR;
-    }
-    return SRSRAN_SUCCESS;
-  }
-  PHY_HIP_CHECK(hipMemcpyAsync(s.pin + o_e, s.dev, n_out, hipMemcpyDeviceToHost, s.st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
   // The unused low bits of the last byte: srsran_rm_turbo_tx_lut copies every block's circular buffer piece by piece with srsran_bit_copy
   // (rm_turbo.c:362-374), which ZEROES the rest of a piece's last byte when the piece starts byte aligned on both sides and preserves it
   // otherwise (bit.c:685-698): replay the pieces of the last code block for the byte the transport block ends in.
+  const uint32_t C    = cb_segm->C;
   const uint32_t tail = nof_e_bits & 7u;
   uint8_t        keep = 0;
   if (tail) {
@@ -885,7 +813,7 @@ int phyhip::sch::encode_tb_staged(srsran_softbuffer_tx_t* softbuffer, srsran_cbs
     }
     keep = zeroed ? 0 : (uint8_t)(e_bits[n_out - 1] & (0xffu >> tail));
   }
-  memcpy(e_bits, s.pin + o_e, n_out);
+  memcpy(e_bits, c.h_e, n_out);
   if (tail) {
     e_bits[n_out - 1] = (uint8_t)((e_bits[n_out - 1] & (0xff00u >> tail)) | keep);
   }

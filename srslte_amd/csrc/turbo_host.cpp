@@ -5,6 +5,7 @@
 #include "coalesce.h"
 #include "hip_common.h"
 #include "srsran_amd/phy_sch_abi.h"
+#include "stage.h"
 #include "tables/lte_qpp_table.h"
 #include "turbo_device.h"
 
@@ -210,7 +211,7 @@ void* cached_const(uint64_t key, size_t bytes, Fill fill)
         return &c; // placeholder
       }
     }
-    const size_t off = (c.img.size() + 255) & ~(size_t)255;
+    const size_t off = al256(c.img.size());
     c.img.resize(off + bytes);
     fill(c.img.data() + off);
     c.pending.emplace_back(key, off);

@@ -1,5 +1,6 @@
 // turbo_device.h -- kernel parameter blocks and launchers of turbo_kernels.hip
 #pragma once
+#include "turbo_arith.h" // TD_WIN_OVERLAP
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -92,7 +93,13 @@ hipError_t launch_lat(int nb, bool arith8, const WinParams& p, hipStream_t strea
 // so a run may change between the two forms from launch to launch
 hipError_t launch_lat2(bool arith8, const WinParams& p, hipStream_t stream);
 size_t     lat2_lds_bytes(uint32_t K);
-constexpr uint32_t kLat2MaxBlocks = 256; // per block-per-CU the filed rows allow (turbo_host.cpp: want_lat2)
+// what the two-wave form can run: its filed rows fit the LDS a workgroup may take, and a sub-block holds the warm-up window and one 8-step block more.
+// The router (turbo_host.cpp: route) and the launcher both go by this
+static inline bool lat2_can_run(uint32_t K)
+{
+  return lat2_lds_bytes(K) <= 120 * 1024 && K >= 16 * (TD_WIN_OVERLAP + 8);
+}
+constexpr uint32_t kLat2MaxBlocks = 256; // per block-per-CU the filed rows allow (turbo_host.cpp: route)
 uint32_t   lat_ws_dwords(uint32_t K, int nb);
 static inline bool lat_exists(int nb, bool arith8)
 {

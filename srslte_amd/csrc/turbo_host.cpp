@@ -157,20 +157,17 @@ struct srsran_hip_tdec_batch {
   uint16_t* d_deinter16 = nullptr;
   // optional parity aid
   short* d_dec_llr = nullptr;
-  // early stop on CRC: multipliers x^(W (nb-1-d)) mod g for the generators used so far
-  std::map<uint32_t, uint32_t*> crc_mult;
   // the "persistent" launch variant's unit counter (development knob) and the CU count of the object's device
   uint32_t* d_unit_counter = nullptr;
   int       cus            = 0;
   // latency kernel (small batches): its own workspace, allocated on first use for lat_cap code blocks
   uint32_t* d_ws_lat      = nullptr;
   uint32_t  lat_cap       = 0;
-  std::map<uint32_t, uint32_t*> crc_mult_lat; // per generator: one multiplier per 32-bit word of the kernel's hard-bit image
   bool      state_in_lat  = false; // the decoder state of the last launch lives in the latency kernel's workspace
   bool      state_in_gen_lat = false; // scalar decoder: ... in the latency kernel's per-block layout of d_ws_gen
-  // tables borrowed from the process-wide cache (never freed by the object); workspace taken from a caller's arena at every launch
-  bool              tables_cached = false;
-  turbo::WsArena*   arena         = nullptr;
+  // workspace taken from a caller's arena at every launch: the object then owns none (d_ws, d_ws_gen and d_ws_lat stay null)
+  turbo::WsArena* arena = nullptr;
+  // (the tables are borrowed from the process-wide cache, never freed by the object)
 };
 
 // ---- process-wide cache of the small device constants a decoder of (K, sub-blocks) needs: exchange tables, interleaver tables, CRC multipliers.
@@ -230,32 +227,32 @@ void* cached_const(uint64_t key, size_t bytes, Fill fill)
 }
 } // namespace
 
-// which kernel takes a launch of n_cb blocks starting at half iteration n_begin (a resumed run stays where its state is)
-static bool want_lat(srsran_hip_tdec_batch* h, uint32_t n_cb, uint32_t n_begin)
+// x^e mod g over GF(2), g of degree 24 given with its x^24 term
+static uint32_t xpow_mod(uint64_t e, uint32_t poly)
 {
-  if (!h->nb || !turbo::lat_exists(h->nb, h->arith8)) {
-    return false;
+  auto mul = [&](uint32_t a, uint32_t b) {
+    uint32_t r = 0;
+    for (int i = 23; i >= 0; i--) {
+      r = ((r << 1) & 0xffffffu) ^ (((r >> 23) & 1u) ? (poly & 0xffffffu) : 0u);
+      if ((b >> i) & 1u) {
+        r ^= a;
+      }
+    }
+    return r;
+  };
+  uint32_t result = 1, base = 2; // the polynomials 1 and x
+  while (e) {
+    if (e & 1) {
+      result = mul(result, base);
+    }
+    base = mul(base, base);
+    e >>= 1;
   }
-  if (n_begin > 0) {
-    return h->state_in_lat;
-  }
-  const int k = knob(KNOB_TDEC_LAT);
-  return k == 0 ? false : (k > 0 ? true : turbo::lat_waves(h->nb, n_cb) <= turbo::kLatMaxBlocks);
+  return result;
 }
-static uint32_t xpow_mod(uint64_t e, uint32_t poly);
-// the same for the scalar decoder (K <= 400 with AUTO): 8 lanes per block with the block in LDS, or one lane per block
-static bool want_gen_lat(srsran_hip_tdec_batch* h, uint32_t n_cb, uint32_t n_begin)
-{
-  if (h->nb || (h->K & 7u) || turbo::gen_lat_lds_bytes(h->K) > 156 * 1024) {
-    return false;
-  }
-  if (n_begin > 0) {
-    return h->state_in_gen_lat;
-  }
-  const int k = knob(KNOB_TDEC_LAT);
-  return k == 0 ? false : (k > 0 ? true : n_cb <= turbo::kGenLatMaxBlocks);
-}
-// lane l of a block's 8 takes the bits [l c, min((l + 1) c, K)), c = ceil(K / 8): x^(K - end) mod g shifts its remainder into place
+
+// ---- CRC multipliers of the early stop, one table per (K, sub-blocks, generator) in the process-wide cache
+// scalar latency kernel: lane l of a block's 8 takes the bits [l c, min((l + 1) c, K)), c = ceil(K / 8): x^(K - end) mod g shifts its remainder into place
 static uint32_t* gen_crc_mult8(uint32_t K, uint32_t poly)
 {
   return static_cast<uint32_t*>(cached_const(ckey(CK_CRC_GEN, K, 0, poly), 8 * sizeof(uint32_t), [&](void* dst) {
@@ -267,29 +264,167 @@ static uint32_t* gen_crc_mult8(uint32_t K, uint32_t poly)
     }
   }));
 }
-// the latency kernel's two-wave form: 16 sub-blocks, few blocks (it takes two waves and up to 96 KB of LDS per block)
-static bool want_lat2(srsran_hip_tdec_batch* h, uint32_t n_cb)
+// throughput kernel: x^(W (nb-1-d)) mod g shifts the remainder of sub-block d (W = K / nb bits) into place
+static uint32_t* crc_mult_win(uint32_t K, int nb, uint32_t poly)
 {
-  if (h->nb != 16 || turbo::lat2_lds_bytes(h->K) > 120 * 1024) {
-    return false;
+  const uint32_t nbq = (uint32_t)nb;
+  return static_cast<uint32_t*>(cached_const(ckey(CK_CRC_WIN, K, nb, poly), nbq * sizeof(uint32_t), [&](void* dst) {
+    uint32_t*      m = static_cast<uint32_t*>(dst);
+    const uint64_t W = K / nbq;
+    for (uint32_t d = 0; d < nbq; d++) {
+      m[d] = xpow_mod(W * (uint64_t)(nbq - 1 - d), poly);
+    }
+  }));
+}
+// the latency kernel forms the CRC from 32-bit words of its hard-bit image (sub-block d at d * sbs4 bytes): word (d, w) holds the steps
+// 32 w ... of sub-block d and is shifted into place with x^(bits behind it) mod g
+static uint32_t* crc_mult_lat(uint32_t K, int nb, uint32_t poly)
+{
+  const uint32_t nbq = (uint32_t)nb, W = K / nbq, nblk = (W + 7) / 8, wps = (((nblk + 1 + 3) & ~3u) >> 2);
+  return static_cast<uint32_t*>(cached_const(ckey(CK_CRC_LAT, K, nb, poly), (size_t)nbq * wps * sizeof(uint32_t), [&](void* dst) {
+    uint32_t* m = static_cast<uint32_t*>(dst);
+    memset(m, 0, (size_t)nbq * wps * sizeof(uint32_t));
+    for (uint32_t d = 0; d < nbq; d++) {
+      for (uint32_t w = 0; w < wps; w++) {
+        if (32 * w < W) {
+          const uint32_t nbit = W - 32 * w > 32 ? 32 : W - 32 * w;
+          m[d * wps + w]      = xpow_mod((uint64_t)K - ((uint64_t)d * W + 32 * w + nbit), poly);
+        }
+      }
+    }
+  }));
+}
+
+// ---- one route, one workspace, one launch: every turbo launch of the library (batch ABI, transport blocks, srsran_tdec_* handles) goes through these
+enum class Route {
+  Win,    // throughput kernel: 8 code blocks per wave (turbo_kernels.hip)
+  Lat,    // latency kernel: one code block per wave (turbo_lat_kernels.hip)
+  Lat2,   //   its two-wave form; same workspace layout as Lat
+  Gen,    // scalar decoder (K <= 400 with AUTO): one lane per code block
+  GenLat, // scalar latency kernel: 8 lanes per block with the block in LDS (turbo_gen_lat_kernels.hip)
+};
+// which kernel takes a launch of n_cb blocks starting at half iteration n_begin: every kernel's precondition, then the knobs, then the batch size
+// (a resumed run stays where its state is)
+static Route route(const srsran_hip_tdec_batch* h, uint32_t n_cb, uint32_t n_begin)
+{
+  const int k = knob(KNOB_TDEC_LAT);
+  if (!h->nb) {
+    if ((h->K & 7u) || turbo::gen_lat_lds_bytes(h->K) > 156 * 1024) {
+      return Route::Gen;
+    }
+    const bool lat = n_begin > 0 ? h->state_in_gen_lat : (k == 0 ? false : (k > 0 ? true : n_cb <= turbo::kGenLatMaxBlocks));
+    return lat ? Route::GenLat : Route::Gen;
   }
-  const int k = knob(KNOB_TDEC_LAT2);
+  if (!turbo::lat_exists(h->nb, h->arith8)) {
+    return Route::Win;
+  }
+  const bool lat = n_begin > 0 ? h->state_in_lat : (k == 0 ? false : (k > 0 ? true : turbo::lat_waves(h->nb, n_cb) <= turbo::kLatMaxBlocks));
+  if (!lat) {
+    return Route::Win;
+  }
+  // the two-wave form: 16 sub-blocks, few blocks (it takes two waves and up to 96 KB of LDS per block).  The two forms share a workspace layout, so a
+  // resumed run chooses between them like a new one
+  if (h->nb != 16 || !turbo::lat2_can_run(h->K)) {
+    return Route::Lat;
+  }
+  const int k2 = knob(KNOB_TDEC_LAT2);
   // one round of the chip: a block's two waves and its filed rows -- up to four blocks per CU where the rows are small (K = 1024: 1024 blocks 0.155 against
   // 0.199 ms per 8 half iterations, 2048 blocks 0.37 against 0.28; K = 6144, one block per CU: 256 blocks 0.27 against 0.51, 512 blocks 0.54 against 0.57)
   const size_t per_cu = std::min<size_t>(4, (150 * 1024) / turbo::lat2_lds_bytes(h->K));
-  return k == 0 ? false : (k > 0 ? true : n_cb <= turbo::kLat2MaxBlocks * per_cu);
+  const bool   two    = k2 == 0 ? false : (k2 > 0 ? true : n_cb <= turbo::kLat2MaxBlocks * per_cu);
+  return two ? Route::Lat2 : Route::Lat;
 }
-static int ensure_lat_ws(srsran_hip_tdec_batch* h, uint32_t n_cb)
+
+// the workspace a launch of n_cb blocks on route r runs in: the caller's arena when the object has one, else the object's own allocation (p is null
+// when there is none to be had: error reported)
+struct Workspace {
+  void*  p      = nullptr;
+  size_t stride = 0; // dwords per code block (window decoders), int16 per wave (scalar decoder)
+};
+static Workspace workspace(srsran_hip_tdec_batch* h, Route r, uint32_t n_cb, hipStream_t stream)
 {
-  if (n_cb <= h->lat_cap) {
-    return SRSRAN_SUCCESS;
+  Workspace ws;
+  size_t    bytes = 0; // what n_cb blocks need (asked of the arena)
+  if (r == Route::Gen || r == Route::GenLat) {
+    ws.stride = turbo::gen_ws_shorts(h->K);
+    ws.p      = h->d_ws_gen;
+    bytes     = ws.stride * ceil_div(n_cb, 64) * sizeof(short);
+  } else if (r == Route::Win) {
+    const uint32_t cpw = 64 / ((uint32_t)h->nb / 2); // one slab per wave
+    ws.stride = h->ws_stride;
+    ws.p      = h->d_ws;
+    bytes     = ws.stride * ceil_div(n_cb, cpw) * cpw * sizeof(uint32_t);
+  } else {
+    ws.stride = turbo::lat_ws_dwords(h->K, h->nb);
+    bytes     = ws.stride * ((n_cb + 1u) & ~1u) * sizeof(uint32_t);
+    if (!h->arena && n_cb > h->lat_cap) {
+      // the object's own is allocated on first use, for a subframe's worth of blocks at least
+      (void)hipFree(h->d_ws_lat);
+      h->d_ws_lat = nullptr;
+      h->lat_cap  = 0;
+      const uint32_t cap = ((n_cb > turbo::kLatMaxBlocks ? n_cb : (h->max_cb < turbo::kLatMaxBlocks ? h->max_cb : turbo::kLatMaxBlocks)) + 1u) & ~1u;
+      PHY_HIP_CHECK(hipMalloc(&h->d_ws_lat, ws.stride * cap * sizeof(uint32_t)), Workspace());
+      h->lat_cap = cap;
+    }
+    ws.p = h->d_ws_lat;
   }
-  (void)hipFree(h->d_ws_lat);
-  h->d_ws_lat = nullptr;
-  h->lat_cap  = 0;
-  const uint32_t cap = ((n_cb > turbo::kLatMaxBlocks ? n_cb : (h->max_cb < turbo::kLatMaxBlocks ? h->max_cb : turbo::kLatMaxBlocks)) + 1u) & ~1u;
-  PHY_HIP_CHECK(hipMalloc(&h->d_ws_lat, (size_t)turbo::lat_ws_dwords(h->K, h->nb) * cap * sizeof(uint32_t)), SRSRAN_ERROR);
-  h->lat_cap = cap;
+  if (h->arena) {
+    ws.p = h->arena->ensure(bytes, stream);
+  }
+  return ws;
+}
+
+// what every launch of a window decoder / the scalar decoder passes to its kernel; the entry points add what is theirs
+static turbo::WinParams win_params(const srsran_hip_tdec_batch* h, const Workspace& ws, const void* d_input, bool in_is8, uint8_t* d_output, uint32_t n_cb,
+                                   uint32_t n_begin, uint32_t n_end, int sb_layout)
+{
+  turbo::WinParams p = {};
+  p.input     = static_cast<const short*>(d_input);
+  p.output    = d_output;
+  p.ws        = static_cast<uint32_t*>(ws.p);
+  p.deint     = h->d_deint;
+  p.inter     = h->d_inter;
+  p.ws_stride = (uint32_t)ws.stride;
+  p.K         = h->K;
+  p.n_begin   = n_begin;
+  p.n_end     = n_end;
+  p.n_cb      = (int)n_cb;
+  p.sb_layout = sb_layout;
+  p.in_is8    = in_is8 ? 1 : 0;
+  return p;
+}
+static turbo::GenParams gen_params(const srsran_hip_tdec_batch* h, const Workspace& ws, const void* d_input, bool in_is8, uint8_t* d_output, uint32_t n_cb,
+                                   uint32_t n_begin, uint32_t n_end)
+{
+  turbo::GenParams p = {};
+  p.input     = static_cast<const short*>(d_input);
+  p.output    = d_output;
+  p.ws        = static_cast<short*>(ws.p);
+  p.inter     = h->d_inter16;
+  p.deinter   = h->d_deinter16;
+  p.ws_stride = ws.stride;
+  p.K         = h->K;
+  p.n_begin   = n_begin;
+  p.n_end     = n_end;
+  p.n_cb      = (int)n_cb;
+  p.in_is8    = in_is8 ? 1 : 0;
+  return p;
+}
+
+// the launch itself, and the note of where it leaves the decoder state (what a resumed run goes by)
+static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::WinParams& p, hipStream_t stream)
+{
+  PHY_HIP_CHECK(r == Route::Lat2  ? turbo::launch_lat2(h->arith8, p, stream)
+                : r == Route::Lat ? turbo::launch_lat(h->nb, h->arith8, p, stream)
+                                  : turbo::launch_win(h->nb, h->arith8, p, stream),
+                SRSRAN_ERROR);
+  h->state_in_lat = r != Route::Win;
+  return SRSRAN_SUCCESS;
+}
+static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::GenParams& p, hipStream_t stream)
+{
+  PHY_HIP_CHECK(r == Route::GenLat ? turbo::launch_gen_lat(p, stream) : turbo::launch_gen(p, stream), SRSRAN_ERROR);
+  h->state_in_gen_lat = r == Route::GenLat;
   return SRSRAN_SUCCESS;
 }
 
@@ -375,7 +510,6 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
   h->nb     = nb;
   h->arith8 = arith8;
   h->arena  = arena;
-  h->tables_cached = true;
   const uint32_t K = long_cb;
   if (nb) {
     const uint32_t lpc = nb / 2, long_sb = K / nb, nblk = (long_sb + 7) / 8;
@@ -450,18 +584,16 @@ extern "C" void srsran_hip_tdec_batch_free(srsran_hip_tdec_batch_t* h)
   if (!h) {
     return;
   }
-  if (!h->arena) {
-    hipFree(h->d_ws);
-    hipFree(h->d_ws_lat);
-    hipFree(h->d_ws_gen);
-  }
+  hipFree(h->d_ws);
+  hipFree(h->d_ws_lat);
+  hipFree(h->d_ws_gen);
   hipFree(h->d_dec_llr);
   // (exchange / interleaver tables and CRC multipliers belong to the process-wide cache)
   delete h;
 }
 
 // run half iterations [n_begin, n_end) and take the hard decision for n_iter = n_end
-static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input_v, bool in_is8, uint32_t in_stride,
+static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input, bool in_is8, uint32_t in_stride,
                                 uint8_t* d_output, uint32_t out_stride, uint32_t n_cb, uint32_t n_begin, uint32_t n_end,
                                 int sb_layout, bool want_llr, hipStream_t stream)
 {
@@ -469,7 +601,6 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input_
   if (h) {
     PHY_DEV_GUARD(h->tag, "srsran_hip_tdec_batch_run", SRSRAN_ERROR);
   }
-  const int16_t* d_input = static_cast<const int16_t*>(d_input_v);
   if (h && n_cb == 0) {
     return SRSRAN_SUCCESS; // an empty batch is a no-op
   }
@@ -493,80 +624,43 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input_
   if (want_llr && !h->d_dec_llr) {
     PHY_HIP_CHECK(hipMalloc(&h->d_dec_llr, (size_t)h->K * h->max_cb * sizeof(short)), SRSRAN_ERROR);
   }
-  if (h->nb) {
-    turbo::WinParams p = {};
-    p.input      = d_input;
-    p.output     = d_output;
-    p.dec_llr    = want_llr ? h->d_dec_llr : nullptr;
-    p.ws         = h->d_ws;
-    p.deint      = h->d_deint;
-    p.inter      = h->d_inter;
-    p.in_stride  = in_stride;
-    p.out_stride = out_stride;
-    p.ws_stride  = h->ws_stride;
-    p.K          = h->K;
-    p.n_begin    = n_begin;
-    p.n_end      = n_end;
-    p.n_cb       = (int)n_cb;
-    p.sb_layout  = sb_layout;
-    p.in_is8     = in_is8 ? 1 : 0;
-    if (knob(KNOB_TDEC_EXTRACT_ONLY) > 0) {
-      p.n_end = 0; // development aid: input extraction + decision only
-    }
-    // launch-shape alternatives kept for measurement (profiles/r02_turbo_variants.txt); the product path is variant 0
-    const int variant = knob(KNOB_TDEC_VARIANT) > 0 ? knob(KNOB_TDEC_VARIANT) : 0;
-    if (variant == 2 && n_begin == 0 && h->nb == 16 && !h->arith8) {
-      // the unit counter belongs to the batch object (launches of different objects / streams must not share one) and lives on
-      // the device the object was created on
-      if (!h->d_unit_counter) {
-        int dev = 0;
-        PHY_HIP_CHECK(hipGetDevice(&dev), SRSRAN_ERROR);
-        PHY_HIP_CHECK(hipMalloc(&h->d_unit_counter, sizeof(uint32_t)), SRSRAN_ERROR);
-        PHY_HIP_CHECK(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev), SRSRAN_ERROR);
-      }
-      PHY_HIP_CHECK(hipMemsetAsync(h->d_unit_counter, 0, sizeof(uint32_t), stream), SRSRAN_ERROR);
-      p.n_units      = ceil_div(n_cb, 8);
-      p.max_resident = (uint32_t)h->cus * 8u; // 4 SIMDs x 2 waves
-      p.unit_counter = h->d_unit_counter;
-    }
-    p.variant = variant;
-    if (want_lat(h, n_cb, n_begin)) {
-      if (ensure_lat_ws(h, n_cb)) {
-        return SRSRAN_ERROR;
-      }
-      p.ws        = h->d_ws_lat;
-      p.ws_stride = turbo::lat_ws_dwords(h->K, h->nb);
-      PHY_HIP_CHECK(want_lat2(h, n_cb) ? turbo::launch_lat2(h->arith8, p, stream) : turbo::launch_lat(h->nb, h->arith8, p, stream), SRSRAN_ERROR);
-      h->state_in_lat = true;
-    } else {
-      PHY_HIP_CHECK(turbo::launch_win(h->nb, h->arith8, p, stream), SRSRAN_ERROR);
-      h->state_in_lat = false;
-    }
-  } else {
-    turbo::GenParams p = {};
-    p.input      = d_input;
-    p.output     = d_output;
-    p.dec_llr    = want_llr ? h->d_dec_llr : nullptr;
-    p.ws         = h->d_ws_gen;
-    p.inter      = h->d_inter16;
-    p.deinter    = h->d_deinter16;
-    p.ws_stride  = turbo::gen_ws_shorts(h->K);
-    p.in_stride  = in_stride;
-    p.out_stride = out_stride;
-    p.K          = h->K;
-    p.n_begin    = n_begin;
-    p.n_end      = n_end;
-    p.n_cb       = (int)n_cb;
-    p.in_is8     = in_is8 ? 1 : 0;
-    if (want_gen_lat(h, n_cb, n_begin)) {
-      PHY_HIP_CHECK(turbo::launch_gen_lat(p, stream), SRSRAN_ERROR);
-      h->state_in_gen_lat = true;
-    } else {
-      PHY_HIP_CHECK(turbo::launch_gen(p, stream), SRSRAN_ERROR);
-      h->state_in_gen_lat = false;
-    }
+  const Route     r  = route(h, n_cb, n_begin);
+  const Workspace ws = workspace(h, r, n_cb, stream);
+  if (!ws.p) {
+    return SRSRAN_ERROR;
   }
-  return SRSRAN_SUCCESS;
+  auto mine = [&](auto& p) {
+    p.in_stride  = in_stride;
+    p.out_stride = out_stride;
+    p.dec_llr    = want_llr ? h->d_dec_llr : nullptr;
+  };
+  if (!h->nb) {
+    turbo::GenParams p = gen_params(h, ws, d_input, in_is8, d_output, n_cb, n_begin, n_end);
+    mine(p);
+    return launch(h, r, p, stream);
+  }
+  turbo::WinParams p = win_params(h, ws, d_input, in_is8, d_output, n_cb, n_begin, n_end, sb_layout);
+  mine(p);
+  if (knob(KNOB_TDEC_EXTRACT_ONLY) > 0) {
+    p.n_end = 0; // development aid: input extraction + decision only
+  }
+  // launch-shape alternatives kept for measurement (profiles/r02_turbo_variants.txt); the product path is variant 0
+  p.variant = knob(KNOB_TDEC_VARIANT) > 0 ? knob(KNOB_TDEC_VARIANT) : 0;
+  if (p.variant == 2 && n_begin == 0 && h->nb == 16 && !h->arith8) {
+    // the unit counter belongs to the batch object (launches of different objects / streams must not share one) and lives on
+    // the device the object was created on
+    if (!h->d_unit_counter) {
+      int dev = 0;
+      PHY_HIP_CHECK(hipGetDevice(&dev), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMalloc(&h->d_unit_counter, sizeof(uint32_t)), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev), SRSRAN_ERROR);
+    }
+    PHY_HIP_CHECK(hipMemsetAsync(h->d_unit_counter, 0, sizeof(uint32_t), stream), SRSRAN_ERROR);
+    p.n_units      = ceil_div(n_cb, 8);
+    p.max_resident = (uint32_t)h->cus * 8u; // 4 SIMDs x 2 waves
+    p.unit_counter = h->d_unit_counter;
+  }
+  return launch(h, r, p, stream);
 }
 
 extern "C" int srsran_hip_tdec_batch_run(srsran_hip_tdec_batch_t* h, const int16_t* d_input, uint32_t in_stride,
@@ -617,30 +711,6 @@ extern "C" SRSRAN_API int srsran_hip_tdec_batch_run_dbg_8bit(srsran_hip_tdec_bat
                               (hipStream_t)stream);
 }
 
-// x^e mod g over GF(2), g of degree 24 given with its x^24 term
-static uint32_t xpow_mod(uint64_t e, uint32_t poly)
-{
-  auto mul = [&](uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-    for (int i = 23; i >= 0; i--) {
-      r = ((r << 1) & 0xffffffu) ^ (((r >> 23) & 1u) ? (poly & 0xffffffu) : 0u);
-      if ((b >> i) & 1u) {
-        r ^= a;
-      }
-    }
-    return r;
-  };
-  uint32_t result = 1, base = 2; // the polynomials 1 and x
-  while (e) {
-    if (e & 1) {
-      result = mul(result, base);
-    }
-    base = mul(base, base);
-    e >>= 1;
-  }
-  return result;
-}
-
 // Transport-block decoding (sch_host.cpp): all half iterations up to max_iterations with the per-block CRC early
 // stop of decode_tb_cb (sch.c:420-454); d_desc places every block's input / output.
 int phyhip::turbo::batch_run_early_stop(srsran_hip_tdec_batch_t* h, const void* d_input, bool in_is8, const turbo::CbDesc* d_desc,
@@ -654,114 +724,34 @@ int phyhip::turbo::batch_run_early_stop(srsran_hip_tdec_batch_t* h, const void* 
     set_error("tdec early stop: invalid arguments");
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!h->nb) {
-    // K <= 400: the scalar decoder (turbodecoder.c:381-408 sends these blocks to gen_impl), one lane per code block
-    turbo::GenParams g = {};
-    g.input     = static_cast<const short*>(d_input);
-    g.output    = d_output;
-    g.ws        = h->arena ? static_cast<short*>(h->arena->ensure(turbo::gen_ws_shorts(h->K) * ceil_div(n_cb, 64) * sizeof(short), stream)) : h->d_ws_gen;
-    if (!g.ws) {
-      return SRSRAN_ERROR;
-    }
-    g.inter     = h->d_inter16;
-    g.deinter   = h->d_deinter16;
-    g.ws_stride = turbo::gen_ws_shorts(h->K);
-    g.K         = h->K;
-    g.n_begin   = 0;
-    g.n_end     = max_iterations;
-    g.n_cb      = (int)n_cb;
-    g.in_is8    = in_is8 ? 1 : 0;
-    g.desc      = d_desc;
-    g.crc_poly  = crc_poly;
-    g.noi       = d_noi;
-    g.crc_ok    = d_crc_ok;
-    if (want_gen_lat(h, n_cb, 0)) {
-      g.crc_mult8 = gen_crc_mult8(h->K, crc_poly);
-      if (!g.crc_mult8) {
-        return SRSRAN_ERROR;
-      }
-      PHY_HIP_CHECK(turbo::launch_gen_lat(g, stream), SRSRAN_ERROR);
-      h->state_in_gen_lat = true;
-      return SRSRAN_SUCCESS;
-    }
-    h->state_in_gen_lat = false;
-    PHY_HIP_CHECK(turbo::launch_gen(g, stream), SRSRAN_ERROR);
-    return SRSRAN_SUCCESS;
-  }
-  const uint32_t nbq = (uint32_t)h->nb, Kq = h->K;
-  uint32_t*      d_mult = static_cast<uint32_t*>(cached_const(ckey(CK_CRC_WIN, Kq, h->nb, crc_poly), nbq * sizeof(uint32_t), [&](void* dst) {
-    uint32_t*      m = static_cast<uint32_t*>(dst);
-    const uint64_t W = Kq / nbq;
-    for (uint32_t d = 0; d < nbq; d++) {
-      m[d] = xpow_mod(W * (uint64_t)(nbq - 1 - d), crc_poly);
-    }
-  }));
-  if (!d_mult) {
+  const Route     r  = route(h, n_cb, 0);
+  const Workspace ws = workspace(h, r, n_cb, stream);
+  if (!ws.p) {
     return SRSRAN_ERROR;
   }
-  turbo::WinParams p = {};
-  p.input      = static_cast<const short*>(d_input);
-  p.output     = d_output;
-  p.ws         = h->d_ws;
-  p.deint      = h->d_deint;
-  p.inter      = h->d_inter;
-  p.ws_stride  = h->ws_stride;
-  p.K          = h->K;
-  p.n_begin    = 0;
-  p.n_end      = max_iterations;
-  p.n_cb       = (int)n_cb;
-  p.sb_layout  = sb_layout;
-  p.in_is8     = in_is8 ? 1 : 0;
-  p.desc       = d_desc;
-  p.crc_poly   = crc_poly;
-  p.crc_mult   = d_mult;
-  p.noi        = d_noi;
-  p.crc_ok     = d_crc_ok;
-  if (want_lat(h, n_cb, 0)) {
-    // a subframe's worth of code blocks: one block per wave instead of eight (turbo_lat_kernels.hip)
-    if (h->arena) {
-      h->d_ws_lat = static_cast<uint32_t*>(h->arena->ensure((size_t)turbo::lat_ws_dwords(h->K, h->nb) * ((n_cb + 1u) & ~1u) * sizeof(uint32_t), stream));
-      if (!h->d_ws_lat) {
-        return SRSRAN_ERROR;
-      }
-    } else if (ensure_lat_ws(h, n_cb)) {
+  auto mine = [&](auto& p) {
+    p.desc     = d_desc;
+    p.crc_poly = crc_poly;
+    p.noi      = d_noi;
+    p.crc_ok   = d_crc_ok;
+  };
+  if (!h->nb) {
+    // K <= 400: the scalar decoder (turbodecoder.c:381-408 sends these blocks to gen_impl)
+    turbo::GenParams g = gen_params(h, ws, d_input, in_is8, d_output, n_cb, 0, max_iterations);
+    mine(g);
+    if (r == Route::GenLat && !(g.crc_mult8 = gen_crc_mult8(h->K, crc_poly))) {
       return SRSRAN_ERROR;
     }
-    // the latency kernel forms the CRC from 32-bit words of its hard-bit image (sub-block d at d * sbs4 bytes): word (d, w) holds the steps
-    // 32 w ... of sub-block d and is shifted into place with x^(bits behind it) mod g
-    const uint32_t Wl = h->K / h->nb, nblkl = (Wl + 7) / 8, wps = (((nblkl + 1 + 3) & ~3u) >> 2);
-    uint32_t*      d_ml = static_cast<uint32_t*>(cached_const(ckey(CK_CRC_LAT, Kq, h->nb, crc_poly), (size_t)nbq * wps * sizeof(uint32_t), [&](void* dst) {
-      uint32_t* m = static_cast<uint32_t*>(dst);
-      memset(m, 0, (size_t)nbq * wps * sizeof(uint32_t));
-      for (uint32_t d = 0; d < nbq; d++) {
-        for (uint32_t w = 0; w < wps; w++) {
-          if (32 * w < Wl) {
-            const uint32_t nbit = Wl - 32 * w > 32 ? 32 : Wl - 32 * w;
-            m[d * wps + w]      = xpow_mod((uint64_t)Kq - ((uint64_t)d * Wl + 32 * w + nbit), crc_poly);
-          }
-        }
-      }
-    }));
-    if (!d_ml) {
-      return SRSRAN_ERROR;
-    }
-    p.crc_mult  = d_ml;
-    p.ws        = h->d_ws_lat;
-    p.ws_stride = turbo::lat_ws_dwords(h->K, h->nb);
-    PHY_HIP_CHECK(want_lat2(h, n_cb) ? turbo::launch_lat2(h->arith8, p, stream) : turbo::launch_lat(h->nb, h->arith8, p, stream), SRSRAN_ERROR);
-    h->state_in_lat = true;
-    return SRSRAN_SUCCESS;
+    return launch(h, r, g, stream);
   }
-  h->state_in_lat = false;
-  if (h->arena) {
-    const uint32_t cpw = 64 / (nbq / 2);
-    p.ws = static_cast<uint32_t*>(h->arena->ensure((size_t)h->ws_stride * ceil_div(n_cb, cpw) * cpw * sizeof(uint32_t), stream));
-    if (!p.ws) {
-      return SRSRAN_ERROR;
-    }
+  // (the latency kernels: a subframe's worth of code blocks, one block per wave instead of eight)
+  turbo::WinParams p = win_params(h, ws, d_input, in_is8, d_output, n_cb, 0, max_iterations, sb_layout);
+  mine(p);
+  p.crc_mult = r == Route::Win ? crc_mult_win(h->K, h->nb, crc_poly) : crc_mult_lat(h->K, h->nb, crc_poly);
+  if (!p.crc_mult) {
+    return SRSRAN_ERROR;
   }
-  PHY_HIP_CHECK(turbo::launch_win(h->nb, h->arith8, p, stream), SRSRAN_ERROR);
-  return SRSRAN_SUCCESS;
+  return launch(h, r, p, stream);
 }
 
 void* phyhip::turbo::WsArena::ensure(size_t bytes, hipStream_t stream)
@@ -824,35 +814,14 @@ bool phyhip::turbo::prebuild_tables()
         if (tdec_batch_create(&b, K, 1, SRSRAN_TDEC_AUTO, api8 != 0, &none) != SRSRAN_SUCCESS) {
           continue;
         }
-        if (!b->nb) {
-          for (uint32_t poly : polys) {
+        for (uint32_t poly : polys) {
+          if (!b->nb) {
             (void)gen_crc_mult8(K, poly);
+            continue;
           }
-        }
-        if (b->nb) {
-          const uint32_t nbq = (uint32_t)b->nb;
-          for (uint32_t poly : polys) {
-            (void)cached_const(ckey(CK_CRC_WIN, K, b->nb, poly), nbq * sizeof(uint32_t), [&](void* dst) {
-              uint32_t* m = static_cast<uint32_t*>(dst);
-              for (uint32_t d = 0; d < nbq; d++) {
-                m[d] = xpow_mod((uint64_t)(K / nbq) * (uint64_t)(nbq - 1 - d), poly);
-              }
-            });
-            if (turbo::lat_exists(b->nb, b->arith8)) {
-              const uint32_t Wl = K / nbq, nblkl = (Wl + 7) / 8, wps = (((nblkl + 1 + 3) & ~3u) >> 2);
-              (void)cached_const(ckey(CK_CRC_LAT, K, b->nb, poly), (size_t)nbq * wps * sizeof(uint32_t), [&](void* dst) {
-                uint32_t* m = static_cast<uint32_t*>(dst);
-                memset(m, 0, (size_t)nbq * wps * sizeof(uint32_t));
-                for (uint32_t d = 0; d < nbq; d++) {
-                  for (uint32_t w = 0; w < wps; w++) {
-                    if (32 * w < Wl) {
-                      const uint32_t nbit = Wl - 32 * w > 32 ? 32 : Wl - 32 * w;
-                      m[d * wps + w]      = xpow_mod((uint64_t)K - ((uint64_t)d * Wl + 32 * w + nbit), poly);
-                    }
-                  }
-                }
-              });
-            }
+          (void)crc_mult_win(K, b->nb, poly);
+          if (turbo::lat_exists(b->nb, b->arith8)) {
+            (void)crc_mult_lat(K, b->nb, poly);
           }
         }
         delete b; // (its table pointers are placeholders: nothing to free)
@@ -1009,6 +978,58 @@ extern "C" int srsran_tdec_get_nof_iterations(srsran_tdec_t* h)
   return h->n_iter;
 }
 
+// what a handle's decoder type makes of the current code block for callers with 8- or 16-bit LLRs: the batch object that runs it, the layout of
+// the caller's input and the values the reference leaves in the handle's fields
+struct HandleCfg {
+  int                    nb;
+  bool                   arith8;
+  int                    sb_layout;
+  size_t                 in_len; // elements of the caller's input
+  int                    impl;   // the manual implementation with these sub-blocks and this arithmetic
+  srsran_tdec_llr_type_t current_llr_type;
+  uint32_t               current_dec;
+  uint32_t               current_inter_idx;
+};
+// nonzero: the HIP engine does not reproduce the handle's decoder type
+static int handle_cfg(const srsran_tdec_t* h, bool in8, HandleCfg* c)
+{
+  const uint32_t K = h->current_long_cb;
+  if (impl_to_cfg(h->dec_type, in8, K, &c->nb, &c->arith8)) {
+    return -1;
+  }
+  const int  nb = c->nb;
+  const bool a8 = c->arith8;
+  // Input layout (turbodecoder_iter.h:88): the 8-bit decoders always expect the rm_turbo sub-block layout, the
+  // 16-bit ones only in AUTO mode with a window decoder; srsran_tdec_force_not_sb() turns it off.
+  const bool auto_mode = h->dec_type == SRSRAN_TDEC_AUTO;
+  c->sb_layout         = (!h->force_not_sb && (a8 || (auto_mode && nb > 0))) ? 1 : 0;
+  c->in_len            = c->sb_layout ? 3 * ((size_t)K + 32) + 12 : 3 * (size_t)K + 12;
+  c->impl              = a8 ? (nb == 32 ? SRSRAN_TDEC_AVX8_WINDOW : SRSRAN_TDEC_SSE8_WINDOW)
+                            : (nb == 16 ? SRSRAN_TDEC_AVX_WINDOW : (nb == 8 ? SRSRAN_TDEC_SSE_WINDOW : SRSRAN_TDEC_GENERIC));
+  c->current_llr_type  = auto_mode ? (a8 ? SRSRAN_TDEC_8 : SRSRAN_TDEC_16) : h->current_llr_type;
+  c->current_dec       = auto_mode ? (a8 ? (nb == 32 ? 1 : 0) : (nb == 16 ? 2 : (nb == 8 ? 1 : 0))) : 0;
+  c->current_inter_idx = nb == 32 ? 3 : (nb == 16 ? 2 : (nb == 8 ? 1 : 0)); // interleaver_idx(), turbodecoder.c:134-148
+  return 0;
+}
+static void apply_cfg(srsran_tdec_t* h, const HandleCfg& c)
+{
+  h->current_llr_type  = c.current_llr_type;
+  h->current_dec       = c.current_dec;
+  h->current_inter_idx = c.current_inter_idx;
+}
+// the reference writes the tail into the caller's buffer when it takes the sub-block layout without a width conversion (turbodecoder_iter.h:58-70,92-96)
+template <typename ELEM>
+static void write_back_tail(ELEM* input, uint32_t K, const HandleCfg& c)
+{
+  if (c.sb_layout && (sizeof(ELEM) == 1) == c.arith8) {
+    for (uint32_t i = K; i < K + 3; i++) {
+      input[i]                = input[3 * (K + 32) + 2 * (i - K)];
+      input[K + 32 + i]       = input[3 * (K + 32) + 2 * (i - K) + 1];
+      input[2 * (K + 32) + i] = input[3 * (K + 32) + 6 + 2 * (i - K) + 1];
+    }
+  }
+}
+
 // half iterations [n_iter, n_end) on the device + hard decision into `output` (turbodecoder.c:455-533).
 // ELEM is the caller's LLR type: int16_t (srsran_tdec_iteration / run_all) or int8_t (the *_8bit entry points).
 template <typename ELEM>
@@ -1026,28 +1047,15 @@ static void tdec_handle_iterate(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
     fprintf(stderr, "[srsran_phy_hip] srsran_tdec: K=%u is not a valid turbo block size\n", K);
     return;
   }
-  int  nb     = 0;
-  bool arith8 = false;
-  impl_to_cfg(h->dec_type, in8, K, &nb, &arith8);
-  // Input layout (turbodecoder_iter.h:88): the 8-bit decoders always expect the rm_turbo sub-block layout, the
-  // 16-bit ones only in AUTO mode with a window decoder; srsran_tdec_force_not_sb() turns it off.
-  const bool auto_mode = h->dec_type == SRSRAN_TDEC_AUTO;
-  const int  sb_layout = (!h->force_not_sb && (arith8 || (auto_mode && nb > 0))) ? 1 : 0;
-  if (auto_mode) {
-    h->current_llr_type = arith8 ? SRSRAN_TDEC_8 : SRSRAN_TDEC_16;
-    h->current_dec      = arith8 ? (nb == 32 ? 1 : 0) : (nb == 16 ? 2 : (nb == 8 ? 1 : 0));
-  } else {
-    h->current_dec = 0;
-  }
-  h->current_inter_idx = nb == 32 ? 3 : (nb == 16 ? 2 : (nb == 8 ? 1 : 0)); // interleaver_idx(), turbodecoder.c:134-148
+  HandleCfg cfg = {};
+  handle_cfg(h, in8, &cfg); // (srsran_tdec_init_manual refused the decoder types this fails for)
+  apply_cfg(h, cfg);
 
-  uint64_t key = ((uint64_t)K << 8) | ((uint64_t)nb << 1) | (arith8 ? 1u : 0u);
+  uint64_t key = ((uint64_t)K << 8) | ((uint64_t)cfg.nb << 1) | (cfg.arith8 ? 1u : 0u);
   auto     it  = c->dec.find(key);
   if (it == c->dec.end()) {
     srsran_hip_tdec_batch_t* b = nullptr;
-    int impl = arith8 ? (nb == 32 ? SRSRAN_TDEC_AVX8_WINDOW : SRSRAN_TDEC_SSE8_WINDOW)
-                      : (nb == 16 ? SRSRAN_TDEC_AVX_WINDOW : (nb == 8 ? SRSRAN_TDEC_SSE_WINDOW : SRSRAN_TDEC_GENERIC));
-    if (srsran_hip_tdec_batch_create(&b, K, 1, impl)) {
+    if (srsran_hip_tdec_batch_create(&b, K, 1, cfg.impl)) {
       fprintf(stderr, "[srsran_phy_hip] srsran_tdec: %s\n", get_error());
       return;
     }
@@ -1056,23 +1064,16 @@ static void tdec_handle_iterate(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
   // a run that went through the shared submission queue left no decoder state in this handle's private object: a caller that
   // resumes it with srsran_tdec_iteration gets the earlier half iterations re-run from its input first
   const uint32_t n_begin = c->dev_state_valid ? (uint32_t)h->n_iter : 0u;
-  const size_t   in_len  = sb_layout ? 3 * ((size_t)K + 32) + 12 : 3 * (size_t)K + 12;
+  const size_t   in_len  = cfg.in_len;
   if (n_begin == 0) {
     // The reference converts between LLR widths on the host when API and decoder differ (convert_8_to_16 /
     // convert_16_to_8, turbodecoder.c:443-453); here the kernel's extraction does it.  (The reference
     // converts only 3K+12 elements even for the longer sub-block layout; all of it is converted here.)
     memcpy(c->h_in, input, in_len * sizeof(ELEM));
-    if (sb_layout && in8 == arith8) {
-      // the reference writes the tail into the caller's buffer here (turbodecoder_iter.h:58-70,92-96)
-      for (uint32_t i = K; i < K + 3; i++) {
-        input[i]                = input[3 * (K + 32) + 2 * (i - K)];
-        input[K + 32 + i]       = input[3 * (K + 32) + 2 * (i - K) + 1];
-        input[2 * (K + 32) + i] = input[3 * (K + 32) + 6 + 2 * (i - K) + 1];
-      }
-    }
+    write_back_tail(input, K, cfg);
     PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_in, c->h_in, in_len * sizeof(ELEM), hipMemcpyHostToDevice, c->stream));
   }
-  if (tdec_batch_run_range(it->second, c->d_in, in8, (uint32_t)in_len, c->d_out, K / 8, 1, n_begin, n_end, sb_layout, false,
+  if (tdec_batch_run_range(it->second, c->d_in, in8, (uint32_t)in_len, c->d_out, K / 8, 1, n_begin, n_end, cfg.sb_layout, false,
                            c->stream)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_tdec: %s\n", get_error());
     return;
@@ -1098,29 +1099,24 @@ static bool tdec_run_all_queued(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
   // handles are often initialised on one thread and run on another: the queue's lanes (streams, staging buffers, engines) must be
   // created on the process's device even when this worker thread has not touched the device yet
   bind_thread();
-  int  nb     = 0;
-  bool arith8 = false;
-  if (impl_to_cfg(h->dec_type, in8, K, &nb, &arith8) || (nb && (K % nb || K / nb <= 40))) {
+  HandleCfg cfg;
+  if (handle_cfg(h, in8, &cfg) || (cfg.nb && (K % cfg.nb || K / cfg.nb <= 40))) {
     return false; // the private path reports the error
   }
-  const bool   auto_mode = h->dec_type == SRSRAN_TDEC_AUTO;
-  const int    sb_layout = (!h->force_not_sb && (arith8 || (auto_mode && nb > 0))) ? 1 : 0;
-  const size_t in_len    = sb_layout ? 3 * ((size_t)K + 32) + 12 : 3 * (size_t)K + 12;
+  const size_t in_len = cfg.in_len;
   char         key[96];
-  snprintf(key, sizeof(key), "tdec:d%d:K%u:nb%d:a%d:sb%d:e%d:it%u", current_device(), K, nb, arith8 ? 1 : 0, sb_layout, in8 ? 1 : 0, nit);
+  snprintf(key, sizeof(key), "tdec:d%d:K%u:nb%d:a%d:sb%d:e%d:it%u", current_device(), K, cfg.nb, cfg.arith8 ? 1 : 0, cfg.sb_layout, in8 ? 1 : 0, nit);
   std::shared_ptr<Coalescer> q = coalescer_for(key, [&]() -> Coalescer* {
-    const uint32_t cap  = 64;
-    const int      impl = arith8 ? (nb == 32 ? SRSRAN_TDEC_AVX8_WINDOW : SRSRAN_TDEC_SSE8_WINDOW)
-                                 : (nb == 16 ? SRSRAN_TDEC_AVX_WINDOW : (nb == 8 ? SRSRAN_TDEC_SSE_WINDOW : SRSRAN_TDEC_GENERIC));
+    const uint32_t cap = 64;
     const uint32_t in_stride  = (uint32_t)(Coalescer::stride_of(in_len * sizeof(ELEM)) / sizeof(ELEM));
     const uint32_t out_stride = (uint32_t)Coalescer::stride_of(K / 8);
     return new Coalescer(in_len * sizeof(ELEM), K / 8, cap, 4, [=](int) -> Coalescer::Engine {
       srsran_hip_tdec_batch_t* b = nullptr;
-      if (srsran_hip_tdec_batch_create(&b, K, cap, impl)) {
+      if (srsran_hip_tdec_batch_create(&b, K, cap, cfg.impl)) {
         return Coalescer::Engine();
       }
       return Coalescer::Engine{[=](const void* d_in, void* d_out, uint32_t n, uint64_t, hipStream_t st) {
-                                 return tdec_batch_run_range(b, d_in, in8, in_stride, static_cast<uint8_t*>(d_out), out_stride, n, 0, nit, sb_layout,
+                                 return tdec_batch_run_range(b, d_in, in8, in_stride, static_cast<uint8_t*>(d_out), out_stride, n, 0, nit, cfg.sb_layout,
                                                              false, st);
                                },
                                [=]() { srsran_hip_tdec_batch_free(b); }};
@@ -1129,64 +1125,50 @@ static bool tdec_run_all_queued(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
   if (!q) {
     return false;
   }
-  if (auto_mode) {
-    h->current_llr_type = arith8 ? SRSRAN_TDEC_8 : SRSRAN_TDEC_16;
-    h->current_dec      = arith8 ? (nb == 32 ? 1 : 0) : (nb == 16 ? 2 : (nb == 8 ? 1 : 0));
-  } else {
-    h->current_dec = 0;
-  }
-  h->current_inter_idx = nb == 32 ? 3 : (nb == 16 ? 2 : (nb == 8 ? 1 : 0));
+  apply_cfg(h, cfg);
   if (q->submit(input, output) != SRSRAN_SUCCESS) {
     fprintf(stderr, "[srsran_phy_hip] srsran_tdec_run_all: %s\n", get_error());
     return false;
   }
-  if (sb_layout && in8 == arith8) {
-    // the reference writes the tail into the caller's buffer (turbodecoder_iter.h:58-70,92-96)
-    for (uint32_t i = K; i < K + 3; i++) {
-      input[i]                = input[3 * (K + 32) + 2 * (i - K)];
-      input[K + 32 + i]       = input[3 * (K + 32) + 2 * (i - K) + 1];
-      input[2 * (K + 32) + i] = input[3 * (K + 32) + 6 + 2 * (i - K) + 1];
-    }
-  }
+  write_back_tail(input, K, cfg);
   h->n_iter          = (int)nit;
   c->dev_state_valid = false;
   return true;
 }
 
+template <typename ELEM>
+static void tdec_iteration(srsran_tdec_t* h, ELEM* input, uint8_t* output)
+{
+  if (h->current_cbidx >= 0) {
+    tdec_handle_iterate(h, input, output, (uint32_t)h->n_iter + 1);
+  }
+}
+template <typename ELEM>
+static int tdec_run_all(srsran_tdec_t* h, ELEM* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
+{
+  if (srsran_tdec_new_cb(h, long_cb)) {
+    return SRSRAN_ERROR;
+  }
+  if (tdec_run_all_queued(h, input, output, nof_iterations ? nof_iterations : 1)) {
+    return SRSRAN_SUCCESS;
+  }
+  tdec_handle_iterate(h, input, output, nof_iterations ? nof_iterations : 1);
+  return h->n_iter ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+}
+
 extern "C" void srsran_tdec_iteration(srsran_tdec_t* h, int16_t* input, uint8_t* output)
 {
-  if (h->current_cbidx >= 0) {
-    tdec_handle_iterate(h, input, output, (uint32_t)h->n_iter + 1);
-  }
+  tdec_iteration(h, input, output);
 }
-
-extern "C" int srsran_tdec_run_all(srsran_tdec_t* h, int16_t* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
-{
-  if (srsran_tdec_new_cb(h, long_cb)) {
-    return SRSRAN_ERROR;
-  }
-  if (tdec_run_all_queued(h, input, output, nof_iterations ? nof_iterations : 1)) {
-    return SRSRAN_SUCCESS;
-  }
-  tdec_handle_iterate(h, input, output, nof_iterations ? nof_iterations : 1);
-  return h->n_iter ? SRSRAN_SUCCESS : SRSRAN_ERROR;
-}
-
 extern "C" void srsran_tdec_iteration_8bit(srsran_tdec_t* h, int8_t* input, uint8_t* output)
 {
-  if (h->current_cbidx >= 0) {
-    tdec_handle_iterate(h, input, output, (uint32_t)h->n_iter + 1);
-  }
+  tdec_iteration(h, input, output);
 }
-
+extern "C" int srsran_tdec_run_all(srsran_tdec_t* h, int16_t* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
+{
+  return tdec_run_all(h, input, output, nof_iterations, long_cb);
+}
 extern "C" int srsran_tdec_run_all_8bit(srsran_tdec_t* h, int8_t* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
 {
-  if (srsran_tdec_new_cb(h, long_cb)) {
-    return SRSRAN_ERROR;
-  }
-  if (tdec_run_all_queued(h, input, output, nof_iterations ? nof_iterations : 1)) {
-    return SRSRAN_SUCCESS;
-  }
-  tdec_handle_iterate(h, input, output, nof_iterations ? nof_iterations : 1);
-  return h->n_iter ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+  return tdec_run_all(h, input, output, nof_iterations, long_cb);
 }

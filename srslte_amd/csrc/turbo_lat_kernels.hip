@@ -1031,7 +1031,7 @@ hipError_t launch_lat2(bool arith8, const WinParams& p, hipStream_t stream)
 {
   const bool   es  = p.crc_poly || p.desc;
   const size_t lds = lat2_lds_bytes(p.K);
-  if (lds > 120 * 1024 || p.K < 16 * (TD_WIN_OVERLAP + 8)) {
+  if (!lat2_can_run(p.K)) {
     return hipErrorInvalidValue;
   }
   if (arith8) {

@@ -62,8 +62,11 @@ def test_every_block_size_once(hiplib):
 
 
 @pytest.mark.parametrize("impl_g,impl_o,K", [("GENERIC", O.ORC_TDEC_GENERIC, 1024), ("SSE_WINDOW", O.ORC_TDEC_SSE_WINDOW, 6144),
-                                              ("AVX_WINDOW", O.ORC_TDEC_AVX_WINDOW, 1024), ("SSE_WINDOW", O.ORC_TDEC_SSE_WINDOW, 328)])
+                                              ("AVX_WINDOW", O.ORC_TDEC_AVX_WINDOW, 1024), ("SSE_WINDOW", O.ORC_TDEC_SSE_WINDOW, 328),
+                                              ("AVX_WINDOW", O.ORC_TDEC_AVX_WINDOW, 656), ("AVX_WINDOW", O.ORC_TDEC_AVX_WINDOW, 752)])
 def test_manual_implementations(hiplib, impl_g, impl_o, K):
+    """K = 656 and 752: the smallest and the largest block 16 sub-blocks take (K / 16 > 40) that is too short for the two-wave form of the latency
+    kernel (K >= 768): the one-wave form runs them in both latency modes of this module"""
     import srslte_amd as S
     from srslte_amd import capi
 
@@ -154,7 +157,8 @@ def test_8bit_every_block_size(hiplib):
     assert not bad, bad[:10]
 
 
-@pytest.mark.parametrize("impl,K", [("SSE8_WINDOW", 816), ("SSE8_WINDOW", 6144), ("AVX8_WINDOW", 1344), ("AVX8_WINDOW", 6144)])
+@pytest.mark.parametrize("impl,K", [("SSE8_WINDOW", 816), ("SSE8_WINDOW", 6144), ("AVX8_WINDOW", 1344), ("AVX8_WINDOW", 6144),
+                                    ("SSE8_WINDOW", 656), ("SSE8_WINDOW", 752)])
 def test_8bit_manual_implementations(hiplib, impl, K):
     import srslte_amd as S
     from srslte_amd import capi
@@ -285,6 +289,18 @@ def test_handle_api_matches_batch(hiplib):
     assert lib.srsran_tdec_run_all(C.byref(h2), O.P(sb), O.P(out), 8, K) == 0
     assert np.array_equal(out, O.turbo_decode(llr, 8, K)[0])
     lib.srsran_tdec_free(C.byref(h2))
+    # 16 sub-blocks chosen by hand on a block too short for the two-wave latency kernel, resumed half iteration by half iteration
+    h3 = capi.Tdec()
+    assert lib.srsran_tdec_init_manual(C.byref(h3), 6144, capi.TDEC_AVX_WINDOW) == 0
+    K = 752
+    msgs, llr = O.turbo_llrs(K, 1, -1.0, seed=K + 3)
+    assert lib.srsran_tdec_new_cb(C.byref(h3), K) == 0
+    inp = llr[0].copy()
+    for nit in range(1, 4):
+        out = np.zeros(K // 8, np.uint8)
+        lib.srsran_tdec_iteration(C.byref(h3), O.P(inp), O.P(out))
+        assert np.array_equal(out, O.turbo_decode(llr[:1], nit, K, O.ORC_TDEC_AVX_WINDOW)[0]), (K, nit)
+    lib.srsran_tdec_free(C.byref(h3))
 
 
 def test_full_size_roundtrip_property(hiplib):

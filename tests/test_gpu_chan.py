@@ -7,7 +7,18 @@ returns is held to the oracle's decode_tb (orc_sch_decode_tb: verdict, payload b
 run on the soft bits the SAME stages produce one call at a time through the reference-named entry points (srsran_predecoding_single ->
 srsran_dft_precoding -> srsran_demod_soft_demodulate_{s,b} -> srsran_sequence_pusch_apply_{s,c}; each of them is held to the oracle in
 test_gpu_modem.py / test_gpu_dft.py) and the oracle's channel de-interleaver.  Transmit side: bit-exact against the oracle's chain, which
-tests/test_oracle_golden.py pins to the reference's modulator output."""
+tests/test_oracle_golden.py pins to the reference's modulator output.
+
+Which test holds what to what:
+  test_pusch_grant_in_one_call, test_pdsch_codeword_in_one_call   verdict, payload, iteration average (PUSCH: EPRE; PDSCH: the _dbg call's symbols and soft bits) to the
+                                                                  oracle, on grants that DECODE: a data soft bit in the wrong slot can decode to the same payload
+  test_pusch_grant_harq_and_failure                               the rows of failed blocks to the oracle over three transmissions, at one shape (20 PRB, 16-QAM)
+  test_pusch_grants_of_a_tti_in_one_call, *_from_worker_threads   the _multi call to the SINGLE call, not to the oracle
+  test_*_encode_*, test_modulator_*                               the transmit side bit for bit to the oracle's chain / the reference's tables
+  tests/test_gpu_chan_softbits.py                                 the PLACEMENT of every transport-block soft bit to the oracle: grants of random bits, where no block
+                                                                  decodes and all rows come back -- every modulation, store width and column count, small and
+                                                                  tile-crossing allocations, with control information, single and _multi calls, PDSCH
+_pusch_signal = a code word's bits + _pusch_grid (bits -> grid), which that module feeds with random bits."""
 import ctypes as C
 import os
 
@@ -46,11 +57,21 @@ def _pusch_signal(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, tbs, rv,
     """the subframe grid a UE's PUSCH leaves at the eNB (pusch.c:258-350 srsran_pusch_encode without UCI) through a channel: returns (grid, ce, seed)"""
     Qm = O.QM[mod]
     nsymb = 2 * (cp_nsymb - 1) - (1 if shortened else 0)
-    nsc = 12 * L_prb
-    nof_re = nsymb * nsc
+    nof_re = nsymb * 12 * L_prb
     g = _oracle_tx_bits(tbs, Qm, nof_re * Qm, rv, payload_bits)
     lut = O.ulsch_interleaver_lut(nof_re, Qm, nsymb)
     q = g[lut]  # q[position] = g[lut[position]] (sch.c:995-1018: the de-interleaver reads q through the same table)
+    return _pusch_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, q, rnti, tti, cell_id, snr_db)
+
+
+def _pusch_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, q, rnti, tti, cell_id, snr_db):
+    """the "bits -> grid" half of the signal path: the interleaved bits q (uint8 [nof_re Qm], a code word or anything else) -> scrambling -> constellation ->
+    transform precoding -> the allocation's REs of the subframe grid, a frequency-selective channel with per-symbol phase and noise: (grid, ce, seed)"""
+    Qm = O.QM[mod]
+    nsymb = 2 * (cp_nsymb - 1) - (1 if shortened else 0)
+    nsc = 12 * L_prb
+    nof_re = nsymb * nsc
+    assert q.size == nof_re * Qm
     seed = O.pusch_seed(rnti, 2 * (tti % 10), cell_id)
     d = O.modulate_bytes(mod, np.packbits(q), nof_re * Qm, seed=seed, scramble=True)
     z = (np.fft.fft(d.reshape(nsymb, nsc).astype(np.complex128), axis=1) / np.sqrt(nsc)).astype(np.complex64)  # srsran_dft_precoding, tx: forward, normalised

@@ -77,10 +77,16 @@ def _uci_signal(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, tbs, rv, r
     """the grid a UE's PUSCH with control information leaves at the eNB: (grid, ce, seed)"""
     Qm = O.QM[mod]
     cols = 2 * (cp_nsymb - 1) - (1 if shortened else 0)
-    rows = 12 * L_prb
-    H = rows * cols
-    G = H - Qr - Qc
+    G = cols * 12 * L_prb - Qr - Qc
     e = T._oracle_tx_bits(tbs, Qm, G * Qm, rv, payload_bits)
+    return _uci_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, e, rnti, tti, cell_id, snr_db, Qa, Qr, Qc)
+
+
+def _uci_mux(rng, e, H, cols, Qm, Qa, Qr, Qc):
+    """TS 36.212 5.2.2.8 on bits: e (uint8 [(H - Qr - Qc) Qm], the transport block's part of the data stream -- a code word or anything else) behind a random
+    CQI code word, written row by row around the RI positions, random RI bits, the ACK positions overwritten with random bits: q (uint8 [H Qm])"""
+    rows = H // cols
+    assert e.size == (H - Qr - Qc) * Qm
     g = np.concatenate([rng.integers(0, 2, Qc * Qm).astype(np.uint8), e])
     rip = [p for n in range(Qr) for p in _positions(n, Qm, H, cols, RI_COLS)]
     ackp = [p for n in range(Qa) for p in _positions(n, Qm, H, cols, ACK_COLS)]
@@ -95,30 +101,14 @@ def _uci_signal(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, tbs, rv, r
     q[order] = g
     q[rip] = rng.integers(0, 2, len(rip))
     q[ackp] = rng.integers(0, 2, len(ackp))
-    seed = O.pusch_seed(rnti, 2 * (tti % 10), cell_id)
-    d = O.modulate_bytes(mod, np.packbits(q), H * Qm, seed=seed, scramble=True)
-    z = (np.fft.fft(d.reshape(cols, rows).astype(np.complex128), axis=1) / np.sqrt(rows)).astype(np.complex64)
-    grid = np.zeros((2 * cp_nsymb, 12 * nof_prb), np.complex64)
-    ce = np.zeros_like(grid)
-    kk = np.arange(12 * nof_prb)
-    h = (0.9 + 0.2 * np.exp(2j * np.pi * kk / 97.0) + 0.1 * np.exp(-2j * np.pi * kk / 31.0))
-    L_ref = 3 if cp_nsymb == 7 else 2
-    row = 0
-    for slot in range(2):
-        nl = cp_nsymb - (1 if (shortened and slot == 1) else 0)
-        for l in range(nl):
-            sym = l + slot * cp_nsymb
-            hs = (h * np.exp(1j * 0.03 * sym)).astype(np.complex64)
-            ce[sym] = hs
-            if l == L_ref:
-                continue
-            a = 12 * n_prb[slot]
-            grid[sym, a:a + rows] = z[row] * hs[a:a + rows]
-            row += 1
-    assert row == cols
-    sigma = 10 ** (-snr_db / 20) / np.sqrt(2)
-    grid = (grid + sigma * (rng.standard_normal(grid.shape) + 1j * rng.standard_normal(grid.shape))).astype(np.complex64)
-    return np.ascontiguousarray(grid.reshape(-1)), np.ascontiguousarray(ce.reshape(-1)), seed
+    return q
+
+
+def _uci_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, e, rnti, tti, cell_id, snr_db, Qa, Qr, Qc):
+    """the "bits -> grid" half: e multiplexed with control information (_uci_mux), then the signal path of tests/test_gpu_chan.py: (grid, ce, seed)"""
+    cols = 2 * (cp_nsymb - 1) - (1 if shortened else 0)
+    q = _uci_mux(rng, e, cols * 12 * L_prb, cols, O.QM[mod], Qa, Qr, Qc)
+    return T._pusch_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, q, rnti, tti, cell_id, snr_db)
 
 
 class _UciOut:

@@ -29,6 +29,9 @@ struct WinParams {
   uint32_t        K;
   uint32_t        n_begin; // first half iteration of this launch (0: also extract the input)
   uint32_t        n_end;   // one past the last half iteration; the hard decision is taken for n_iter = n_end
+  // this launch completes the run (n_begin = 0, nobody resumes it, no dec_llr): the window decoder's last half iteration then files
+  // one sign bit per value for the hard decision instead of the int16 rows, and no a-priori array for a half iteration that never runs
+  int             final_run;
   int             n_cb;
   int             sb_layout;
   int             in_is8;
@@ -85,6 +88,13 @@ static inline size_t gen_ws_shorts(uint32_t K)
   return (size_t)15 * (K + 4) * 64;
 }
 
+// final_run keeps the filed sign bits (16 bytes per trellis step and wave) in the kernel's 16 KB beta buffer, behind the byte image that
+// ragged sub-blocks (not a multiple of 8 steps) are cut from.  Every LTE block size fits; a size that does not keeps the int16 rows
+static inline bool win_final_fits(uint32_t K, int nb)
+{
+  const uint32_t long_sb = K / nb, nblk = (long_sb + 7) / 8;
+  return 16u * long_sb + ((long_sb & 7u) ? 128u * (nblk + 1) : 0u) <= 16384u;
+}
 hipError_t launch_win(int nb, bool arith8, const WinParams& p, hipStream_t stream);
 // latency kernel (turbo_lat_kernels.hip): one code block per wave, states across lanes; same WinParams with its own workspace layout
 // (lat_ws_dwords per code block).  Exists for every window decoder: 16 / 8 sub-blocks (16-bit), 32 / 16 sub-blocks (8-bit; 32 sub-blocks = two waves per block).

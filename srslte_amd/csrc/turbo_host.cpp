@@ -165,6 +165,7 @@ struct srsran_hip_tdec_batch {
   uint32_t  lat_cap       = 0;
   bool      state_in_lat  = false; // the decoder state of the last launch lives in the latency kernel's workspace
   bool      state_in_gen_lat = false; // scalar decoder: ... in the latency kernel's per-block layout of d_ws_gen
+  bool      state_final   = false; // the last launch completed a run (WinParams::final_run): it left no state a later launch could resume
   // workspace taken from a caller's arena at every launch: the object then owns none (d_ws, d_ws_gen and d_ws_lat stay null)
   turbo::WsArena* arena = nullptr;
   // (the tables are borrowed from the process-wide cache, never freed by the object)
@@ -412,19 +413,21 @@ static turbo::GenParams gen_params(const srsran_hip_tdec_batch* h, const Workspa
 }
 
 // the launch itself, and the note of where it leaves the decoder state (what a resumed run goes by)
-static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::WinParams& p, hipStream_t stream)
+static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::WinParams& p, hipStream_t stream, bool final_run = false)
 {
   PHY_HIP_CHECK(r == Route::Lat2  ? turbo::launch_lat2(h->arith8, p, stream)
                 : r == Route::Lat ? turbo::launch_lat(h->nb, h->arith8, p, stream)
                                   : turbo::launch_win(h->nb, h->arith8, p, stream),
                 SRSRAN_ERROR);
   h->state_in_lat = r != Route::Win;
+  h->state_final  = final_run;
   return SRSRAN_SUCCESS;
 }
-static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::GenParams& p, hipStream_t stream)
+static int launch(srsran_hip_tdec_batch* h, Route r, const turbo::GenParams& p, hipStream_t stream, bool final_run = false)
 {
   PHY_HIP_CHECK(r == Route::GenLat ? turbo::launch_gen_lat(p, stream) : turbo::launch_gen(p, stream), SRSRAN_ERROR);
   h->state_in_gen_lat = r == Route::GenLat;
+  h->state_final      = final_run;
   return SRSRAN_SUCCESS;
 }
 
@@ -592,10 +595,12 @@ extern "C" void srsran_hip_tdec_batch_free(srsran_hip_tdec_batch_t* h)
   delete h;
 }
 
-// run half iterations [n_begin, n_end) and take the hard decision for n_iter = n_end
+// run half iterations [n_begin, n_end) and take the hard decision for n_iter = n_end.  final_run: the caller has no way to resume this
+// run, so its last half iteration files only what the hard decision needs (WinParams::final_run); the object remembers that and
+// refuses to resume.  The decision LLRs (want_llr) need the full rows: they turn it off.
 static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input, bool in_is8, uint32_t in_stride,
                                 uint8_t* d_output, uint32_t out_stride, uint32_t n_cb, uint32_t n_begin, uint32_t n_end,
-                                int sb_layout, bool want_llr, hipStream_t stream)
+                                int sb_layout, bool want_llr, bool final_run, hipStream_t stream)
 {
   TraceRange trace_("srsran_hip_tdec_batch_run");
   if (h) {
@@ -616,6 +621,11 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input,
     set_error("tdec batch: a decoder on a shared workspace runs whole transport-block launches only");
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
+  if (n_begin > 0 && h->state_final) {
+    set_error("tdec batch: the last launch completed its run and kept no state to resume from (n_begin=%u)", n_begin);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  final_run = final_run && n_begin == 0 && !want_llr;
   const uint32_t need_in = sb_layout ? 3 * (h->K + 32) + 12 : 3 * h->K + 12;
   if ((n_cb > 1 && (in_stride < need_in || out_stride < h->K / 8))) {
     set_error("tdec batch: strides too small");
@@ -637,12 +647,14 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input,
   if (!h->nb) {
     turbo::GenParams p = gen_params(h, ws, d_input, in_is8, d_output, n_cb, n_begin, n_end);
     mine(p);
-    return launch(h, r, p, stream);
+    return launch(h, r, p, stream, final_run);
   }
   turbo::WinParams p = win_params(h, ws, d_input, in_is8, d_output, n_cb, n_begin, n_end, sb_layout);
   mine(p);
+  p.final_run = final_run && turbo::win_final_fits(h->K, h->nb) ? 1 : 0;
   if (knob(KNOB_TDEC_EXTRACT_ONLY) > 0) {
-    p.n_end = 0; // development aid: input extraction + decision only
+    p.n_end     = 0; // development aid: input extraction + decision only
+    p.final_run = 0;
   }
   // launch-shape alternatives kept for measurement (profiles/r02_turbo_variants.txt); the product path is variant 0
   p.variant = knob(KNOB_TDEC_VARIANT) > 0 ? knob(KNOB_TDEC_VARIANT) : 0;
@@ -660,7 +672,7 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input,
     p.max_resident = (uint32_t)h->cus * 8u; // 4 SIMDs x 2 waves
     p.unit_counter = h->d_unit_counter;
   }
-  return launch(h, r, p, stream);
+  return launch(h, r, p, stream, final_run);
 }
 
 extern "C" int srsran_hip_tdec_batch_run(srsran_hip_tdec_batch_t* h, const int16_t* d_input, uint32_t in_stride,
@@ -669,7 +681,7 @@ extern "C" int srsran_hip_tdec_batch_run(srsran_hip_tdec_batch_t* h, const int16
 {
   // turbodecoder.c:542-544 is a do/while: at least one half iteration runs
   uint32_t nit = nof_iterations ? nof_iterations : 1;
-  return tdec_batch_run_range(h, d_input, false, in_stride, d_output, out_stride, n_cb, 0, nit, sb_layout, false, (hipStream_t)stream);
+  return tdec_batch_run_range(h, d_input, false, in_stride, d_output, out_stride, n_cb, 0, nit, sb_layout, false, true, (hipStream_t)stream);
 }
 
 extern "C" int srsran_hip_tdec_batch_run_8bit(srsran_hip_tdec_batch_t* h, const int8_t* d_input, uint32_t in_stride,
@@ -677,7 +689,7 @@ extern "C" int srsran_hip_tdec_batch_run_8bit(srsran_hip_tdec_batch_t* h, const 
                                               uint32_t nof_iterations, int sb_layout, void* stream)
 {
   uint32_t nit = nof_iterations ? nof_iterations : 1;
-  return tdec_batch_run_range(h, d_input, true, in_stride, d_output, out_stride, n_cb, 0, nit, sb_layout, false, (hipStream_t)stream);
+  return tdec_batch_run_range(h, d_input, true, in_stride, d_output, out_stride, n_cb, 0, nit, sb_layout, false, true, (hipStream_t)stream);
 }
 
 extern "C" int srsran_hip_tdec_batch_last_llr(srsran_hip_tdec_batch_t* h, int16_t* d_llr, uint32_t n_cb, void* stream)
@@ -699,7 +711,7 @@ extern "C" SRSRAN_API int srsran_hip_tdec_batch_run_dbg(srsran_hip_tdec_batch_t*
                                                         void* stream)
 {
   return tdec_batch_run_range(h, d_input, false, in_stride, d_output, out_stride, n_cb, n_begin, n_end, sb_layout, true,
-                              (hipStream_t)stream);
+                              false, (hipStream_t)stream);
 }
 
 extern "C" SRSRAN_API int srsran_hip_tdec_batch_run_dbg_8bit(srsran_hip_tdec_batch_t* h, const int8_t* d_input,
@@ -708,7 +720,7 @@ extern "C" SRSRAN_API int srsran_hip_tdec_batch_run_dbg_8bit(srsran_hip_tdec_bat
                                                              void* stream)
 {
   return tdec_batch_run_range(h, d_input, true, in_stride, d_output, out_stride, n_cb, n_begin, n_end, sb_layout, true,
-                              (hipStream_t)stream);
+                              false, (hipStream_t)stream);
 }
 
 // Transport-block decoding (sch_host.cpp): all half iterations up to max_iterations with the per-block CRC early
@@ -1074,7 +1086,7 @@ static void tdec_handle_iterate(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
     PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_in, c->h_in, in_len * sizeof(ELEM), hipMemcpyHostToDevice, c->stream));
   }
   if (tdec_batch_run_range(it->second, c->d_in, in8, (uint32_t)in_len, c->d_out, K / 8, 1, n_begin, n_end, cfg.sb_layout, false,
-                           c->stream)) {
+                           false, c->stream)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_tdec: %s\n", get_error());
     return;
   }
@@ -1117,7 +1129,7 @@ static bool tdec_run_all_queued(srsran_tdec_t* h, ELEM* input, uint8_t* output, 
       }
       return Coalescer::Engine{[=](const void* d_in, void* d_out, uint32_t n, uint64_t, hipStream_t st) {
                                  return tdec_batch_run_range(b, d_in, in8, in_stride, static_cast<uint8_t*>(d_out), out_stride, n, 0, nit, cfg.sb_layout,
-                                                             false, st);
+                                                             false, false, st);
                                },
                                [=]() { srsran_hip_tdec_batch_free(b); }};
     });

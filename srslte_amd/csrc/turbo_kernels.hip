@@ -546,8 +546,9 @@ __device__ __forceinline__ void extract_input_sb16(const short* in, uint32_t K, 
 }
 
 // One unit of work: the CPW = 64 / LPC code blocks wb * CPW ... of the batch, decoded by one wave in the workspace slab `slab`.
-// Bl: re-derived backward metrics of the current 8-step block (8 steps x 8 states x int16x2 per lane); Tr: staging image of 8
-// exchanged rows (rows_to_lane).
+// Bl: re-derived backward metrics of the current 8-step block (8 steps x 8 states x int16x2 per lane) -- and, while the forward main pass
+// does not run, the operands the forward warm-up hands to the backward pass, the staging image of the input extraction and the
+// hard decision's byte / bit images; Tr: staging image of 8 exchanged rows (rows_to_lane).
 // ES: early-stop / descriptor mode (transport-block decoding, sch_host.cpp).  A separate instantiation: the CRC state and
 // the per-block descriptors must not cost the fixed-iteration kernel registers (it runs at 2 waves per SIMD).
 template <int LPC, class AR, bool ES>
@@ -641,6 +642,9 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   }
 #define M_OWN (ES ? m_own_v : ~0u)
 #define M_ROW (ES ? m_row_v : ~0u)
+  // A launch that completes the run (WinParams::final_run) files, in its last half iteration, one sign bit per value instead: row k
+  // of the wave is 16 bytes at D + 4 k dwords, the 64-bit masks (one bit per lane) of the low and of the high sub-block.
+  const bool bit_rows = !ES && p.final_run && !p.dec_llr && p.n_end > p.n_begin;
   auto decide = [&](bool write, bool final_try) -> uint32_t {
     short*         o16   = (p.dec_llr && live && write) ? p.dec_llr + (size_t)cb * K : nullptr;
     const bool     whole = (long_sb & 7) == 0;
@@ -657,17 +661,38 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       sbuf[(2 * pl) * sbs + nblk]     = 0;
       sbuf[(2 * pl + 1) * sbs + nblk] = 0;
     }
+    // the filed sign bits: the whole image of the wave (16 bytes x long_sb) comes into the beta buffer with coalesced 16-byte loads,
+    // behind the byte image of ragged sub-blocks (turbo_device.h: win_final_fits); every lane then picks its own bit of both masks
+    uint4* img = &Bl[0][0][0] + (whole ? 0u : (CPW * NB * sbs + 15u) / 16u);
+    if (bit_rows) {
+      for (uint32_t k = lane; k < long_sb; k += 64) {
+        img[k] = ws_load16<NT>(D + (size_t)k * 4);
+      }
+      __syncthreads();
+    }
     {
       const bool wide = whole && ((bps & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 3) == 0) && out_bytes == K / 8;
       uint32_t   w0 = 0, w1 = 0;
       uint32_t   t[8], tn[8];
-      issue_rows_raw<AR::kIs8, NT>(D, 0, lane, t);
+      if (!bit_rows) {
+        issue_rows_raw<AR::kIs8, NT>(D, 0, lane, t);
+      }
       for (uint32_t b = 0; b < nblk; b++) {
-        if (b + 1 < nblk) {
+        if (!bit_rows && b + 1 < nblk) {
           issue_rows_raw<AR::kIs8, NT>(D, (b + 1) & M_ROW, lane, tn);
         }
         uint32_t r[8];
-        rows_to_lane_v<AR::kIs8>(Tr, lane, t, r);
+        if (bit_rows) {
+#pragma unroll
+          for (int j = 0; j < 8; j++) {
+            const uint32_t k = b * 8 + j < long_sb ? b * 8 + j : long_sb - 1;
+            const uint4    m = img[k];
+            // (a positive int16 in each half stands for the bit: the code below only looks at the signs)
+            r[j] = (uint32_t)(((((uint64_t)m.y << 32) | m.x) >> lane) & 1u) | ((uint32_t)(((((uint64_t)m.w << 32) | m.z) >> lane) & 1u) << 16);
+          }
+        } else {
+          rows_to_lane_v<AR::kIs8>(Tr, lane, t, r);
+        }
         uint32_t b0 = 0, b1 = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -708,9 +733,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
             }
           }
         }
+        if (!bit_rows) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          t[j] = tn[j];
+          for (int j = 0; j < 8; j++) {
+            t[j] = tn[j];
+          }
         }
       }
     }
@@ -834,6 +861,55 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     };
     Ops cur, nxt, nx2; // the two main passes keep TWO blocks in flight: HBM latency under load exceeds one block of compute
 
+    // ================= forward warm-up (turbodecoder_win.h:684-750): the last 40 steps of every sub-block, all states unknown.
+    // It needs nothing the backward recursion produces and runs FIRST: the backward main pass starts with the very blocks it
+    // ends with, so the operands (x: systematic + a-priori, already summed; y: parity) of its last four blocks -- whole blocks,
+    // also where the window starts inside one or the last one is ragged -- stay in this lane's slots of the beta buffer, which is
+    // idle until the forward main pass, and are not fetched from HBM a second time.  fw[]: the start metrics the main pass takes over.
+    s2 fw[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      fw[i] = splat(-AR::kInf);
+    }
+    {
+      const uint32_t w0 = long_sb - TD_WIN_OVERLAP;
+      const uint32_t bl = nblk - 1;
+      issue(w0 >> 3, cur);
+      for (uint32_t b = w0 >> 3; b <= bl; b++) {
+        issue(b < bl ? b + 1 : TD_WIN_OVERLAP / 8 - 1, nxt); // after the warm-up the backward warm-up starts at the end of the head window
+        s2 xs[8], ys[8], ap[8];
+        prep(cur, xs, ys, ap);
+        if (b + 4 > bl) {
+          const uint32_t s = b + 3 - bl;
+          Bl[2 * s][0][lane]     = make_uint4(to_u(xs[0]), to_u(xs[1]), to_u(xs[2]), to_u(xs[3]));
+          Bl[2 * s][1][lane]     = make_uint4(to_u(xs[4]), to_u(xs[5]), to_u(xs[6]), to_u(xs[7]));
+          Bl[2 * s + 1][0][lane] = make_uint4(to_u(ys[0]), to_u(ys[1]), to_u(ys[2]), to_u(ys[3]));
+          Bl[2 * s + 1][1][lane] = make_uint4(to_u(ys[4]), to_u(ys[5]), to_u(ys[6]), to_u(ys[7]));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          uint32_t k = b * 8 + j;
+          if (k >= w0 && k < long_sb) {
+            alpha_step<AR, false>(fw, fw, xs[j], ys[j]);
+            uint32_t kk = k - w0;
+            if (AR::norm_at(kk)) {
+              AR::normalize(fw);
+            }
+          }
+        }
+        cur = nxt;
+      }
+    }
+    // hand every estimate to the next sub-block; the first one starts in state 0
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      uint32_t u   = to_u(fw[i]);
+      uint32_t prv = __shfl_up(u, 1, LPC);
+      uint32_t lo  = (pl == 0) ? (uint32_t)(uint16_t)(short)(i ? -AR::kInf : 0) : (prv >> 16);
+      uint32_t hi  = u & 0xffffu;
+      fw[i]        = from_u(lo | (hi << 16));
+    }
+
     s2 o[8];
     // ================= backward recursion (turbodecoder_win.h:551-681)
 #pragma unroll
@@ -841,9 +917,10 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       o[i] = splat(-AR::kInf);
     }
     // pass 0: 40 steps on the head of every sub-block, all states unknown
-    issue(TD_WIN_OVERLAP / 8 - 1, cur);
     for (int b = TD_WIN_OVERLAP / 8 - 1; b >= 0; b--) {
-      issue(b > 0 ? b - 1 : nblk - 1, nxt); // after the warm-up, pass 1 starts at the last block
+      if (b > 0) {
+        issue(b - 1, nxt); // (pass 1 starts with the four blocks the forward warm-up left in the beta buffer)
+      }
       s2 xs[8], ys[8], ap[8];
       prep(cur, xs, ys, ap);
 #pragma unroll
@@ -875,16 +952,24 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
       store_block_v<AR::kIs8>(CK, (nblk & M_OWN) * 64 + lane, ck);
     }
-    // pass 1: whole sub-block, keep a check-point at every block boundary
-    if (nblk > 1) {
-      issue(nblk - 2, nxt);
-    }
+    // pass 1: whole sub-block, keep a check-point at every block boundary.  Blocks nblk-1 ... nblk-4 come from the beta buffer; the first
+    // one fetched from HBM is nblk-5 (a sub-block has more than 40 steps: nblk >= 6), requested two blocks ahead like every other
     for (int b = (int)nblk - 1; b >= 0; b--) {
-      if (b > 1) {
+      const bool ahead = b + 3 <= (int)nblk; // block b - 2 is one of those
+      if (b > 1 && ahead) {
         issue(b - 2, nx2);
       }
       s2 xs[8], ys[8], ap[8];
-      prep(cur, xs, ys, ap);
+      if (b + 4 >= (int)nblk) {
+        const uint32_t s  = (uint32_t)b + 4 - nblk;
+        const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
+        xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
+        xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
+        ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
+        ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
+      } else {
+        prep(cur, xs, ys, ap);
+      }
 #pragma unroll
       for (int j = 7; j >= 0; j--) {
         uint32_t k = b * 8 + j;
@@ -903,46 +988,17 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           }
         }
       }
-      cur = nxt;
-      nxt = nx2;
+      if (b > 0 && ahead) { // (block 0 stays in `cur`: the forward main pass starts with it)
+        cur = nxt;
+        nxt = nx2;
+      }
     }
     __syncthreads(); // orders this lane's check-point stores before its loads below
 
-    // ================= forward recursion + LLR (turbodecoder_win.h:684-832)
+    // ================= forward recursion + LLR (turbodecoder_win.h:751-832), from the warm-up's metrics
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-      o[i] = splat(-AR::kInf);
-    }
-    {
-      const uint32_t w0 = long_sb - TD_WIN_OVERLAP;
-      const uint32_t bl = (long_sb - 1) >> 3;
-      issue(w0 >> 3, cur);
-      for (uint32_t b = w0 >> 3; b <= bl; b++) {
-        issue(b < bl ? b + 1 : 0, nxt); // after the warm-up the main pass starts at block 0
-        s2 xs[8], ys[8], ap[8];
-        prep(cur, xs, ys, ap);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          uint32_t k = b * 8 + j;
-          if (k >= w0 && k < long_sb) {
-            alpha_step<AR, false>(o, o, xs[j], ys[j]);
-            uint32_t kk = k - w0;
-            if (AR::norm_at(kk)) {
-              AR::normalize(o);
-            }
-          }
-        }
-        cur = nxt;
-      }
-    }
-    // hand every estimate to the next sub-block; the first one starts in state 0
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      uint32_t u   = to_u(o[i]);
-      uint32_t prv = __shfl_up(u, 1, LPC);
-      uint32_t lo  = (pl == 0) ? (uint32_t)(uint16_t)(short)(i ? -AR::kInf : 0) : (prv >> 16);
-      uint32_t hi  = u & 0xffffu;
-      o[i]         = from_u(lo | (hi << 16));
+      o[i] = fw[i];
     }
 
     const uint32_t* lut = dec1 ? p.deint : p.inter; // per (step, destination lane): row | source sub-blocks
@@ -955,6 +1011,8 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // The raw SISO output is only needed by the hard decision: the LAST half iteration of a launch files it in D.
     const bool fuse = dec1 && n >= 2;
     const bool last = (n + 1 == p.n_end) || crc_poly; // with early stop every half iteration may be the last
+    // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
+    const bool fin  = bit_rows && n + 1 == p.n_end;
 
     uint32_t ck[8], tr[8], ckn[8], trn[8];
     load_block_raw<AR::kIs8, NT>(CK, (1u & M_OWN) * 64 + lane, ck);
@@ -1026,6 +1084,16 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       for (int j = 0; j < 8; j++) {
         if (j < len) {
           const uint32_t row = tr[j] & 0xffffu & M_OWN;
+          if (fin) {
+            // the values tdec_decision_byte reads (below), reduced to "> 0": one 16-byte row per step, stored by one lane
+            const s2       v  = from_u(dec1 ? rawv[j] : permute_pair<LPC>(rawv[j], tr[j] >> 16));
+            const uint64_t mx = __ballot(v.x > 0), my = __ballot(v.y > 0);
+            if (lane == 0) {
+              *reinterpret_cast<uint4*>(D + (size_t)(dec1 ? b * 8 + j : row) * 4) =
+                  make_uint4((uint32_t)mx, (uint32_t)(mx >> 32), (uint32_t)my, (uint32_t)(my >> 32));
+            }
+            continue;
+          }
           store_row<AR::kIs8>(dst, row, lane, permute_pair<LPC>(outv[j], tr[j] >> 16));
           if (last) {
             // what tdec_decision_byte reads (turbodecoder.c:370-378), in natural order: ext1 after decoder 1,

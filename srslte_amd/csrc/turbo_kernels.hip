@@ -20,6 +20,8 @@
 //     bytes.
 //   * extrinsic exchange (turbodecoder_iter.h:104-128) is fused into the forward pass: a-priori
 //     subtraction on load, QPP scatter on store.
+#include <type_traits>
+
 #include "hip_common.h"
 #include "turbo_arith.h"
 #include "turbo_device.h"
@@ -551,7 +553,8 @@ __device__ __forceinline__ void extract_input_sb16(const short* in, uint32_t K, 
 // hard decision's byte / bit images; Tr: staging image of 8 exchanged rows (rows_to_lane).
 // ES: early-stop / descriptor mode (transport-block decoding, sch_host.cpp).  A separate instantiation: the CRC state and
 // the per-block descriptors must not cost the fixed-iteration kernel registers (it runs at 2 waves per SIMD).
-template <int LPC, class AR, bool ES>
+// CKS: spacing of the backward check-points in trellis steps, 8 or 16 (win_ck_spacing, below, says which instantiation takes which).
+template <int LPC, class AR, bool ES, int CKS>
 __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t wb, const uint32_t slab, const int lane, uint4 (&Bl)[8][2][64],
                                               uint32_t (&Tr)[512])
 {
@@ -560,6 +563,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   constexpr int  NB  = 2 * LPC;
   constexpr int  CPW = 64 / LPC;
   constexpr bool NT  = !ES && !AR::kIs8; // non-temporal workspace loads (see ws_load16)
+  static_assert(CKS == 8 || CKS == 16, "check-points every 8 or every 16 steps");
   const int     pl   = lane % LPC;
   const int     cb_raw = (int)wb * CPW + lane / LPC;
   // Lane groups past the end of the batch stay in the wave: the exchanged rows are loaded 16 bytes per lane and
@@ -859,6 +863,15 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         }
       }
     };
+    // "the values of this set are taken": a compiler-level use of every register issue() loads.  Where the values are only renamed on their way
+    // to their use (block_values of int16 storage), the wait for them would otherwise sink below loads requested later.
+    auto taken = [&](const Ops& q) {
+      asm volatile("" ::"v"(q.x[0]), "v"(q.x[1]), "v"(q.x[2]), "v"(q.x[3]), "v"(q.x[4]), "v"(q.x[5]), "v"(q.x[6]), "v"(q.x[7]));
+      asm volatile("" ::"v"(q.y[0]), "v"(q.y[1]), "v"(q.y[2]), "v"(q.y[3]), "v"(q.y[4]), "v"(q.y[5]), "v"(q.y[6]), "v"(q.y[7]));
+      if (has_app) {
+        asm volatile("" ::"v"(q.a[0]), "v"(q.a[1]), "v"(q.a[2]), "v"(q.a[3]), "v"(q.a[4]), "v"(q.a[5]), "v"(q.a[6]), "v"(q.a[7]));
+      }
+    };
     Ops cur, nxt, nx2; // the two main passes keep TWO blocks in flight: HBM latency under load exceeds one block of compute
 
     // ================= forward warm-up (turbodecoder_win.h:684-750): the last 40 steps of every sub-block, all states unknown.
@@ -952,7 +965,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
       store_block_v<AR::kIs8>(CK, (nblk & M_OWN) * 64 + lane, ck);
     }
-    // pass 1: whole sub-block, keep a check-point at every block boundary.  Blocks nblk-1 ... nblk-4 come from the beta buffer; the first
+    // pass 1: whole sub-block, keep a check-point at every block boundary (CKS = 16: at every even one, the odd slots of CK stay unused).  Blocks nblk-1 ... nblk-4 come from the beta buffer; the first
     // one fetched from HBM is nblk-5 (a sub-block has more than 40 steps: nblk >= 6), requested two blocks ahead like every other
     for (int b = (int)nblk - 1; b >= 0; b--) {
       const bool ahead = b + 3 <= (int)nblk; // block b - 2 is one of those
@@ -975,7 +988,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         uint32_t k = b * 8 + j;
         if (k < long_sb) {
           beta_step<AR>(o, xs[j], ys[j]);
-          if (j == 0 && b > 0) {
+          if (j == 0 && b > 0 && (CKS == 8 || !(b & 1))) {
             uint32_t ck[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) {
@@ -1014,48 +1027,32 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
     const bool fin  = bit_rows && n + 1 == p.n_end;
 
-    uint32_t ck[8], tr[8], ckn[8], trn[8];
-    load_block_raw<AR::kIs8, NT>(CK, (1u & M_OWN) * 64 + lane, ck);
-    load_lut(lut, pl, tr);
-    if (nblk > 1) {
-      issue(1, nxt);
-    }
-    for (uint32_t b = 0; b < nblk; b++) {
-      const int len = (long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8;
-      s2        xs[8], ys[8], ap[8];
-      if (b + 2 < nblk) {
-        issue(b + 2, nx2);
-      }
-      if (b + 1 < nblk) {
-        load_block_raw<AR::kIs8, NT>(CK, ((b + 2) & M_OWN) * 64 + lane, ckn);
-        load_lut(lut, (b + 1) * LPC + pl, trn);
-      }
-      prep(cur, xs, ys, ap);
-      // re-derive beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the check-point into
-      // this lane's private LDS slots (registers are needed for the prefetched operands)
-      {
-        s2       st[8];
-        uint32_t ckv[8];
-        block_values<AR::kIs8>(ck, ckv);
+    // one block of the main pass, in two parts (between them the 16-step form requests its next check-point).
+    // rederive: beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the value at the block's upper boundary into
+    // this lane's private LDS slots (registers are needed for the prefetched operands)
+    auto rederive = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const uint32_t(&ckv)[8]) {
+      s2 st[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          st[i] = from_u(ckv[i]);
-        }
-        Bl[len - 1][0][lane] = make_uint4(ckv[0], ckv[1], ckv[2], ckv[3]);
-        Bl[len - 1][1][lane] = make_uint4(ckv[4], ckv[5], ckv[6], ckv[7]);
+      for (int i = 0; i < 8; i++) {
+        st[i] = from_u(ckv[i]);
+      }
+      Bl[len - 1][0][lane] = make_uint4(ckv[0], ckv[1], ckv[2], ckv[3]);
+      Bl[len - 1][1][lane] = make_uint4(ckv[4], ckv[5], ckv[6], ckv[7]);
 #pragma unroll
-        for (int j = 6; j >= 0; j--) {
-          if (j <= len - 2) {
-            uint32_t idx = b * 8 + j + 2; // index of the stored value we start from
-            if (idx != long_sb && AR::norm_at(idx)) {
-              AR::normalize(st);
-            }
-            beta_step<AR>(st, xs[j + 1], ys[j + 1]);
-            Bl[j][0][lane] = make_uint4(to_u(st[0]), to_u(st[1]), to_u(st[2]), to_u(st[3]));
-            Bl[j][1][lane] = make_uint4(to_u(st[4]), to_u(st[5]), to_u(st[6]), to_u(st[7]));
+      for (int j = 6; j >= 0; j--) {
+        if (j <= len - 2) {
+          uint32_t idx = b * 8 + j + 2; // index of the stored value we start from
+          if (idx != long_sb && AR::norm_at(idx)) {
+            AR::normalize(st);
           }
+          beta_step<AR>(st, xs[j + 1], ys[j + 1]);
+          Bl[j][0][lane] = make_uint4(to_u(st[0]), to_u(st[1]), to_u(st[2]), to_u(st[3]));
+          Bl[j][1][lane] = make_uint4(to_u(st[4]), to_u(st[5]), to_u(st[6]), to_u(st[7]));
         }
       }
+    };
+    // emit: the forward steps, their outputs, the exchange
+    auto emit = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const s2(&ap)[8], const uint32_t(&tr)[8]) {
       uint32_t outv[8], rawv[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -1079,6 +1076,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           outv[j] = to_u(proc);
           rawv[j] = to_u(llr);
         }
+      }
+      if constexpr (CKS == 16) {
+        // every entry counts as used here, also those behind a ragged block's end: a register that a load may still be writing makes
+        // the compiler wait, before its next write, for whatever has been requested since -- the next block's operands
+        asm volatile("" ::"v"(tr[0]), "v"(tr[1]), "v"(tr[2]), "v"(tr[3]), "v"(tr[4]), "v"(tr[5]), "v"(tr[6]), "v"(tr[7]));
       }
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -1106,12 +1108,129 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           }
         }
       }
-      cur = nxt;
-      nxt = nx2;
+    };
+
+    if constexpr (CKS == 8) {
+      uint32_t ck[8], tr[8], ckn[8], trn[8];
+      load_block_raw<AR::kIs8, NT>(CK, (1u & M_OWN) * 64 + lane, ck);
+      load_lut(lut, pl, tr);
+      if (nblk > 1) {
+        issue(1, nxt);
+      }
+      for (uint32_t b = 0; b < nblk; b++) {
+        const int len = (long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8;
+        s2        xs[8], ys[8], ap[8];
+        if (b + 2 < nblk) {
+          issue(b + 2, nx2);
+        }
+        if (b + 1 < nblk) {
+          load_block_raw<AR::kIs8, NT>(CK, ((b + 2) & M_OWN) * 64 + lane, ckn);
+          load_lut(lut, (b + 1) * LPC + pl, trn);
+        }
+        prep(cur, xs, ys, ap);
+        uint32_t ckv[8];
+        block_values<AR::kIs8>(ck, ckv);
+        rederive(b, len, xs, ys, ckv);
+        emit(b, len, xs, ys, ap, tr);
+        cur = nxt;
+        nxt = nx2;
 #pragma unroll
-      for (int i = 0; i < 8; i++) {
-        ck[i] = ckn[i];
-        tr[i] = trn[i];
+        for (int i = 0; i < 8; i++) {
+          ck[i] = ckn[i];
+          tr[i] = trn[i];
+        }
+      }
+    } else {
+      // Check-points at the even block boundaries only.  Blocks go in pairs (b even, b + 1): both start from the check-point at
+      // boundary b + 2 (the last pair: at the sub-block's end, slot nblk).  The odd block re-derives its betas from it as above; the even
+      // block first walks it back through block b + 1 -- whose operands are here one block early: FOUR operand sets, block b + 3 is
+      // requested while block b runs, so two blocks stay in flight behind the held one -- replaying the normalisation schedule of the
+      // backward pass: what comes out is the pre-normalisation value at boundary b + 1, the check-point that was not stored.
+      // The check-point is loaded in place (once per pair, right after its last use, a whole block of forward steps before the next
+      // one) and so are the exchange-table entries (requested at the top of the block, used at its end): no second copy of either.
+      // The four sets keep their registers (the loop is unrolled by hand over four blocks instead of copying set to set: a copy of
+      // a set that was just requested waits for it), and a block requests nothing before it has taken what it needs from earlier
+      // requests, so no wait reaches into the loads of its own block -- the exchange entries apart, behind which the odd block's
+      // check-point load is unconditional for that reason (the last block of an even count re-loads slot nblk for nothing).
+      Ops&     q0 = cur;
+      Ops&     q1 = nxt;
+      Ops&     q2 = nx2;
+      Ops      q3;
+      uint32_t ck[8], tr[8];
+      load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & M_OWN) * 64 + lane, ck);
+      if (nblk > 1) {
+        issue(1, q1);
+      }
+      if (nblk > 2) {
+        issue(2, q2);
+      }
+      auto block = [&](auto even, uint32_t b, const Ops& c, const Ops& held, Ops& tgt) {
+        const int len = (long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8;
+        s2       xs[8], ys[8], ap[8];
+        uint32_t  ckv[8];
+        asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
+        block_values<AR::kIs8>(ck, ckv);
+        taken(c);
+        if constexpr (even.value) {
+          const bool paired = b + 1 < nblk;
+          s2        x1[8], y1[8], a1[8];
+          if (paired) {
+            taken(held);
+            prep(held, x1, y1, a1);
+          }
+          prep(c, xs, ys, ap);
+          if (b + 3 < nblk) {
+            issue(b + 3, tgt);
+          }
+          load_lut(lut, b * LPC + pl, tr);
+          if (paired) {
+            const int len1 = (long_sb - (b + 1) * 8) < 8 ? (int)(long_sb - (b + 1) * 8) : 8;
+            s2       st[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+              st[i] = from_u(ckv[i]);
+            }
+#pragma unroll
+            for (int j = 7; j >= 0; j--) {
+              if (j < len1) {
+                uint32_t idx = (b + 1) * 8 + j + 1; // index of the value we start from
+                if (idx != long_sb && AR::norm_at(idx)) {
+                  AR::normalize(st);
+                }
+                beta_step<AR>(st, x1[j], y1[j]);
+              }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+              ckv[i] = to_u(st[i]);
+            }
+          }
+          rederive(b, len, xs, ys, ckv);
+        } else {
+          prep(c, xs, ys, ap);
+          if (b + 3 < nblk) {
+            issue(b + 3, tgt);
+          }
+          load_lut(lut, b * LPC + pl, tr);
+          rederive(b, len, xs, ys, ckv);
+          const uint32_t bn = b + 3 < nblk ? b + 3 : nblk;
+          load_block_raw<AR::kIs8, NT>(CK, (bn & M_OWN) * 64 + lane, ck);
+        }
+        emit(b, len, xs, ys, ap, tr);
+      };
+      constexpr std::integral_constant<bool, true>  kEven{};
+      constexpr std::integral_constant<bool, false> kOdd{};
+      for (uint32_t b = 0; b < nblk; b += 4) {
+        block(kEven, b, q0, q1, q3);
+        if (b + 1 < nblk) {
+          block(kOdd, b + 1, q1, q2, q0);
+        }
+        if (b + 2 < nblk) {
+          block(kEven, b + 2, q2, q3, q1);
+        }
+        if (b + 3 < nblk) {
+          block(kOdd, b + 3, q3, q0, q2);
+        }
       }
     }
     __syncthreads();
@@ -1144,12 +1263,17 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
 }
 
 // The product kernel: one workgroup (= one wave) per unit, two waves per SIMD.
-template <int LPC, class AR, bool ES>
+// Check-point spacing: 16 steps where the kernel is bound by its HBM traffic (int16, fixed iterations: a quarter of it was check-points),
+// 8 where the extra re-derivation can only cost (the 8-bit decoders are bound by VALU issue) or the working set partly hits in L2 (early stop).
+template <class AR, bool ES>
+constexpr int win_ck_spacing = (!AR::kIs8 && !ES) ? 16 : 8;
+
+template <int LPC, class AR, bool ES, int CKS = win_ck_spacing<AR, ES>>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void tdec_win_kernel(const WinParams p)
 {
   __shared__ uint4    Bl[8][2][64];
   __shared__ uint32_t Tr[512];
-  tdec_win_unit<LPC, AR, ES>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
+  tdec_win_unit<LPC, AR, ES, CKS>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
 }
 
 #ifdef SRSRAN_HIP_WITH_VARIANTS // compiled into tools/probe/lib/libsrsran_phy_hip_variants.so only (srslte_amd/build.py --variants)
@@ -1160,7 +1284,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 {
   __shared__ uint4    Bl[8][2][64];
   __shared__ uint32_t Tr[512];
-  tdec_win_unit<8, Ar16, false>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
+  tdec_win_unit<8, Ar16, false, win_ck_spacing<Ar16, false>>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
 }
 // "persistent": the grid holds only as many workgroups as the chip keeps resident (p.max_resident), every workgroup owns ONE slab and
 // takes units from a counter until the batch is used up, so the workspace could be sized by the residency (1.2 GB) instead of the
@@ -1177,7 +1301,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const WinParams& q = *(const WinParams*)ka;
     int lane = threadIdx.x;
     asm volatile("" : "+v"(lane));
-    tdec_win_unit<8, Ar16, false>(q, wb, blockIdx.x, lane, Bl, Tr);
+    tdec_win_unit<8, Ar16, false, win_ck_spacing<Ar16, false>>(q, wb, blockIdx.x, lane, Bl, Tr);
     __syncthreads();
     uint32_t nx = 0;
     if (threadIdx.x == 0) {

@@ -830,15 +830,36 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     struct Ops {
       uint32_t x[8], y[8], a[8];
     };
-    auto issue = [&](uint32_t b, Ops& q) {
-      if (dec1) {
-        load_block_raw<AR::kIs8, NT>(S, (b & M_OWN) * 64 + lane, q.x);
+    // ok = false: there is no block b (the pipeline runs out at the end of a pass).
+    // The 16-step form requests without a branch, always six loads.  A branch around a request merges an arm without loads into the path, and
+    // the compiler's wait for anything requested before the branch becomes a wait for everything (it counts the most conservative arm); two
+    // arms that load the same registers from different arrays cost a wait for the first arm's loads in the second.  So: the systematic block
+    // of decoder 1 and the exchanged rows of decoder 2 are the same bytes of their arrays (a block of a blocked array and the 8 rows of a block
+    // of a row array are one contiguous run of the wave's slab, 16 bytes per lane and half), only the array differs; and a request that is not
+    // needed (no block b, no a-priori array in this half iteration) goes, from every lane, to the first 16 bytes of the array.
+    const uint32_t* X = dec1 ? S : A2;
+    auto issue = [&](uint32_t b, Ops& q, bool ok = true) {
+      if constexpr (CKS == 16) {
+        static_assert(!ES, "the early-stop masks differ between blocked and row arrays");
+        const bool oka = ok && has_app;
+        uint32_t   bb = ok ? b : 0u, ba = oka ? b : 0u;
+        int        ln = ok ? lane : 0, la = oka ? lane : 0;
+        // (opaque: the addresses of the requests whose block index is the same in every half iteration -- the first ones of each pass -- are
+        // otherwise all formed once in front of the half-iteration loop and held across it, in registers the forward main pass does not have)
+        asm volatile("" : "+v"(ln), "+v"(la));
+        issue_rows_raw<AR::kIs8, NT>(X, bb, ln, q.x);
+        issue_rows_raw<AR::kIs8, NT>(Y, bb, ln, q.y);
+        issue_rows_raw<AR::kIs8, NT>(A1, ba, la, q.a);
       } else {
-        issue_rows_raw<AR::kIs8, NT>(A2, b & M_ROW, lane, q.x);
-      }
-      load_block_raw<AR::kIs8, NT>(Y, (b & M_OWN) * 64 + lane, q.y);
-      if (has_app) {
-        issue_rows_raw<AR::kIs8, NT>(A1, b & M_ROW, lane, q.a);
+        if (dec1) {
+          load_block_raw<AR::kIs8, NT>(S, (b & M_OWN) * 64 + lane, q.x);
+        } else {
+          issue_rows_raw<AR::kIs8, NT>(A2, b & M_ROW, lane, q.x);
+        }
+        load_block_raw<AR::kIs8, NT>(Y, (b & M_OWN) * 64 + lane, q.y);
+        if (has_app) {
+          issue_rows_raw<AR::kIs8, NT>(A1, b & M_ROW, lane, q.a);
+        }
       }
     };
     auto prep = [&](const Ops& q, s2(&xs)[8], s2(&ys)[8], s2(&ap)[8]) {
@@ -868,11 +889,14 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     auto taken = [&](const Ops& q) {
       asm volatile("" ::"v"(q.x[0]), "v"(q.x[1]), "v"(q.x[2]), "v"(q.x[3]), "v"(q.x[4]), "v"(q.x[5]), "v"(q.x[6]), "v"(q.x[7]));
       asm volatile("" ::"v"(q.y[0]), "v"(q.y[1]), "v"(q.y[2]), "v"(q.y[3]), "v"(q.y[4]), "v"(q.y[5]), "v"(q.y[6]), "v"(q.y[7]));
-      if (has_app) {
+      if (has_app || CKS == 16) { // (the 16-step form always loads all three)
         asm volatile("" ::"v"(q.a[0]), "v"(q.a[1]), "v"(q.a[2]), "v"(q.a[3]), "v"(q.a[4]), "v"(q.a[5]), "v"(q.a[6]), "v"(q.a[7]));
       }
     };
-    Ops cur, nxt, nx2; // the two main passes keep TWO blocks in flight: HBM latency under load exceeds one block of compute
+    // The two main passes keep at least TWO blocks in flight behind the one they work on: HBM latency under load exceeds one block of
+    // compute.  Four sets whose roles rotate (the loops are unrolled by hand over four blocks): a set-to-set copy would wait for the set
+    // that was just requested.
+    Ops cur, nxt, nx2, nx3;
 
     // ================= forward warm-up (turbodecoder_win.h:684-750): the last 40 steps of every sub-block, all states unknown.
     // It needs nothing the backward recursion produces and runs FIRST: the backward main pass starts with the very blocks it
@@ -965,45 +989,99 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
       store_block_v<AR::kIs8>(CK, (nblk & M_OWN) * 64 + lane, ck);
     }
-    // pass 1: whole sub-block, keep a check-point at every block boundary (CKS = 16: at every even one, the odd slots of CK stay unused).  Blocks nblk-1 ... nblk-4 come from the beta buffer; the first
-    // one fetched from HBM is nblk-5 (a sub-block has more than 40 steps: nblk >= 6), requested two blocks ahead like every other
-    for (int b = (int)nblk - 1; b >= 0; b--) {
-      const bool ahead = b + 3 <= (int)nblk; // block b - 2 is one of those
-      if (b > 1 && ahead) {
-        issue(b - 2, nx2);
-      }
-      s2 xs[8], ys[8], ap[8];
-      if (b + 4 >= (int)nblk) {
-        const uint32_t s  = (uint32_t)b + 4 - nblk;
-        const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
-        xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
-        xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
-        ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
-        ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
-      } else {
-        prep(cur, xs, ys, ap);
-      }
+    // pass 1: whole sub-block, keep a check-point at every block boundary (CKS = 16: at every even one, the odd slots of CK stay unused).
+    // Blocks nblk-1 ... nblk-4 come from the beta buffer; the first one fetched from HBM is `top` = nblk-5 (a sub-block has more than 40
+    // steps: nblk >= 6).
+    if constexpr (CKS == 16) {
+      // Every block requests, once it has taken its own operands, the block THREE below it, so two requests stay in flight behind the one a
+      // block waits for.  Block b lives in set b mod 4 (cur, nxt, nx2, nx3): block 0 ends up in `cur`, where the forward main pass expects
+      // it.  The loop goes over four blocks by hand and has ONE way in and one way out: it starts at the multiple of four above the last
+      // block, and a block that does not exist only makes its request.  (Leaving the loop where the blocks end -- a `break` behind each
+      // block -- the compiler routes every exit through the loop's latch, and the waits at the loop's top are counted as if a block's own
+      // request could still be open there.)  The blocks from the beta buffer run in the same loop: their requests are blocks top ... top-2.
+      const int top = (int)nblk - 5;
+      auto      block = [&](int b, const Ops& c, Ops& tgt) {
+        s2 xs[8], ys[8], ap[8];
+        if (b > top) {
+          const uint32_t s  = (uint32_t)(b < (int)nblk ? b : (int)nblk - 1) + 4 - nblk;
+          const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
+          xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
+          xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
+          ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
+          ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
+        } else {
+          taken(c);
+          prep(c, xs, ys, ap);
+        }
+        issue(b - 3, tgt, b >= 3 && b - 3 <= top);
+        if (b < (int)nblk) {
 #pragma unroll
-      for (int j = 7; j >= 0; j--) {
-        uint32_t k = b * 8 + j;
-        if (k < long_sb) {
-          beta_step<AR>(o, xs[j], ys[j]);
-          if (j == 0 && b > 0 && (CKS == 8 || !(b & 1))) {
-            uint32_t ck[8];
+          for (int j = 7; j >= 0; j--) {
+            uint32_t k = b * 8 + j;
+            if (k < long_sb) {
+              beta_step<AR>(o, xs[j], ys[j]);
+              if (j == 0 && b > 0 && !(b & 1)) {
+                uint32_t ck[8];
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-              ck[i] = to_u(o[i]);
+                for (int i = 0; i < 8; i++) {
+                  ck[i] = to_u(o[i]);
+                }
+                store_block_v<AR::kIs8>(CK, ((uint32_t)b & M_OWN) * 64 + lane, ck);
+              }
+              if (AR::norm_at(k)) {
+                AR::normalize(o);
+              }
             }
-            store_block_v<AR::kIs8>(CK, ((uint32_t)b & M_OWN) * 64 + lane, ck);
-          }
-          if (AR::norm_at(k)) {
-            AR::normalize(o);
           }
         }
+      };
+      for (int b = ((int)nblk - 1) | 3; b >= 0; b -= 4) {
+        block(b, nx3, cur);
+        block(b - 1, nx2, nx3);
+        block(b - 2, nxt, nx2);
+        block(b - 3, cur, nxt);
       }
-      if (b > 0 && ahead) { // (block 0 stays in `cur`: the forward main pass starts with it)
-        cur = nxt;
-        nxt = nx2;
+    } else {
+      // (8-step check-points: the 8-bit and the early-stop kernels.  With four rotating sets the int16 early-stop kernels spill -- their forward
+      // main pass double-buffers check-point and table entries on top of the CRC state -- so they all keep three sets, copied set to set, two blocks ahead)
+      for (int b = (int)nblk - 1; b >= 0; b--) {
+        const bool ahead = b + 3 <= (int)nblk; // block b - 2 is one of those
+        if (b > 1 && ahead) {
+          issue(b - 2, nx2);
+        }
+        s2 xs[8], ys[8], ap[8];
+        if (b + 4 >= (int)nblk) {
+          const uint32_t s  = (uint32_t)b + 4 - nblk;
+          const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
+          xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
+          xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
+          ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
+          ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
+        } else {
+          prep(cur, xs, ys, ap);
+        }
+#pragma unroll
+        for (int j = 7; j >= 0; j--) {
+          uint32_t k = b * 8 + j;
+          if (k < long_sb) {
+            beta_step<AR>(o, xs[j], ys[j]);
+            if (j == 0 && b > 0 && (CKS == 8 || !(b & 1))) {
+              uint32_t ck[8];
+#pragma unroll
+              for (int i = 0; i < 8; i++) {
+                ck[i] = to_u(o[i]);
+              }
+              store_block_v<AR::kIs8>(CK, ((uint32_t)b & M_OWN) * 64 + lane, ck);
+            }
+            if (AR::norm_at(k)) {
+              AR::normalize(o);
+            }
+          }
+        }
+        if (b > 0 && ahead) { // (block 0 stays in `cur`: the forward main pass starts with it)
+          cur = nxt;
+          nxt = nx2;
+        }
       }
     }
     __syncthreads(); // orders this lane's check-point stores before its loads below
@@ -1030,14 +1108,17 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // one block of the main pass, in two parts (between them the 16-step form requests its next check-point).
     // rederive: beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the value at the block's upper boundary into
     // this lane's private LDS slots (registers are needed for the prefetched operands)
-    auto rederive = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const uint32_t(&ckv)[8]) {
-      s2 st[8];
+    // in two steps: once the start value is taken, the 16-step form requests its next check-point into the same registers
+    auto rederive_start = [&](int len, const uint32_t(&ckv)[8], s2(&st)[8]) {
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         st[i] = from_u(ckv[i]);
       }
-      Bl[len - 1][0][lane] = make_uint4(ckv[0], ckv[1], ckv[2], ckv[3]);
-      Bl[len - 1][1][lane] = make_uint4(ckv[4], ckv[5], ckv[6], ckv[7]);
+      const int top = CKS == 16 ? (len - 1) & 7 : len - 1; // (len = 0: a block of the 16-step form that is not there)
+      Bl[top][0][lane] = make_uint4(ckv[0], ckv[1], ckv[2], ckv[3]);
+      Bl[top][1][lane] = make_uint4(ckv[4], ckv[5], ckv[6], ckv[7]);
+    };
+    auto rederive_rest = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], s2(&st)[8]) {
 #pragma unroll
       for (int j = 6; j >= 0; j--) {
         if (j <= len - 2) {
@@ -1052,7 +1133,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
     };
     // emit: the forward steps, their outputs, the exchange
-    auto emit = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const s2(&ap)[8], const uint32_t(&tr)[8]) {
+    auto emit = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const s2(&ap)[8], const uint32_t(&tr)[8], auto&& ck_taken) {
       uint32_t outv[8], rawv[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -1080,7 +1161,10 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       if constexpr (CKS == 16) {
         // every entry counts as used here, also those behind a ragged block's end: a register that a load may still be writing makes
         // the compiler wait, before its next write, for whatever has been requested since -- the next block's operands
-        asm volatile("" ::"v"(tr[0]), "v"(tr[1]), "v"(tr[2]), "v"(tr[3]), "v"(tr[4]), "v"(tr[5]), "v"(tr[6]), "v"(tr[7]));
+        asm volatile("" ::"v"(tr[0]), "v"(tr[1]), "v"(tr[2]), "v"(tr[3]), "v"(tr[4]), "v"(tr[5]), "v"(tr[6]), "v"(tr[7]));        // ... and so does the check-point an odd block has requested for the next pair, just before its operand request: here the count that
+        // retires it is exact.  At the next block's top it is not: the row stores below sit in conditional arms, the compiler counts the
+        // arm with the fewest, and what it leaves in flight there are the last stores, not the operand loads.
+        ck_taken();
       }
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -1130,8 +1214,10 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         prep(cur, xs, ys, ap);
         uint32_t ckv[8];
         block_values<AR::kIs8>(ck, ckv);
-        rederive(b, len, xs, ys, ckv);
-        emit(b, len, xs, ys, ap, tr);
+        s2 st[8];
+        rederive_start(len, ckv, st);
+        rederive_rest(b, len, xs, ys, st);
+        emit(b, len, xs, ys, ap, tr, [] {});
         cur = nxt;
         nxt = nx2;
 #pragma unroll
@@ -1155,82 +1241,84 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       Ops&     q0 = cur;
       Ops&     q1 = nxt;
       Ops&     q2 = nx2;
-      Ops      q3;
+      Ops&     q3 = nx3;
       uint32_t ck[8], tr[8];
       load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & M_OWN) * 64 + lane, ck);
-      if (nblk > 1) {
-        issue(1, q1);
-      }
-      if (nblk > 2) {
-        issue(2, q2);
-      }
+      issue(1, q1, nblk > 1);
+      // The loop is entered with exactly what its back edge brings: one request in flight, everything before it taken.  The waits at the top of
+      // the loop are counted for the worse of the two ways in; with all of these requests still open on this one, the count that suits it
+      // would, on the back edge, reach into the last block's request.  (Once per half iteration: block 1's operands are waited for here.)
+      asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
+      taken(q1);
+      issue(2, q2, nblk > 2);
+      // b may lie behind the last block (the loop below goes over four blocks whatever the count): such a block has no steps, len = 0.  It makes
+      // its requests and goes the same way as every other: an arm of its own, or one around the others' work, is a way on which the compiler
+      // sees the table entries and the check-point still open, and its wait for them, placed behind the row stores, reaches into the request.
       auto block = [&](auto even, uint32_t b, const Ops& c, const Ops& held, Ops& tgt) {
-        const int len = (long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8;
-        s2       xs[8], ys[8], ap[8];
-        uint32_t  ckv[8];
-        asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
+        const int rem = (int)long_sb - (int)b * 8;
+        const int len = rem < 0 ? 0 : rem < 8 ? rem : 8;
+        s2         xs[8], ys[8], ap[8], st[8];
+        uint32_t   ckv[8];
+        auto       ck_taken = [&] { asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7])); };
+        ck_taken();
         block_values<AR::kIs8>(ck, ckv);
+        load_lut(lut, (b < nblk ? b : nblk - 1) * LPC + pl, tr);
         taken(c);
         if constexpr (even.value) {
-          const bool paired = b + 1 < nblk;
-          s2        x1[8], y1[8], a1[8];
-          if (paired) {
-            taken(held);
-            prep(held, x1, y1, a1);
-          }
-          prep(c, xs, ys, ap);
-          if (b + 3 < nblk) {
-            issue(b + 3, tgt);
-          }
-          load_lut(lut, b * LPC + pl, tr);
-          if (paired) {
-            const int len1 = (long_sb - (b + 1) * 8) < 8 ? (int)(long_sb - (b + 1) * 8) : 8;
-            s2       st[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-              st[i] = from_u(ckv[i]);
-            }
-#pragma unroll
-            for (int j = 7; j >= 0; j--) {
-              if (j < len1) {
-                uint32_t idx = (b + 1) * 8 + j + 1; // index of the value we start from
-                if (idx != long_sb && AR::norm_at(idx)) {
-                  AR::normalize(st);
-                }
-                beta_step<AR>(st, x1[j], y1[j]);
-              }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-              ckv[i] = to_u(st[i]);
-            }
-          }
-          rederive(b, len, xs, ys, ckv);
+          taken(held); // (also where there is no block b + 1: the set was requested all the same)
+          issue(b + 3, tgt, b + 3 < nblk);
         } else {
+          // the check-point's last use is the copy at the start of the re-derivation: the next pair's is requested there, ahead of the operands
           prep(c, xs, ys, ap);
-          if (b + 3 < nblk) {
-            issue(b + 3, tgt);
-          }
-          load_lut(lut, b * LPC + pl, tr);
-          rederive(b, len, xs, ys, ckv);
+          rederive_start(len, ckv, st);
           const uint32_t bn = b + 3 < nblk ? b + 3 : nblk;
           load_block_raw<AR::kIs8, NT>(CK, (bn & M_OWN) * 64 + lane, ck);
+          issue(b + 3, tgt, b + 3 < nblk);
         }
-        emit(b, len, xs, ys, ap, tr);
+        {
+          if constexpr (even.value) {
+            const bool paired = b + 1 < nblk;
+            s2        x1[8], y1[8], a1[8];
+            if (paired) {
+              prep(held, x1, y1, a1);
+            }
+            prep(c, xs, ys, ap);
+            if (paired) {
+              const int len1 = (long_sb - (b + 1) * 8) < 8 ? (int)(long_sb - (b + 1) * 8) : 8;
+#pragma unroll
+              for (int i = 0; i < 8; i++) {
+                st[i] = from_u(ckv[i]);
+              }
+#pragma unroll
+              for (int j = 7; j >= 0; j--) {
+                if (j < len1) {
+                  uint32_t idx = (b + 1) * 8 + j + 1; // index of the value we start from
+                  if (idx != long_sb && AR::norm_at(idx)) {
+                    AR::normalize(st);
+                  }
+                  beta_step<AR>(st, x1[j], y1[j]);
+                }
+              }
+#pragma unroll
+              for (int i = 0; i < 8; i++) {
+                ckv[i] = to_u(st[i]);
+              }
+            }
+            rederive_start(len, ckv, st);
+          }
+          rederive_rest(b, len, xs, ys, st);
+          emit(b, len, xs, ys, ap, tr, ck_taken);
+        }
       };
       constexpr std::integral_constant<bool, true>  kEven{};
       constexpr std::integral_constant<bool, false> kOdd{};
+      // (one way out, at the bottom: a `break` behind each block is routed through the loop's latch, and the waits at the loop's top are
+      // then counted as if a block's own request could still be open there; a block skipped as a whole is an arm without requests)
       for (uint32_t b = 0; b < nblk; b += 4) {
         block(kEven, b, q0, q1, q3);
-        if (b + 1 < nblk) {
-          block(kOdd, b + 1, q1, q2, q0);
-        }
-        if (b + 2 < nblk) {
-          block(kEven, b + 2, q2, q3, q1);
-        }
-        if (b + 3 < nblk) {
-          block(kOdd, b + 3, q3, q0, q2);
-        }
+        block(kOdd, b + 1, q1, q2, q0);
+        block(kEven, b + 2, q2, q3, q1);
+        block(kOdd, b + 3, q3, q0, q2);
       }
     }
     __syncthreads();

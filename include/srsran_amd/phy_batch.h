@@ -51,7 +51,7 @@ SRSRAN_API void srsran_hip_coalesce_stats(uint64_t* nof_batches, uint64_t* nof_u
 /* submission queues alive right now: one per kernel shape, at most 12 -- the least recently used idle one is released (streams, pinned
  * staging, batch engine) when a new shape arrives, so a long-running process that walks through many block / lifting sizes stays bounded */
 SRSRAN_API uint32_t srsran_hip_coalesce_shapes(void);
-/* development knobs (measured kernel alternatives kept behind SRSRAN_HIP_TDEC_VARIANT / SRSRAN_HIP_PSS_VARIANT and a few sizing overrides):
+/* development knobs (which kernel a batch size is routed to, e.g. SRSRAN_HIP_TDEC_LAT, and a few sizing overrides):
  * their environment variables are read once; this overrides one at run time (value NULL = unset).  Never needed by an application. */
 SRSRAN_API int      srsran_hip_dev_knob(const char* env_name, const char* value);
 

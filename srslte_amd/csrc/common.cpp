@@ -194,33 +194,21 @@ void trace_pop()
 
 // ---- development knobs (hip_common.h)
 namespace {
-const char* const kKnobEnv[KNOB_COUNT] = {"SRSRAN_HIP_TDEC_VARIANT", "SRSRAN_HIP_PSS_VARIANT", "TDEC_DBG_EXTRACT_ONLY", "LDPC_PCPB", "LDPC_SLOTS", "LDPC_PACKED", "SRSRAN_HIP_TDEC_LAT",
-                                          "SRSRAN_HIP_LDPC_C2V_LDS", "SRSRAN_HIP_TCOD_LAT", "SRSRAN_HIP_LOGICAL_DEVICES", "SRSRAN_HIP_TDEC_LAT2"};
+const char* const kKnobEnv[KNOB_COUNT] = {"LDPC_PCPB", "LDPC_SLOTS", "LDPC_PACKED", "SRSRAN_HIP_TDEC_LAT", "SRSRAN_HIP_LDPC_C2V_LDS", "SRSRAN_HIP_TCOD_LAT",
+                                          "SRSRAN_HIP_LOGICAL_DEVICES", "SRSRAN_HIP_TDEC_LAT2"};
 std::atomic<int>  g_knob[KNOB_COUNT];
 std::atomic<bool> g_knob_read[KNOB_COUNT];
 
-int knob_parse(int k, const char* v)
+int knob_parse(const char* v)
 {
-  if (!v) {
-    return -1;
-  }
-  switch (k) {
-    case KNOB_TDEC_VARIANT:
-      return !strcmp(v, "waves1") ? 1 : (!strcmp(v, "persistent") ? 2 : 0);
-    case KNOB_PSS_VARIANT:
-      return !strcmp(v, "pair") ? 1 : (!strcmp(v, "block") ? 2 : (!strcmp(v, "recompute") ? 3 : 0));
-    case KNOB_TDEC_EXTRACT_ONLY:
-      return 1;
-    default:
-      return atoi(v);
-  }
+  return v ? atoi(v) : -1;
 }
 } // namespace
 
 int knob(Knob k)
 {
   if (!g_knob_read[k].load(std::memory_order_acquire)) {
-    g_knob[k].store(knob_parse(k, getenv(kKnobEnv[k])), std::memory_order_relaxed);
+    g_knob[k].store(knob_parse(getenv(kKnobEnv[k])), std::memory_order_relaxed);
     g_knob_read[k].store(true, std::memory_order_release);
   }
   return g_knob[k].load(std::memory_order_relaxed);
@@ -353,7 +341,7 @@ extern "C" int srsran_hip_dev_knob(const char* env_name, const char* value)
 {
   for (int k = 0; env_name && k < KNOB_COUNT; k++) {
     if (!strcmp(env_name, kKnobEnv[k])) {
-      g_knob[k].store(knob_parse(k, value), std::memory_order_relaxed);
+      g_knob[k].store(knob_parse(value), std::memory_order_relaxed);
       g_knob_read[k].store(true, std::memory_order_release);
       return SRSRAN_SUCCESS;
     }

@@ -5,10 +5,10 @@
 //
 // The reference correlates with ONE FFT of length frame+fft (e.g. 309,248 = 2^11 * 151 points for a 10 ms
 // capture at 30.72 Msps), once per N_id_2.  Here the same linear convolution is evaluated by overlap-save
-// with 4096-point blocks: one workgroup transforms one input block ONCE (LDS Stockham FFT, fft_device.h),
-// keeps the spectrum in LDS, and for each of the three N_id_2 hypotheses multiplies by the cached filter
-// spectrum, inverse-transforms, takes |.|^2 (optionally the exponential moving average of pss.c:496-503)
-// and reduces a block arg-max -- the capture is read from HBM once for all three hypotheses.
+// with 4096-point blocks: an input block is transformed ONCE and, for each of the three N_id_2 hypotheses,
+// multiplied by the cached filter spectrum, inverse-transformed, turned into |.|^2 (optionally the exponential
+// moving average of pss.c:496-503) and reduced to a block arg-max -- the capture is read from HBM once for all
+// three hypotheses.  That kernel is pss_wave_kernels.hip; what is here works on its block partials.
 #include "fft_device.h"
 #include "fft_reg.h"
 
@@ -21,118 +21,6 @@ namespace phyhip {
 namespace sync {
 
 using namespace fft;
-
-typedef Plan<4096, 256, 16, 16, 16, 1> BlockPlan;
-
-struct SegLoad {
-  const float2* x;  // capture
-  int           i0; // capture index of segment element 0
-  int           frame;
-  __device__ __forceinline__ float2 operator()(int m) const
-  {
-    const int i = i0 + m;
-    return (i >= 0 && i < frame) ? x[i] : make_float2(0.f, 0.f);
-  }
-};
-
-struct SpecStore {
-  float2* spec;
-  __device__ __forceinline__ void operator()(int k, float2 v) const { spec[k] = v; }
-};
-
-struct ProdLoad {
-  const float2* spec;
-  const float2* filt; // DFT of the zero-padded replica, already scaled by 1/4096
-  __device__ __forceinline__ float2 operator()(int k) const { return cmul(spec[k], filt[k]); }
-};
-
-struct PowerStore {
-  float* corr;  // |conv|^2 (or its moving average) of this hypothesis, index = convolution output index
-  int    off;   // block output m corresponds to convolution index i = off + m
-  int    m_lo;  // first valid m (fft_size - 1)
-  int    m_hi;  // one past the last m owned by this block
-  int    n_out; // number of valid convolution outputs (L - 2)
-  float  alpha; // EMA weight, <= 0 or >= 1: no averaging
-  float  best;
-  int    besti;
-  __device__ __forceinline__ void operator()(int m, float2 v)
-  {
-    const int i = off + m;
-    if (m >= m_lo && m < m_hi && i < n_out) {
-      float pw = v.x * v.x + v.y * v.y; // srsran_vec_abs_square_cf
-      if (alpha > 0.0f && alpha < 1.0f) {
-        pw = pw * alpha + corr[i] * (1.0f - alpha); // pss.c:497-500
-      }
-      corr[i] = pw;
-      if (pw > best || (pw == best && i < besti)) {
-        best  = pw;
-        besti = i;
-      }
-    }
-  }
-};
-
-#ifdef SRSRAN_HIP_WITH_VARIANTS // round 1's workgroup-per-block correlation kernel: a measured alternative, compiled into the variants library only
-__global__ __launch_bounds__(256) void pss_block_kernel(const PssParams p)
-{
-  extern __shared__ float2 lds_all[];
-  float2*   lds  = lds_all;                    // FFT exchange image
-  float2*   spec = lds_all + lds_elems(4096);  // spectrum of the input block
-  __shared__ float s_best[4];
-  __shared__ int   s_besti[4];
-
-  const int cap = blockIdx.y;
-  const int blk = blockIdx.x;
-  const int tid = threadIdx.x;
-  const float2* x  = reinterpret_cast<const float2*>(p.in) + (size_t)cap * p.in_stride;
-  const float2* tw = reinterpret_cast<const float2*>(p.twiddle);
-
-  const int i0 = blk * p.hop; // first convolution output of this block
-  SegLoad   ld{x, i0 - (p.fft_size - 1), p.frame_size};
-  SpecStore ss{spec};
-  transform<BlockPlan, false>(lds, tid, true, tw, ld, ss);
-  __syncthreads();
-
-  for (int h = 0; h < 3; h++) {
-    if (!(p.n_id_2_mask & (1 << h))) {
-      continue;
-    }
-    ProdLoad   pl{spec, reinterpret_cast<const float2*>(p.filt) + (size_t)h * 4096};
-    float*     corr = p.corr + ((size_t)cap * 3 + h) * p.corr_stride;
-    PowerStore ps{corr, i0 - (p.fft_size - 1), p.fft_size - 1, p.fft_size - 1 + p.hop, p.n_out, p.ema_alpha, -1.0f, 0x7fffffff};
-    transform<BlockPlan, true>(lds, tid, true, tw, pl, ps);
-    // block arg-max (first maximum wins on ties, as srsran_vec_max_fi)
-    float b  = ps.best;
-    int   bi = ps.besti;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      float ob  = __shfl_down(b, o);
-      int   obi = __shfl_down(bi, o);
-      if (ob > b || (ob == b && obi < bi)) {
-        b  = ob;
-        bi = obi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      s_best[tid >> 6]  = b;
-      s_besti[tid >> 6] = bi;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; w++) {
-        if (s_best[w] > b || (s_best[w] == b && s_besti[w] < bi)) {
-          b  = s_best[w];
-          bi = s_besti[w];
-        }
-      }
-      const size_t o = ((size_t)cap * 3 + h) * p.n_blocks + blk;
-      p.part_val[o] = b;
-      p.part_idx[o] = bi;
-    }
-    __syncthreads();
-  }
-}
-#endif // SRSRAN_HIP_WITH_VARIANTS
 
 // Per (capture, hypothesis): global arg-max from the block partials, then the peak / side-lobe ratio of
 // pss.c:408-437 evaluated on the correlation-power array.
@@ -467,26 +355,9 @@ hipError_t launch_pack(const PssResult* a, const SssResult* b, CellResult* out, 
 
 hipError_t launch_pss(const PssParams& p, PssResult* d_res, hipStream_t stream)
 {
-#ifdef SRSRAN_HIP_WITH_VARIANTS
-  // development knob (tests/test_gpu_variants.py, in the variants library): "block" = the workgroup-per-block kernel of round 1
-  if (knob(KNOB_PSS_VARIANT) == 2) {
-    static bool  attr_set = false;
-    const size_t lds      = (lds_elems(4096) + 4096) * sizeof(float2);
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pss_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        return e;
-      }
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(pss_block_kernel, dim3(p.n_blocks, p.n_cap), dim3(256), lds, stream, p);
-  } else
-#endif
-  {
-    hipError_t e = launch_pss_wave_blocks(p, stream);
-    if (e != hipSuccess) {
-      return e;
-    }
+  hipError_t e = launch_pss_wave_blocks(p, stream);
+  if (e != hipSuccess) {
+    return e;
   }
   hipLaunchKernelGGL(pss_peak_kernel, dim3(3, p.n_cap), dim3(256), 0, stream, p, d_res);
   return hipGetLastError();

@@ -1,5 +1,5 @@
 // turbo_arith.h -- arithmetic policies and trellis helpers shared by the turbo decoder kernels (turbo_kernels.hip: throughput kernel,
-// turbo_lat_kernels.hip: latency kernel).  Device code only.
+// turbo_lat_kernels.hip: latency kernel; turbo_gen_kernels.hip / turbo_gen_lat_kernels.hip: the scalar decoder).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -31,6 +31,16 @@ __device__ __forceinline__ s2 vmax(s2 a, s2 b)
 __device__ __forceinline__ s2 vmin(s2 a, s2 b)
 {
   return __builtin_elementwise_min(a, b);
+}
+// what one or two dwordx4 loads brought, as the dwords of an array
+__device__ __forceinline__ void unpack4(const uint4& a, uint32_t (&r)[8])
+{
+  r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
+}
+__device__ __forceinline__ void unpack8(const uint4& a, const uint4& c, uint32_t (&r)[8])
+{
+  unpack4(a, r);
+  r[4] = c.x, r[5] = c.y, r[6] = c.z, r[7] = c.w;
 }
 
 // Arithmetic of the 16-bit window decoders (WINIMP_IS_SSE16 / AVX16, turbodecoder_win.h:60-150): saturating

@@ -1,4 +1,4 @@
-// turbo_device.h -- kernel parameter blocks and launchers of turbo_kernels.hip
+// turbo_device.h -- kernel parameter blocks and launchers of the turbo decoder kernels (turbo_kernels.hip, turbo_gen_kernels.hip and their latency forms)
 #pragma once
 #include "turbo_arith.h" // TD_WIN_OVERLAP
 #include <hip/hip_runtime.h>
@@ -41,11 +41,6 @@ struct WinParams {
   const uint32_t* crc_mult; // nb multipliers x^(W (nb-1-d)) mod g
   int*            noi;      // out: half iterations run per code block
   uint8_t*        crc_ok;   // out: 1 = CRC matched
-  // measured launch-shape alternatives (SRSRAN_HIP_TDEC_VARIANT, never the default): 0 product, 1 one wave per SIMD, 2 persistent grid
-  int             variant;
-  uint32_t        n_units;      // persistent grid: units of 64 / (nb / 2) code blocks,
-  uint32_t        max_resident; //   workgroups launched at most,
-  uint32_t*       unit_counter; //   device counter, zero at launch
 };
 
 struct GenParams {

@@ -1,7 +1,7 @@
 // turbo_gen_lat_kernels.hip -- LATENCY kernel of the scalar turbo decoder (turbodecoder_gen.c: what AUTO runs for K <= 400, i.e. the
 // transport blocks of small grants -- a VoLTE frame, a control message).
 //
-// tdec_gen_kernel (turbo_kernels.hip) gives a code block ONE lane and keeps its backward metrics in HBM: right for tens of thousands of
+// tdec_gen_kernel (turbo_gen_kernels.hip) gives a code block ONE lane and keeps its backward metrics in HBM: right for tens of thousands of
 // small blocks, 130-300 us per half iteration when the call carries one grant.  The decoder has no windows: the K + 3 backward steps and the
 // K forward steps of a half iteration are one dependent chain each.  What a small batch can use:
 //   * the 8 trellis states side by side: a recursion owns 8 lanes and runs the in-place butterflies of the window decoders' latency kernel

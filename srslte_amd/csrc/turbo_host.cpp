@@ -157,9 +157,6 @@ struct srsran_hip_tdec_batch {
   uint16_t* d_deinter16 = nullptr;
   // optional parity aid
   short* d_dec_llr = nullptr;
-  // the "persistent" launch variant's unit counter (development knob) and the CU count of the object's device
-  uint32_t* d_unit_counter = nullptr;
-  int       cus            = 0;
   // latency kernel (small batches): its own workspace, allocated on first use for lat_cap code blocks
   uint32_t* d_ws_lat      = nullptr;
   uint32_t  lat_cap       = 0;
@@ -301,7 +298,7 @@ enum class Route {
   Win,    // throughput kernel: 8 code blocks per wave (turbo_kernels.hip)
   Lat,    // latency kernel: one code block per wave (turbo_lat_kernels.hip)
   Lat2,   //   its two-wave form; same workspace layout as Lat
-  Gen,    // scalar decoder (K <= 400 with AUTO): one lane per code block
+  Gen,    // scalar decoder (K <= 400 with AUTO): one lane per code block (turbo_gen_kernels.hip)
   GenLat, // scalar latency kernel: 8 lanes per block with the block in LDS (turbo_gen_lat_kernels.hip)
 };
 // which kernel takes a launch of n_cb blocks starting at half iteration n_begin: every kernel's precondition, then the knobs, then the batch size
@@ -652,26 +649,6 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input,
   turbo::WinParams p = win_params(h, ws, d_input, in_is8, d_output, n_cb, n_begin, n_end, sb_layout);
   mine(p);
   p.final_run = final_run && turbo::win_final_fits(h->K, h->nb) ? 1 : 0;
-  if (knob(KNOB_TDEC_EXTRACT_ONLY) > 0) {
-    p.n_end     = 0; // development aid: input extraction + decision only
-    p.final_run = 0;
-  }
-  // launch-shape alternatives kept for measurement (profiles/r02_turbo_variants.txt); the product path is variant 0
-  p.variant = knob(KNOB_TDEC_VARIANT) > 0 ? knob(KNOB_TDEC_VARIANT) : 0;
-  if (p.variant == 2 && n_begin == 0 && h->nb == 16 && !h->arith8) {
-    // the unit counter belongs to the batch object (launches of different objects / streams must not share one) and lives on
-    // the device the object was created on
-    if (!h->d_unit_counter) {
-      int dev = 0;
-      PHY_HIP_CHECK(hipGetDevice(&dev), SRSRAN_ERROR);
-      PHY_HIP_CHECK(hipMalloc(&h->d_unit_counter, sizeof(uint32_t)), SRSRAN_ERROR);
-      PHY_HIP_CHECK(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev), SRSRAN_ERROR);
-    }
-    PHY_HIP_CHECK(hipMemsetAsync(h->d_unit_counter, 0, sizeof(uint32_t), stream), SRSRAN_ERROR);
-    p.n_units      = ceil_div(n_cb, 8);
-    p.max_resident = (uint32_t)h->cus * 8u; // 4 SIMDs x 2 waves
-    p.unit_counter = h->d_unit_counter;
-  }
   return launch(h, r, p, stream, final_run);
 }
 

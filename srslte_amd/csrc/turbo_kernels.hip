@@ -1,10 +1,10 @@
-// turbo_kernels.hip -- LTE turbo decoder (max-log-MAP SISO + QPP interleaver) for gfx950.
+// turbo_kernels.hip -- LTE turbo decoder (max-log-MAP SISO + QPP interleaver) for gfx950: the window decoders' throughput kernel.
 //
 // Bit-exact re-design of the decoders srsran_tdec_run_all() dispatches to on an AVX2 host
 // (reference: lib/src/phy/fec/turbo/turbodecoder.c:381-408):
 //   * window decoder, 16 sub-blocks  (turbodecoder_win.h, WINIMP_IS_AVX16)  K%16==0 && K>800
 //   * window decoder,  8 sub-blocks  (turbodecoder_win.h, WINIMP_IS_SSE16)  K%8==0  && K>400
-//   * scalar decoder                 (turbodecoder_gen.c)                   otherwise
+//   * scalar decoder                 (turbodecoder_gen.c)                   otherwise      -> turbo_gen_kernels.hip
 //
 // MI355X mapping (not the SIMD layout of the reference):
 //   * one lane owns TWO adjacent sub-blocks of one code block, packed as int16x2 in one VGPR; all 8
@@ -25,27 +25,11 @@
 #include "hip_common.h"
 #include "turbo_arith.h"
 #include "turbo_device.h"
+#include "turbo_extract.h"
+#include "turbo_layout.h"
 
 namespace phyhip {
 namespace turbo {
-
-// Non-temporal workspace loads (NT): nothing the fixed-iteration 16-bit decoder reads is read again before several hundred KB per
-// wave have passed, so keeping it in L2 only evicts lines that are still being written.  Measured on one box (K = 6144, 65,520 blocks,
-// 8 half iterations): 12.03 ms without, 11.81 ms with the systematic / parity operands non-temporal, 11.74 ms with the exchanged rows
-// too, 11.58 ms with the check-points as well; non-temporal STORES cost (12.2 ms).  The 8-bit decoders (14.7 -> 15.8 ms) and the
-// early-stop mode (-2.5 % on the transport-block benches) lose with it -- their smaller, partly re-touched working sets do hit in L2 --
-// so NT = fixed iterations and int16 only.
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4 ws_load16(const void* p)
-{
-  if constexpr (NT) {
-    const u4v v = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-  } else {
-    return *reinterpret_cast<const uint4*>(p);
-  }
-}
 
 // one backward step, turbodecoder_win.h:626-652
 template <class AR>
@@ -112,57 +96,22 @@ __device__ __forceinline__ s2 alpha_step(s2 (&o)[8], const s2 (&b)[8], s2 x, s2 
   return out;
 }
 
-__device__ __forceinline__ short wrap16(int v)
+// The forward warm-up leaves the operands of the last four blocks in this lane's slots of the beta buffer, slot s = 0 ... 3 for blocks
+// nblk-4 ... nblk-1; the backward main pass takes them from there (tdec_win_unit says why)
+__device__ __forceinline__ void keep_ops(uint4 (&Bl)[8][2][64], uint32_t s, int lane, const s2 (&xs)[8], const s2 (&ys)[8])
 {
-  return (short)v;
+  Bl[2 * s][0][lane]     = make_uint4(to_u(xs[0]), to_u(xs[1]), to_u(xs[2]), to_u(xs[3]));
+  Bl[2 * s][1][lane]     = make_uint4(to_u(xs[4]), to_u(xs[5]), to_u(xs[6]), to_u(xs[7]));
+  Bl[2 * s + 1][0][lane] = make_uint4(to_u(ys[0]), to_u(ys[1]), to_u(ys[2]), to_u(ys[3]));
+  Bl[2 * s + 1][1][lane] = make_uint4(to_u(ys[4]), to_u(ys[5]), to_u(ys[6]), to_u(ys[7]));
 }
-
-// Blocked arrays hold, per 8-step block and lane, 8 dwords.  They are stored as two half-blocks of 4 dwords so
-// that each dwordx4 access of a wave covers one contiguous 1 KB (measured: 5.5 TB/s against 4.5 TB/s for a
-// 32-byte-per-lane layout where every 128-byte line is touched by two instructions).
-template <bool NT = false>
-__device__ __forceinline__ void load_block(const uint32_t* arr, uint32_t blk_lane, uint32_t (&r)[8])
+__device__ __forceinline__ void kept_ops(const uint4 (&Bl)[8][2][64], uint32_t s, int lane, s2 (&xs)[8], s2 (&ys)[8])
 {
-  const uint32_t blk = blk_lane >> 6, ln = blk_lane & 63u;
-  const uint4    a = ws_load16<NT>(arr + ((size_t)(blk * 2) * 64 + ln) * 4);
-  const uint4    c = ws_load16<NT>(arr + ((size_t)(blk * 2 + 1) * 64 + ln) * 4);
-  r[0] = a.x;
-  r[1] = a.y;
-  r[2] = a.z;
-  r[3] = a.w;
-  r[4] = c.x;
-  r[5] = c.y;
-  r[6] = c.z;
-  r[7] = c.w;
-}
-
-__device__ __forceinline__ void store_block(uint32_t* arr, uint32_t blk_lane, const uint32_t (&r)[8])
-{
-  const uint32_t blk = blk_lane >> 6, ln = blk_lane & 63u;
-  *reinterpret_cast<uint4*>(arr + ((size_t)(blk * 2) * 64 + ln) * 4)     = make_uint4(r[0], r[1], r[2], r[3]);
-  *reinterpret_cast<uint4*>(arr + ((size_t)(blk * 2 + 1) * 64 + ln) * 4) = make_uint4(r[4], r[5], r[6], r[7]);
-}
-
-// exchange tables: 8 dwords per (block, lane of the code block), contiguous
-__device__ __forceinline__ void load_lut(const uint32_t* arr, uint32_t idx, uint32_t (&r)[8])
-{
-  const uint4* q = reinterpret_cast<const uint4*>(arr + (size_t)idx * 8);
-  const uint4  a = q[0], c = q[1];
-  r[0] = a.x;
-  r[1] = a.y;
-  r[2] = a.z;
-  r[3] = a.w;
-  r[4] = c.x;
-  r[5] = c.y;
-  r[6] = c.z;
-  r[7] = c.w;
-}
-
-// Blocked int16 index of trellis step k of sub-block d (LPC lanes per code block)
-template <int LPC>
-__host__ __device__ __forceinline__ uint32_t elem_index(uint32_t k, uint32_t d)
-{
-  return ((((k >> 3) * LPC + (d >> 1)) * 8 + (k & 7)) << 1) + (d & 1);
+  const uint4 x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
+  xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
+  xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
+  ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
+  ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -178,376 +127,10 @@ __host__ __device__ __forceinline__ uint32_t elem_index(uint32_t k, uint32_t d)
 // trellis step land in ONE row of the destination, permuted.  So the extrinsic exchange is, per step,
 // one in-register permutation across the lanes of the code block (ds_bpermute) and one full 32-byte
 // row store -- never a 2-byte scatter.
+// The arrays' layouts and their loads / stores: turbo_layout.h; phase 0, the input extraction: turbo_extract.h.
 // ------------------------------------------------------------------------------------------------
-// rows of the 64/LPC code blocks of a wave are interleaved: row k of the wave is 64 contiguous dwords
-__device__ __forceinline__ void load_rows(const uint32_t* arr, uint32_t b, int lane, uint32_t (&r)[8])
-{
-  const uint32_t* q = arr + (size_t)(b * 8) * 64 + lane;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    r[j] = q[j * 64];
-  }
-}
 
-// The same 8 rows fetched with TWO dwordx4 per lane (the 2 KB of rows 8b..8b+7 are contiguous): dword-per-lane
-// loads top out near 3 TB/s on this part, 16-byte ones reach 5.5 TB/s.  Lane L then holds columns 4(L%16)..+3
-// of rows L/16 and 4 + L/16; rows_to_lane() turns that into "8 rows of column L" through a 2 KB LDS image.
-template <bool NT = false>
-__device__ __forceinline__ void issue_rows(const uint32_t* arr, uint32_t b, int lane, uint32_t (&t)[8])
-{
-  const uint4* q = reinterpret_cast<const uint4*>(arr + (size_t)(b * 8) * 64) + lane;
-  const uint4  a = ws_load16<NT>(q), c = ws_load16<NT>(q + 64);
-  t[0] = a.x;
-  t[1] = a.y;
-  t[2] = a.z;
-  t[3] = a.w;
-  t[4] = c.x;
-  t[5] = c.y;
-  t[6] = c.z;
-  t[7] = c.w;
-}
-
-__device__ __forceinline__ void rows_to_lane(uint32_t* stage, int lane, const uint32_t (&t)[8], uint32_t (&r)[8])
-{
-  // one wave per workgroup and the LDS pipeline is in order: no barrier between the write and the read
-  reinterpret_cast<uint4*>(stage)[lane]      = make_uint4(t[0], t[1], t[2], t[3]);
-  reinterpret_cast<uint4*>(stage)[64 + lane] = make_uint4(t[4], t[5], t[6], t[7]);
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    r[j] = stage[j * 64 + lane];
-  }
-}
-
-// ---- storage policy.  The 16-bit decoders keep one int16x2 dword per (lane, step) in the workspace.  The 8-bit decoders' values are
-// int8 by construction (in registers: value << 8 in each int16 half, low bytes zero -- see Ar8), so their workspace holds ONE 16-bit
-// word per (lane, step): half the HBM traffic of a kernel that runs at the HBM ceiling.  S8 = AR::kIs8 selects the layout:
-//   blocked arrays (S, P0, P1, check-points): 8 steps of a lane = 16 bytes = ONE dwordx4 (1 KB contiguous per wave instruction)
-//   row arrays (A1, A2, D): a row of the wave = 64 x 2 bytes; the 8 rows of a block are 1 KB = ONE dwordx4 per lane
-// Loads stay PACKED in the prefetch registers (4 dwords instead of 8 per operand block) and are widened where they are consumed:
-// one v_perm_b32 per step puts the two bytes into the high bytes of the halves; one v_perm_b32 packs two steps for a store.
-__device__ __forceinline__ uint32_t s8_unpack_lo(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x010c000cu); } // bytes 0, 1
-__device__ __forceinline__ uint32_t s8_unpack_hi(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x030c020cu); } // bytes 2, 3
-__device__ __forceinline__ uint32_t s8_pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07050301u); } // (a.b1, a.b3, b.b1, b.b3)
-__device__ __forceinline__ uint16_t s8_pack1(uint32_t a) { return (uint16_t)__builtin_amdgcn_perm(0u, a, 0x0c0c0301u); }
-
-// raw (as stored) form of one 8-step block of a blocked array: 8 dwords, or 4 with 8-bit storage
-template <bool S8, bool NT = false>
-__device__ __forceinline__ void load_block_raw(const uint32_t* arr, uint32_t blk_lane, uint32_t (&r)[8])
-{
-  if constexpr (S8) {
-    const uint4 a = ws_load16<NT>(arr + (size_t)blk_lane * 4);
-    r[0] = a.x;
-    r[1] = a.y;
-    r[2] = a.z;
-    r[3] = a.w;
-  } else {
-    load_block<NT>(arr, blk_lane, r);
-  }
-}
-// raw -> the 8 int16x2 values of the block
-template <bool S8>
-__device__ __forceinline__ void block_values(const uint32_t (&raw)[8], uint32_t (&v)[8])
-{
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    v[2 * d]     = S8 ? s8_unpack_lo(raw[d]) : raw[2 * d];
-    v[2 * d + 1] = S8 ? s8_unpack_hi(raw[d]) : raw[2 * d + 1];
-  }
-}
-template <bool S8>
-__device__ __forceinline__ void store_block_v(uint32_t* arr, uint32_t blk_lane, const uint32_t (&v)[8])
-{
-  if constexpr (S8) {
-    *reinterpret_cast<uint4*>(arr + (size_t)blk_lane * 4) = make_uint4(s8_pack2(v[0], v[1]), s8_pack2(v[2], v[3]), s8_pack2(v[4], v[5]), s8_pack2(v[6], v[7]));
-  } else {
-    store_block(arr, blk_lane, v);
-  }
-}
-// the 8 rows of block b of a row array, as stored: two dwordx4 per lane, or one with 8-bit storage
-template <bool S8, bool NT = false>
-__device__ __forceinline__ void issue_rows_raw(const uint32_t* arr, uint32_t b, int lane, uint32_t (&t)[8])
-{
-  if constexpr (S8) {
-    const uint4 a = ws_load16<NT>(reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(arr) + (size_t)(b * 8) * 64) + lane);
-    t[0] = a.x;
-    t[1] = a.y;
-    t[2] = a.z;
-    t[3] = a.w;
-  } else {
-    issue_rows<NT>(arr, b, lane, t);
-  }
-}
-// ... turned into "8 rows of this lane's column" (int16x2 values) through the LDS stage
-template <bool S8>
-__device__ __forceinline__ void rows_to_lane_v(uint32_t* stage, int lane, const uint32_t (&t)[8], uint32_t (&r)[8])
-{
-  if constexpr (S8) {
-    reinterpret_cast<uint4*>(stage)[lane] = make_uint4(t[0], t[1], t[2], t[3]); // in-order LDS pipeline, one wave per workgroup: no barrier
-    const uint16_t* s16 = reinterpret_cast<const uint16_t*>(stage);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      r[j] = s8_unpack_lo((uint32_t)s16[j * 64 + lane]);
-    }
-  } else {
-    rows_to_lane(stage, lane, t, r);
-  }
-}
-// one element of a row array: (row, lane) <- int16x2 value
-template <bool S8>
-__device__ __forceinline__ void store_row(uint32_t* arr, size_t row, int lane, uint32_t v)
-{
-  if constexpr (S8) {
-    reinterpret_cast<uint16_t*>(arr)[row * 64 + lane] = s8_pack1(v);
-  } else {
-    arr[row * 64 + lane] = v;
-  }
-}
-
-// value for this lane's two destination sub-blocks, fetched from the lanes holding the source sub-blocks
-template <int LPC>
-__device__ __forceinline__ uint32_t permute_pair(uint32_t v, uint32_t sel)
-{
-  const uint32_t jlo = sel & 31u, jhi = (sel >> 5) & 31u;
-  const uint32_t a   = __shfl(v, (int)(jlo >> 1), LPC);
-  const uint32_t c   = __shfl(v, (int)(jhi >> 1), LPC);
-  const uint32_t lo  = (jlo & 1u) ? (a >> 16) : (a & 0xffffu);
-  const uint32_t hi  = (jhi & 1u) ? (c >> 16) : (c & 0xffffu);
-  return lo | (hi << 16);
-}
-
-// phase 0: input extraction (turbodecoder_win.h:888-930 / turbodecoder_iter.h:58-70,88-102) from int16 or int8
-// LLRs.  All 48 element loads of an 8-step block are issued before the first use (addresses clamped instead
-// of branching on the ragged last block), so the block costs one memory round trip, not eight.
-template <int LPC, class AR, typename T>
-__device__ __forceinline__ void extract_input(const T* in, int sb_layout, uint32_t K, uint32_t long_sb, uint32_t nblk,
-                                              int lane, int pl, uint32_t* S, uint32_t* P0, uint32_t* P1, short* TL,
-                                              uint32_t b_first = 0, bool tails = true)
-{
-  constexpr int NB = 2 * LPC;
-  for (uint32_t b = b_first; b < nblk; b++) {
-    const int nv = (int)(long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8; // valid steps in this block
-    short     r[2][24];
-    if (sb_layout) {
-      // rm_turbo layout: element (step k, sub-block d) of array a at in[a*(K+32) + k*NB + d]
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const uint32_t k = b * 8 + (j < nv ? j : nv - 1);
-#pragma unroll
-        for (int a3 = 0; a3 < 3; a3++) {
-          r[0][3 * j + a3] = AR::conv_in(in[a3 * (K + 32) + k * NB + 2 * pl]);
-          r[1][3 * j + a3] = AR::conv_in(in[a3 * (K + 32) + k * NB + 2 * pl + 1]);
-        }
-      }
-    } else {
-      // natural order: the 8 steps of one sub-block are 24 consecutive LLRs [s p0 p1]...
-      const T*  c0  = in + 3 * ((size_t)(2 * pl) * long_sb + b * 8);
-      const T*  c1  = in + 3 * ((size_t)(2 * pl + 1) * long_sb + b * 8);
-      const int lim = 3 * nv - 1;
-#pragma unroll
-      for (int t = 0; t < 24; t++) {
-        const int tt = t < lim ? t : lim;
-        r[0][t]      = AR::conv_in(c0[tt]);
-        r[1][t]      = AR::conv_in(c1[tt]);
-      }
-    }
-    uint32_t s[8], y0[8], y1[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      s[j]  = (uint32_t)(uint16_t)r[0][3 * j] | ((uint32_t)(uint16_t)r[1][3 * j] << 16);
-      y0[j] = (uint32_t)(uint16_t)r[0][3 * j + 1] | ((uint32_t)(uint16_t)r[1][3 * j + 1] << 16);
-      y1[j] = (uint32_t)(uint16_t)r[0][3 * j + 2] | ((uint32_t)(uint16_t)r[1][3 * j + 2] << 16);
-    }
-    store_block_v<AR::kIs8>(S, b * 64 + lane, s);
-    store_block_v<AR::kIs8>(P0, b * 64 + lane, y0);
-    store_block_v<AR::kIs8>(P1, b * 64 + lane, y1);
-  }
-  if (pl == 0 && tails) {
-    const uint32_t tb = sb_layout ? 3 * (K + 32) : 3 * K;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      TL[i]     = AR::conv_in(in[tb + 2 * i]);         // syst tail
-      TL[3 + i] = AR::conv_in(in[tb + 2 * i + 1]);     // parity0 tail
-      TL[6 + i] = AR::conv_in(in[tb + 6 + 2 * i]);     // app2 tail
-      TL[9 + i] = AR::conv_in(in[tb + 6 + 2 * i + 1]); // parity1 tail
-    }
-  }
-}
-
-// Fast input extraction for natural-order int16 LLRs [s p0 p1]xK (what srsran_tdec_run_all gets with
-// srsran_tdec_force_not_sb): the stream is sub-block major (the 3W LLRs of a sub-block are contiguous) while the
-// decoder wants step-major data spread over lanes, so every code block of the wave is staged through LDS in chunks of
-// NBK 8-step blocks: the 64 lanes copy the NB contiguous runs of 48*NBK bytes with 8-byte loads (each wave-level load
-// covers >= 256 contiguous bytes), then lane (p', g) assembles the blocked dwords of sub-block pair p' for two blocks
-// and stores them into the slots of the lane that owns that pair.  Needs W % 4 == 0 and 8-byte aligned code blocks.
-template <int LPC, class AR>
-__device__ __forceinline__ void extract_input_natural16(const short* in_wave, uint32_t in_stride, int n_cb_left, uint32_t K,
-                                                        uint32_t long_sb, uint32_t nblk, int lane, uint32_t* S, uint32_t* P0,
-                                                        uint32_t* P1, short* TL_wave, uint2* stage)
-{
-  constexpr int NB  = 2 * LPC;
-  constexpr int CPW = 64 / LPC;
-  constexpr int NBK = 256 / NB;  // blocks per chunk: NB runs of 48*NBK bytes = 12 KB of LDS
-  constexpr int RS  = 6 * NBK + 1; // run stride in the LDS image, in 8-byte units (+1: spreads the LDS banks)
-  const int     pp  = lane % LPC, g = lane / LPC;
-  // chunks are (code block, block range) pairs; the loads of the next chunk are in flight while the current one is
-  // re-distributed (24 8-byte loads per lane and chunk: NB * 6 * NBK / 64)
-  constexpr int NLD = NB * 6 * NBK / 64;
-  const uint32_t nchunk = (nblk + NBK - 1) / NBK, total = CPW * nchunk;
-  auto chunk_src = [&](uint32_t c, const short*& in, uint32_t& b0, int& nbt) {
-    const int cw = (int)(c % CPW); // block range outermost: the 8 code blocks' 128-byte pieces of a 1 KB line are written back to back
-    in           = in_wave + (size_t)(cw < n_cb_left ? cw : n_cb_left - 1) * in_stride;
-    b0           = (c / CPW) * NBK;
-    nbt          = (int)(nblk - b0) < NBK ? (int)(nblk - b0) : NBK;
-  };
-  auto issue_chunk = [&](uint32_t c, uint2(&rg)[NLD]) {
-    const short* in;
-    uint32_t     b0;
-    int          nbt;
-    chunk_src(c, in, b0, nbt);
-    if (nbt == NBK) { // full chunk: the run length is a compile-time constant (no integer division by a variable)
-      constexpr int rl = 6 * NBK;
-#pragma unroll
-      for (int t = 0; t < NLD; t++) {
-        const int i = t * 64 + lane, d = i / rl, o = i - d * rl;
-        rg[t]       = *(reinterpret_cast<const uint2*>(in + 3 * ((size_t)d * long_sb + (size_t)b0 * 8)) + o);
-      }
-    } else {
-      const int rl = 6 * nbt; // run length in 8-byte units
-#pragma unroll
-      for (int t = 0; t < NLD; t++) {
-        const int i = t * 64 + lane;
-        if (i < NB * rl) {
-          const int d = i / rl, o = i - d * rl;
-          rg[t]       = *(reinterpret_cast<const uint2*>(in + 3 * ((size_t)d * long_sb + (size_t)b0 * 8)) + o);
-        }
-      }
-    }
-  };
-  uint2 rg[NLD];
-  issue_chunk(0, rg);
-  for (uint32_t c = 0; c < total; c++) {
-    const short* in;
-    uint32_t     b0;
-    int          nbt;
-    chunk_src(c, in, b0, nbt);
-    const int cw = (int)(c % CPW);
-    if (nbt == NBK) {
-      constexpr int rl = 6 * NBK;
-#pragma unroll
-      for (int t = 0; t < NLD; t++) {
-        const int i = t * 64 + lane, d = i / rl, o = i - d * rl;
-        stage[d * RS + o] = rg[t];
-      }
-    } else {
-      const int rl = 6 * nbt;
-#pragma unroll
-      for (int t = 0; t < NLD; t++) {
-        const int i = t * 64 + lane;
-        if (i < NB * rl) {
-          const int d = i / rl, o = i - d * rl;
-          stage[d * RS + o] = rg[t];
-        }
-      }
-    }
-    if (c + 1 < total) {
-      issue_chunk(c + 1, rg);
-    }
-    {
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int lb = g * 2 + h; // NBK * LPC / 64 == 2 blocks per lane
-        if (lb < nbt) {
-          short r[2][24];
-#pragma unroll
-          for (int dd = 0; dd < 2; dd++) {
-            const uint2* q = stage + (2 * pp + dd) * RS + lb * 6;
-#pragma unroll
-            for (int t = 0; t < 6; t++) {
-              const uint2 v    = q[t];
-              r[dd][4 * t]     = (short)(v.x & 0xffffu);
-              r[dd][4 * t + 1] = (short)(v.x >> 16);
-              r[dd][4 * t + 2] = (short)(v.y & 0xffffu);
-              r[dd][4 * t + 3] = (short)(v.y >> 16);
-            }
-          }
-          uint32_t sv[8], y0[8], y1[8];
-#pragma unroll
-          for (int j = 0; j < 8; j++) {
-            sv[j] = (uint32_t)(uint16_t)AR::conv_in(r[0][3 * j]) | ((uint32_t)(uint16_t)AR::conv_in(r[1][3 * j]) << 16);
-            y0[j] = (uint32_t)(uint16_t)AR::conv_in(r[0][3 * j + 1]) | ((uint32_t)(uint16_t)AR::conv_in(r[1][3 * j + 1]) << 16);
-            y1[j] = (uint32_t)(uint16_t)AR::conv_in(r[0][3 * j + 2]) | ((uint32_t)(uint16_t)AR::conv_in(r[1][3 * j + 2]) << 16);
-          }
-          const uint32_t slot = (b0 + lb) * 64 + cw * LPC + pp;
-          store_block_v<AR::kIs8>(S, slot, sv);
-          store_block_v<AR::kIs8>(P0, slot, y0);
-          store_block_v<AR::kIs8>(P1, slot, y1);
-        }
-      }
-    }
-  }
-  // tail LLRs: lane cw * LPC of every code block
-  if (pp == 0) {
-    const short* in = in_wave + (size_t)(g < n_cb_left ? g : n_cb_left - 1) * in_stride;
-    short*       TL = TL_wave + 16 * g;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      TL[i]     = AR::conv_in(in[3 * K + 2 * i]);
-      TL[3 + i] = AR::conv_in(in[3 * K + 2 * i + 1]);
-      TL[6 + i] = AR::conv_in(in[3 * K + 6 + 2 * i]);
-      TL[9 + i] = AR::conv_in(in[3 * K + 6 + 2 * i + 1]);
-    }
-  }
-}
-
-// Fast input extraction for the rm_turbo sub-block layout (int16): element (step k, sub-block d) of stream a sits at
-// in[a (K+32) + k NB + d], i.e. the 8 steps of a block are 8 * NB contiguous int16 per code block and stream.  The LPC
-// lanes of a code block fetch them with two dwordx4 each (128 contiguous bytes per code block and instruction) and the
-// [step][sub-block pair] image is turned into "8 steps of pair p" through the 2 KB LDS stage.  Handles the `nblk` full
-// 8-step blocks it is given (a ragged last block goes through extract_input); needs 16-byte aligned code blocks.
-template <int LPC, class AR>
-__device__ __forceinline__ void extract_input_sb16(const short* in, uint32_t K, uint32_t nblk, int lane, int pl, uint32_t* S,
-                                                   uint32_t* P0, uint32_t* P1, short* TL, uint32_t* stage)
-{
-  constexpr int  NB  = 2 * LPC;
-  const int      cbw = lane / LPC;
-  uint4*         st4 = reinterpret_cast<uint4*>(stage);
-  // one stream (systematic / parity 0 / parity 1) of one 8-step block: two 16-byte pieces per lane through the staging image
-  auto put = [&](uint32_t* dst, uint32_t b, const uint4& lo, const uint4& hi) {
-    st4[cbw * 2 * LPC + pl]       = lo;
-    st4[cbw * 2 * LPC + LPC + pl] = hi;
-    uint32_t r[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const uint32_t w = stage[cbw * 8 * LPC + j * LPC + pl];
-      r[j] = (uint32_t)(uint16_t)AR::conv_in((short)(w & 0xffffu)) | ((uint32_t)(uint16_t)AR::conv_in((short)(w >> 16)) << 16);
-    }
-    store_block_v<AR::kIs8>(dst, b * 64 + lane, r);
-  };
-  for (uint32_t b = 0; b < nblk; b++) {
-    // all six loads of the block are issued before the first use (named registers: an indexed local array ends up in scratch)
-    const uint4* q0 = reinterpret_cast<const uint4*>(in + (size_t)b * 8 * NB);
-    const uint4* q1 = reinterpret_cast<const uint4*>(in + (size_t)(K + 32) + (size_t)b * 8 * NB);
-    const uint4* q2 = reinterpret_cast<const uint4*>(in + (size_t)2 * (K + 32) + (size_t)b * 8 * NB);
-    const uint4  s_lo = q0[pl], s_hi = q0[LPC + pl];
-    const uint4  y_lo = q1[pl], y_hi = q1[LPC + pl];
-    const uint4  z_lo = q2[pl], z_hi = q2[LPC + pl];
-    put(S, b, s_lo, s_hi);
-    put(P0, b, y_lo, y_hi);
-    put(P1, b, z_lo, z_hi);
-  }
-  if (pl == 0) {
-    const uint32_t tb = 3 * (K + 32);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      TL[i]     = AR::conv_in(in[tb + 2 * i]);
-      TL[3 + i] = AR::conv_in(in[tb + 2 * i + 1]);
-      TL[6 + i] = AR::conv_in(in[tb + 6 + 2 * i]);
-      TL[9 + i] = AR::conv_in(in[tb + 6 + 2 * i + 1]);
-    }
-  }
-}
-
-// One unit of work: the CPW = 64 / LPC code blocks wb * CPW ... of the batch, decoded by one wave in the workspace slab `slab`.
+// One unit of work: the CPW = 64 / LPC code blocks wb * CPW ... of the batch, decoded by one wave in the workspace slab wb.
 // Bl: re-derived backward metrics of the current 8-step block (8 steps x 8 states x int16x2 per lane) -- and, while the forward main pass
 // does not run, the operands the forward warm-up hands to the backward pass, the staging image of the input extraction and the
 // hard decision's byte / bit images; Tr: staging image of 8 exchanged rows (rows_to_lane).
@@ -555,7 +138,7 @@ __device__ __forceinline__ void extract_input_sb16(const short* in, uint32_t K, 
 // the per-block descriptors must not cost the fixed-iteration kernel registers (it runs at 2 waves per SIMD).
 // CKS: spacing of the backward check-points in trellis steps, 8 or 16 (win_ck_spacing, below, says which instantiation takes which).
 template <int LPC, class AR, bool ES, int CKS>
-__device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t wb, const uint32_t slab, const int lane, uint4 (&Bl)[8][2][64],
+__device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t wb, const int lane, uint4 (&Bl)[8][2][64],
                                               uint32_t (&Tr)[512])
 {
   const uint32_t crc_poly = ES ? p.crc_poly : 0u;
@@ -580,7 +163,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   // granularity: every wave-level load/store touches one contiguous 256 B (dword) or 1 KB (dwordx4) run,
   // and the per-step row exchange of all the wave's code blocks is a single contiguous 256 B store.
   const uint32_t AWG = AW * CPW; // dwords per array per wave
-  uint32_t* ws  = p.ws + (size_t)slab * p.ws_stride * CPW;
+  uint32_t* ws  = p.ws + (size_t)wb * p.ws_stride * CPW;
   uint32_t* S   = ws;
   uint32_t* P0  = ws + AWG;
   uint32_t* P1  = ws + 2 * AWG;
@@ -621,7 +204,6 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   const uint32_t wrap_row = (AR::kIs8 && (K & 31u)) ? long_sb - 1 : 0xffffffffu;
   __syncthreads();
 
-  // ---- half iterations (turbodecoder_iter.h:72-141)
   // ---- hard decision (turbodecoder.c:370-378 + turbodecoder_win.h:973-993): bit = LLR > 0, MSB first.
   // Source: app1 after an even number of half iterations, else ext1; the last half iteration filed it in D.
   // With a CRC generator the checksum of the K hard bits is formed on the way (sch.c:430-447: zero means the code
@@ -644,8 +226,8 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   if (ES) {
     set_masks(!live);
   }
-#define M_OWN (ES ? m_own_v : ~0u)
-#define M_ROW (ES ? m_row_v : ~0u)
+  auto m_own = [&]() -> uint32_t { return ES ? m_own_v : ~0u; }; // (without early stop both fold to "no mask")
+  auto m_row = [&]() -> uint32_t { return ES ? m_row_v : ~0u; };
   // A launch that completes the run (WinParams::final_run) files, in its last half iteration, one sign bit per value instead: row k
   // of the wave is 16 bytes at D + 4 k dwords, the 64-bit masks (one bit per lane) of the low and of the high sub-block.
   const bool bit_rows = !ES && p.final_run && !p.dec_llr && p.n_end > p.n_begin;
@@ -683,7 +265,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
       for (uint32_t b = 0; b < nblk; b++) {
         if (!bit_rows && b + 1 < nblk) {
-          issue_rows_raw<AR::kIs8, NT>(D, (b + 1) & M_ROW, lane, tn);
+          issue_rows_raw<AR::kIs8, NT>(D, (b + 1) & m_row(), lane, tn);
         }
         uint32_t r[8];
         if (bit_rows) {
@@ -817,6 +399,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   bool     done = false; // early stop: the CRC of this code block has matched
   uint32_t noi  = 0;     // half iterations run for this code block in this launch (sch.c:424: cb_noi)
 
+  // ---- half iterations (turbodecoder_iter.h:72-141)
   for (uint32_t n = p.n_begin; n < p.n_end; n++) {
     const bool      dec1    = !(n & 1);
     const bool      has_app = dec1 && n > 0;
@@ -852,13 +435,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         issue_rows_raw<AR::kIs8, NT>(A1, ba, la, q.a);
       } else {
         if (dec1) {
-          load_block_raw<AR::kIs8, NT>(S, (b & M_OWN) * 64 + lane, q.x);
+          load_block_raw<AR::kIs8, NT>(S, (b & m_own()) * 64 + lane, q.x);
         } else {
-          issue_rows_raw<AR::kIs8, NT>(A2, b & M_ROW, lane, q.x);
+          issue_rows_raw<AR::kIs8, NT>(A2, b & m_row(), lane, q.x);
         }
-        load_block_raw<AR::kIs8, NT>(Y, (b & M_OWN) * 64 + lane, q.y);
+        load_block_raw<AR::kIs8, NT>(Y, (b & m_own()) * 64 + lane, q.y);
         if (has_app) {
-          issue_rows_raw<AR::kIs8, NT>(A1, b & M_ROW, lane, q.a);
+          issue_rows_raw<AR::kIs8, NT>(A1, b & m_row(), lane, q.a);
         }
       }
     };
@@ -917,11 +500,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         s2 xs[8], ys[8], ap[8];
         prep(cur, xs, ys, ap);
         if (b + 4 > bl) {
-          const uint32_t s = b + 3 - bl;
-          Bl[2 * s][0][lane]     = make_uint4(to_u(xs[0]), to_u(xs[1]), to_u(xs[2]), to_u(xs[3]));
-          Bl[2 * s][1][lane]     = make_uint4(to_u(xs[4]), to_u(xs[5]), to_u(xs[6]), to_u(xs[7]));
-          Bl[2 * s + 1][0][lane] = make_uint4(to_u(ys[0]), to_u(ys[1]), to_u(ys[2]), to_u(ys[3]));
-          Bl[2 * s + 1][1][lane] = make_uint4(to_u(ys[4]), to_u(ys[5]), to_u(ys[6]), to_u(ys[7]));
+          keep_ops(Bl, b + 3 - bl, lane, xs, ys);
         }
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -977,9 +556,9 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         uint32_t u   = to_u(o[i]);
-        uint32_t nxt = __shfl_down(u, 1, LPC);
+        uint32_t nbr = __shfl_down(u, 1, LPC);
         uint32_t lo  = u >> 16;
-        uint32_t hi  = (pl == LPC - 1) ? (uint32_t)(uint16_t)tr[i] : (nxt & 0xffffu);
+        uint32_t hi  = (pl == LPC - 1) ? (uint32_t)(uint16_t)tr[i] : (nbr & 0xffffu);
         o[i]         = from_u(lo | (hi << 16));
       }
       uint32_t ck[8];
@@ -987,7 +566,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       for (int i = 0; i < 8; i++) {
         ck[i] = to_u(o[i]);
       }
-      store_block_v<AR::kIs8>(CK, (nblk & M_OWN) * 64 + lane, ck);
+      store_block_v<AR::kIs8>(CK, (nblk & m_own()) * 64 + lane, ck);
     }
     // pass 1: whole sub-block, keep a check-point at every block boundary (CKS = 16: at every even one, the odd slots of CK stay unused).
     // Blocks nblk-1 ... nblk-4 come from the beta buffer; the first one fetched from HBM is `top` = nblk-5 (a sub-block has more than 40
@@ -1003,12 +582,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       auto      block = [&](int b, const Ops& c, Ops& tgt) {
         s2 xs[8], ys[8], ap[8];
         if (b > top) {
-          const uint32_t s  = (uint32_t)(b < (int)nblk ? b : (int)nblk - 1) + 4 - nblk;
-          const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
-          xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
-          xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
-          ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
-          ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
+          kept_ops(Bl, (uint32_t)(b < (int)nblk ? b : (int)nblk - 1) + 4 - nblk, lane, xs, ys);
         } else {
           taken(c);
           prep(c, xs, ys, ap);
@@ -1026,7 +600,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
                 for (int i = 0; i < 8; i++) {
                   ck[i] = to_u(o[i]);
                 }
-                store_block_v<AR::kIs8>(CK, ((uint32_t)b & M_OWN) * 64 + lane, ck);
+                store_block_v<AR::kIs8>(CK, ((uint32_t)b & m_own()) * 64 + lane, ck);
               }
               if (AR::norm_at(k)) {
                 AR::normalize(o);
@@ -1051,12 +625,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         }
         s2 xs[8], ys[8], ap[8];
         if (b + 4 >= (int)nblk) {
-          const uint32_t s  = (uint32_t)b + 4 - nblk;
-          const uint4    x0 = Bl[2 * s][0][lane], x1 = Bl[2 * s][1][lane], y0 = Bl[2 * s + 1][0][lane], y1 = Bl[2 * s + 1][1][lane];
-          xs[0] = from_u(x0.x), xs[1] = from_u(x0.y), xs[2] = from_u(x0.z), xs[3] = from_u(x0.w);
-          xs[4] = from_u(x1.x), xs[5] = from_u(x1.y), xs[6] = from_u(x1.z), xs[7] = from_u(x1.w);
-          ys[0] = from_u(y0.x), ys[1] = from_u(y0.y), ys[2] = from_u(y0.z), ys[3] = from_u(y0.w);
-          ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
+          kept_ops(Bl, (uint32_t)b + 4 - nblk, lane, xs, ys);
         } else {
           prep(cur, xs, ys, ap);
         }
@@ -1071,7 +640,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
               for (int i = 0; i < 8; i++) {
                 ck[i] = to_u(o[i]);
               }
-              store_block_v<AR::kIs8>(CK, ((uint32_t)b & M_OWN) * 64 + lane, ck);
+              store_block_v<AR::kIs8>(CK, ((uint32_t)b & m_own()) * 64 + lane, ck);
             }
             if (AR::norm_at(k)) {
               AR::normalize(o);
@@ -1103,7 +672,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     const bool fuse = dec1 && n >= 2;
     const bool last = (n + 1 == p.n_end) || crc_poly; // with early stop every half iteration may be the last
     // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
-    const bool fin  = bit_rows && n + 1 == p.n_end;
+    const bool sign_rows = bit_rows && n + 1 == p.n_end;
 
     // one block of the main pass, in two parts (between them the 16-step form requests its next check-point).
     // rederive: beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the value at the block's upper boundary into
@@ -1161,7 +730,8 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       if constexpr (CKS == 16) {
         // every entry counts as used here, also those behind a ragged block's end: a register that a load may still be writing makes
         // the compiler wait, before its next write, for whatever has been requested since -- the next block's operands
-        asm volatile("" ::"v"(tr[0]), "v"(tr[1]), "v"(tr[2]), "v"(tr[3]), "v"(tr[4]), "v"(tr[5]), "v"(tr[6]), "v"(tr[7]));        // ... and so does the check-point an odd block has requested for the next pair, just before its operand request: here the count that
+        asm volatile("" ::"v"(tr[0]), "v"(tr[1]), "v"(tr[2]), "v"(tr[3]), "v"(tr[4]), "v"(tr[5]), "v"(tr[6]), "v"(tr[7]));
+        // ... and so does the check-point an odd block has requested for the next pair, just before its operand request: here the count that
         // retires it is exact.  At the next block's top it is not: the row stores below sit in conditional arms, the compiler counts the
         // arm with the fewest, and what it leaves in flight there are the last stores, not the operand loads.
         ck_taken();
@@ -1169,8 +739,8 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         if (j < len) {
-          const uint32_t row = tr[j] & 0xffffu & M_OWN;
-          if (fin) {
+          const uint32_t row = tr[j] & 0xffffu & m_own();
+          if (sign_rows) {
             // the values tdec_decision_byte reads (below), reduced to "> 0": one 16-byte row per step, stored by one lane
             const s2       v  = from_u(dec1 ? rawv[j] : permute_pair<LPC>(rawv[j], tr[j] >> 16));
             const uint64_t mx = __ballot(v.x > 0), my = __ballot(v.y > 0);
@@ -1185,7 +755,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
             // what tdec_decision_byte reads (turbodecoder.c:370-378), in natural order: ext1 after decoder 1,
             // the de-interleaved ext2 (= app1 before the subtraction) after decoder 2
             if (dec1) {
-              store_row<AR::kIs8>(D, (b * 8 + j) & M_OWN, lane, rawv[j]);
+              store_row<AR::kIs8>(D, (b * 8 + j) & m_own(), lane, rawv[j]);
             } else {
               store_row<AR::kIs8>(D, row, lane, permute_pair<LPC>(rawv[j], tr[j] >> 16));
             }
@@ -1196,7 +766,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
 
     if constexpr (CKS == 8) {
       uint32_t ck[8], tr[8], ckn[8], trn[8];
-      load_block_raw<AR::kIs8, NT>(CK, (1u & M_OWN) * 64 + lane, ck);
+      load_block_raw<AR::kIs8, NT>(CK, (1u & m_own()) * 64 + lane, ck);
       load_lut(lut, pl, tr);
       if (nblk > 1) {
         issue(1, nxt);
@@ -1208,7 +778,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           issue(b + 2, nx2);
         }
         if (b + 1 < nblk) {
-          load_block_raw<AR::kIs8, NT>(CK, ((b + 2) & M_OWN) * 64 + lane, ckn);
+          load_block_raw<AR::kIs8, NT>(CK, ((b + 2) & m_own()) * 64 + lane, ckn);
           load_lut(lut, (b + 1) * LPC + pl, trn);
         }
         prep(cur, xs, ys, ap);
@@ -1243,7 +813,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       Ops&     q2 = nx2;
       Ops&     q3 = nx3;
       uint32_t ck[8], tr[8];
-      load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & M_OWN) * 64 + lane, ck);
+      load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & m_own()) * 64 + lane, ck);
       issue(1, q1, nblk > 1);
       // The loop is entered with exactly what its back edge brings: one request in flight, everything before it taken.  The waits at the top of
       // the loop are counted for the worse of the two ways in; with all of these requests still open on this one, the count that suits it
@@ -1272,7 +842,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           prep(c, xs, ys, ap);
           rederive_start(len, ckv, st);
           const uint32_t bn = b + 3 < nblk ? b + 3 : nblk;
-          load_block_raw<AR::kIs8, NT>(CK, (bn & M_OWN) * 64 + lane, ck);
+          load_block_raw<AR::kIs8, NT>(CK, (bn & m_own()) * 64 + lane, ck);
           issue(b + 3, tgt, b + 3 < nblk);
         }
         {
@@ -1325,23 +895,21 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     if (crc_poly) {
       // decode_tb_cb (sch.c:420-454): hard bits + CRC after every half iteration; a code block stops at its first
       // match (its bits are written then and never again), the wave stops when all its code blocks have
-      const bool     fin = n + 1 == p.n_end;
-      const bool     wr  = !done; // bits of the last half iteration THIS code block took part in
-      const uint32_t crc = decide(wr, fin);
+      const bool     last_try = n + 1 == p.n_end;
+      const bool     wr       = !done; // bits of the last half iteration THIS code block took part in
+      const uint32_t crc      = decide(wr, last_try);
       if (!done) {
         noi++;
         done = crc == 0;
       }
       set_masks(done || !live);
       __syncthreads();
-      if (__all(done || !live) || fin) {
+      if (__all(done || !live) || last_try) {
         break;
       }
     }
   }
 
-#undef M_OWN
-#undef M_ROW
   if (!crc_poly) {
     decide(true, true);
   } else if (p.noi && live && pl == 0) {
@@ -1361,266 +929,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 {
   __shared__ uint4    Bl[8][2][64];
   __shared__ uint32_t Tr[512];
-  tdec_win_unit<LPC, AR, ES, CKS>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
+  tdec_win_unit<LPC, AR, ES, CKS>(p, blockIdx.x, threadIdx.x, Bl, Tr);
 }
-
-#ifdef SRSRAN_HIP_WITH_VARIANTS // compiled into tools/probe/lib/libsrsran_phy_hip_variants.so only (srslte_amd/build.py --variants)
-// ---- measured alternatives of the launch shape (profiles/r02_turbo_variants.txt, DESIGN.md par. 3.2); selected with
-// SRSRAN_HIP_TDEC_VARIANT for the 16-sub-block int16 decoder without early stop only, never by default.
-// "waves1": one wave per SIMD (half the code blocks in flight, up to 512 VGPRs per lane).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void tdec_win_kernel_waves1(const WinParams p)
-{
-  __shared__ uint4    Bl[8][2][64];
-  __shared__ uint32_t Tr[512];
-  tdec_win_unit<8, Ar16, false, win_ck_spacing<Ar16, false>>(p, blockIdx.x, blockIdx.x, threadIdx.x, Bl, Tr);
-}
-// "persistent": the grid holds only as many workgroups as the chip keeps resident (p.max_resident), every workgroup owns ONE slab and
-// takes units from a counter until the batch is used up, so the workspace could be sized by the residency (1.2 GB) instead of the
-// batch (5.6 GB for 65,520 blocks).  The parameter block and the lane index go through an opaque asm so that what derives from
-// them is not hoisted in front of the loop (without that: 333 spilled VGPRs; with it 47, all in the input extraction).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void tdec_win_kernel_persistent(const WinParams p)
-{
-  __shared__ uint4    Bl[8][2][64];
-  __shared__ uint32_t Tr[512];
-  uint32_t wb = blockIdx.x;
-  while (wb < p.n_units) {
-    auto ka = __builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    const WinParams& q = *(const WinParams*)ka;
-    int lane = threadIdx.x;
-    asm volatile("" : "+v"(lane));
-    tdec_win_unit<8, Ar16, false, win_ck_spacing<Ar16, false>>(q, wb, blockIdx.x, lane, Bl, Tr);
-    __syncthreads();
-    uint32_t nx = 0;
-    if (threadIdx.x == 0) {
-      nx = gridDim.x + atomicAdd(q.unit_counter, 1u);
-    }
-    wb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nx);
-  }
-}
-
-#endif // SRSRAN_HIP_WITH_VARIANTS
-// ------------------------------------------------------------------------------------------------
-// Scalar decoder (turbodecoder_gen.c): one lane per code block, wrapping int16, beta kept in HBM.
-// Used for K <= 400 (AUTO) or SRSRAN_TDEC_GENERIC.  Vectors are stored lane-interleaved
-// [index][64 lanes] so that a wave's accesses coalesce.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gen_acs_beta(short (&old)[8], short x, short y)
-{
-  short xy = wrap16(x + y);
-  short m_b[8], nw[8];
-  m_b[0] = wrap16(old[4] + xy);
-  m_b[1] = old[4];
-  m_b[2] = wrap16(old[5] + y);
-  m_b[3] = wrap16(old[5] + x);
-  m_b[4] = wrap16(old[6] + x);
-  m_b[5] = wrap16(old[6] + y);
-  m_b[6] = old[7];
-  m_b[7] = wrap16(old[7] + xy);
-  nw[0] = old[0];
-  nw[1] = wrap16(old[0] + xy);
-  nw[2] = wrap16(old[1] + x);
-  nw[3] = wrap16(old[1] + y);
-  nw[4] = wrap16(old[2] + y);
-  nw[5] = wrap16(old[2] + x);
-  nw[6] = wrap16(old[3] + xy);
-  nw[7] = old[3];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    old[i] = m_b[i] > nw[i] ? m_b[i] : nw[i];
-  }
-}
-
-__global__ __launch_bounds__(64) void tdec_gen_kernel(const GenParams p)
-{
-  const int lane = threadIdx.x;
-  const int cb   = blockIdx.x * 64 + lane;
-  if (cb >= p.n_cb) {
-    return;
-  }
-  const uint32_t K  = p.K;
-  const uint32_t L  = K + 4; // K + 3 tail (+1 for the beta terminal state)
-  // per-wave slab, element (array, index, lane): ((array_base + index) * 64 + lane)
-  short* ws = p.ws + (size_t)blockIdx.x * p.ws_stride;
-#define GV(base, idx) ws[((size_t)(base) + (idx)) * 64 + lane]
-  const uint32_t oS = 0, oP0 = L, oP1 = 2 * L, oA1 = 3 * L, oA2 = 4 * L, oE1 = 5 * L, oE2 = 6 * L, oB = 7 * L;
-  // beta: 8 * (K+4) from oB
-
-  if (p.n_begin == 0) {
-    // int8 input: the 8-bit API widens to int16 when no 8-bit decoder takes this K (turbodecoder.c:455-478)
-    const size_t       in_off = p.desc ? (size_t)p.desc[cb].in_off : (size_t)cb * p.in_stride;
-    const short*       in16 = p.input + in_off;
-    const signed char* in8  = reinterpret_cast<const signed char*>(p.input) + in_off;
-    auto               in   = [&](uint32_t i) -> short { return p.in_is8 ? (short)in8[i] : in16[i]; };
-    for (uint32_t i = 0; i < K; i++) { // turbodecoder_gen.c:238-258
-      GV(oS, i)  = in(3 * i);
-      GV(oP0, i) = in(3 * i + 1);
-      GV(oP1, i) = in(3 * i + 2);
-    }
-    for (uint32_t i = K; i < K + 3; i++) {
-      GV(oS, i)  = in(3 * K + 2 * (i - K));
-      GV(oP0, i) = in(3 * K + 2 * (i - K) + 1);
-      GV(oA2, i) = in(3 * K + 6 + 2 * (i - K));
-      GV(oP1, i) = in(3 * K + 6 + 2 * (i - K) + 1);
-    }
-  }
-  const uint16_t* inter   = p.inter;
-  const uint16_t* deinter = p.deinter;
-  uint32_t        n_run    = p.n_end; // half iterations completed when the loop is left
-  bool            crc_good = false;
-
-  for (uint32_t n = p.n_begin; n < p.n_end; n++) {
-    const bool     dec1    = !(n & 1);
-    const bool     has_app = dec1 && n > 0;
-    const uint32_t oX = dec1 ? oS : oA2, oY = dec1 ? oP0 : oP1, oOut = dec1 ? oE1 : oE2;
-    if (dec1) {
-      if (n) {
-        for (uint32_t i = 0; i < K; i++) {
-          GV(oA1, i) = wrap16(GV(oA1, i) - GV(oE1, i));
-        }
-      }
-    } else {
-      for (uint32_t i = 0; i < K; i++) {
-        short e = GV(oE1, i);
-        if (n > 1) {
-          e          = wrap16(e - GV(oA1, i));
-          GV(oE1, i) = e;
-        }
-        GV(oA2, deinter[i]) = e;
-      }
-    }
-    // map_gen_beta (turbodecoder_gen.c:58-112)
-    short old[8];
-    old[0] = 0;
-#pragma unroll
-    for (int i = 1; i < 8; i++) {
-      old[i] = -TD_INF;
-    }
-    const uint32_t end = K + 3;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      GV(oB + 8 * end, i) = old[i];
-    }
-    for (int k = (int)end - 1; k >= 0; k--) {
-      short x = GV(oX, k);
-      if (has_app && (uint32_t)k < K) {
-        x = wrap16(x + GV(oA1, k));
-      }
-      short y = GV(oY, k);
-      gen_acs_beta(old, x, y);
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        GV(oB + 8 * k, i) = old[i];
-      }
-      if ((k % 4) == 0 && (uint32_t)k < K) {
-#pragma unroll
-        for (int i = 1; i < 8; i++) {
-          old[i] = wrap16(old[i] - old[0]);
-        }
-        old[0] = 0;
-      }
-    }
-    // map_gen_alpha (turbodecoder_gen.c:114-198)
-    old[0] = 0;
-#pragma unroll
-    for (int i = 1; i < 8; i++) {
-      old[i] = -TD_INF;
-    }
-    for (uint32_t k = 1; k < K + 1; k++) {
-      short x = GV(oX, k - 1);
-      if (has_app) {
-        x = wrap16(x + GV(oA1, k - 1));
-      }
-      short y  = GV(oY, k - 1);
-      short xy = wrap16(x + y);
-      short m_b[8], nw[8];
-      m_b[0] = old[0];
-      m_b[1] = wrap16(old[3] + y);
-      m_b[2] = wrap16(old[4] + y);
-      m_b[3] = old[7];
-      m_b[4] = old[1];
-      m_b[5] = wrap16(old[2] + y);
-      m_b[6] = wrap16(old[5] + y);
-      m_b[7] = old[6];
-      nw[0] = wrap16(old[1] + xy);
-      nw[1] = wrap16(old[2] + x);
-      nw[2] = wrap16(old[5] + x);
-      nw[3] = wrap16(old[6] + xy);
-      nw[4] = wrap16(old[0] + xy);
-      nw[5] = wrap16(old[3] + x);
-      nw[6] = wrap16(old[4] + x);
-      nw[7] = wrap16(old[7] + xy);
-      short m1 = 0, m0 = 0;
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        short bq = GV(oB + 8 * k, i);
-        short v0 = wrap16(m_b[i] + bq);
-        short v1 = wrap16(nw[i] + bq);
-        m0 = (i == 0) ? v0 : (v0 > m0 ? v0 : m0);
-        m1 = (i == 0) ? v1 : (v1 > m1 ? v1 : m1);
-      }
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        old[i] = m_b[i] > nw[i] ? m_b[i] : nw[i];
-      }
-      if ((k % 4) == 0) {
-#pragma unroll
-        for (int i = 1; i < 8; i++) {
-          old[i] = wrap16(old[i] - old[0]);
-        }
-        old[0] = 0;
-      }
-      GV(oOut, k - 1) = wrap16(m1 - m0);
-    }
-    if (!dec1) {
-      for (uint32_t i = 0; i < K; i++) {
-        GV(oA1, inter[i]) = GV(oE2, i);
-      }
-    }
-    n_run = n + 1;
-    if (p.crc_poly) {
-      // decode_tb_cb (sch.c:420-454): the checksum of the K hard bits after every half iteration (crc.c:92-140: MSB first,
-      // zero initial state; zero = the block is good); this lane's block stops at its first match
-      const uint32_t oC = (n_run & 1) ? oE1 : oA1;
-      const uint32_t g  = p.crc_poly & 0xffffffu;
-      uint32_t       c  = 0;
-      for (uint32_t i = 0; i < K; i++) {
-        const uint32_t x = GV(oC, i) > 0 ? 1u : 0u;
-        c = ((c << 1) & 0xffffffu) ^ ((((c >> 23) ^ x) & 1u) ? g : 0u);
-      }
-      if (c == 0) {
-        crc_good = true;
-        break;
-      }
-    }
-  }
-  if (p.noi) {
-    p.noi[cb] = (int)(n_run - p.n_begin);
-  }
-  if (p.crc_ok) {
-    p.crc_ok[cb] = crc_good ? 1 : 0;
-  }
-  // decision (turbodecoder.c:370-378, turbodecoder_gen.c:260-277)
-  const uint32_t oD        = (n_run & 1) ? oE1 : oA1;
-  uint8_t*       out       = p.output + (p.desc ? (size_t)p.desc[cb].out_off : (size_t)cb * p.out_stride);
-  const uint32_t out_bytes = p.desc ? p.desc[cb].out_bytes : K / 8;
-  for (uint32_t jb = 0; jb < out_bytes; jb++) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-      byte |= (GV(oD, jb * 8 + t) > 0 ? 0x80u : 0u) >> t;
-    }
-    out[jb] = (uint8_t)byte;
-  }
-  if (p.dec_llr) {
-    short* o16 = p.dec_llr + (size_t)cb * K;
-    for (uint32_t i = 0; i < K; i++) {
-      o16[i] = GV(oD, i);
-    }
-  }
-#undef GV
-}
-
 
 // ------------------------------------------------------------------------------------------------ launchers
 
@@ -1629,13 +939,6 @@ static hipError_t launch_win_es(int nb, bool arith8, const WinParams& p, hipStre
 {
   const int lpc = nb / 2;
   dim3      grid(ceil_div(p.n_cb, 64 / lpc));
-#ifdef SRSRAN_HIP_WITH_VARIANTS
-  if (!ES && !arith8 && nb == 16 && p.variant == 1) {
-    hipLaunchKernelGGL(tdec_win_kernel_waves1, grid, dim3(64), 0, stream, p);
-  } else if (!ES && !arith8 && nb == 16 && p.variant == 2 && p.unit_counter) {
-    hipLaunchKernelGGL(tdec_win_kernel_persistent, dim3(p.n_units < p.max_resident ? p.n_units : p.max_resident), dim3(64), 0, stream, p);
-  } else
-#endif
   if (!arith8 && nb == 16) {
     hipLaunchKernelGGL((tdec_win_kernel<8, Ar16, ES>), grid, dim3(64), 0, stream, p);
   } else if (!arith8 && nb == 8) {
@@ -1653,13 +956,6 @@ static hipError_t launch_win_es(int nb, bool arith8, const WinParams& p, hipStre
 hipError_t launch_win(int nb, bool arith8, const WinParams& p, hipStream_t stream)
 {
   return (p.crc_poly || p.desc) ? launch_win_es<true>(nb, arith8, p, stream) : launch_win_es<false>(nb, arith8, p, stream);
-}
-
-hipError_t launch_gen(const GenParams& p, hipStream_t stream)
-{
-  dim3 grid(ceil_div(p.n_cb, 64));
-  hipLaunchKernelGGL(tdec_gen_kernel, grid, dim3(64), 0, stream, p);
-  return hipGetLastError();
 }
 
 uint32_t win_elem_index(int nb, uint32_t k, uint32_t d)

@@ -187,8 +187,7 @@ __device__ __forceinline__ void alpha_branches(s2& a, s2 g_own, s2 g_cross, s2& 
 
 __device__ __forceinline__ void load8(const uint32_t* q, uint32_t (&r)[8])
 {
-  const uint4 a = *reinterpret_cast<const uint4*>(q), c = *reinterpret_cast<const uint4*>(q + 4);
-  r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w, r[4] = c.x, r[5] = c.y, r[6] = c.z, r[7] = c.w;
+  unpack8(*reinterpret_cast<const uint4*>(q), *reinterpret_cast<const uint4*>(q + 4), r);
 }
 
 } // namespace lat

@@ -1,0 +1,173 @@
+// turbo_layout.h -- how the throughput window decoder (turbo_kernels.hip) keeps its per-wave workspace in HBM, and the loads / stores of that
+// layout: blocked arrays, row arrays, their 8-bit storage forms and the exchange across the lanes of a code block.  Device code only.
+#pragma once
+#include "turbo_arith.h"
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace phyhip {
+namespace turbo {
+
+// Non-temporal workspace loads (NT): nothing the fixed-iteration 16-bit decoder reads is read again before several hundred KB per
+// wave have passed, so keeping it in L2 only evicts lines that are still being written.  Measured on one box (K = 6144, 65,520 blocks,
+// 8 half iterations): 12.03 ms without, 11.81 ms with the systematic / parity operands non-temporal, 11.74 ms with the exchanged rows
+// too, 11.58 ms with the check-points as well; non-temporal STORES cost (12.2 ms).  The 8-bit decoders (14.7 -> 15.8 ms) and the
+// early-stop mode (-2.5 % on the transport-block benches) lose with it -- their smaller, partly re-touched working sets do hit in L2 --
+// so NT = fixed iterations and int16 only.
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 ws_load16(const void* p)
+{
+  if constexpr (NT) {
+    const u4v v = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const uint4*>(p);
+  }
+}
+
+// Blocked arrays hold, per 8-step block and lane, 8 dwords.  They are stored as two half-blocks of 4 dwords so
+// that each dwordx4 access of a wave covers one contiguous 1 KB (measured: 5.5 TB/s against 4.5 TB/s for a
+// 32-byte-per-lane layout where every 128-byte line is touched by two instructions).
+template <bool NT = false>
+__device__ __forceinline__ void load_block(const uint32_t* arr, uint32_t blk_lane, uint32_t (&r)[8])
+{
+  const uint32_t blk = blk_lane >> 6, ln = blk_lane & 63u;
+  unpack8(ws_load16<NT>(arr + ((size_t)(blk * 2) * 64 + ln) * 4), ws_load16<NT>(arr + ((size_t)(blk * 2 + 1) * 64 + ln) * 4), r);
+}
+
+__device__ __forceinline__ void store_block(uint32_t* arr, uint32_t blk_lane, const uint32_t (&r)[8])
+{
+  const uint32_t blk = blk_lane >> 6, ln = blk_lane & 63u;
+  *reinterpret_cast<uint4*>(arr + ((size_t)(blk * 2) * 64 + ln) * 4)     = make_uint4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<uint4*>(arr + ((size_t)(blk * 2 + 1) * 64 + ln) * 4) = make_uint4(r[4], r[5], r[6], r[7]);
+}
+
+// exchange tables: 8 dwords per (block, lane of the code block), contiguous
+__device__ __forceinline__ void load_lut(const uint32_t* arr, uint32_t idx, uint32_t (&r)[8])
+{
+  const uint4* q = reinterpret_cast<const uint4*>(arr + (size_t)idx * 8);
+  unpack8(q[0], q[1], r);
+}
+
+// Blocked int16 index of trellis step k of sub-block d (LPC lanes per code block)
+template <int LPC>
+__host__ __device__ __forceinline__ uint32_t elem_index(uint32_t k, uint32_t d)
+{
+  return ((((k >> 3) * LPC + (d >> 1)) * 8 + (k & 7)) << 1) + (d & 1);
+}
+
+// Rows of the 64/LPC code blocks of a wave are interleaved: row k of the wave is 64 contiguous dwords.
+// The 8 rows of block b are fetched with TWO dwordx4 per lane (the 2 KB of rows 8b..8b+7 are contiguous): dword-per-lane
+// loads top out near 3 TB/s on this part, 16-byte ones reach 5.5 TB/s.  Lane L then holds columns 4(L%16)..+3
+// of rows L/16 and 4 + L/16; rows_to_lane() turns that into "8 rows of column L" through a 2 KB LDS image.
+template <bool NT = false>
+__device__ __forceinline__ void issue_rows(const uint32_t* arr, uint32_t b, int lane, uint32_t (&t)[8])
+{
+  const uint4* q = reinterpret_cast<const uint4*>(arr + (size_t)(b * 8) * 64) + lane;
+  unpack8(ws_load16<NT>(q), ws_load16<NT>(q + 64), t);
+}
+
+__device__ __forceinline__ void rows_to_lane(uint32_t* stage, int lane, const uint32_t (&t)[8], uint32_t (&r)[8])
+{
+  // one wave per workgroup and the LDS pipeline is in order: no barrier between the write and the read
+  reinterpret_cast<uint4*>(stage)[lane]      = make_uint4(t[0], t[1], t[2], t[3]);
+  reinterpret_cast<uint4*>(stage)[64 + lane] = make_uint4(t[4], t[5], t[6], t[7]);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    r[j] = stage[j * 64 + lane];
+  }
+}
+
+// ---- storage policy.  The 16-bit decoders keep one int16x2 dword per (lane, step) in the workspace.  The 8-bit decoders' values are
+// int8 by construction (in registers: value << 8 in each int16 half, low bytes zero -- see Ar8), so their workspace holds ONE 16-bit
+// word per (lane, step): half the HBM traffic of a kernel that runs at the HBM ceiling.  S8 = AR::kIs8 selects the layout:
+//   blocked arrays (S, P0, P1, check-points): 8 steps of a lane = 16 bytes = ONE dwordx4 (1 KB contiguous per wave instruction)
+//   row arrays (A1, A2, D): a row of the wave = 64 x 2 bytes; the 8 rows of a block are 1 KB = ONE dwordx4 per lane
+// Loads stay PACKED in the prefetch registers (4 dwords instead of 8 per operand block) and are widened where they are consumed:
+// one v_perm_b32 per step puts the two bytes into the high bytes of the halves; one v_perm_b32 packs two steps for a store.
+__device__ __forceinline__ uint32_t s8_unpack_lo(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x010c000cu); } // bytes 0, 1
+__device__ __forceinline__ uint32_t s8_unpack_hi(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x030c020cu); } // bytes 2, 3
+__device__ __forceinline__ uint32_t s8_pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07050301u); } // (a.b1, a.b3, b.b1, b.b3)
+__device__ __forceinline__ uint16_t s8_pack1(uint32_t a) { return (uint16_t)__builtin_amdgcn_perm(0u, a, 0x0c0c0301u); }
+
+// raw (as stored) form of one 8-step block of a blocked array: 8 dwords, or 4 with 8-bit storage
+template <bool S8, bool NT = false>
+__device__ __forceinline__ void load_block_raw(const uint32_t* arr, uint32_t blk_lane, uint32_t (&r)[8])
+{
+  if constexpr (S8) {
+    unpack4(ws_load16<NT>(arr + (size_t)blk_lane * 4), r);
+  } else {
+    load_block<NT>(arr, blk_lane, r);
+  }
+}
+// raw -> the 8 int16x2 values of the block
+template <bool S8>
+__device__ __forceinline__ void block_values(const uint32_t (&raw)[8], uint32_t (&v)[8])
+{
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    v[2 * d]     = S8 ? s8_unpack_lo(raw[d]) : raw[2 * d];
+    v[2 * d + 1] = S8 ? s8_unpack_hi(raw[d]) : raw[2 * d + 1];
+  }
+}
+template <bool S8>
+__device__ __forceinline__ void store_block_v(uint32_t* arr, uint32_t blk_lane, const uint32_t (&v)[8])
+{
+  if constexpr (S8) {
+    *reinterpret_cast<uint4*>(arr + (size_t)blk_lane * 4) = make_uint4(s8_pack2(v[0], v[1]), s8_pack2(v[2], v[3]), s8_pack2(v[4], v[5]), s8_pack2(v[6], v[7]));
+  } else {
+    store_block(arr, blk_lane, v);
+  }
+}
+// the 8 rows of block b of a row array, as stored: two dwordx4 per lane, or one with 8-bit storage
+template <bool S8, bool NT = false>
+__device__ __forceinline__ void issue_rows_raw(const uint32_t* arr, uint32_t b, int lane, uint32_t (&t)[8])
+{
+  if constexpr (S8) {
+    unpack4(ws_load16<NT>(reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(arr) + (size_t)(b * 8) * 64) + lane), t);
+  } else {
+    issue_rows<NT>(arr, b, lane, t);
+  }
+}
+// ... turned into "8 rows of this lane's column" (int16x2 values) through the LDS stage
+template <bool S8>
+__device__ __forceinline__ void rows_to_lane_v(uint32_t* stage, int lane, const uint32_t (&t)[8], uint32_t (&r)[8])
+{
+  if constexpr (S8) {
+    reinterpret_cast<uint4*>(stage)[lane] = make_uint4(t[0], t[1], t[2], t[3]); // in-order LDS pipeline, one wave per workgroup: no barrier
+    const uint16_t* s16 = reinterpret_cast<const uint16_t*>(stage);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      r[j] = s8_unpack_lo((uint32_t)s16[j * 64 + lane]);
+    }
+  } else {
+    rows_to_lane(stage, lane, t, r);
+  }
+}
+// one element of a row array: (row, lane) <- int16x2 value
+template <bool S8>
+__device__ __forceinline__ void store_row(uint32_t* arr, size_t row, int lane, uint32_t v)
+{
+  if constexpr (S8) {
+    reinterpret_cast<uint16_t*>(arr)[row * 64 + lane] = s8_pack1(v);
+  } else {
+    arr[row * 64 + lane] = v;
+  }
+}
+
+// value for this lane's two destination sub-blocks, fetched from the lanes holding the source sub-blocks
+template <int LPC>
+__device__ __forceinline__ uint32_t permute_pair(uint32_t v, uint32_t sel)
+{
+  const uint32_t jlo = sel & 31u, jhi = (sel >> 5) & 31u;
+  const uint32_t a   = __shfl(v, (int)(jlo >> 1), LPC);
+  const uint32_t c   = __shfl(v, (int)(jhi >> 1), LPC);
+  const uint32_t lo  = (jlo & 1u) ? (a >> 16) : (a & 0xffffu);
+  const uint32_t hi  = (jhi & 1u) ? (c >> 16) : (c & 0xffffu);
+  return lo | (hi << 16);
+}
+
+} // namespace turbo
+} // namespace phyhip

@@ -74,6 +74,28 @@ def test_cellsearch_vs_oracle(hiplib, prb, N, frame, alg):
     S.lib().srsran_hip_cellsearch_free(h)
 
 
+@pytest.mark.parametrize("N,frame", [(128, 9600), (2048, 61440)])
+def test_pss_kernel_agrees_with_the_oracle(hiplib, N, frame):
+    """four cells at known delays, alternating subframe 0 / 5: every hypothesis' peak, peak value and PSR against the oracle's"""
+    import srslte_amd as S
+
+    prb = 6 if N == 128 else 100
+    rng = np.random.default_rng(7 * N)
+    cells_id = [3, 151, 302, 500]
+    delays = [0] + [int(rng.integers(0, frame - 15 * N)) for _ in cells_id[1:]]
+    caps = np.stack([_capture(c, prb, N, frame, d, 0.05, rng, sf5=(i % 2 == 1)) for i, (c, d) in enumerate(zip(cells_id, delays))])
+    h, got = _run_batch(S, caps, frame, N, 1)
+    for i, (cid, d) in enumerate(zip(cells_id, delays)):
+        for n2 in range(3):
+            g = got[i * 3 + n2]
+            pk, pv, psr = O.pss_find(caps[i], N, n2)[:3]
+            assert g.peak_pos == pk, (cid, n2, g.peak_pos, pk)
+            assert abs(g.peak_value - pv) <= 1e-4 * pv and abs(g.psr - psr) <= 1e-3 * psr
+        g = got[i * 3 + cid % 3]
+        assert g.peak_pos == d + 15 * N // 2 and g.N_id_1 == cid // 3 and g.sf_idx == (5 if i % 2 else 0)
+    S.lib().srsran_hip_cellsearch_free(h)
+
+
 def test_all_504_physical_cell_ids(hiplib):
     """every physical cell id once (fft 128, one 5 ms capture per id, random delay, alternating subframe 0 / 5): the right hypothesis finds the peak where
     the cell was put, N_id_1 = id / 3 from the 168-entry table and the whole 31 x 31 (m0, m1) space; peak position, m0, m1, N_id_1 and subframe equal to

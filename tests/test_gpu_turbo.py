@@ -73,6 +73,14 @@ def test_manual_implementations(hiplib, impl_g, impl_o, K):
     _check(S, K, getattr(capi, "TDEC_" + impl_g), impl_o, 5, -1.0, (1, 2, 5, 8), seed=K)
 
 
+def test_forty_blocks_of_6144(hiplib):
+    """40 blocks = 5 waves of 8 in the throughput kernel: more than one unit of work, 1 and 4 half iterations"""
+    import srslte_amd as S
+    from srslte_amd import capi
+
+    _check(S, 6144, capi.TDEC_AUTO, O.ORC_TDEC_AUTO, 40, 0.0, [1, 4], seed=5)
+
+
 @pytest.mark.parametrize("K", [6144, 5824, 2112, 1024, 1008, 512])
 def test_rm_turbo_subblock_layout(hiplib, K):
     """input in the layout srsran_rm_turbo_rx_lut produces for the window decoders (turbodecoder_iter.h:88-102)"""

@@ -8,6 +8,7 @@
 #include "stage.h"
 #include "tables/lte_qpp_table.h"
 #include "turbo_device.h"
+#include "turbo_layout.h"
 
 #include <map>
 #include <mutex>
@@ -514,13 +515,17 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
   if (nb) {
     const uint32_t lpc = nb / 2, long_sb = K / nb, nblk = (long_sb + 7) / 8;
     h->ws_stride = turbo::win_ws_dwords(K, nb);
-    // Exchange tables, one dword per (step k, destination lane p'), stored blocked [k/8][p'][k%8]:
-    //   bits 0..15  destination row o = PI'(k) mod W  (common to all sub-blocks: QPP is contention free)
-    //   bits 16..20 source sub-block whose output lands in destination sub-block 2p'
-    //   bits 21..25 source sub-block whose output lands in destination sub-block 2p'+1
+    // Exchange tables, one dword per (step k, destination lane p'), stored blocked [k/8][p'][k%8]: the destination row
+    // o = PI'(k) mod W (common to all sub-blocks: QPP is contention free) and the source sub-blocks whose outputs land in destination
+    // sub-blocks 2p' and 2p'+1, encoded by turbo::xch_pack (turbo_layout.h), which the kernels' decode helpers sit next to
     // deint: app2[reverse[n]] = ext1[n]   inter: app1[forward[n]] = ext2[n]   (turbodecoder_iter.h:118,124)
     const size_t tb = (size_t)nblk * lpc * 8 * sizeof(uint32_t);
     bool         contention = false;
+    if (!turbo::xch_fits(long_sb, (uint32_t)nb)) {
+      set_error("window decoder with %d sub-blocks of %u steps does not fit the exchange-table entry", nb, long_sb);
+      delete h;
+      return SRSRAN_ERROR;
+    }
     auto         fill_dir = [&](int dir, void* dst) {
       std::vector<uint16_t> f, r;
       qpp_natural(K, f, r);
@@ -538,7 +543,7 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
           src_of[t / long_sb] = j;
         }
         for (uint32_t pp = 0; pp < lpc; pp++) {
-          out[((k >> 3) * lpc + pp) * 8 + (k & 7)] = row | (src_of[2 * pp] << 16) | (src_of[2 * pp + 1] << 21);
+          out[((k >> 3) * lpc + pp) * 8 + (k & 7)] = turbo::xch_pack(row, src_of[2 * pp], src_of[2 * pp + 1]);
         }
       }
     };

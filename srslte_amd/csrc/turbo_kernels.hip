@@ -148,6 +148,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   constexpr bool NT  = !ES && !AR::kIs8; // non-temporal workspace loads (see ws_load16)
   static_assert(CKS == 8 || CKS == 16, "check-points every 8 or every 16 steps");
   const int     pl   = lane % LPC;
+  const uint32_t xbase = xch_group_base<LPC>(lane); // of the exchange across the lanes of a code block (permute_pair)
   const int     cb_raw = (int)wb * CPW + lane / LPC;
   // Lane groups past the end of the batch stay in the wave: the exchanged rows are loaded 16 bytes per lane and
   // re-distributed through LDS (issue_rows / rows_to_lane), which needs all 64 lanes.  They decode a copy of the last
@@ -661,7 +662,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       o[i] = fw[i];
     }
 
-    const uint32_t* lut = dec1 ? p.deint : p.inter; // per (step, destination lane): row | source sub-blocks
+    const uint32_t* lut = dec1 ? p.deint : p.inter; // per (step, destination lane): row and source sub-blocks (turbo_layout.h: xch_pack)
     uint32_t*       dst = dec1 ? A2 : A1;
     // The subtractions of the NEXT half iteration (turbodecoder_iter.h:108,115) are applied on the way out:
     //   decoder 1: ext1 -= app1 (the a-priori it just used) before the interleaved copy goes to A2
@@ -670,6 +671,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     //              difference is formed before the permutation and no ext1 array is exchanged at all.
     // The raw SISO output is only needed by the hard decision: the LAST half iteration of a launch files it in D.
     const bool fuse = dec1 && n >= 2;
+    // int16: that subtraction wraps, and ap[] is zero wherever no a-priori array is loaded, so every output has ONE subtrahend without a decision per
+    // step: ap[j] | (xs[j] & sub_x) -- decoder 1 subtracts its a-priori value (zero in the first half iteration), decoder 2 its systematic input.
+    // (The 8-bit decoders saturate except in the rows that wrap, and the two modes compare different rows: they keep their arms.)
+    uint32_t sub_x = dec1 ? 0u : ~0u;
+    asm volatile("" : "+s"(sub_x)); // (opaque: a mask known to be 0 or ~0 is turned back into the two arms)
     const bool last = (n + 1 == p.n_end) || crc_poly; // with early stop every half iteration may be the last
     // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
     const bool sign_rows = bit_rows && n + 1 == p.n_end;
@@ -718,10 +724,12 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
             AR::normalize(o);
           }
           s2 proc = llr;
-          if (fuse) {
+          if constexpr (!AR::kIs8) {
+            proc = AR::ex_sub(llr, from_u(to_u(ap[j]) | (to_u(xs[j]) & sub_x)), false);
+          } else if (fuse) {
             proc = AR::ex_sub(llr, ap[j], k == wrap_row);
           } else if (!dec1) {
-            proc = AR::ex_sub(llr, xs[j], (tr[j] & 0xffffu) == wrap_row); // wrap flag: row of the DESTINATION element
+            proc = AR::ex_sub(llr, xs[j], xch_row(tr[j]) == wrap_row); // wrap flag: row of the DESTINATION element
           }
           outv[j] = to_u(proc);
           rawv[j] = to_u(llr);
@@ -736,28 +744,34 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         // arm with the fewest, and what it leaves in flight there are the last stores, not the operand loads.
         ck_taken();
       }
+      // the hot store phase: per step the exchange and one row store, nothing else
+      if (!sign_rows) {
 #pragma unroll
-      for (int j = 0; j < 8; j++) {
-        if (j < len) {
-          const uint32_t row = tr[j] & 0xffffu & m_own();
-          if (sign_rows) {
-            // the values tdec_decision_byte reads (below), reduced to "> 0": one 16-byte row per step, stored by one lane
-            const s2       v  = from_u(dec1 ? rawv[j] : permute_pair<LPC>(rawv[j], tr[j] >> 16));
-            const uint64_t mx = __ballot(v.x > 0), my = __ballot(v.y > 0);
-            if (lane == 0) {
-              *reinterpret_cast<uint4*>(D + (size_t)(dec1 ? b * 8 + j : row) * 4) =
-                  make_uint4((uint32_t)mx, (uint32_t)(mx >> 32), (uint32_t)my, (uint32_t)(my >> 32));
-            }
-            continue;
+        for (int j = 0; j < 8; j++) {
+          if (j < len) {
+            store_xch_row<AR::kIs8>(dst, tr[j], m_own(), lane, permute_pair(outv[j], tr[j], xbase));
           }
-          store_row<AR::kIs8>(dst, row, lane, permute_pair<LPC>(outv[j], tr[j] >> 16));
-          if (last) {
-            // what tdec_decision_byte reads (turbodecoder.c:370-378), in natural order: ext1 after decoder 1,
-            // the de-interleaved ext2 (= app1 before the subtraction) after decoder 2
-            if (dec1) {
+        }
+      }
+      // ... and what only the last half iteration of a launch files, behind ONE decision per block
+      if (last) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          if (j < len) {
+            if (sign_rows) {
+              // the values tdec_decision_byte reads (below), reduced to "> 0": one 16-byte row per step, stored by one lane
+              const s2       v  = from_u(dec1 ? rawv[j] : permute_pair(rawv[j], tr[j], xbase));
+              const uint64_t mx = __ballot(v.x > 0), my = __ballot(v.y > 0);
+              if (lane == 0) {
+                *reinterpret_cast<uint4*>(D + (size_t)(dec1 ? b * 8 + j : xch_row(tr[j]) & m_own()) * 4) =
+                    make_uint4((uint32_t)mx, (uint32_t)(mx >> 32), (uint32_t)my, (uint32_t)(my >> 32));
+              }
+            } else if (dec1) {
+              // what tdec_decision_byte reads (turbodecoder.c:370-378), in natural order: ext1 after decoder 1,
+              // the de-interleaved ext2 (= app1 before the subtraction) after decoder 2
               store_row<AR::kIs8>(D, (b * 8 + j) & m_own(), lane, rawv[j]);
             } else {
-              store_row<AR::kIs8>(D, row, lane, permute_pair<LPC>(rawv[j], tr[j] >> 16));
+              store_xch_row<AR::kIs8>(D, tr[j], m_own(), lane, permute_pair(rawv[j], tr[j], xbase));
             }
           }
         }

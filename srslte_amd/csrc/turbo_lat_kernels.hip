@@ -24,6 +24,7 @@
 #include "turbo_arith.h"
 #include "turbo_device.h"
 #include "turbo_lat_common.h"
+#include "turbo_layout.h"
 
 #include <type_traits>
 
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(DUAL ? 128 : (LPC > 8 ? 8 * LPC : 64)) void tdec_la
 
     // ---- outputs of the 8 steps of block b from the branch sums of the forward recursion (t_o, t_c) and the backward metrics (bt): max-log-MAP
     // output, extrinsic subtraction, exchange of the 8 rows into the other decoder's a-priori array, decision source
-    const uint32_t* lut  = dec1 ? p.deint : p.inter; // per (block, destination pair, step): row | source sub-blocks (turbo_host.cpp)
+    const uint32_t* lut  = dec1 ? p.deint : p.inter; // per (block, destination pair, step): row and source sub-blocks (turbo_layout.h: xch_pack)
     uint32_t*       dst  = dec1 ? A2 : A1;
     const bool      last = (n + 1 == p.n_end) || crc_poly;
     auto emit = [&](auto R0C, auto FULLC, uint32_t b, int len, const s2(&bt)[8], const s2(&t_o)[8], const s2(&t_c)[8], const s2(&xs)[8], const s2(&ap)[8],
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(DUAL ? 128 : (LPC > 8 ? 8 * LPC : 64)) void tdec_la
           if constexpr (dec1) {
             proc = AR::ex_sub(llr, ap[j], k == wrap_row);
           } else {
-            proc = AR::ex_sub(llr, xs[j], AR::kIs8 && (wrapj[j] & 0xffffu) == wrap_row);
+            proc = AR::ex_sub(llr, xs[j], AR::kIs8 && xch_row(wrapj[j]) == wrap_row);
           }
           kept    = slot == j ? proc : kept; // lane (pair, j) keeps the output of step j
           keptraw = slot == j ? llr : keptraw;
@@ -436,14 +437,13 @@ __global__ __launch_bounds__(DUAL ? 128 : (LPC > 8 ? 8 * LPC : 64)) void tdec_la
       }
       // exchange of the block's 8 rows: lane (pair p', step j) assembles the two values of its destination sub-blocks
       const uint32_t trl = trl_in;
-      const uint32_t row = trl & 0xffffu, jlo = (trl >> 16) & 31u, jhi = (trl >> 21) & 31u;
-      const int      a_l = gbase + (int)(jlo >> 1) * 8 + slot, c_l = gbase + (int)(jhi >> 1) * 8 + slot;
+      const uint32_t row = xch_row(trl);
+      // (pair p of the code block is the 8 lanes gbase + 8 p ...: twice the entry's "4 x lane of the throughput kernel")
+      const int      a_l = gbase + (int)(xch_lane4_lo(trl) << 1) + slot, c_l = gbase + (int)(xch_lane4_hi(trl) << 1) + slot;
       auto           pick = [&](uint32_t v) {
         uint32_t a, c;
         read2(v, a_l, c_l, a, c);
-        const uint32_t lo = (jlo & 1u) ? (a >> 16) : (a & 0xffffu);
-        const uint32_t hi = (jhi & 1u) ? (c >> 16) : (c & 0xffffu);
-        return lo | (hi << 16);
+        return xch_merge(a, c, trl);
       };
       const uint32_t v   = pick(to_u(kept));
       const uint32_t dat = ((row >> 3) * LPC + pl) * 8 + (row & 7u);

@@ -1,5 +1,6 @@
 // turbo_layout.h -- how the throughput window decoder (turbo_kernels.hip) keeps its per-wave workspace in HBM, and the loads / stores of that
-// layout: blocked arrays, row arrays, their 8-bit storage forms and the exchange across the lanes of a code block.  Device code only.
+// layout: blocked arrays, row arrays, their 8-bit storage forms and the exchange across the lanes of a code block.  Device code, but for the
+// exchange-table entry's encoding, which the host's table builder shares.
 #pragma once
 #include "turbo_arith.h"
 
@@ -157,16 +158,64 @@ __device__ __forceinline__ void store_row(uint32_t* arr, size_t row, int lane, u
   }
 }
 
-// value for this lane's two destination sub-blocks, fetched from the lanes holding the source sub-blocks
-template <int LPC>
-__device__ __forceinline__ uint32_t permute_pair(uint32_t v, uint32_t sel)
+// ---- exchange-table entries: one dword per (trellis step, destination lane of the code block), built once per (K, sub-blocks) by the
+// host (turbo_host.cpp) and decoded by every window kernel through the helpers below -- nothing else knows the layout.  Every field sits
+// where the instruction that consumes it wants it, so a step's exchange costs no index arithmetic:
+//   bit  1      the value for the LOW destination sub-block is the HIGH half of its source lane's dword   } the flag bits of a
+//   bit  17     the same for the HIGH destination sub-block                                              } v_perm_b32 selector
+//   bits 2..5   4 x the lane (within the code block) holding the source of the low destination sub-block: OR-ed with the byte address of
+//               the code block's first lane it is the ds_bpermute address (one v_and_or_b32)
+//   byte 1      4 x the lane holding the source of the high destination sub-block, nothing else: one byte-selecting OR
+//   bits 22..31 destination row (a shift)
+// The other bits are zero.  Sub-block j lives in half j & 1 of lane j >> 1 of the code block.
+constexpr uint32_t kXchRowBits = 10, kXchLaneBits = 4; // rows < 1024 (K = 6144 in 8 sub-blocks: 768), at most 16 lanes per code block
+__host__ __device__ __forceinline__ uint32_t xch_pack(uint32_t row, uint32_t src_lo, uint32_t src_hi)
 {
-  const uint32_t jlo = sel & 31u, jhi = (sel >> 5) & 31u;
-  const uint32_t a   = __shfl(v, (int)(jlo >> 1), LPC);
-  const uint32_t c   = __shfl(v, (int)(jhi >> 1), LPC);
-  const uint32_t lo  = (jlo & 1u) ? (a >> 16) : (a & 0xffffu);
-  const uint32_t hi  = (jhi & 1u) ? (c >> 16) : (c & 0xffffu);
-  return lo | (hi << 16);
+  return ((src_lo & 1u) << 1) | ((src_lo >> 1) << 2) | ((src_hi >> 1) << 10) | ((src_hi & 1u) << 17) | (row << 22);
+}
+__host__ __device__ __forceinline__ bool xch_fits(uint32_t rows, uint32_t sub_blocks)
+{
+  return rows <= (1u << kXchRowBits) && sub_blocks <= (2u << kXchLaneBits);
+}
+__host__ __device__ __forceinline__ uint32_t xch_row(uint32_t e) { return e >> 22; }
+__host__ __device__ __forceinline__ uint32_t xch_lane4_lo(uint32_t e) { return e & 0x3cu; }        // 4 x source lane, low sub-block
+__host__ __device__ __forceinline__ uint32_t xch_lane4_hi(uint32_t e) { return (e >> 8) & 0xffu; } // 4 x source lane, high sub-block
+__host__ __device__ __forceinline__ uint32_t xch_src_lo(uint32_t e) { return (xch_lane4_lo(e) >> 1) | ((e >> 1) & 1u); } // source sub-blocks,
+__host__ __device__ __forceinline__ uint32_t xch_src_hi(uint32_t e) { return (xch_lane4_hi(e) >> 1) | ((e >> 17) & 1u); } // as packed
+// a, c: the dwords of the two source lanes -> the chosen half of each, in ONE v_perm_b32 (selector bytes 0|2, 1|3 pick from a, 4|6, 5|7 from c)
+__device__ __forceinline__ uint32_t xch_merge(uint32_t a, uint32_t c, uint32_t e)
+{
+  return __builtin_amdgcn_perm(c, a, (e & 0x00020002u) * 0x101u + 0x05040100u);
+}
+
+// byte address (ds_bpermute) of the first lane of this lane's code block
+template <int LPC>
+__device__ __forceinline__ uint32_t xch_group_base(int lane)
+{
+  return (uint32_t)(lane & ~(LPC - 1)) << 2;
+}
+// value for this lane's two destination sub-blocks, fetched from the lanes holding the source sub-blocks
+__device__ __forceinline__ uint32_t permute_pair(uint32_t v, uint32_t e, uint32_t group_base)
+{
+  const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(xch_lane4_lo(e) | group_base), (int)v);
+  // (xch_lane4_hi(e) | group_base in one instruction: the compiler forms shift + v_and_or_b32, which has no byte-selecting form)
+  uint32_t addr_c;
+  asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(addr_c) : "v"(e), "v"(group_base));
+  const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute((int)addr_c, (int)v);
+  return xch_merge(a, c, e);
+}
+// one element of a row array, the row taken from an exchange-table entry (own: the early-stop mask of the row index, ~0 without)
+template <bool S8>
+__device__ __forceinline__ void store_xch_row(uint32_t* arr, uint32_t e, uint32_t own, int lane, uint32_t v)
+{
+  // a 32-bit byte offset from the (wave-uniform) array: the store takes the array from scalar registers, no 64-bit vector address is formed
+  if constexpr (S8) {
+    const uint32_t off = ((xch_row(e) & own) << 7) | ((uint32_t)lane << 1);
+    *reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(arr) + off) = s8_pack1(v);
+  } else {
+    const uint32_t off = ((xch_row(e) & own) << 8) | ((uint32_t)lane << 2);
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(arr) + off) = v;
+  }
 }
 
 } // namespace turbo

@@ -22,6 +22,7 @@
  * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, MIMO layer mapping /
  * precoding (more than one port), a PUSCH without a transport block (tbs == 0: CQI only), 8-bit soft bits on a grant with control information,
  * the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the control bits themselves, EVM measurement.
+ * The NR shared channels (pdsch_nr.c / pusch_nr.c, LDPC) have their own one-call-per-codeword entry points in phy_nr_chan_abi.h.
  */
 #ifndef SRSRAN_AMD_PHY_CHAN_ABI_H
 #define SRSRAN_AMD_PHY_CHAN_ABI_H

@@ -196,6 +196,15 @@ class HipNrTbResult(C.Structure):
     _fields_ = [("crc_ok", C.c_int32), ("all_decoded", C.c_int32), ("avg_iter", C.c_float), ("nof_cb", C.c_uint32)]
 
 
+class HipNrCwRx(C.Structure):  # srsran_hip_nr_cw_rx_t, include/srsran_amd/phy_nr_chan_abi.h
+    _fields_ = [("tb", HipNrTb), ("nof_re", C.c_uint32), ("seed", C.c_uint32), ("scaling_fctr", C.c_float), ("max_nof_iter", C.c_uint32),
+                ("noise_estimate", C.c_float), ("reserved", C.c_uint32)]
+
+
+class HipNrCwTx(C.Structure):  # srsran_hip_nr_cw_tx_t
+    _fields_ = [("tb", HipNrTb), ("nof_re", C.c_uint32), ("seed", C.c_uint32), ("scaling", C.c_float), ("reserved", C.c_uint32)]
+
+
 class HipCell(C.Structure):
     _fields_ = [("peak_pos", C.c_int32), ("peak_value", C.c_float), ("psr", C.c_float), ("sss_available", C.c_int32),
                 ("m0", C.c_uint32), ("m1", C.c_uint32), ("m0_value", C.c_float), ("m1_value", C.c_float), ("N_id_1", C.c_int32),
@@ -518,6 +527,13 @@ def lib():
             "srsran_hip_pdsch_encode_multi": (i32, [u32, C.POINTER(HipPdschTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_modulate_bytes": (i32, [u32, vp, vp, u32, u32, u32, C.c_float]),
+            "srsran_hip_sequence_nr_seed": (u32, [C.c_uint16, u32, u32]),
+            "srsran_hip_nr_cw_decode": (i32, [C.POINTER(HipNrCwRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult)]),
+            "srsran_hip_nr_cw_decode_dbg": (i32, [C.POINTER(HipNrCwRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult), vp]),
+            "srsran_hip_nr_cw_decode_multi": (i32, [u32, C.POINTER(HipNrCwRx), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.POINTER(SoftbufferRx)),
+                                                    C.POINTER(vp), C.POINTER(HipNrTbResult)]),
+            "srsran_hip_nr_cw_encode": (i32, [C.POINTER(HipNrCwTx), vp, vp]),
+            "srsran_hip_nr_cw_encode_multi": (i32, [u32, C.POINTER(HipNrCwTx), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

@@ -793,6 +793,7 @@ extern "C" int srsran_hip_modulate_bytes(uint32_t mod, const uint8_t* bits, cf_t
 #include <condition_variable>
 #include <thread>
 
+#include "srsran_amd/phy_nr_chan_abi.h"
 #include "turbo_device.h"
 namespace phyhip {
 namespace rm {
@@ -865,6 +866,26 @@ void warm_one_worker()
         (void)srsran_hip_ulsch_encode(&tb, nsymb, &sb.tx, data.data(), qbits.data());
       }
     }
+  }
+  // NR: one codeword through the one-call paths of phy_nr_chan_abi.h, transmit then receive -- the 8-block 256-QAM transport block of a 100 MHz
+  // carrier with the reference's default decoder parameters, so a worker's first slot finds its context, decoder objects and kernels ready
+  {
+    const uint32_t            nr_re = 12672, nr_cb = 8, nr_N = 66 * 384;
+    srsran_hip_nr_tb_t        ntb   = {0.67, 67368, SRSRAN_MOD_256QAM, 0, 1, 8 * nr_re, 0, 0, 0, 0, 0};
+    std::vector<cf_t>         nsym(nr_re), nce(nr_re, cf_t(1.f, 0.f));
+    std::vector<uint8_t>      npay(ntb.tbs / 8 + 8, 0x5a), nrows((size_t)nr_cb * nr_N, 0), nkeep((size_t)nr_cb * (8448 / 8), 0), nflags(nr_cb, 0);
+    std::vector<int16_t*>     nrp(nr_cb);
+    std::vector<uint8_t*>     nkp(nr_cb);
+    for (uint32_t r = 0; r < nr_cb; r++) {
+      nrp[r] = reinterpret_cast<int16_t*>(nrows.data() + (size_t)r * nr_N);
+      nkp[r] = nkeep.data() + (size_t)r * (8448 / 8);
+    }
+    srsran_softbuffer_rx_t    nsb = {nr_cb, nr_N, nrp.data(), nkp.data(), reinterpret_cast<bool*>(nflags.data()), false};
+    srsran_hip_nr_cw_tx_t     ntx = {ntb, nr_re, 12345u, 1.0f, 0};
+    srsran_hip_nr_cw_rx_t     nrx = {ntb, nr_re, 12345u, 0.f, 0, 0.01f, 0};
+    srsran_hip_nr_tb_result_t nres;
+    (void)srsran_hip_nr_cw_encode(&ntx, npay.data(), nsym.data());
+    (void)srsran_hip_nr_cw_decode(&nrx, nsym.data(), nce.data(), &nsb, npay.data(), &nres);
   }
 }
 

@@ -1,0 +1,456 @@
+// nr_chan_host.cpp -- one device call per NR codeword (include/srsran_amd/phy_nr_chan_abi.h):
+//   receive   pdsch_nr_decode_codeword (lib/src/phy/phch/pdsch_nr.c:426-483, behind the single-port equaliser of :540) and pusch_nr_decode_codeword
+//             without control information (pusch_nr.c:830-911): nr_front_kernel, then the transport-block loop of sch_nr_host.cpp on soft bits that
+//             never leave the device
+//   transmit  pdsch_nr_encode_codeword (pdsch_nr.c:304-351): srsran_hip_sch_nr_encode, then nr_mod_kernel on its bit-per-byte output
+// The staging context is the transport-block one of sch_nr_host.cpp (one per worker thread).  One image layout serves the pinned host image and the
+// device buffer; every region starts on a multiple of 256 bytes -- in particular every codeword's soft bits, so the front end's 16-byte stores are
+// aligned whatever the lengths of the codewords in front of it (the kernel falls back to byte stores on a base that is not):
+//   [soft rows | data rows | per codeword: symbols, channel estimates | per codeword: soft bits / coded bits | per codeword: payload | job lists]
+// Symbols, estimates, payloads and job lists are read from the pinned image by the kernels themselves; soft rows, data rows and soft bits live in the
+// device buffer.
+#include "hip_common.h"
+#include "nr_chan_device.h"
+#include "sch_nr_internal.h"
+#include "srsran_amd/phy_nr_chan_abi.h"
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+using namespace phyhip;
+using namespace phyhip::nrtb;
+
+namespace {
+
+#define NR_CW_REFUSE(...)                                                                                              \
+  do {                                                                                                                 \
+    fprintf(stderr, "[srsran_phy_hip] " __VA_ARGS__);                                                                  \
+    fputc('\n', stderr);                                                                                               \
+    return SRSRAN_ERROR_INVALID_INPUTS;                                                                                \
+  } while (0)
+
+// the checks both directions share; fills the transport-block parameters
+int check_tb(const char* who, uint32_t i, const srsran_hip_nr_tb_t& tb, uint32_t nof_re, TbCfg* c)
+{
+  if (tb.mod < SRSRAN_MOD_QPSK || tb.mod > SRSRAN_MOD_256QAM) {
+    NR_CW_REFUSE("%s: codeword %u: modulation %u outside QPSK .. 256-QAM", who, i, tb.mod);
+  }
+  if (!tb_cfg(tb, c)) {
+    NR_CW_REFUSE("%s: codeword %u: invalid transport block (tbs %u, layers %u, rv 0x%x)", who, i, tb.tbs, tb.N_L, tb.rv);
+  }
+  if (nof_re == 0 || (uint64_t)nof_re * c->Qm != tb.nof_bits) {
+    NR_CW_REFUSE("%s: codeword %u: nof_bits %u is not nof_re %u x %u", who, i, tb.nof_bits, nof_re, c->Qm);
+  }
+  if (tb.nof_bits > SRSRAN_HIP_SEQUENCE_MAX_LEN) {
+    NR_CW_REFUSE("%s: codeword %u: %u bits exceed the sequence tables (%u)", who, i, tb.nof_bits, SRSRAN_HIP_SEQUENCE_MAX_LEN);
+  }
+  if (tb.nof_bits < c->C * c->Nl * c->Qm) { // sch_nr_get_E would hand a code block no bit at all
+    NR_CW_REFUSE("%s: codeword %u: %u bits for %u code blocks", who, i, tb.nof_bits, c->C);
+  }
+  return SRSRAN_SUCCESS;
+}
+
+struct RxCw { // one codeword of a receive call
+  TbCfg    c;
+  uint32_t first_cb;
+  bool     fresh;              // rows are written, not accumulated into, and not uploaded
+  bool     any_flag;
+  int      first, last;        // undecoded blocks on entry
+  size_t   o_sym, o_ce, o_e, o_pay;
+  uint8_t  flags_in[NrTbStage::MAX_CB];
+};
+
+int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* symbols, const cf_t* const* ce, srsran_softbuffer_rx_t* const* softbuffers,
+                 uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res, int8_t* e_out)
+{
+  static const char* who = "nr_cw_decode";
+  TraceRange         trace_("srsran_hip_nr_cw_decode");
+  if (res) {
+    memset(res, 0, (size_t)n * sizeof(*res)); // every result is initialised before anything is checked
+  }
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!g || !symbols || !softbuffers || !payloads || !res) {
+    NR_CW_REFUSE("%s: NULL argument", who);
+  }
+  // ---- validation: nothing is enqueued and nothing of the caller's is written before every entry has passed
+  std::vector<RxCw> cw(n);
+  uint32_t          n_cb = 0, sb_stride = 0, data_stride = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const srsran_softbuffer_rx_t* sb = softbuffers[i];
+    if (!symbols[i] || !sb || !payloads[i] || !sb->buffer_f || !sb->data || !sb->cb_crc) {
+      NR_CW_REFUSE("%s: codeword %u: NULL symbols, soft buffer or payload", who, i);
+    }
+    TbCfg& c = cw[i].c;
+    if (check_tb(who, i, g[i].tb, g[i].nof_re, &c) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (sb->max_cb < c.C || sb->max_cb_size < c.N) { // sch_nr.c:556-559
+      NR_CW_REFUSE("%s: codeword %u: soft buffer of %u rows x %u for %u code blocks of %u soft bits", who, i, sb->max_cb, sb->max_cb_size, c.C, c.N);
+    }
+    if (c.C > NrTbStage::MAX_CB - n_cb) {
+      NR_CW_REFUSE("%s: codeword %u: more than %u code blocks in one call", who, i, NrTbStage::MAX_CB);
+    }
+    for (uint32_t r = 0; r < c.C; r++) {
+      if (!sb->buffer_f[r] || !sb->data[r]) {
+        NR_CW_REFUSE("%s: codeword %u: soft-buffer provided NULL buffer for cb_idx=%u", who, i, r); // sch_nr.c:571-574
+      }
+    }
+    cw[i].first_cb = n_cb;
+    n_cb += c.C;
+    sb_stride   = std::max(sb_stride, (uint32_t)al256(c.N));
+    data_stride = std::max(data_stride, (uint32_t)al256((c.Kr + 7) / 8));
+  }
+  NrTbStage& s = tb_stage();
+  if (!s.ready()) {
+    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
+    return SRSRAN_ERROR;
+  }
+  // ---- layout
+  const size_t o_soft = 0, o_data = al256(o_soft + (size_t)n_cb * sb_stride);
+  size_t       o      = al256(o_data + (size_t)n_cb * data_stride);
+  uint32_t     n_tiles = 0;
+  const size_t o_in    = o;
+  for (uint32_t i = 0; i < n; i++) {
+    cw[i].o_sym = o;
+    o           = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
+    cw[i].o_ce  = o;
+    if (ce && ce[i]) {
+      o = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
+    }
+    n_tiles += ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+  }
+  const size_t o_e = o;
+  for (uint32_t i = 0; i < n; i++) {
+    cw[i].o_e = o;
+    o         = al256(o + g[i].tb.nof_bits);
+  }
+  const size_t e_bytes = o - o_e, o_pay = o;
+  for (uint32_t i = 0; i < n; i++) {
+    cw[i].o_pay = o;
+    o           = al256(o + cw[i].c.A / 8 + 8);
+  }
+  const size_t pay_bytes = o - o_pay, o_jobs = o, o_tj = al256(o_jobs + (size_t)n * sizeof(nrchan::FrontJob));
+  o                      = al256(o_tj + (size_t)n_tiles * sizeof(uint32_t));
+  if (o - o_in > 0xffffffffull) {
+    NR_CW_REFUSE("%s: %zu bytes of symbols and soft bits in one call", who, o - o_in);
+  }
+  if (!s.grow(o)) {
+    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
+    return SRSRAN_ERROR;
+  }
+  nrchan::FrontParams fp;
+  {
+    modem::Params mp;
+    if (!modem::params_for(mp, modem::LLR_I8)) {
+      fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
+      return SRSRAN_ERROR;
+    }
+    fp.in       = reinterpret_cast<const float2*>(s.pin + o_in);
+    fp.out      = reinterpret_cast<int8_t*>(s.dev + o_e);
+    fp.jobs     = reinterpret_cast<const nrchan::FrontJob*>(s.pin + o_jobs);
+    fp.tile_job = reinterpret_cast<const uint32_t*>(s.pin + o_tj);
+    fp.n_tiles  = n_tiles;
+    fp.x1_bits = mp.x1_bits, fp.x2_cols = mp.x2_cols, fp.k = mp.k;
+  }
+  // ---- staging: symbols, estimates, job lists; rows and stored blocks of retransmissions
+  auto*     jobs  = reinterpret_cast<nrchan::FrontJob*>(s.pin + o_jobs);
+  uint32_t* tjob  = reinterpret_cast<uint32_t*>(s.pin + o_tj);
+  uint32_t  tile0 = 0;
+  uint8_t   flags[NrTbStage::MAX_CB];
+  std::vector<srsran_hip_nr_tb_t> tbs(n);
+  for (uint32_t i = 0; i < n; i++) {
+    RxCw&                         w  = cw[i];
+    const TbCfg&                  c  = w.c;
+    const srsran_softbuffer_rx_t* sb = softbuffers[i];
+    const size_t                  nb = (size_t)g[i].nof_re * sizeof(cf_t);
+    const bool                    eq = ce && ce[i];
+    memcpy(s.pin + w.o_sym, symbols[i], nb);
+    if (eq) {
+      memcpy(s.pin + w.o_ce, ce[i], nb);
+    }
+    const uint32_t nt = ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+    jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
+                               (uint32_t)(w.o_e - o_e), g[i].seed, tile0, nt, g[i].noise_estimate, g[i].noise_estimate > 0.f ? 1u : 0u};
+    for (uint32_t t = 0; t < nt; t++) {
+      tjob[tile0 + t] = i;
+    }
+    tile0 += nt;
+    const bool new_data = (g[i].tb.rv & SRSRAN_HIP_NR_TB_NEW_DATA) != 0;
+    const uint32_t cb_bytes = (c.Kp - c.L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (sch_nr.c:650-652)
+    bool any_soft = false;
+    w.any_flag = false, w.first = w.last = -1;
+    for (uint32_t r = 0; r < c.C; r++) {
+      const uint8_t f = (!new_data && sb->cb_crc[r]) ? 1 : 0;
+      w.flags_in[r] = flags[w.first_cb + r] = f;
+      if (f) {
+        w.any_flag = true;
+        memcpy(s.pin + o_data + (size_t)(w.first_cb + r) * data_stride, sb->data[r], cb_bytes); // decoded earlier: its packed bits join the assembly
+      } else {
+        any_soft = any_soft || (!new_data && !all_zero(reinterpret_cast<const uint8_t*>(sb->buffer_f[r]), c.N));
+        w.first  = w.first < 0 ? (int)r : w.first;
+        w.last   = (int)r;
+      }
+    }
+    w.fresh = new_data || (!any_soft && !w.any_flag); // rows as srsran_softbuffer_rx_reset left them: written, not accumulated into, and not uploaded
+    if (!w.fresh && w.first >= 0) {
+      const size_t lo = o_soft + (size_t)(w.first_cb + w.first) * sb_stride;
+      for (int r = w.first; r <= w.last; r++) {
+        if (!w.flags_in[r]) {
+          memcpy(s.pin + o_soft + (size_t)(w.first_cb + r) * sb_stride, sb->buffer_f[r], c.N);
+        }
+      }
+      PHY_HIP_CHECK(hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)(w.last - w.first) * sb_stride + c.N, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+    }
+    if (w.any_flag) {
+      const size_t lo = o_data + (size_t)w.first_cb * data_stride;
+      PHY_HIP_CHECK(hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)c.C * data_stride, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+    }
+    tbs[i]                = g[i].tb;
+    tbs[i].rv             = (g[i].tb.rv & 3u) | (w.fresh ? SRSRAN_HIP_NR_TB_NEW_DATA : 0u);
+    tbs[i].e_offset       = (uint32_t)(w.o_e - o_e);
+    tbs[i].payload_offset = (uint32_t)(w.o_pay - o_pay);
+    tbs[i].first_cb       = w.first_cb;
+  }
+  // ---- one front-end launch over all codewords, one transport-block pass per (scaling factor, iterations)
+  auto fail = [&](const char* what) {
+    (void)hipStreamSynchronize(s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
+    fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
+    return SRSRAN_ERROR;
+  };
+  {
+    const hipError_t e = nrchan::launch_front(fp, s.st);
+    if (e != hipSuccess) {
+      set_error("nr_front_kernel: %s", hipGetErrorString(e));
+      return fail("front end");
+    }
+  }
+  std::vector<uint32_t> order(n);
+  for (uint32_t i = 0; i < n; i++) {
+    order[i] = i;
+  }
+  auto dec_key = [&](uint32_t i) {
+    const float sc = std::isnormal(g[i].scaling_fctr) ? g[i].scaling_fctr : 0.8f; // sch_nr.c:275
+    uint32_t    b;
+    memcpy(&b, &sc, 4);
+    return ((uint64_t)b << 32) | (g[i].max_nof_iter ? g[i].max_nof_iter : 10u);
+  };
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return dec_key(a) < dec_key(b); });
+  std::vector<srsran_hip_nr_tb_t>        gtb;
+  std::vector<srsran_hip_nr_tb_result_t> gres;
+  for (uint32_t i = 0; i < n;) {
+    uint32_t e = i;
+    gtb.clear();
+    while (e < n && dec_key(order[e]) == dec_key(order[i])) {
+      gtb.push_back(tbs[order[e]]);
+      e++;
+    }
+    gres.assign(gtb.size(), srsran_hip_nr_tb_result_t{});
+    const uint32_t       i0 = order[i];
+    srsran_hip_sch_nr_t* h  = s.decoder(std::isnormal(g[i0].scaling_fctr) ? g[i0].scaling_fctr : 0.8f, g[i0].max_nof_iter ? g[i0].max_nof_iter : 10u);
+    if (!h) {
+      return fail("decoder object");
+    }
+    // the last pass carries the downloads in front of its host wait: stored code blocks, payloads, and the soft bits where they are asked for
+    const TailCopy tail[3] = {{s.pin + o_data, s.dev + o_data, (size_t)n_cb * data_stride}, {s.pin + o_pay, s.dev + o_pay, pay_bytes},
+                              {s.pin + o_e, s.dev + o_e, e_out ? e_bytes : 0}};
+    if (sch_nr_decode(h, reinterpret_cast<const int8_t*>(s.dev + o_e), gtb.data(), (uint32_t)gtb.size(), reinterpret_cast<int8_t*>(s.dev + o_soft), sb_stride,
+                      flags, s.dev + o_data, data_stride, s.dev + o_pay, gres.data(), s.st, tail, e == n ? 3 : 0) != SRSRAN_SUCCESS) {
+      return fail("transport blocks");
+    }
+    for (uint32_t k = i; k < e; k++) {
+      res[order[k]] = gres[k - i];
+    }
+    i = e;
+  }
+  // ---- host side effects of sch_nr.c:633-652: flags, the packed bits of the blocks decoded now; rows of the blocks that are still undecoded
+  bool rows_left = false;
+  for (uint32_t i = 0; i < n; i++) {
+    RxCw&                   w  = cw[i];
+    srsran_softbuffer_rx_t* sb = softbuffers[i];
+    const uint32_t          cb_bytes = (w.c.Kp - w.c.L_cb + 7) / 8;
+    w.first = w.last = -1;
+    for (uint32_t r = 0; r < w.c.C; r++) {
+      if (w.flags_in[r]) {
+        continue;
+      }
+      if (flags[w.first_cb + r]) {
+        sb->cb_crc[r] = true;
+        memcpy(sb->data[r], s.pin + o_data + (size_t)(w.first_cb + r) * data_stride, cb_bytes);
+      } else {
+        sb->cb_crc[r] = false;
+        w.first       = w.first < 0 ? (int)r : w.first;
+        w.last        = (int)r;
+      }
+    }
+    if (w.first >= 0) {
+      const size_t lo = o_soft + (size_t)(w.first_cb + w.first) * sb_stride;
+      PHY_HIP_CHECK(hipMemcpyAsync(s.pin + lo, s.dev + lo, (size_t)(w.last - w.first) * sb_stride + w.c.N, hipMemcpyDeviceToHost, s.st), SRSRAN_ERROR);
+      rows_left = true;
+    }
+  }
+  if (rows_left) {
+    PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const RxCw&             w  = cw[i];
+    srsran_softbuffer_rx_t* sb = softbuffers[i];
+    // (the circular buffer of a block ends at Ncb = min(N, Nref), ldpc_rm.c:704-705: nothing behind it is ever written or read)
+    const uint32_t n_cb_buf = w.c.N <= w.c.Nref ? w.c.N : w.c.Nref;
+    for (int r = w.first; w.first >= 0 && r <= w.last; r++) {
+      if (!sb->cb_crc[r]) {
+        memcpy(sb->buffer_f[r], s.pin + o_soft + (size_t)(w.first_cb + r) * sb_stride, n_cb_buf);
+      }
+    }
+    if (res[i].all_decoded) { // sch_nr.c:664-666: otherwise the payload is not touched
+      memcpy(payloads[i], s.pin + w.o_pay, w.c.A / 8);
+    }
+    if (e_out && i == 0) {
+      memcpy(e_out, s.pin + w.o_e, g[i].tb.nof_bits);
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* const* data, cf_t* const* symbols)
+{
+  static const char* who = "nr_cw_encode";
+  TraceRange         trace_("srsran_hip_nr_cw_encode");
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!g || !data || !symbols) {
+    NR_CW_REFUSE("%s: NULL argument", who);
+  }
+  std::vector<TbCfg> cfg(n);
+  uint32_t           n_cb = 0, n_tiles = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!data[i] || !symbols[i]) {
+      NR_CW_REFUSE("%s: codeword %u: NULL payload or symbols", who, i);
+    }
+    if (check_tb(who, i, g[i].tb, g[i].nof_re, &cfg[i]) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (g[i].tb.rv > 3) {
+      NR_CW_REFUSE("%s: codeword %u: rv %u", who, i, g[i].tb.rv);
+    }
+    if (cfg[i].C > NrTbStage::MAX_CB - n_cb) {
+      NR_CW_REFUSE("%s: codeword %u: more than %u code blocks in one call", who, i, NrTbStage::MAX_CB);
+    }
+    n_cb += cfg[i].C;
+    n_tiles += ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+  }
+  NrTbStage& s = tb_stage();
+  if (!s.ready()) {
+    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
+    return SRSRAN_ERROR;
+  }
+  srsran_hip_sch_nr_t* h = s.decoder(0.8f, 10); // (the transmit side has no decoder parameters: one object per thread)
+  if (!h) {
+    return SRSRAN_ERROR;
+  }
+  // layout: [payloads | coded bits (device) | symbols | job lists]
+  std::vector<size_t> o_pay(n), o_e(n), o_sym(n);
+  size_t              o = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    o_pay[i] = o;
+    o        = al256(o + cfg[i].A / 8 + 8);
+  }
+  const size_t e0 = o;
+  for (uint32_t i = 0; i < n; i++) {
+    o_e[i] = o;
+    o      = al256(o + g[i].tb.nof_bits);
+  }
+  const size_t s0 = o;
+  for (uint32_t i = 0; i < n; i++) {
+    o_sym[i] = o;
+    o        = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
+  }
+  const size_t o_jobs = o, o_tj = al256(o_jobs + (size_t)n * sizeof(nrchan::ModJob));
+  o                   = al256(o_tj + (size_t)n_tiles * sizeof(uint32_t));
+  if (o > 0xffffffffull) {
+    NR_CW_REFUSE("%s: %zu bytes in one call", who, o);
+  }
+  modem::Params mp;
+  const float2* tab = modem::mod_tables();
+  if (!s.grow(o) || !modem::params_for(mp, modem::LLR_I8) || !tab) {
+    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
+    return SRSRAN_ERROR;
+  }
+  auto*                           jobs  = reinterpret_cast<nrchan::ModJob*>(s.pin + o_jobs);
+  uint32_t*                       tjob  = reinterpret_cast<uint32_t*>(s.pin + o_tj);
+  uint32_t                        tile0 = 0;
+  std::vector<srsran_hip_nr_tb_t> tbs(n);
+  for (uint32_t i = 0; i < n; i++) {
+    memcpy(s.pin + o_pay[i], data[i], cfg[i].A / 8);
+    tbs[i]                = g[i].tb;
+    tbs[i].e_offset       = (uint32_t)(o_e[i] - e0);
+    tbs[i].payload_offset = (uint32_t)o_pay[i];
+    tbs[i].first_cb       = 0;
+    const uint32_t nt     = ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+    const float    scale  = (g[i].scaling != 0.f && !std::isnan(g[i].scaling)) ? g[i].scaling : 1.0f;
+    jobs[i] = nrchan::ModJob{g[i].tb.mod, g[i].nof_re, g[i].seed, scale, (uint32_t)(o_e[i] - e0), (uint32_t)((o_sym[i] - s0) / sizeof(cf_t)), tile0, nt};
+    for (uint32_t t = 0; t < nt; t++) {
+      tjob[tile0 + t] = i;
+    }
+    tile0 += nt;
+  }
+  auto fail = [&](const char* what) {
+    (void)hipStreamSynchronize(s.st);
+    fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
+    return SRSRAN_ERROR;
+  };
+  // the coding kernels read the payloads from the pinned image; the rate matcher's bits stay on the device; the modulator writes the pinned image
+  if (srsran_hip_sch_nr_encode(h, s.pin, tbs.data(), n, s.dev + e0, s.st) != SRSRAN_SUCCESS) {
+    return fail("transport blocks");
+  }
+  nrchan::ModParams p;
+  p.bits = s.dev + e0, p.out = reinterpret_cast<float2*>(s.pin + s0), p.table = tab, p.jobs = jobs, p.tile_job = tjob, p.n_tiles = n_tiles;
+  p.x1_bits = mp.x1_bits, p.x2_cols = mp.x2_cols;
+  const hipError_t e = nrchan::launch_mod(p, s.st);
+  if (e != hipSuccess) {
+    set_error("nr_mod_kernel: %s", hipGetErrorString(e));
+    return fail("modulator");
+  }
+  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
+  for (uint32_t i = 0; i < n; i++) {
+    memcpy(symbols[i], s.pin + o_sym[i], (size_t)g[i].nof_re * sizeof(cf_t));
+  }
+  return SRSRAN_SUCCESS;
+}
+
+} // namespace
+
+extern "C" uint32_t srsran_hip_sequence_nr_seed(uint16_t rnti, uint32_t cw_idx, uint32_t n_id)
+{
+  return ((uint32_t)rnti << 15) + (cw_idx << 14) + n_id; // pdsch_nr.c:297, pusch_nr.c:346
+}
+
+extern "C" int srsran_hip_nr_cw_decode_multi(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* symbols, const cf_t* const* ce,
+                                             srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res)
+{
+  return nr_cw_decode(n, g, symbols, ce, softbuffers, payloads, res, nullptr);
+}
+
+extern "C" int srsran_hip_nr_cw_decode_dbg(const srsran_hip_nr_cw_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
+                                           uint8_t* payload, srsran_hip_nr_tb_result_t* res, int8_t* e_out)
+{
+  return nr_cw_decode(1, g, &symbols, &ce, &softbuffer, &payload, res, e_out);
+}
+
+extern "C" int srsran_hip_nr_cw_decode(const srsran_hip_nr_cw_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
+                                       uint8_t* payload, srsran_hip_nr_tb_result_t* res)
+{
+  return nr_cw_decode(1, g, &symbols, &ce, &softbuffer, &payload, res, nullptr);
+}
+
+extern "C" int srsran_hip_nr_cw_encode_multi(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* const* data, cf_t* const* symbols)
+{
+  return nr_cw_encode(n, g, data, symbols);
+}
+
+extern "C" int srsran_hip_nr_cw_encode(const srsran_hip_nr_cw_tx_t* g, const uint8_t* data, cf_t* symbols)
+{
+  return nr_cw_encode(1, g, &data, &symbols);
+}

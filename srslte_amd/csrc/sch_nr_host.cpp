@@ -9,6 +9,7 @@
 // srsran_ra_nr_tbs, the reference's resource-allocation code, which is outside this library).
 #include "hip_common.h"
 #include "nr_sch_device.h"
+#include "sch_nr_internal.h"
 #include "stage.h"
 #include "srsran_amd/phy_batch.h"
 #include "srsran_amd/phy_modem_abi.h"
@@ -21,15 +22,11 @@
 #include <vector>
 
 using namespace phyhip;
+using namespace phyhip::nrtb;
 
 extern "C" const uint8_t LSindex[385]; // ldpc_host.cpp (base_graph.c:50)
 
 namespace {
-
-struct TbCfg { // srsran_sch_nr_tb_info_t
-  int      bg;
-  uint32_t Qm, A, L_tb, L_cb, B, Bp, Kp, Kr, F, Z, G, Nl, Nref, C, N;
-};
 
 // TS 38.212 5.2.2 as srsran_cbsegm_ldpc (cbsegm.c:201-275): transport CRC length, number of code blocks, lifting size
 bool nr_segment(int bg, uint32_t tbs, uint32_t* L_tb, uint32_t* C_out, uint32_t* Z_out)
@@ -78,6 +75,11 @@ int cbsegm_ldpc(srsran_cbsegm_t* s, int bg, uint32_t tbs)
   return SRSRAN_SUCCESS;
 }
 
+} // namespace
+
+namespace phyhip {
+namespace nrtb {
+
 // srsran_sch_nr_fill_tb_info with cbsegm_ldpc; false where the reference fails
 bool tb_cfg(const srsran_hip_nr_tb_t& tb, TbCfg* c)
 {
@@ -117,6 +119,11 @@ uint32_t get_E(const TbCfg& c, uint32_t j) // sch_nr_get_E, sch_nr.c:146-157 (al
   }
   return q * ((c.G + q * c.C - 1) / (q * c.C));
 }
+
+} // namespace nrtb
+} // namespace phyhip
+
+namespace {
 
 struct Job {
   uint32_t tb, cb, E, in_off, n_llr, cb_len, fresh;
@@ -269,15 +276,9 @@ static uint32_t crc_row_of(srsran_hip_sch_nr_t* h, uint32_t tbs_bits, uint32_t o
   return row;
 }
 
-// (tail: device-to-host copies a caller wants queued behind the last kernel and in front of the call's one host wait)
-struct TailCopy {
-  void*       dst;
-  const void* src;
-  size_t      bytes;
-};
-static int sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, const srsran_hip_nr_tb_t* tbs, uint32_t n_tb, int8_t* d_softbuffer,
-                         uint32_t sb_stride, uint8_t* cb_crc, uint8_t* d_cb_data, uint32_t data_stride, uint8_t* d_payload,
-                         srsran_hip_nr_tb_result_t* res, void* stream, const TailCopy* tail, int n_tail)
+int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, const srsran_hip_nr_tb_t* tbs, uint32_t n_tb, int8_t* d_softbuffer,
+                                uint32_t sb_stride, uint8_t* cb_crc, uint8_t* d_cb_data, uint32_t data_stride, uint8_t* d_payload,
+                                srsran_hip_nr_tb_result_t* res, void* stream, const TailCopy* tail, int n_tail)
 {
   TraceRange trace_("srsran_hip_sch_nr_decode");
   if (h) {
@@ -522,41 +523,35 @@ extern "C" int srsran_hip_sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_
 // caller's HOST buffers in the reference's soft-buffer struct: one upload, one de-matching launch, one early-stop LDPC launch, the
 // code-block and transport-block finish kernels, one download.  The staging context is private to the calling thread.
 
-namespace {
-
-struct NrTbStage {
-  StageStream                               st;
-  std::map<uint64_t, srsran_hip_sch_nr_t*>  sch; // (scaling factor, iterations) -> decoder object
-  HostImage                                 pin; // pinned image: [soft rows | data rows | e bits | payload]
-  DeviceBuf                                 dev;
-  static const uint32_t                     MAX_CB = 160; // > SRSRAN_SCH_NR_MAX_NOF_CB_LDPC (sch_nr.h:41)
-  ~NrTbStage()
-  {
-    for (auto& kv : sch) {
-      srsran_hip_sch_nr_free(kv.second);
-    }
+NrTbStage::~NrTbStage()
+{
+  for (auto& kv : sch) {
+    srsran_hip_sch_nr_free(kv.second);
   }
-  bool ready() { return st.open(); }
-  srsran_hip_sch_nr_t* decoder(float scaling, uint32_t iters)
-  {
-    uint32_t sbits;
-    memcpy(&sbits, &scaling, 4);
-    const uint64_t key = ((uint64_t)sbits << 32) | iters;
-    auto           it  = sch.find(key);
-    if (it != sch.end()) {
-      return it->second;
-    }
-    srsran_hip_sch_nr_t* h = nullptr;
-    if (srsran_hip_sch_nr_create(&h, scaling, iters, MAX_CB) != SRSRAN_SUCCESS) {
-      return nullptr;
-    }
-    sch[key] = h;
-    return h;
-  }
-  bool grow(size_t need) { return dev.grow(need) && pin.grow(need); }
-};
+}
 
-} // namespace
+srsran_hip_sch_nr_t* NrTbStage::decoder(float scaling, uint32_t iters)
+{
+  uint32_t sbits;
+  memcpy(&sbits, &scaling, 4);
+  const uint64_t key = ((uint64_t)sbits << 32) | iters;
+  auto           it  = sch.find(key);
+  if (it != sch.end()) {
+    return it->second;
+  }
+  srsran_hip_sch_nr_t* h = nullptr;
+  if (srsran_hip_sch_nr_create(&h, scaling, iters, MAX_CB) != SRSRAN_SUCCESS) {
+    return nullptr;
+  }
+  sch[key] = h;
+  return h;
+}
+
+NrTbStage& phyhip::nrtb::tb_stage()
+{
+  static thread_local StageRef<NrTbStage> ref;
+  return ref.get();
+}
 
 extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_iter, const srsran_hip_nr_tb_t* tb_in, const int8_t* e_bits,
                                            srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, bool* crc, float* avg_iter)
@@ -572,7 +567,7 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
   if (softbuffer->max_cb < c.C || softbuffer->max_cb_size < c.N || c.C > NrTbStage::MAX_CB) { // :556-559
     return SRSRAN_ERROR;
   }
-  NrTbStage& s = thread_device_local<NrTbStage>();
+  NrTbStage& s = tb_stage();
   if (!s.ready()) {
     fprintf(stderr, "[srsran_phy_hip] sch_nr decode: %s (there is no CPU fallback)\n", get_error());
     return SRSRAN_ERROR;
@@ -801,7 +796,7 @@ extern "C" int srsran_hip_sch_nr_encode_tb(const srsran_hip_nr_tb_t* tb_in, cons
     fprintf(stderr, "[srsran_phy_hip] sch_nr encode: invalid transport block (tbs %u, mod %u, layers %u)\n", tb_in->tbs, tb_in->mod, tb_in->N_L);
     return SRSRAN_ERROR;
   }
-  NrTbStage& s = thread_device_local<NrTbStage>();
+  NrTbStage& s = tb_stage();
   if (!s.ready()) {
     fprintf(stderr, "[srsran_phy_hip] sch_nr encode: %s (there is no CPU fallback)\n", get_error());
     return SRSRAN_ERROR;

@@ -19,9 +19,14 @@
  * the de-multiplexer is part of the demodulator's store, the few soft bits of the control fields come down with the payload, and the caller runs the
  * reference's own small decoders (uci.c) on them.
  *
- * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, MIMO layer mapping /
- * precoding (more than one port), a PUSCH without a transport block (tbs == 0: CQI only), 8-bit soft bits on a grant with control information,
- * the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the control bits themselves, EVM measurement.
+ * A PDSCH codeword of a 2- or 4-port cell sent with transmit diversity (SRSRAN_TXSCHEME_DIVERSITY: TM2, the common channels and the TM3 / TM4 fallback of such a
+ * cell) is taken by srsran_hip_pdsch_decode_txdiv / srsran_hip_pdsch_encode_txdiv: SFBC combining over 1 or 2 receive antennas and layer de-mapping sit in
+ * front of the demodulator in one kernel, the layer map and the SFBC precoder are the modulator's store.
+ *
+ * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD
+ * (two codewords, 2x2 ZF / MMSE, PMI), CSI weighting of the soft bits (cfg->csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI only),
+ * 8-bit soft bits on a grant with control information, the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the
+ * control bits themselves, EVM measurement.
  * The NR shared channels (pdsch_nr.c / pusch_nr.c, LDPC) have their own one-call-per-codeword entry points in phy_nr_chan_abi.h.
  */
 #ifndef SRSRAN_AMD_PHY_CHAN_ABI_H
@@ -138,6 +143,42 @@ SRSRAN_API int srsran_hip_pdsch_encode_multi(uint32_t n, const srsran_hip_pdsch_
                                              cf_t* const* symbols);
 SRSRAN_API int srsran_hip_pdsch_encode_dbg(const srsran_hip_pdsch_tx_t* g, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, cf_t* symbols, uint8_t* e_out);
 
+/* ---- PDSCH with transmit diversity, one codeword on a 2- or 4-port cell (pdsch.c:788 / :1017 with tx_scheme == SRSRAN_TXSCHEME_DIVERSITY, nof_tb == 1,
+ * nof_layers == cell.nof_ports).  Receive: symbols[rx] are the grant's nof_re extracted REs of each receive antenna, ce[port][rx] the channel estimates at the
+ * same REs (q->symbols, q->ce after srsran_pdsch_get), HOST memory.  srsran_predecoding_diversity_multi (phy_modem_abi.h: the arithmetic and its limits) ->
+ * srsran_layerdemap_diversity -> demodulator -> descrambler are ONE kernel; the combined symbols never reach memory.  One host wait.
+ * Refused before anything is enqueued, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *res zeroed and nothing else written: NULL pointers or a NULL
+ * plane inside the used range, nof_ports not 2 or 4, nof_rx not 1 or 2, nof_re odd (2 ports) or not a multiple of 4 (4 ports), scaling 0 or not finite,
+ * and what every grant call refuses (modulation, tbs, rv, length); *res = {0, 0, NAN} then.  A device-side failure returns SRSRAN_ERROR. */
+typedef struct SRSRAN_API {
+  srsran_hip_grant_tb_t tb; /* tb.nl is taken as 2 (sch.c:590,632: nof_layers != nof_tb); tb.nof_re = REs of the grant */
+  uint32_t nof_ports;       /* 2 or 4 */
+  uint32_t nof_rx;          /* 1 or 2 */
+  float    scaling;         /* pdsch_scaling: rho_a as pdsch.c:486-520 returns it (with the sqrt 2 of a multi-port cell) */
+  uint32_t reserved;
+} srsran_hip_pdsch_txdiv_rx_t;
+/* symbols, ce: what a caller passes q->symbols and q->ce as (cf_t* symbols[SRSRAN_MAX_PORTS], cf_t* ce[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = [port][rx]:
+ * plain C converts both without a cast); the planes are only read */
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
+/* the same, and d_out (or NULL) <- the nof_re combined, layer-demapped symbols (q->d[0]; made by the per-stage kernels in this case only: same arithmetic),
+ * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[0]: int16, int8 with llr_is_8bit) */
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
+/* Transmit: srsran_hip_pdsch_encode's coding pass, then scrambling + modulation + srsran_layermap_diversity + srsran_precoding_diversity in one kernel:
+ * symbols[port] <- nof_re points each (HOST memory), ready for srsran_pdsch_put per port; no intermediate d reaches memory.  scaling: what pdsch.c:486-492
+ * returns on an eNB object (rho_a sqrt 2 on a multi-port cell); the precoder's 1 / sqrt 2 is applied inside.  data == NULL: a
+ * retransmission of what the soft buffer holds.  Refusals as on the receive side. */
+typedef struct SRSRAN_API {
+  srsran_hip_grant_tb_t tb; /* tb.nl taken as 2; max_nof_iterations, llr_is_8bit unused */
+  uint32_t nof_ports;       /* 2 or 4 */
+  float    scaling;
+} srsran_hip_pdsch_txdiv_tx_t;
+SRSRAN_API int srsran_hip_pdsch_encode_txdiv(const srsran_hip_pdsch_txdiv_tx_t* g, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, cf_t* const symbols[]);
+/* the codewords of one TTI in ONE call: one coding launch, one modulation + precoding launch, one host wait; symbols[i][port] */
+SRSRAN_API int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_pdsch_txdiv_tx_t* g, srsran_softbuffer_tx_t* const* softbuffers,
+                                                   uint8_t* const* data, cf_t* const* const* symbols);
+
 /* ---- UL-SCH transmit without UCI (srsran_ulsch_encode, sch.c:1194-1340, with no ACK / RI / CQI configured): encode_tb -> channel
  * interleaver of 36.212 5.2.2.8 over nof_symb columns.  q_bits: nof_bits = nof_re * Qm bits, byte packed (what pusch.c:322 scrambles next). */
 SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t nof_symb, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, uint8_t* q_bits);
@@ -145,7 +186,7 @@ SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t
 /* ---- warm start.  The first grant of a process / of a worker thread otherwise pays for loading the kernels' device code, creating the thread's staging
  * context (stream, pinned and device images, decoder / encoder objects, transform plans) and building rate-matching tables: 20-28 ms where a warm
  * call takes 0.1-0.4 ms.  srsran_hip_warmup(n) builds every rate-matching table and prepares n staging contexts by running real grants (the
- * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits) on short-lived threads; a worker
+ * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits; one 2-port transmit-diversity grant each way) on short-lived threads; a worker
  * thread adopts a prepared context at its first call.  srsran_rm_turbo_gentables() -- which srsran_sch_init calls (sch.c:166) -- does the same
  * for one worker, so an application that does nothing gets a warm first subframe on one thread; srsenb's pool of nof_phy_threads workers
  * wants srsran_hip_warmup(nof_phy_threads) once after its objects are created.  Idempotent; returns SRSRAN_ERROR without a device. */

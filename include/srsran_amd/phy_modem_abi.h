@@ -85,6 +85,38 @@ SRSRAN_API int srsran_predecoding_single(cf_t* y, cf_t* h, cf_t* x, float* csi, 
 SRSRAN_API int srsran_hip_predecoding_single(const cf_t* d_y, const cf_t* d_h, cf_t* d_x, float* d_csi, uint32_t nof_symbols, float scaling,
                                              float noise_estimate, void* stream);
 
+/* ---- transmit diversity (SFBC, TS 36.211 6.3.3.3 / 6.3.4.3) on 2 and 4 ports: lib/include/srsran/phy/mimo/precoding.h, layermap.h
+ * (precoding.c:673-802 receive, :1943-1992 transmit; layermap.c:38-47, 138-147).  HOST buffers; only planes [0, nof_rxant) / [0, nof_ports) / [0, nof_layers)
+ * of the pointer arrays are read. */
+#define SRSRAN_MAX_PORTS 4
+#define SRSRAN_MAX_LAYERS 4
+#define SRSRAN_MAX_CODEWORDS 2
+/* Receive: y[rx][nof_symbols], h[port][rx][nof_symbols] -> x[layer][nof_symbols / nof_ports]; nof_rxant 1 or 2.  The formulas are those of the reference's
+ * _csi variant (srsran_predecoding_diversity_csi, the one srsran_pdsch_decode runs: a UE object always has q->csi) whether or not csi is given; csi[0]
+ * (nof_symbols floats) is written when csi and csi[0] are non-NULL.  On 2 ports the reference's variants without csi are the same formula; on 4 ports its
+ * generic body without csi reads OTHER channel samples (precoding.c:473-476: ports 0 / 2 at 4i and ports 1 / 3 at 4i + 2 for all four layers, against
+ * :723-743) and is not reproduced.  2 ports: a pair whose channel gain is 0 divides by 1e-4 (:699-701).  Float arithmetic, every operation rounded once
+ * in a fixed order: equals the reference to a few ulp of the sum of products.  nof_symbols must be even (2 ports) or a multiple of 4 (4 ports: the
+ * reference leaves the last two symbols of any other grant unwritten, :715; here it is refused with -1).  Returns nof_symbols / nof_ports, or -1. */
+SRSRAN_API int srsran_predecoding_diversity_multi(cf_t* y[SRSRAN_MAX_PORTS], cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], cf_t* x[SRSRAN_MAX_LAYERS],
+                                                  float* csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_symbols, float scaling);
+/* Transmit: x[layer][nof_symbols] -> y[port][nof_ports * nof_symbols], zeros on the idle ports of a 4-port pair; one float product per component by
+ * the reference's own factor ((float)(scaling * M_SQRT1_2) on 2 ports, the float scaling / M_SQRT2 on 4).  Returns nof_ports * nof_symbols, or -1. */
+SRSRAN_API int srsran_precoding_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRSRAN_MAX_PORTS], int nof_ports, int nof_symbols, float scaling);
+/* x[j][i] = d[nof_layers i + j], i < nof_symbols / nof_layers; returns nof_symbols / nof_layers */
+SRSRAN_API int srsran_layermap_diversity(cf_t* d, cf_t* x[SRSRAN_MAX_LAYERS], int nof_layers, int nof_symbols);
+/* d[nof_layers i + j] = x[j][i], i < nof_layer_symbols; returns nof_layers * nof_layer_symbols */
+SRSRAN_API int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, int nof_layers, int nof_layer_symbols);
+/* the same four on device buffers (every plane 16-byte aligned, d_csi 8-byte), asynchronous on `stream`; they return SRSRAN_SUCCESS or an error code */
+SRSRAN_API int srsran_hip_predecoding_diversity_multi(const cf_t* const d_y[SRSRAN_MAX_PORTS], const cf_t* const d_h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                                      cf_t* const d_x[SRSRAN_MAX_LAYERS], float* d_csi, uint32_t nof_rxant, uint32_t nof_ports,
+                                                      uint32_t nof_symbols, float scaling, void* stream);
+SRSRAN_API int srsran_hip_precoding_diversity(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* const d_y[SRSRAN_MAX_PORTS], uint32_t nof_ports,
+                                              uint32_t nof_symbols, float scaling, void* stream);
+SRSRAN_API int srsran_hip_layermap_diversity(const cf_t* d_d, cf_t* const d_x[SRSRAN_MAX_LAYERS], uint32_t nof_layers, uint32_t nof_symbols, void* stream);
+SRSRAN_API int srsran_hip_layerdemap_diversity(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* d_d, uint32_t nof_layers, uint32_t nof_layer_symbols,
+                                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

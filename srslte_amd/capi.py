@@ -162,6 +162,19 @@ class HipPdschTx(C.Structure):
     _fields_ = [("tb", HipGrantTb), ("scaling", C.c_float)]
 
 
+class HipPdschTxdivRx(C.Structure):  # srsran_hip_pdsch_txdiv_rx_t
+    _fields_ = [("tb", HipGrantTb), ("nof_ports", C.c_uint32), ("nof_rx", C.c_uint32), ("scaling", C.c_float), ("reserved", C.c_uint32)]
+
+
+class HipPdschTxdivTx(C.Structure):  # srsran_hip_pdsch_txdiv_tx_t
+    _fields_ = [("tb", HipGrantTb), ("nof_ports", C.c_uint32), ("scaling", C.c_float)]
+
+
+SRSRAN_MAX_PORTS = 4
+PlaneArray = C.c_void_p * SRSRAN_MAX_PORTS  # cf_t* [SRSRAN_MAX_PORTS]: symbols[rx], x[layer], y[port]
+PlaneMatrix = PlaneArray * SRSRAN_MAX_PORTS  # cf_t* [SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]: ce[port][rx]
+
+
 class SoftbufferRx(C.Structure):  # srsran_softbuffer_rx_t, softbuffer.h:40-47
     _fields_ = [("max_cb", C.c_uint32), ("max_cb_size", C.c_uint32), ("buffer_f", C.POINTER(C.c_void_p)), ("data", C.POINTER(C.c_void_p)),
                 ("cb_crc", C.POINTER(C.c_bool)), ("tb_crc", C.c_bool)]
@@ -525,6 +538,20 @@ def lib():
             "srsran_hip_pdsch_decode_dbg": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp]),
             "srsran_hip_pdsch_encode_dbg": (i32, [C.POINTER(HipPdschTx), C.POINTER(SoftbufferTx), vp, vp, vp]),
             "srsran_hip_pdsch_encode_multi": (i32, [u32, C.POINTER(HipPdschTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_predecoding_diversity_multi": (i32, [C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, C.c_float]),
+            "srsran_precoding_diversity": (i32, [C.POINTER(vp), C.POINTER(vp), i32, i32, C.c_float]),
+            "srsran_layermap_diversity": (i32, [vp, C.POINTER(vp), i32, i32]),
+            "srsran_layerdemap_diversity": (i32, [C.POINTER(vp), vp, i32, i32]),
+            "srsran_hip_predecoding_diversity_multi": (i32, [C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(vp), vp, u32, u32, u32, C.c_float, vp]),
+            "srsran_hip_precoding_diversity": (i32, [C.POINTER(vp), C.POINTER(vp), u32, u32, C.c_float, vp]),
+            "srsran_hip_layermap_diversity": (i32, [vp, C.POINTER(vp), u32, u32, vp]),
+            "srsran_hip_layerdemap_diversity": (i32, [C.POINTER(vp), vp, u32, u32, vp]),
+            "srsran_hip_pdsch_decode_txdiv": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_txdiv_dbg": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp,
+                                                        C.POINTER(HipGrantRes), vp, vp]),
+            "srsran_hip_pdsch_encode_txdiv": (i32, [C.POINTER(HipPdschTxdivTx), C.POINTER(SoftbufferTx), vp, C.POINTER(vp)]),
+            "srsran_hip_pdsch_encode_txdiv_multi": (i32, [u32, C.POINTER(HipPdschTxdivTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp),
+                                                          C.POINTER(C.POINTER(vp))]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_modulate_bytes": (i32, [u32, vp, vp, u32, u32, u32, C.c_float]),
             "srsran_hip_sequence_nr_seed": (u32, [C.c_uint16, u32, u32]),

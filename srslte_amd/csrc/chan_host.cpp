@@ -6,6 +6,7 @@
 #include "modem_device.h"
 #include "sch_stage.h"
 #include "stage.h"
+#include "txdiv_device.h"
 #include "srsran_amd/phy_chan_abi.h"
 
 #include <algorithm>
@@ -779,6 +780,531 @@ extern "C" int srsran_hip_modulate_bytes(uint32_t mod, const uint8_t* bits, cf_t
   return (int)n;
 }
 
+// ------------------------------------------------------------------------------------------------ transmit diversity on 2 and 4 ports
+//
+// The reference-named stages on HOST buffers (one kernel each on the calling thread's stage, like srsran_hip_modulate_bytes), their device-pointer twins, and
+// the PDSCH codeword of a multi-port cell in one call each way (txdiv_kernels.hip).
+
+namespace {
+
+bool txdiv_shape(const char* who, int nof_ports, int nof_rx, int nof_symbols)
+{
+  if (nof_ports != 2 && nof_ports != 4) {
+    fprintf(stderr, "Number of ports must be 2 or 4 for transmit diversity (nof_ports=%d)\n", nof_ports); // precoding.c:775
+    return false;
+  }
+  if (nof_rx != 1 && nof_rx != 2) {
+    fprintf(stderr, "[srsran_phy_hip] %s: 1 or 2 receive antennas are taken (nof_rxant=%d)\n", who, nof_rx);
+    return false;
+  }
+  if (nof_symbols % nof_ports) {
+    fprintf(stderr, "[srsran_phy_hip] %s: %d symbols are not whole groups of %d\n", who, nof_symbols, nof_ports);
+    return false;
+  }
+  return true;
+}
+
+// the transmit factor as the reference computes it (precoding.c:1958, :1962): double arithmetic on the float argument, converted to float once
+inline float txdiv_tx_scale(uint32_t nof_ports, float scaling)
+{
+  return nof_ports == 2 ? (float)(scaling * M_SQRT1_2) : (float)(scaling / M_SQRT2);
+}
+
+inline bool al16(const void* p)
+{
+  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
+} // namespace
+
+extern "C" int srsran_hip_predecoding_diversity_multi(const cf_t* const d_y[SRSRAN_MAX_PORTS], const cf_t* const d_h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                                      cf_t* const d_x[SRSRAN_MAX_LAYERS], float* d_csi, uint32_t nof_rxant, uint32_t nof_ports,
+                                                      uint32_t nof_symbols, float scaling, void* stream)
+{
+  if (!d_y || !d_h || !d_x || nof_symbols > 0x7fffffffu || !txdiv_shape("srsran_hip_predecoding_diversity_multi", (int)nof_ports, (int)nof_rxant, (int)nof_symbols) ||
+      (reinterpret_cast<uintptr_t>(d_csi) & 7u)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  txdiv::EqParams p = {};
+  for (uint32_t r = 0; r < nof_rxant; r++) {
+    p.y[r] = reinterpret_cast<const float4*>(d_y[r]);
+    for (uint32_t k = 0; k < nof_ports; k++) {
+      p.h[k][r] = reinterpret_cast<const float4*>(d_h[k][r]);
+      if (nof_symbols && (!d_h[k][r] || !al16(d_h[k][r]))) {
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+    }
+    if (nof_symbols && (!d_y[r] || !al16(d_y[r]))) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  for (uint32_t k = 0; k < nof_ports; k++) {
+    p.x[k] = reinterpret_cast<float2*>(d_x[k]);
+    if (nof_symbols && (!d_x[k] || !al16(d_x[k]))) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  if (!device_available()) {
+    return SRSRAN_ERROR;
+  }
+  p.csi      = d_csi;
+  p.x_stride = 1;
+  p.ports    = nof_ports;
+  p.nof_rx   = nof_rxant;
+  p.n        = nof_symbols;
+  p.scaling  = scaling;
+  PHY_HIP_CHECK(txdiv::launch_eq(p, (hipStream_t)stream), SRSRAN_ERROR);
+  return SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_precoding_diversity(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* const d_y[SRSRAN_MAX_PORTS], uint32_t nof_ports,
+                                              uint32_t nof_symbols, float scaling, void* stream)
+{
+  if (!d_x || !d_y || nof_symbols > 0x7fffffffu / 4 || !txdiv_shape("srsran_hip_precoding_diversity", (int)nof_ports, 1, 0)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  txdiv::PrecodeParams p = {};
+  for (uint32_t k = 0; k < nof_ports; k++) {
+    p.x[k] = reinterpret_cast<const float2*>(d_x[k]);
+    p.y[k] = reinterpret_cast<float2*>(d_y[k]);
+    if (nof_symbols && (!d_x[k] || !d_y[k] || !al16(d_y[k]) || (reinterpret_cast<uintptr_t>(d_x[k]) & 7u))) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  if (!device_available()) {
+    return SRSRAN_ERROR;
+  }
+  p.ports = nof_ports;
+  p.n     = nof_symbols;
+  p.scale = txdiv_tx_scale(nof_ports, scaling);
+  PHY_HIP_CHECK(txdiv::launch_precode(p, (hipStream_t)stream), SRSRAN_ERROR);
+  return SRSRAN_SUCCESS;
+}
+
+static int hip_layers(const cf_t* const* d_x, const cf_t* d_d, uint32_t nof_layers, uint32_t n, bool to_layers, void* stream)
+{
+  if (!d_x || nof_layers == 0 || nof_layers > SRSRAN_MAX_LAYERS || (uint64_t)n * nof_layers > 0x7fffffffu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  txdiv::LayerParams p = {};
+  for (uint32_t k = 0; k < nof_layers; k++) {
+    p.x[k] = reinterpret_cast<float2*>(const_cast<cf_t*>(d_x[k]));
+    if (n && (!d_x[k] || (reinterpret_cast<uintptr_t>(d_x[k]) & 7u))) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  if (n && (!d_d || (reinterpret_cast<uintptr_t>(d_d) & 7u))) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (!device_available()) {
+    return SRSRAN_ERROR;
+  }
+  p.d         = reinterpret_cast<float2*>(const_cast<cf_t*>(d_d));
+  p.layers    = nof_layers;
+  p.n         = n;
+  p.to_layers = to_layers ? 1u : 0u;
+  PHY_HIP_CHECK(txdiv::launch_layers(p, (hipStream_t)stream), SRSRAN_ERROR);
+  return SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_layermap_diversity(const cf_t* d_d, cf_t* const d_x[SRSRAN_MAX_LAYERS], uint32_t nof_layers, uint32_t nof_symbols, void* stream)
+{
+  return hip_layers(d_x, d_d, nof_layers, nof_layers ? nof_symbols / nof_layers : 0u, true, stream);
+}
+
+extern "C" int srsran_hip_layerdemap_diversity(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* d_d, uint32_t nof_layers, uint32_t nof_layer_symbols,
+                                               void* stream)
+{
+  return hip_layers(d_x, d_d, nof_layers, nof_layer_symbols, false, stream);
+}
+
+// the HOST-buffer forms: planes into the thread's pinned image (the kernels work on it directly), one kernel, one wait, planes out
+extern "C" int srsran_predecoding_diversity_multi(cf_t* y[SRSRAN_MAX_PORTS], cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], cf_t* x[SRSRAN_MAX_LAYERS],
+                                                  float* csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_symbols, float scaling)
+{
+  if (!y || !h || !x || nof_symbols < 0 || !txdiv_shape("srsran_predecoding_diversity_multi", nof_ports, nof_rxant, nof_symbols)) {
+    return -1;
+  }
+  if (nof_symbols == 0) {
+    return 0;
+  }
+  for (int r = 0; r < nof_rxant; r++) {
+    bool ok = y[r] != nullptr;
+    for (int k = 0; k < nof_ports && ok; k++) {
+      ok = h[k][r] != nullptr && x[k] != nullptr;
+    }
+    if (!ok) {
+      return -1;
+    }
+  }
+  ChanStage* sp = stage_for("srsran_predecoding_diversity_multi");
+  if (!sp) {
+    return -1;
+  }
+  ChanStage&   s  = *sp;
+  hipStream_t  st = sch::stage_stream();
+  const size_t n = (size_t)nof_symbols, nb = al256(n * sizeof(cf_t)), nl = al256(n / nof_ports * sizeof(cf_t));
+  const size_t o_h = (size_t)nof_rxant * nb, o_x = o_h + (size_t)nof_rxant * nof_ports * nb, o_csi = o_x + (size_t)nof_ports * nl;
+  float*       c = (csi && csi[0]) ? csi[0] : nullptr;
+  if (!st || !s.grow(o_csi + al256(n * sizeof(float)), 0)) {
+    return -1;
+  }
+  txdiv::EqParams p = {};
+  for (int r = 0; r < nof_rxant; r++) {
+    memcpy(s.pin + (size_t)r * nb, y[r], n * sizeof(cf_t));
+    p.y[r] = reinterpret_cast<const float4*>(s.pin + (size_t)r * nb);
+    for (int k = 0; k < nof_ports; k++) {
+      uint8_t* at = s.pin + o_h + ((size_t)k * nof_rxant + r) * nb;
+      memcpy(at, h[k][r], n * sizeof(cf_t));
+      p.h[k][r] = reinterpret_cast<const float4*>(at);
+    }
+  }
+  for (int k = 0; k < nof_ports; k++) {
+    p.x[k] = reinterpret_cast<float2*>(s.pin + o_x + (size_t)k * nl);
+  }
+  p.csi      = c ? reinterpret_cast<float*>(s.pin + o_csi) : nullptr;
+  p.x_stride = 1;
+  p.ports    = (uint32_t)nof_ports;
+  p.nof_rx   = (uint32_t)nof_rxant;
+  p.n        = (uint32_t)nof_symbols;
+  p.scaling  = scaling;
+  const bool launched = txdiv::launch_eq(p, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+    return -1;
+  }
+  for (int k = 0; k < nof_ports; k++) {
+    memcpy(x[k], s.pin + o_x + (size_t)k * nl, n / nof_ports * sizeof(cf_t));
+  }
+  if (c) {
+    memcpy(c, s.pin + o_csi, n * sizeof(float));
+  }
+  return nof_symbols / nof_ports;
+}
+
+extern "C" int srsran_precoding_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRSRAN_MAX_PORTS], int nof_ports, int nof_symbols, float scaling)
+{
+  if (!x || !y || nof_symbols < 0 || nof_symbols > 0x7fffffff / 4 || !txdiv_shape("srsran_precoding_diversity", nof_ports, 1, 0)) {
+    return -1;
+  }
+  if (nof_symbols == 0) {
+    return 0;
+  }
+  for (int k = 0; k < nof_ports; k++) {
+    if (!x[k] || !y[k]) {
+      return -1;
+    }
+  }
+  ChanStage* sp = stage_for("srsran_precoding_diversity");
+  if (!sp) {
+    return -1;
+  }
+  ChanStage&   s  = *sp;
+  hipStream_t  st = sch::stage_stream();
+  const size_t n = (size_t)nof_symbols, nl = al256(n * sizeof(cf_t)), nb = al256(n * nof_ports * sizeof(cf_t));
+  const size_t o_y = (size_t)nof_ports * nl;
+  if (!st || !s.grow(o_y + (size_t)nof_ports * nb, 0)) {
+    return -1;
+  }
+  txdiv::PrecodeParams p = {};
+  for (int k = 0; k < nof_ports; k++) {
+    memcpy(s.pin + (size_t)k * nl, x[k], n * sizeof(cf_t));
+    p.x[k] = reinterpret_cast<const float2*>(s.pin + (size_t)k * nl);
+    p.y[k] = reinterpret_cast<float2*>(s.pin + o_y + (size_t)k * nb);
+  }
+  p.ports = (uint32_t)nof_ports;
+  p.n     = (uint32_t)nof_symbols;
+  p.scale = txdiv_tx_scale((uint32_t)nof_ports, scaling);
+  const bool launched = txdiv::launch_precode(p, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+    return -1;
+  }
+  for (int k = 0; k < nof_ports; k++) {
+    memcpy(y[k], s.pin + o_y + (size_t)k * nb, n * nof_ports * sizeof(cf_t));
+  }
+  return nof_ports * nof_symbols;
+}
+
+static int host_layers(cf_t* d, cf_t* x[SRSRAN_MAX_LAYERS], int nof_layers, int n, bool to_layers, const char* who)
+{
+  if (!d || !x || nof_layers < 1 || nof_layers > SRSRAN_MAX_LAYERS || n < 0 || (int64_t)n * nof_layers > 0x7fffffff) {
+    return -1;
+  }
+  if (n == 0) {
+    return 0;
+  }
+  for (int k = 0; k < nof_layers; k++) {
+    if (!x[k]) {
+      return -1;
+    }
+  }
+  ChanStage* sp = stage_for(who);
+  if (!sp) {
+    return -1;
+  }
+  ChanStage&   s  = *sp;
+  hipStream_t  st = sch::stage_stream();
+  const size_t nl = al256((size_t)n * sizeof(cf_t)), nd = al256((size_t)n * nof_layers * sizeof(cf_t));
+  if (!st || !s.grow(nd + (size_t)nof_layers * nl, 0)) {
+    return -1;
+  }
+  txdiv::LayerParams p = {};
+  p.d = reinterpret_cast<float2*>(s.pin.get());
+  for (int k = 0; k < nof_layers; k++) {
+    p.x[k] = reinterpret_cast<float2*>(s.pin + nd + (size_t)k * nl);
+    if (!to_layers) {
+      memcpy(p.x[k], x[k], (size_t)n * sizeof(cf_t));
+    }
+  }
+  if (to_layers) {
+    memcpy(p.d, d, (size_t)n * nof_layers * sizeof(cf_t));
+  }
+  p.layers    = (uint32_t)nof_layers;
+  p.n         = (uint32_t)n;
+  p.to_layers = to_layers ? 1u : 0u;
+  const bool launched = txdiv::launch_layers(p, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+    return -1;
+  }
+  if (to_layers) {
+    for (int k = 0; k < nof_layers; k++) {
+      memcpy(x[k], p.x[k], (size_t)n * sizeof(cf_t));
+    }
+  } else {
+    memcpy(d, p.d, (size_t)n * nof_layers * sizeof(cf_t));
+  }
+  return to_layers ? n : n * nof_layers;
+}
+
+extern "C" int srsran_layermap_diversity(cf_t* d, cf_t* x[SRSRAN_MAX_LAYERS], int nof_layers, int nof_symbols)
+{
+  return host_layers(d, x, nof_layers, (nof_layers > 0 && nof_symbols >= 0) ? nof_symbols / nof_layers : -1, true, "srsran_layermap_diversity");
+}
+
+extern "C" int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, int nof_layers, int nof_layer_symbols)
+{
+  return host_layers(d, x, nof_layers, nof_layer_symbols, false, "srsran_layerdemap_diversity");
+}
+
+// ---- PDSCH codeword with transmit diversity, receive
+
+extern "C" int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return srsran_hip_pdsch_decode_txdiv_dbg(g, symbols, ce, softbuffer, data, res, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+{
+  TraceRange trace_("srsran_hip_pdsch_decode_txdiv");
+  if (res) {
+    *res = {0, 0.f, NAN};
+  }
+  if (!g || !symbols || !ce || !softbuffer || !data || !res) {
+    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode_txdiv: NULL argument\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (!tb_valid(g->tb, "srsran_hip_pdsch_decode_txdiv")) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t ports = g->nof_ports, nrx = g->nof_rx, nof_re = g->tb.nof_re;
+  bool           planes = (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2);
+  for (uint32_t r = 0; planes && r < nrx; r++) {
+    planes = symbols[r] != nullptr;
+    for (uint32_t k = 0; planes && k < ports; k++) {
+      planes = ce[k][r] != nullptr;
+    }
+  }
+  if (!planes || nof_re % ports || !(g->scaling != 0.f) || !std::isfinite(g->scaling)) {
+    set_error("srsran_hip_pdsch_decode_txdiv: %u ports, %u receive antennas, %u REs, scaling %g%s is not a transmit-diversity grant", ports, nrx, nof_re, (double)g->scaling,
+              (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2) && !planes ? ", a NULL plane" : "");
+    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  ChanStage* sp = stage_for("srsran_hip_pdsch_decode_txdiv");
+  if (!sp) {
+    return SRSRAN_ERROR;
+  }
+  ChanStage&      s = *sp;
+  srsran_cbsegm_t seg;
+  if (!segment(&seg, g->tb.tbs)) {
+    return SRSRAN_ERROR;
+  }
+  // staging image: nof_rx symbol planes, then nof_ports x nof_rx estimate planes, each 256-byte aligned; behind them room for what _dbg hands back
+  const srsran_hip_grant_tb_t tb = g->tb;
+  const uint32_t              Qm = qm_of(tb.mod);
+  const size_t                nb = al256((size_t)nof_re * sizeof(cf_t));
+  const size_t                ne = (size_t)nof_re * Qm * (tb.llr_is_8bit ? 1 : 2);
+  const size_t                o_d = (size_t)nrx * (1 + ports) * nb, o_e = o_d + nb;
+  const bool                  want_d = d_out != nullptr, want_e = e_out != nullptr;
+  if (!s.grow(o_e + al256(ne), want_d ? nb : 0)) {
+    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode_txdiv: staging allocation failed\n");
+    return SRSRAN_ERROR;
+  }
+  txdiv::FrontParams fp = {};
+  txdiv::EqParams    ep = {};
+  for (uint32_t r = 0; r < nrx; r++) {
+    memcpy(s.pin + (size_t)r * nb, symbols[r], (size_t)nof_re * sizeof(cf_t));
+    fp.y[r] = ep.y[r] = reinterpret_cast<const float4*>(s.pin + (size_t)r * nb);
+    for (uint32_t k = 0; k < ports; k++) {
+      uint8_t* at = s.pin + ((size_t)nrx + (size_t)k * nrx + r) * nb;
+      memcpy(at, ce[k][r], (size_t)nof_re * sizeof(cf_t));
+      fp.h[k][r] = ep.h[k][r] = reinterpret_cast<const float4*>(at);
+    }
+  }
+  fp.mod     = tb.mod;
+  fp.n       = nof_re;
+  fp.seed    = tb.seed;
+  fp.ports   = ports;
+  fp.nof_rx  = nrx;
+  fp.scaling = g->scaling;
+  for (uint32_t k = 0; k < ports; k++) { // the combined symbols layer-demapped: layer k's symbol i is d[ports i + k]
+    ep.x[k] = reinterpret_cast<float2*>(s.dev.get()) + k;
+  }
+  ep.x_stride = ports;
+  ep.ports    = ports;
+  ep.nof_rx   = nrx;
+  ep.n        = nof_re;
+  ep.scaling  = g->scaling;
+  srsran_hip_sch_head_t head = {tb.max_nof_iterations, 0.f, tb.llr_is_8bit != 0};
+  uint8_t *             p_d = s.pin + o_d, *p_e = s.pin + o_e, *dx = s.dev;
+  const sch::FrontEnd   front = [=](hipStream_t st, void* d_e) mutable {
+    modem::Params mp;
+    if (!modem::params_for(mp, tb.llr_is_8bit ? modem::LLR_I8 : modem::LLR_I16)) {
+      return false;
+    }
+    fp.out     = d_e;
+    fp.x1_bits = mp.x1_bits;
+    fp.x2_cols = mp.x2_cols;
+    fp.k       = mp.k;
+    if (txdiv::launch_front(fp, tb.llr_is_8bit != 0, st) != hipSuccess) {
+      set_error("grant front end: transmit-diversity front-end launch failed");
+      return false;
+    }
+    // what the reference leaves in q->d / q->e: the symbols exist in the front end's registers only, so the per-stage kernel makes them (same arithmetic)
+    if (want_d && (txdiv::launch_eq(ep, st) != hipSuccess || hipMemcpyAsync(p_d, dx, (size_t)nof_re * sizeof(cf_t), hipMemcpyDeviceToHost, st) != hipSuccess)) {
+      set_error("grant front end: the combined symbols could not be produced");
+      return false;
+    }
+    if (want_e && hipMemcpyAsync(p_e, d_e, ne, hipMemcpyDeviceToHost, st) != hipSuccess) {
+      set_error("grant front end: copy of the intermediate results failed");
+      return false;
+    }
+    return true;
+  };
+  const bool ok = sch::decode_tb_staged(&head, softbuffer, &seg, 2 * Qm, tb.rv, nof_re * Qm, nullptr, &front, data);
+  if (want_d) {
+    memcpy(d_out, p_d, (size_t)nof_re * sizeof(cf_t));
+  }
+  if (want_e) {
+    memcpy(e_out, p_e, ne);
+  }
+  res->crc_ok               = ok ? 1 : 0;
+  res->avg_iterations_block = head.avg_iterations;
+  return SRSRAN_SUCCESS;
+}
+
+// ---- PDSCH codeword with transmit diversity, transmit
+
+extern "C" int srsran_hip_pdsch_encode_txdiv(const srsran_hip_pdsch_txdiv_tx_t* g, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, cf_t* const symbols[])
+{
+  return srsran_hip_pdsch_encode_txdiv_multi(1, g, &softbuffer, &data, &symbols);
+}
+
+extern "C" int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_pdsch_txdiv_tx_t* g, srsran_softbuffer_tx_t* const* softbuffers,
+                                                   uint8_t* const* data, cf_t* const* const* symbols)
+{
+  TraceRange trace_("srsran_hip_pdsch_encode_txdiv");
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!g || !softbuffers || !data || !symbols) {
+    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_encode_txdiv: NULL argument\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t ports = g[i].nof_ports;
+    bool           ok    = softbuffers[i] && symbols[i] && (ports == 2 || ports == 4);
+    for (uint32_t k = 0; ok && k < ports; k++) {
+      ok = symbols[i][k] != nullptr;
+    }
+    if (!ok || !(g[i].scaling != 0.f) || !std::isfinite(g[i].scaling)) {
+      set_error("srsran_hip_pdsch_encode_txdiv: codeword %u: %u ports, scaling %g or a NULL argument", i, ports, (double)g[i].scaling);
+      fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (!tb_valid(g[i].tb, "srsran_hip_pdsch_encode_txdiv")) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (g[i].tb.nof_re % ports) {
+      set_error("srsran_hip_pdsch_encode_txdiv: codeword %u: %u REs are not whole groups of %u", i, g[i].tb.nof_re, ports);
+      fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  ChanStage* sp = stage_for("srsran_hip_pdsch_encode_txdiv");
+  if (!sp) {
+    return SRSRAN_ERROR;
+  }
+  ChanStage&                   s = *sp;
+  std::vector<srsran_cbsegm_t> seg(n);
+  std::vector<sch::TxItem>     items(n);
+  std::vector<size_t>          o_out(n); // codeword i: nof_ports planes of al256(nof_re points) from here
+  size_t                       out_bytes = 0, tiles = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!segment(&seg[i], g[i].tb.tbs)) {
+      return SRSRAN_ERROR;
+    }
+    const uint32_t Qm = qm_of(g[i].tb.mod);
+    items[i] = {softbuffers[i], &seg[i], 2 * Qm, g[i].tb.rv, g[i].tb.nof_re * Qm, data[i], 0};
+    o_out[i] = out_bytes;
+    out_bytes += g[i].nof_ports * al256((size_t)g[i].tb.nof_re * sizeof(cf_t));
+    tiles += (g[i].tb.nof_re + MODEM_TILE_SYMS - 1) / MODEM_TILE_SYMS;
+  }
+  const size_t o_jobs = out_bytes, o_tj = al256(o_jobs + n * sizeof(txdiv::ModJob));
+  if (out_bytes / sizeof(cf_t) > 0xffffffffull || !s.grow(al256(o_tj + tiles * sizeof(uint32_t)), 0)) {
+    return SRSRAN_ERROR;
+  }
+  const sch::GroupBackEnd back = [&](hipStream_t st, const uint8_t* d_e, const uint32_t* e_byte_off, uint32_t m) -> bool {
+    modem::Params mp;
+    const float2* tab = modem::mod_tables();
+    if (m != n || !modem::params_for(mp, modem::LLR_I16) || !tab) {
+      return false;
+    }
+    auto*    mj = reinterpret_cast<txdiv::ModJob*>(s.pin + o_jobs);
+    auto*    tj = reinterpret_cast<uint32_t*>(s.pin + o_tj);
+    uint32_t nt = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t cnt   = (g[i].tb.nof_re + MODEM_TILE_SYMS - 1) / MODEM_TILE_SYMS;
+      const size_t   plane = al256((size_t)g[i].tb.nof_re * sizeof(cf_t));
+      mj[i] = {g[i].tb.mod, g[i].tb.nof_re, g[i].tb.seed, g[i].nof_ports, txdiv_tx_scale(g[i].nof_ports, g[i].scaling), e_byte_off[i], {0, 0, 0, 0}, nt};
+      for (uint32_t k = 0; k < g[i].nof_ports; k++) {
+        mj[i].out_off[k] = (uint32_t)((o_out[i] + k * plane) / sizeof(cf_t));
+      }
+      for (uint32_t t = 0; t < cnt; t++) {
+        tj[nt++] = i;
+      }
+    }
+    txdiv::ModParams p = {d_e, reinterpret_cast<float2*>(s.pin.get()), tab, mj, tj, nt, mp.x1_bits, mp.x2_cols};
+    if (txdiv::launch_mod(p, st) != hipSuccess) {
+      set_error("transmit-diversity modulator launch failed");
+      return false;
+    }
+    return true;
+  };
+  const int rc = sch::encode_tbs_staged(items.data(), n, &back);
+  if (rc != SRSRAN_SUCCESS) {
+    return rc;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const size_t plane = al256((size_t)g[i].tb.nof_re * sizeof(cf_t));
+    for (uint32_t k = 0; k < g[i].nof_ports; k++) {
+      memcpy(symbols[i][k], s.pin + o_out[i] + k * plane, (size_t)g[i].tb.nof_re * sizeof(cf_t));
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------------ warm start
 //
 // The first grant of a process used to cost 20-28 ms (profiles/r03_ref_programs.json: pdsch_test -X 1): the device code of every kernel on the path is
@@ -841,7 +1367,7 @@ void warm_one_worker()
     uint32_t tbs, mod, L;
   } grants[] = {{13 * 6120 - 24, SRSRAN_MOD_64QAM, L_prb}, {6144 - 24, SRSRAN_MOD_16QAM, 12}, {40 - 24, SRSRAN_MOD_QPSK, 1}};
   HostSoftbuffers      sb(13);
-  std::vector<cf_t>    grid((size_t)14 * 12 * nof_prb, cf_t(0.5f, -0.5f)), ce((size_t)14 * 12 * nof_prb, cf_t(1.f, 0.f)), sym((size_t)nsymb * 12 * L_prb);
+  std::vector<cf_t>    grid((size_t)14 * 12 * nof_prb, cf_t(0.5f, -0.5f)), ce((size_t)14 * 12 * nof_prb, cf_t(1.f, 0.f)), sym((size_t)nsymb * 12 * L_prb), qsym((size_t)nsymb * 12 * 12);
   std::vector<uint8_t> data(13 * 768 + 64, 0x5a), qbits((size_t)nsymb * 12 * L_prb * 6 / 8 + 8);
   for (uint32_t llr8 = 0; llr8 < 2; llr8++) {
     for (const auto& gr : grants) {
@@ -866,6 +1392,21 @@ void warm_one_worker()
         (void)srsran_hip_ulsch_encode(&tb, nsymb, &sb.tx, data.data(), qbits.data());
       }
     }
+  }
+  // one 2-port transmit-diversity codeword each way (the one-block 16-QAM grant above: 1728 REs on two layers), so the device code of txdiv_kernels.hip
+  // is loaded before the first subframe of a 2-port cell
+  {
+    const uint32_t               nof_re = nsymb * 12 * 12;
+    const srsran_hip_grant_tb_t  tb     = {SRSRAN_MOD_16QAM, 6144 - 24, 0, nof_re, 12345u, 1, 0, 2};
+    std::vector<cf_t>            port1(nof_re);
+    cf_t* const                  planes[SRSRAN_MAX_PORTS] = {sym.data(), port1.data(), nullptr, nullptr};
+    cf_t* const                  est[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {{ce.data(), ce.data()}, {ce.data(), ce.data()}};
+    srsran_hip_pdsch_txdiv_tx_t  tx = {tb, 2, 1.0f};
+    srsran_hip_pdsch_txdiv_rx_t  rx = {tb, 2, 2, 1.0f, 0};
+    srsran_hip_grant_res_t       res;
+    (void)srsran_hip_pdsch_encode_txdiv(&tx, &sb.tx, data.data(), planes);
+    sb.reset();
+    (void)srsran_hip_pdsch_decode_txdiv_dbg(&rx, planes, est, &sb.rx, data.data(), &res, qsym.data(), nullptr);
   }
   // NR: one codeword through the one-call paths of phy_nr_chan_abi.h, transmit then receive -- the 8-block 256-QAM transport block of a 100 MHz
   // carrier with the reference's default decoder parameters, so a worker's first slot finds its context, decoder objects and kernels ready

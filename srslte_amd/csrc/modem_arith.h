@@ -1,5 +1,6 @@
-// modem_arith.h -- the device functions the demodulating kernels share (modem_kernels.hip, nr_chan_kernels.hip): the integer soft-bit arithmetic of
-// demod_soft.c as the x86 reference evaluates it, the Gold-sequence chips of one wave, sign flips and the soft-bit stores.  Device code only.
+// modem_arith.h -- the device functions the demodulating kernels share (modem_kernels.hip, nr_chan_kernels.hip, txdiv_kernels.hip): the integer soft-bit
+// arithmetic of demod_soft.c as the x86 reference evaluates it, the transmit-diversity combiner, the Gold-sequence chips of one wave, sign flips and the
+// soft-bit stores.  Device code only.
 #pragma once
 #include "hip_common.h"
 #include "modem_device.h"
@@ -110,6 +111,54 @@ __device__ __forceinline__ void demod_int(float re, float im, uint32_t idx, uint
       v[6 + c] = L::wrap(cvt_tr((float)L::S256 * f));
     }
   }
+}
+
+// ---- transmit-diversity (SFBC) combining: srsran_predecoding_diversity_csi (mimo/precoding.c:673-778), the one arithmetic of the per-stage kernel and
+// the fused front end (txdiv_kernels.hip).  One RE pair (r0, r1 on neighbouring sub-carriers k, k + 1) carries two layer symbols:
+//   x0 += conj(ha) r0 + hb conj(r1)      x1 += conj(hd) r1 - hc conj(r0)      g0 += |ha|^2 + |hb|^2      g1 += |hd|^2 + |hc|^2      per receive antenna
+// with, for the port pair (a, b), ha = h[a][k], hb = h[b][k + 1], hc = h[b][k], hd = h[a][k + 1].  2 ports: (a, b) = (0, 1), ONE gain g0 for both
+// symbols, replaced by 1e-4 inside the antenna loop when it is 0 (:699-701); 4 ports: (0, 2) on the first pair of a quad and (1, 3) on the second,
+// each symbol with its own gain.  Operation order (ours): every product and sum rounded by itself (nothing contracts); per antenna the two complex
+// products of a symbol are formed, added to each other, then to the accumulator; a gain's four squares are summed left to right, then added.
+struct Sfbc {
+  float x0r = 0.f, x0i = 0.f, x1r = 0.f, x1i = 0.f, g0 = 0.f, g1 = 0.f;
+};
+template <int PORTS>
+__device__ __forceinline__ void sfbc_add(Sfbc& a, float2 ha, float2 hb, float2 hc, float2 hd, float2 r0, float2 r1)
+{
+  const float p0r = __fadd_rn(__fmul_rn(ha.x, r0.x), __fmul_rn(ha.y, r0.y)); // conj(ha) r0
+  const float p0i = __fsub_rn(__fmul_rn(ha.x, r0.y), __fmul_rn(ha.y, r0.x));
+  const float p1r = __fadd_rn(__fmul_rn(hb.x, r1.x), __fmul_rn(hb.y, r1.y)); // hb conj(r1)
+  const float p1i = __fsub_rn(__fmul_rn(hb.y, r1.x), __fmul_rn(hb.x, r1.y));
+  const float q0r = __fadd_rn(__fmul_rn(hd.x, r1.x), __fmul_rn(hd.y, r1.y)); // conj(hd) r1
+  const float q0i = __fsub_rn(__fmul_rn(hd.x, r1.y), __fmul_rn(hd.y, r1.x));
+  const float q1r = __fadd_rn(__fmul_rn(hc.x, r0.x), __fmul_rn(hc.y, r0.y)); // hc conj(r0)
+  const float q1i = __fsub_rn(__fmul_rn(hc.y, r0.x), __fmul_rn(hc.x, r0.y));
+  a.x0r           = __fadd_rn(a.x0r, __fadd_rn(p0r, p1r));
+  a.x0i           = __fadd_rn(a.x0i, __fadd_rn(p0i, p1i));
+  a.x1r           = __fadd_rn(a.x1r, __fsub_rn(q0r, q1r));
+  a.x1i           = __fadd_rn(a.x1i, __fsub_rn(q0i, q1i));
+  a.g0 = __fadd_rn(a.g0, __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(ha.x, ha.x), __fmul_rn(ha.y, ha.y)), __fmul_rn(hb.x, hb.x)), __fmul_rn(hb.y, hb.y)));
+  if (PORTS == 2) {
+    a.g0 = a.g0 == 0.f ? 1e-4f : a.g0;
+  } else {
+    a.g1 = __fadd_rn(a.g1, __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(hd.x, hd.x), __fmul_rn(hd.y, hd.y)), __fmul_rn(hc.x, hc.x)), __fmul_rn(hc.y, hc.y)));
+  }
+}
+// x / den * M_SQRT2 as the C expression evaluates it: float quotient, product in double, rounded once to float
+__device__ __forceinline__ float sfbc_quot(float v, float den)
+{
+  return __double2float_rn(__dmul_rn((double)__fdiv_rn(v, den), 1.41421356237309504880));
+}
+// the pair's two symbols and the two csi values the reference files for its REs.  2 ports: division by g0 scaling, csi = g0; 4 ports: the gains are
+// scaled first, csi = scaled gain / nof_rx
+template <int PORTS>
+__device__ __forceinline__ void sfbc_finish(const Sfbc& a, float scaling, float nof_rx, float2& x0, float2& x1, float2& csi)
+{
+  const float d0 = __fmul_rn(a.g0, scaling), d1 = PORTS == 2 ? d0 : __fmul_rn(a.g1, scaling);
+  x0  = make_float2(sfbc_quot(a.x0r, d0), sfbc_quot(a.x0i, d0));
+  x1  = make_float2(sfbc_quot(a.x1r, d1), sfbc_quot(a.x1i, d1));
+  csi = PORTS == 2 ? make_float2(a.g0, a.g0) : make_float2(__fdiv_rn(d0, nof_rx), __fdiv_rn(d1, nof_rx));
 }
 
 // ---- scrambling chips of one tile -> LDS --------------------------------------------------------------------------------

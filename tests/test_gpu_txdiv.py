@@ -1,0 +1,458 @@
+"""PDSCH transmit diversity on 2 and 4 ports (include/srsran_amd/phy_modem_abi.h: srsran_predecoding_diversity_multi, srsran_precoding_diversity,
+srsran_layer{,de}map_diversity; phy_chan_abi.h: srsran_hip_pdsch_decode_txdiv{,_dbg}, srsran_hip_pdsch_encode_txdiv{,_multi}).
+
+Which test holds what to what:
+  test_equaliser_against_arithmetic        the SFBC combiner to a float64 restatement of the reference's _csi formulas (precoding.c:673-778) written here, within the
+                                           forward error bound of its float operations; the zero-channel pair of the 2-port case
+  test_*_against_the_reference_record      combiner and precoder to what the reference's own functions gave (tests/golden/txdiv_ref.npz, tools/gen_golden_txdiv.py)
+  test_codeword_in_one_call                the fused call to the SAME stages one call at a time (combiner -> layer de-map -> demodulator on the library, the oracle's
+                                           descrambler and decode_tb): verdict, iterations, payload; with _dbg the soft bits and the combined symbols bit for bit
+  test_grant_that_cannot_decode            every soft-buffer row over two transmissions (placement of every soft bit, HARQ combining)
+  test_transmit_*                          the fused transmit call to srsran_hip_pdsch_encode + layer map + precoder one call at a time, bit for bit
+  test_loop_back, test_worker_threads      transmit into receive; four threads at once
+The received planes of the codeword tests come from the oracle's transmit bits through the oracle's modulator and an SFBC precoder written here in numpy,
+a channel that is constant over each RE pair / quad, and noise."""
+import ctypes as C
+import functools
+import os
+import threading
+
+import numpy as np
+import pytest
+
+import oracle_api as O
+
+pytestmark = pytest.mark.gpu
+SB = 18600
+ITERS = 10
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+EPS = 2.0 ** -24
+
+
+def _lib():
+    import srslte_amd as S
+    from srslte_amd import capi
+
+    return S.lib(), capi
+
+
+def _planes(capi, arrs):
+    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
+
+
+def _matrix(capi, h, ports, nrx):
+    return capi.PlaneMatrix(*[capi.PlaneArray(*[h[k][r].ctypes.data for r in range(nrx)]) for k in range(ports)])
+
+
+def _rx_softbuffer(capi, max_cb, dt):
+    rows = [np.zeros(SB, dt) for _ in range(max_cb)]
+    keep = [np.zeros(SB // 8, np.uint8) for _ in range(max_cb)]
+    flags = np.zeros(max_cb, np.bool_)
+    sb = capi.SoftbufferRx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows]), (C.c_void_p * max_cb)(*[k.ctypes.data for k in keep]),
+                           flags.ctypes.data_as(C.POINTER(C.c_bool)), False)
+    return sb, rows, keep, flags
+
+
+def _tx_softbuffer(capi, max_cb):
+    rows = [np.zeros(SB, np.uint8) for _ in range(max_cb)]
+    return capi.SoftbufferTx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows])), rows
+
+
+def _taps(rng, ports, nrx, n, group):
+    """channel planes [ports][nrx][n]: taps 0.9 + 0.1 (randn + j randn), an independent draw per plane (and per group of `group` REs)"""
+    t = 0.9 + 0.1 * (rng.standard_normal((ports, nrx, n // group)) + 1j * rng.standard_normal((ports, nrx, n // group)))
+    return np.ascontiguousarray(np.repeat(t, group, axis=2).astype(np.complex64))
+
+
+def _predecode(lib, capi, y, h, scaling, want_csi=True):
+    """the library's srsran_predecoding_diversity_multi on host planes: (x [ports][n / ports], csi [n] or None)"""
+    ports, nrx, n = h.shape
+    x = np.full((ports, n // ports + 2), 7, np.complex64)
+    csi = np.full(n + 4, 7, np.float32)
+    cp = (C.c_void_p * 2)(csi.ctypes.data if want_csi else None, None)
+    assert lib.srsran_predecoding_diversity_multi(_planes(capi, list(y)), _matrix(capi, h, ports, nrx), _planes(capi, list(x)), cp, nrx, ports, n, scaling) == n // ports
+    assert np.all(x[:, n // ports:] == 7) and np.all(csi[n:] == 7) and (want_csi or np.all(csi == 7))
+    return np.ascontiguousarray(x[:, :n // ports]), (csi[:n].copy() if want_csi else None)
+
+
+def _pair64(ha, hb, hc, hd, r0, r1):
+    """one port pair in float64, [nrx][pairs] each: x0 = sum conj(ha) r0 + hb conj(r1), x1 = sum conj(hd) r1 - hc conj(r0), the two gains, and for each of the four
+    output components the sum of the magnitudes of the real products that enter it"""
+    x0 = (np.conj(ha) * r0 + hb * np.conj(r1)).sum(0)
+    x1 = (np.conj(hd) * r1 - hc * np.conj(r0)).sum(0)
+    g0 = (np.abs(ha) ** 2 + np.abs(hb) ** 2).sum(0)
+    g1 = (np.abs(hd) ** 2 + np.abs(hc) ** 2).sum(0)
+    a = np.abs
+    s0 = (a(ha.real * r0.real) + a(ha.imag * r0.imag) + a(hb.real * r1.real) + a(hb.imag * r1.imag)).sum(0) + \
+        1j * (a(ha.real * r0.imag) + a(ha.imag * r0.real) + a(hb.imag * r1.real) + a(hb.real * r1.imag)).sum(0)
+    s1 = (a(hd.real * r1.real) + a(hd.imag * r1.imag) + a(hc.real * r0.real) + a(hc.imag * r0.imag)).sum(0) + \
+        1j * (a(hd.real * r1.imag) + a(hd.imag * r1.real) + a(hc.imag * r0.real) + a(hc.real * r0.imag)).sum(0)
+    return x0, x1, g0, g1, s0, s1
+
+
+def _ref64(y, h, scaling):
+    """float64 restatement of srsran_predecoding_diversity_csi: (x [ports][n / ports] complex128, S the same shape (real part: bound scale of the real component,
+    imaginary part: of the imaginary one), csi [n])"""
+    ports, nrx, n = h.shape
+    y, h, s = y.astype(np.complex128), h.astype(np.complex128), float(np.float32(scaling))
+    r2 = np.sqrt(2.0)
+    if ports == 2:
+        x0, x1, g0, _, s0, s1 = _pair64(h[0][:, 0::2], h[1][:, 1::2], h[1][:, 0::2], h[0][:, 1::2], y[:, 0::2], y[:, 1::2])
+        den = g0 * s
+        return np.stack([x0 / den * r2, x1 / den * r2]), np.stack([s0 / den * r2, s1 / den * r2]), np.repeat(g0, 2)
+    x0, x1, g0, g1, s0, s1 = _pair64(h[0][:, 0::4], h[2][:, 1::4], h[2][:, 0::4], h[0][:, 1::4], y[:, 0::4], y[:, 1::4])
+    x2, x3, g2, g3, s2, s3 = _pair64(h[1][:, 2::4], h[3][:, 3::4], h[3][:, 2::4], h[1][:, 3::4], y[:, 2::4], y[:, 3::4])
+    xs, ss, csi = [], [], np.zeros(n)
+    for j, (xv, gv, sv) in enumerate(((x0, g0, s0), (x1, g1, s1), (x2, g2, s2), (x3, g3, s3))):
+        xs.append(xv / (gv * s) * r2)
+        ss.append(sv / (gv * s) * r2)
+        csi[j::4] = gv * s / nrx
+    return np.stack(xs), np.stack(ss), csi
+
+
+def _within(x, want, S, factor):
+    """every output component within factor * 2^-24 * S_i of the float64 value"""
+    bound = factor * EPS
+    er, ei = np.abs(x.real - want.real), np.abs(x.imag - want.imag)
+    worst = max(float((er / S.real).max()), float((ei / S.imag).max())) / EPS
+    print("worst error %.2f x 2^-24 x S (bound %g)" % (worst, factor))
+    return bool(np.all(er <= bound * S.real) and np.all(ei <= bound * S.imag))
+
+
+# ---- 1. the combiner against arithmetic
+
+@pytest.mark.parametrize("ports,nrx", [(2, 1), (2, 2), (4, 1), (4, 2)])
+def test_equaliser_against_arithmetic(hiplib, ports, nrx):
+    """Tolerance per component: 24 x 2^-24 x S_i, S_i = sqrt 2 x (sum of |real products| entering it) / (hh_i x scaling) in float64: the standard forward bound
+    of at most 8 products + 7 additions, hh's own sum of at most 8 terms, one division and two multiplications in round-to-nearest float, with a little slack.
+    csi: relative 16 x 2^-24.  nof_re: below one wave, one tile exactly, one pair / quad past a tile, two tiles and a bit."""
+    lib, capi = _lib()
+    rng = np.random.default_rng(100 * ports + nrx)
+    for n in (4, 64, 72, 2048, 2052, 4100):
+        y = np.ascontiguousarray(((rng.standard_normal((nrx, n)) + 1j * rng.standard_normal((nrx, n))) / np.sqrt(2)).astype(np.complex64))
+        h = _taps(rng, ports, nrx, n, 1)
+        for scaling in (1.0, 0.7):
+            want, S, wcsi = _ref64(y, h, scaling)
+            x, csi = _predecode(lib, capi, y, h, scaling)
+            assert _within(x, want, S, 24), (n, scaling)
+            assert np.all(np.abs(csi - wcsi) <= 16 * EPS * wcsi), (n, scaling)
+            x2, _ = _predecode(lib, capi, y, h, scaling, want_csi=False)  # the same formulas whether or not csi is asked for
+            assert np.array_equal(x2.view(np.uint32), x.view(np.uint32)), (n, scaling)
+
+
+def test_equaliser_zero_channel_pair(hiplib):
+    """2 ports: a pair whose channel is all zero divides by 1e-4 (precoding.c:699-701): its two outputs are exactly 0, not NaN, and csi is 1e-4f"""
+    lib, capi = _lib()
+    rng = np.random.default_rng(5)
+    for nrx in (1, 2):
+        n = 72
+        y = np.ascontiguousarray((rng.standard_normal((nrx, n)) + 1j * rng.standard_normal((nrx, n))).astype(np.complex64))
+        h = _taps(rng, 2, nrx, n, 1)
+        h[:, :, 10:12] = 0
+        x, csi = _predecode(lib, capi, y, h, 0.7)
+        assert not (np.ascontiguousarray(x[:, 5]).view(np.uint32) & 0x7fffffff).any(), x[:, 5]  # +0 or -0
+        assert np.all(csi[10:12] == np.float32(1e-4))
+        keep = np.arange(n // 2) != 5
+        want, S, wcsi = _ref64(np.delete(y, [10, 11], 1), np.delete(h, [10, 11], 2), 0.7)
+        assert _within(x[:, keep], want, S, 24) and np.all(np.abs(np.delete(csi, [10, 11]) - wcsi) <= 16 * EPS * wcsi)
+
+
+# ---- 2. against the reference's recorded results
+
+def test_equaliser_against_the_reference_record(hiplib):
+    """within 2 x the bound of test 1: both sides are float evaluations of the same expression (the reference's compiled with FMA)"""
+    lib, capi = _lib()
+    d = np.load(os.path.join(G, "txdiv_ref.npz"))
+    assert [tuple(c) for c in d["rx_cases"]] == [(2, 1, 72), (2, 2, 516), (4, 1, 72), (4, 2, 516)]
+    for ports, nrx, n in d["rx_cases"]:
+        tag = "rx_%d_%d_%d" % (ports, nrx, n)
+        y, h = np.ascontiguousarray(d[tag + "_y"]), np.ascontiguousarray(d[tag + "_h"])
+        for si, scaling in enumerate(d["scalings"]):
+            _, S, _ = _ref64(y, h, scaling)
+            x, csi = _predecode(lib, capi, y, h, float(scaling))
+            assert _within(x, d["%s_x%d" % (tag, si)], S, 2 * 24), (tag, si)
+            rc = d["%s_csi%d" % (tag, si)]
+            assert np.all(np.abs(csi - rc) <= 16 * EPS * rc), (tag, si)
+
+
+def test_precoder_against_the_reference_record(hiplib):
+    """equal as numbers (-0 equals 0): every output is one correctly rounded float product by the same float factor"""
+    lib, capi = _lib()
+    d = np.load(os.path.join(G, "txdiv_ref.npz"))
+    assert [tuple(c) for c in d["tx_cases"]] == [(2, 258), (2, 516), (4, 516)]
+    for ports, n in d["tx_cases"]:
+        tag = "tx_%d_%d" % (ports, n)
+        cw = np.ascontiguousarray(d[tag + "_d"])
+        x = np.full((ports, n // ports + 2), 7, np.complex64)
+        assert lib.srsran_layermap_diversity(O.P(cw), _planes(capi, list(x)), ports, n) == n // ports
+        assert np.array_equal(x[:, :n // ports], cw.reshape(n // ports, ports).T) and np.all(x[:, n // ports:] == 7)
+        back = np.full(n + 2, 7, np.complex64)
+        xl = np.ascontiguousarray(x[:, :n // ports])
+        assert lib.srsran_layerdemap_diversity(_planes(capi, list(xl)), O.P(back), ports, n // ports) == n
+        assert np.array_equal(back[:n], cw) and np.all(back[n:] == 7)
+        for si, scaling in enumerate(d["scalings"]):
+            y = np.full((ports, n + 2), 7, np.complex64)
+            assert lib.srsran_precoding_diversity(_planes(capi, list(xl)), _planes(capi, list(y)), ports, n // ports, float(scaling)) == n
+            want = d["%s_y%d" % (tag, si)]
+            assert np.array_equal(y[:, :n], want), (tag, si, int(np.count_nonzero(y[:, :n] != want)))
+            assert np.all(y[:, n:] == 7)
+
+
+# ---- 3. a codeword in one call
+
+def _sfbc_numpy(d, ports, a):
+    """36.211 6.3.3.3 + 6.3.4.3 on the codeword d: [ports][len(d)] planes, amplitude factor a"""
+    n = d.size
+    p = np.zeros((ports, n), np.complex128)
+    if ports == 2:
+        d0, d1 = d[0::2], d[1::2]
+        p[0, 0::2], p[0, 1::2], p[1, 0::2], p[1, 1::2] = d0, d1, -np.conj(d1), np.conj(d0)
+    else:
+        d0, d1, d2, d3 = d[0::4], d[1::4], d[2::4], d[3::4]
+        p[0, 0::4], p[0, 1::4], p[2, 0::4], p[2, 1::4] = d0, d1, -np.conj(d1), np.conj(d0)
+        p[1, 2::4], p[1, 3::4], p[3, 2::4], p[3, 3::4] = d2, d3, -np.conj(d3), np.conj(d2)
+    return p * a
+
+
+CW_CASES = [(3, 75376, 15000, 2, 2, 0), (4, 31704, 5200, 2, 1, 0), (2, 6200, 2400, 4, 2, 0), (1, 328, 300, 2, 1, 1), (1, 328, 300, 4, 1, 0)]
+CW_IDS = ["64qam_13cb_2x2", "256qam_2x1", "16qam_4x2", "qpsk_2x1_8bit", "qpsk_4x1"]
+SCALING = 0.8
+
+
+def _per_stage_bits(lib, capi, y, h, mod, seed, llr8, scaling):
+    """combiner -> layer de-map -> demodulator on the library one call at a time, the oracle's descrambler: (soft bits, de-mapped symbols)"""
+    ports, nrx, n = h.shape
+    x, _ = _predecode(lib, capi, y, h, scaling)
+    d = np.zeros(n, np.complex64)
+    assert lib.srsran_layerdemap_diversity(_planes(capi, list(x)), O.P(d), ports, n // ports) == n
+    dt = np.int8 if llr8 else np.int16
+    llr = np.zeros(n * O.QM[mod], dt)
+    assert (lib.srsran_demod_soft_demodulate_b if llr8 else lib.srsran_demod_soft_demodulate_s)(mod, O.P(d), O.P(llr), n) == 0
+    return O.sequence_apply(llr, seed), d
+
+
+@functools.lru_cache(maxsize=None)
+def _cw_case(mod, tbs, nof_re, ports, nrx, llr8):
+    """the received planes of one case and what the stages, one call at a time, make of them (computed once, shared by the tests; read only)"""
+    lib, capi = _lib()
+    rng = np.random.default_rng(tbs + nof_re + 10 * ports + nrx)
+    Qm = O.QM[mod]
+    nbits = nof_re * Qm
+    seg = O.cbsegm(tbs)
+    seed = O.pdsch_seed(0x1234, 0, 10, 301)
+    payload_bits = rng.integers(0, 2, tbs).astype(np.uint8)
+    e, _ = O.tb_coded_bits(tbs, 2 * Qm, nbits, 0, None, payload=payload_bits, tx_order=True)
+    assert e.size == nbits
+    cw = O.modulate_bytes(mod, np.packbits(e), nbits, seed=seed, scramble=True)
+    p = _sfbc_numpy(cw.astype(np.complex128), ports, SCALING / np.sqrt(2))
+    h = _taps(rng, ports, nrx, nof_re, ports)
+    snr = {0: 6.0, 1: 9.0, 2: 17.0, 3: 28.0, 4: 34.0}[mod]
+    sigma = 10 ** (-snr / 20) / np.sqrt(2)
+    y = np.einsum("krn,kn->rn", h.astype(np.complex128), p) + sigma * (rng.standard_normal((nrx, nof_re)) + 1j * rng.standard_normal((nrx, nof_re)))
+    y = np.ascontiguousarray(y.astype(np.complex64))
+    llr, d = _per_stage_bits(lib, capi, y, h, mod, seed, llr8, SCALING)
+    soft = np.zeros((seg["C"], SB), llr.dtype)
+    crc = np.zeros(seg["C"], np.uint8)
+    ret, want, avg = O.sch_decode_tb(tbs, 2 * Qm, 0, llr, soft, crc, ITERS)
+    for a in (y, h, llr, d, want, payload_bits):
+        a.setflags(write=False)
+    return dict(y=y, h=h, seed=seed, llr=llr, d=d, ret=ret, want=want, avg=avg, payload_bits=payload_bits, C=seg["C"])
+
+
+def _decode_one(lib, capi, case, mod, tbs, nof_re, ports, nrx, llr8, dbg):
+    dt = np.int8 if llr8 else np.int16
+    nbits = nof_re * O.QM[mod]
+    g = capi.HipPdschTxdivRx(capi.HipGrantTb(mod, tbs, 0, nof_re, case["seed"], ITERS, llr8, 2), ports, nrx, SCALING, 0)
+    sb, rows, keep, flags = _rx_softbuffer(capi, case["C"], dt)
+    data = np.zeros(tbs // 8 + 16, np.uint8)
+    res = capi.HipGrantRes(7, 7.0, 7.0)
+    sym, ce = _planes(capi, list(case["y"])), _matrix(capi, case["h"], ports, nrx)
+    if not dbg:
+        assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(g), sym, ce, C.byref(sb), O.P(data), C.byref(res)) == 0, capi.last_error()
+        return res.crc_ok, res.avg_iterations_block, data, None, None
+    d_out, e_out = np.full(nof_re + 4, 7, np.complex64), np.full(nbits + 8, 7, dt)
+    assert lib.srsran_hip_pdsch_decode_txdiv_dbg(C.byref(g), sym, ce, C.byref(sb), O.P(data), C.byref(res), O.P(d_out), O.P(e_out)) == 0, capi.last_error()
+    return res.crc_ok, res.avg_iterations_block, data, d_out, e_out
+
+
+@pytest.mark.parametrize("mod,tbs,nof_re,ports,nrx,llr8", CW_CASES, ids=CW_IDS)
+def test_codeword_in_one_call(hiplib, mod, tbs, nof_re, ports, nrx, llr8):
+    lib, capi = _lib()
+    case = _cw_case(mod, tbs, nof_re, ports, nrx, llr8)
+    nbits = nof_re * O.QM[mod]
+    assert case["ret"] == 0  # the expected chain itself decodes: the test is only valid on such inputs
+    ok, avg, data, _, _ = _decode_one(lib, capi, case, mod, tbs, nof_re, ports, nrx, llr8, False)
+    print("crc_ok %d avg_iterations_block %g (per stage: %g)" % (ok, avg, case["avg"]))
+    assert ok == 1 and abs(avg - case["avg"]) < 1e-6
+    assert np.array_equal(data[:tbs // 8], case["want"][:tbs // 8]) and np.array_equal(np.unpackbits(data[:tbs // 8]), case["payload_bits"])
+    # with the intermediate results handed back: the same verdict; the soft bits and the combined, de-mapped symbols of the stages bit for bit (this holds the
+    # fused kernel and the per-stage kernel to one arithmetic)
+    ok2, avg2, data2, d_out, e_out = _decode_one(lib, capi, case, mod, tbs, nof_re, ports, nrx, llr8, True)
+    assert ok2 == 1 and avg2 == avg and np.array_equal(data2, data)
+    assert np.array_equal(e_out[:nbits], case["llr"]) and np.all(e_out[nbits:] == 7)
+    assert np.array_equal(d_out[:nof_re].view(np.uint32), case["d"].view(np.uint32)) and np.all(d_out[nof_re:] == 7)
+
+
+# ---- 4. a grant that cannot decode
+
+def test_grant_that_cannot_decode(hiplib):
+    """random symbols on 2 ports, 2 receive antennas (16-QAM, two code blocks): crc_ok == 0 and every soft-buffer row is what the per-stage chain leaves; a
+    second transmission (rv 1) into the same soft buffer combines as the per-stage chain does"""
+    lib, capi = _lib()
+    mod, tbs, nof_re, ports, nrx = 2, 6200, 2400, 2, 2
+    rng = np.random.default_rng(77)
+    Qm = O.QM[mod]
+    seg = O.cbsegm(tbs)
+    nb = seg["C"]
+    seed = O.pdsch_seed(0x4321, 0, 4, 77)
+    sb, rows, keep, flags = _rx_softbuffer(capi, nb + 1, np.int16)
+    soft = np.zeros((nb, SB), np.int16)
+    crc = np.zeros(nb, np.uint8)
+    for rv in (0, 1):
+        y = np.ascontiguousarray((rng.standard_normal((nrx, nof_re)) + 1j * rng.standard_normal((nrx, nof_re))).astype(np.complex64))
+        h = _taps(rng, ports, nrx, nof_re, ports)
+        g = capi.HipPdschTxdivRx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, ITERS, 0, 2), ports, nrx, SCALING, 0)
+        data = np.full(tbs // 8 + 16, 0xA5, np.uint8)
+        res = capi.HipGrantRes(7, 7.0, 7.0)
+        assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(g), _planes(capi, list(y)), _matrix(capi, h, ports, nrx), C.byref(sb), O.P(data), C.byref(res)) == 0, capi.last_error()
+        llr, _ = _per_stage_bits(lib, capi, y, h, mod, seed, 0, SCALING)
+        ret, _, avg = O.sch_decode_tb(tbs, 2 * Qm, rv, llr, soft, crc, ITERS)
+        assert ret == -1 and not crc.any(), (rv, ret, crc)  # the precondition: every row comes back
+        assert res.crc_ok == 0 and not sb.tb_crc and not flags.any(), rv
+        assert abs(res.avg_iterations_block - avg) < 1e-6, (rv, res.avg_iterations_block, avg)
+        for i in range(nb):
+            span = 3 * ((seg["K1"] if i < seg["C1"] else seg["K2"]) + 32) + 12
+            bad = np.flatnonzero(rows[i][:span] != soft[i][:span])
+            assert bad.size == 0, (rv, i, bad.size, span, int(bad[0]))
+            assert not rows[i][span:].any(), (rv, i)
+        assert not rows[nb].any(), rv
+        assert np.all(data[tbs // 8 + 6:] == 0xA5), rv
+
+
+# ---- 5. transmit in one call
+
+def _per_stage_tx(lib, capi, sb, payload, mod, tbs, rv, nof_re, seed, ports, scaling):
+    """srsran_hip_pdsch_encode (two layers, unscaled) -> srsran_layermap_diversity -> srsran_precoding_diversity, one call at a time: [ports][nof_re]"""
+    g = capi.HipPdschTx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, 0, 0, 2), 1.0)
+    d = np.zeros(nof_re, np.complex64)
+    assert lib.srsran_hip_pdsch_encode(C.byref(g), C.byref(sb), O.P(payload) if payload is not None else None, O.P(d)) == 0, capi.last_error()
+    x = np.zeros((ports, nof_re // ports), np.complex64)
+    assert lib.srsran_layermap_diversity(O.P(d), _planes(capi, list(x)), ports, nof_re) == nof_re // ports
+    y = np.zeros((ports, nof_re), np.complex64)
+    assert lib.srsran_precoding_diversity(_planes(capi, list(x)), _planes(capi, list(y)), ports, nof_re // ports, scaling) == nof_re
+    return y
+
+
+TX_SCALINGS = [1.0, float(np.float32(np.sqrt(2) * 0.7))]
+
+
+@pytest.mark.parametrize("ports", [2, 4])
+@pytest.mark.parametrize("mod,tbs,nof_re", [(1, 328, 300), (1, 6200, 5200), (3, 328, 300), (3, 18336, 5200)], ids=["qpsk_300", "qpsk_5200", "64qam_300", "64qam_5200"])
+def test_transmit_in_one_call(hiplib, ports, mod, tbs, nof_re):
+    """every port plane bit for bit the per-stage path's, the sentinels behind each plane intact; a retransmission (data == NULL, rv 2) from the same soft buffer"""
+    lib, capi = _lib()
+    rng = np.random.default_rng(tbs + nof_re + ports)
+    seed = O.pdsch_seed(0x77, 0, 8, 499)
+    payload = rng.integers(0, 256, tbs // 8).astype(np.uint8)
+    nb = O.cbsegm(tbs)["C"]
+    for scaling in TX_SCALINGS:
+        sb, rows = _tx_softbuffer(capi, nb)  # (the rows are the soft buffers' memory: both names stay alive)
+        sb_ref, rows_ref = _tx_softbuffer(capi, nb)
+        for rv, pay in ((0, payload), (2, None)):
+            g = capi.HipPdschTxdivTx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, 0, 0, 2), ports, scaling)
+            out = np.full((ports, nof_re + 8), 7, np.complex64)
+            assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(g), C.byref(sb), O.P(pay) if pay is not None else None, _planes(capi, list(out))) == 0, capi.last_error()
+            want = _per_stage_tx(lib, capi, sb_ref, pay, mod, tbs, rv, nof_re, seed, ports, scaling)
+            assert np.array_equal(out[:, :nof_re].view(np.uint32), want.view(np.uint32)), (scaling, rv)
+            assert np.all(out[:, nof_re:] == 7), (scaling, rv)
+            if ports == 4:  # the idle ports of every pair hold zeros
+                assert not out[0, :nof_re].reshape(-1, 4)[:, 2:].any() and not out[1, :nof_re].reshape(-1, 4)[:, :2].any()
+
+
+def test_transmit_codewords_of_a_tti_in_one_call(hiplib):
+    """srsran_hip_pdsch_encode_txdiv_multi: three codewords of mixed port counts, modulations and sizes = the three single calls"""
+    lib, capi = _lib()
+    rng = np.random.default_rng(31)
+    ues = [(3, 18336, 5200, 2, 1.0, 0), (1, 328, 300, 4, TX_SCALINGS[1], 0), (2, 6200, 2400, 4, 0.5, 2)]  # mod, tbs, nof_re, ports, scaling, rv
+    n = len(ues)
+    grants = (capi.HipPdschTxdivTx * n)()
+    sbs, pays, outs, singles = [], [], [], []
+    for i, (mod, tbs, nof_re, ports, scaling, rv) in enumerate(ues):
+        seed = O.pdsch_seed(0x50 + i, 0, 6, 401)
+        payload = rng.integers(0, 256, tbs // 8).astype(np.uint8)
+        grants[i] = capi.HipPdschTxdivTx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, 0, 0, 2), ports, scaling)
+        one = np.full((ports, nof_re + 8), 7, np.complex64)
+        sb1, rows1 = _tx_softbuffer(capi, O.cbsegm(tbs)["C"])
+        assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(grants[i]), C.byref(sb1), O.P(payload), _planes(capi, list(one))) == 0, capi.last_error()
+        del rows1
+        singles.append(one)
+        sbs.append(_tx_softbuffer(capi, O.cbsegm(tbs)["C"]))
+        pays.append(payload)
+        outs.append(np.full((ports, nof_re + 8), 7, np.complex64))
+    planes = [_planes(capi, list(o)) for o in outs]
+    assert lib.srsran_hip_pdsch_encode_txdiv_multi(n, grants, (C.POINTER(capi.SoftbufferTx) * n)(*[C.pointer(s[0]) for s in sbs]),
+                                                   (C.c_void_p * n)(*[p.ctypes.data for p in pays]),
+                                                   (C.POINTER(C.c_void_p) * n)(*[C.cast(p, C.POINTER(C.c_void_p)) for p in planes])) == 0, capi.last_error()
+    for i in range(n):
+        assert np.array_equal(outs[i].view(np.uint32), singles[i].view(np.uint32)), i
+
+
+# ---- 6. loop back
+
+@pytest.mark.parametrize("ports,nrx", [(2, 2), (4, 1)])
+def test_loop_back(hiplib, ports, nrx):
+    """encode in one call, a pair-constant channel without noise, decode in one call: the payload returns after one half iteration per block (the minimum)"""
+    lib, capi = _lib()
+    mod, tbs, nof_re = 2, 6200, 2400
+    rng = np.random.default_rng(ports + nrx)
+    seed = O.pdsch_seed(0x99, 0, 2, 12)
+    payload = rng.integers(0, 256, tbs // 8).astype(np.uint8)
+    nb = O.cbsegm(tbs)["C"]
+    sbt, txrows = _tx_softbuffer(capi, nb)
+    scaling = TX_SCALINGS[1]  # what an eNB object passes at p_a = -3 dB on a multi-port cell: rho_a sqrt 2
+    gt = capi.HipPdschTxdivTx(capi.HipGrantTb(mod, tbs, 0, nof_re, seed, 0, 0, 2), ports, scaling)
+    p = np.zeros((ports, nof_re), np.complex64)
+    assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(gt), C.byref(sbt), O.P(payload), _planes(capi, list(p))) == 0, capi.last_error()
+    h = _taps(rng, ports, nrx, nof_re, ports)
+    y = np.ascontiguousarray(np.einsum("krn,kn->rn", h.astype(np.complex128), p.astype(np.complex128)).astype(np.complex64))
+    # (the receiver's scaling is the transmitter's: both sides of pdsch.c:486-520 return rho_a with the sqrt 2 of a multi-port cell)
+    gr = capi.HipPdschTxdivRx(capi.HipGrantTb(mod, tbs, 0, nof_re, seed, ITERS, 0, 2), ports, nrx, scaling, 0)
+    sbr, rows, keep, flags = _rx_softbuffer(capi, nb, np.int16)
+    data = np.zeros(tbs // 8 + 16, np.uint8)
+    res = capi.HipGrantRes()
+    assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(gr), _planes(capi, list(y)), _matrix(capi, h, ports, nrx), C.byref(sbr), O.P(data), C.byref(res)) == 0, capi.last_error()
+    assert res.crc_ok == 1 and np.array_equal(data[:tbs // 8], payload)
+    assert res.avg_iterations_block == 1.0
+
+
+# ---- 7. worker threads
+
+def test_worker_threads(hiplib):
+    """four threads at once, each decoding its own case of test 3 twice: what the single-threaded call gives (one worker per subframe in flight is the
+    reference's threading model; staging contexts are per thread)"""
+    lib, capi = _lib()
+    cases = CW_CASES[1:]
+    want = []
+    for c in cases:
+        case = _cw_case(*c)
+        assert case["ret"] == 0
+        want.append(_decode_one(lib, capi, case, *c, True))
+    errors = []
+
+    def worker(i):
+        try:
+            case = _cw_case(*cases[i])
+            for _ in range(2):
+                got = _decode_one(lib, capi, case, *cases[i], True)
+                assert got[0] == want[i][0] == 1 and got[1] == want[i][1]
+                for a, b in zip(got[2:], want[i][2:]):
+                    assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        except Exception as e:  # noqa: BLE001
+            errors.append((i, repr(e)))
+
+    th = [threading.Thread(target=worker, args=(i,)) for i in range(len(cases))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not errors, errors

@@ -1,0 +1,124 @@
+// chan_internal.h -- what the grant-level entry points share (chan_host.cpp: one port; txdiv_host.cpp: transmit diversity): the calling thread's staging
+// context, the grant checks, and the two codeword paths that exist once for both -- PDSCH receive of one codeword, PDSCH transmit of a TTI's codewords.
+#pragma once
+#include "hip_common.h"
+#include "joblist.h"
+#include "sch_stage.h"
+#include "stage.h"
+#include "srsran_amd/phy_chan_abi.h"
+
+#include <map>
+#include <vector>
+
+namespace phyhip {
+namespace chan {
+
+inline uint32_t qm_of(uint32_t mod)
+{
+  return mod == 0 ? 1u : 2u * mod;
+}
+inline uint32_t qm_rm(const srsran_hip_grant_tb_t& tb) // what decode_tb / encode_tb get as Qm (sch.c:590,632)
+{
+  return qm_of(tb.mod) * (tb.nl ? tb.nl : 1u);
+}
+
+// per calling thread: pinned images the kernels read the grant's symbols / channel estimates from and write transmit symbols into, device
+// scratch between the front-end kernels, the transform plans of the allocation sizes seen so far
+struct ChanStage {
+  HostImage pin;
+  DeviceBuf dev;
+  std::map<uint32_t, srsran_hip_dft_batch_t*> idft; // L_prb -> backward, normalised plan of 12 L_prb points (srsran_dft_precoding_init_rx)
+  ~ChanStage()
+  {
+    for (auto& kv : idft) {
+      srsran_hip_dft_batch_free(kv.second);
+    }
+  }
+  bool grow(size_t need_pin, size_t need_dev) { return pin.grow(need_pin, need_pin / 2) && dev.grow(need_dev, need_dev / 2); }
+  srsran_hip_dft_batch_t* plan(uint32_t L_prb)
+  {
+    auto it = idft.find(L_prb);
+    if (it != idft.end()) {
+      return it->second;
+    }
+    srsran_hip_dft_batch_t* h = nullptr;
+    if (srsran_hip_dft_batch_create(&h, (int)(12 * L_prb), SRSRAN_DFT_BACKWARD, false, false, true) != SRSRAN_SUCCESS) {
+      return nullptr;
+    }
+    idft[L_prb] = h;
+    return h;
+  }
+};
+
+// the calling thread's stage; nullptr (one line on stderr) without a device
+ChanStage* stage_for(const char* who);
+
+bool segment(srsran_cbsegm_t* seg, uint32_t tbs);
+bool tb_valid(const srsran_hip_grant_tb_t& tb, const char* who);
+
+// a refused grant: the text is what srsran_hip_last_error() returns and one line on stderr
+template <class... Args>
+int refuse(const char* fmt, Args... args)
+{
+  set_error(fmt, args...);
+  fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+  return SRSRAN_ERROR_INVALID_INPUTS;
+}
+
+// One PDSCH codeword, receive, behind the caller's checks and staging: `make_e` enqueues the front end that leaves the soft bits at d_e; the frame adds
+// the downloads of what the reference leaves in q->d / q->e for its callers to look at (d from `dev_d` when the caller wants it, else nullptr; through
+// the pinned image: d at o_d, e one plane behind it), segments and runs the transport block (`Qm`: the rate matcher's), copies out and fills *res.
+int pdsch_decode_codeword(ChanStage& s, const srsran_hip_grant_tb_t& tb, uint32_t Qm, const sch::FrontEnd& make_e, const uint8_t* dev_d, size_t o_d,
+                          srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
+
+// The codewords of a TTI, transmit, behind the caller's checks: one coding launch over the code blocks of all of them, one launch of the caller's
+// modulator, one host wait.  The pinned image holds, per codeword, `planes` output planes of al256(nof_re points) from o_out, then the job list;
+// `launch(stream, d_e, e_byte_off, JobList<J>&)` writes the jobs (e_byte_off[i]: codeword i's first byte in d_e) and enqueues the kernel.
+struct TxCodeword {
+  const srsran_hip_grant_tb_t* tb;
+  uint32_t                     Qm; // the rate matcher's
+  uint32_t                     planes;
+  srsran_softbuffer_tx_t*      sb;
+  uint8_t*                     data;
+  cf_t* const*                 symbols; // [planes]: where the planes go
+  size_t                       o_out;   // out: the first plane's byte offset in the pinned image
+};
+template <class J, class Launch>
+int pdsch_encode_codewords(ChanStage& s, TxCodeword* cw, uint32_t n, Launch launch)
+{
+  std::vector<srsran_cbsegm_t> seg(n);
+  std::vector<sch::TxItem>     items(n);
+  size_t                       out_bytes = 0, tiles = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const srsran_hip_grant_tb_t& tb = *cw[i].tb;
+    if (!segment(&seg[i], tb.tbs)) { // (behind every codeword's checks: it cannot fail for a grant tb_valid has passed)
+      return SRSRAN_ERROR;
+    }
+    items[i]    = {cw[i].sb, &seg[i], cw[i].Qm, tb.rv, tb.nof_re * qm_of(tb.mod), cw[i].data, 0};
+    cw[i].o_out = out_bytes;
+    out_bytes += cw[i].planes * al256((size_t)tb.nof_re * sizeof(cf_t));
+    tiles += modem::tiles_of(tb.mod, tb.nof_re);
+  }
+  const JobListLayout jl = job_list_layout(out_bytes, n * sizeof(J), tiles);
+  if (out_bytes / sizeof(cf_t) > 0xffffffffull || !s.grow(jl.end, 0)) { // (the jobs count their planes' points from the image's start in 32 bits)
+    return SRSRAN_ERROR;
+  }
+  const sch::GroupBackEnd back = [&](hipStream_t st, const uint8_t* d_e, const uint32_t* e_byte_off, uint32_t m) {
+    JobList<J> jobs(s.pin, jl.o_jobs, jl.o_tj);
+    return m == n && launch(st, d_e, e_byte_off, jobs);
+  };
+  const int rc = sch::encode_tbs_staged(items.data(), n, &back);
+  if (rc != SRSRAN_SUCCESS) {
+    return rc;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const size_t nb = (size_t)cw[i].tb->nof_re * sizeof(cf_t);
+    for (uint32_t k = 0; k < cw[i].planes; k++) {
+      memcpy(cw[i].symbols[k], s.pin + cw[i].o_out + k * al256(nb), nb);
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+} // namespace chan
+} // namespace phyhip

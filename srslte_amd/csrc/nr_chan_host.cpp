@@ -10,6 +10,7 @@
 // Symbols, estimates, payloads and job lists are read from the pinned image by the kernels themselves; soft rows, data rows and soft bits live in the
 // device buffer.
 #include "hip_common.h"
+#include "joblist.h"
 #include "nr_chan_device.h"
 #include "sch_nr_internal.h"
 #include "srsran_amd/phy_nr_chan_abi.h"
@@ -119,7 +120,7 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     if (ce && ce[i]) {
       o = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
     }
-    n_tiles += ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+    n_tiles += modem::tiles_of(g[i].tb.mod, g[i].nof_re);
   }
   const size_t o_e = o;
   for (uint32_t i = 0; i < n; i++) {
@@ -131,8 +132,9 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     cw[i].o_pay = o;
     o           = al256(o + cw[i].c.A / 8 + 8);
   }
-  const size_t pay_bytes = o - o_pay, o_jobs = o, o_tj = al256(o_jobs + (size_t)n * sizeof(nrchan::FrontJob));
-  o                      = al256(o_tj + (size_t)n_tiles * sizeof(uint32_t));
+  const size_t        pay_bytes = o - o_pay;
+  const JobListLayout jl        = job_list_layout(o, (size_t)n * sizeof(nrchan::FrontJob), n_tiles);
+  o                             = jl.end;
   if (o - o_in > 0xffffffffull) {
     NR_CW_REFUSE("%s: %zu bytes of symbols and soft bits in one call", who, o - o_in);
   }
@@ -140,7 +142,8 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
     return SRSRAN_ERROR;
   }
-  nrchan::FrontParams fp;
+  JobList<nrchan::FrontJob> jobs(s.pin, jl.o_jobs, jl.o_tj);
+  nrchan::FrontParams       fp;
   {
     modem::Params mp;
     if (!modem::params_for(mp, modem::LLR_I8)) {
@@ -149,16 +152,13 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     }
     fp.in       = reinterpret_cast<const float2*>(s.pin + o_in);
     fp.out      = reinterpret_cast<int8_t*>(s.dev + o_e);
-    fp.jobs     = reinterpret_cast<const nrchan::FrontJob*>(s.pin + o_jobs);
-    fp.tile_job = reinterpret_cast<const uint32_t*>(s.pin + o_tj);
+    fp.jobs     = jobs.jobs;
+    fp.tile_job = jobs.tile_job;
     fp.n_tiles  = n_tiles;
     fp.x1_bits = mp.x1_bits, fp.x2_cols = mp.x2_cols, fp.k = mp.k;
   }
   // ---- staging: symbols, estimates, job lists; rows and stored blocks of retransmissions
-  auto*     jobs  = reinterpret_cast<nrchan::FrontJob*>(s.pin + o_jobs);
-  uint32_t* tjob  = reinterpret_cast<uint32_t*>(s.pin + o_tj);
-  uint32_t  tile0 = 0;
-  uint8_t   flags[NrTbStage::MAX_CB];
+  uint8_t flags[NrTbStage::MAX_CB];
   std::vector<srsran_hip_nr_tb_t> tbs(n);
   for (uint32_t i = 0; i < n; i++) {
     RxCw&                         w  = cw[i];
@@ -170,13 +170,9 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     if (eq) {
       memcpy(s.pin + w.o_ce, ce[i], nb);
     }
-    const uint32_t nt = ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
-    jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
-                               (uint32_t)(w.o_e - o_e), g[i].seed, tile0, nt, g[i].noise_estimate, g[i].noise_estimate > 0.f ? 1u : 0u};
-    for (uint32_t t = 0; t < nt; t++) {
-      tjob[tile0 + t] = i;
-    }
-    tile0 += nt;
+    const uint32_t nt = modem::tiles_of(g[i].tb.mod, g[i].nof_re);
+    jobs.jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
+                                    (uint32_t)(w.o_e - o_e), g[i].seed, jobs.append(i, nt), nt, g[i].noise_estimate, g[i].noise_estimate > 0.f ? 1u : 0u};
     const bool new_data = (g[i].tb.rv & SRSRAN_HIP_NR_TB_NEW_DATA) != 0;
     const uint32_t cb_bytes = (c.Kp - c.L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (sch_nr.c:650-652)
     bool any_soft = false;
@@ -339,7 +335,7 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
       NR_CW_REFUSE("%s: codeword %u: more than %u code blocks in one call", who, i, NrTbStage::MAX_CB);
     }
     n_cb += cfg[i].C;
-    n_tiles += ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+    n_tiles += modem::tiles_of(g[i].tb.mod, g[i].nof_re);
   }
   NrTbStage& s = tb_stage();
   if (!s.ready()) {
@@ -367,8 +363,8 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
     o_sym[i] = o;
     o        = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
   }
-  const size_t o_jobs = o, o_tj = al256(o_jobs + (size_t)n * sizeof(nrchan::ModJob));
-  o                   = al256(o_tj + (size_t)n_tiles * sizeof(uint32_t));
+  const JobListLayout jl = job_list_layout(o, (size_t)n * sizeof(nrchan::ModJob), n_tiles);
+  o                      = jl.end;
   if (o > 0xffffffffull) {
     NR_CW_REFUSE("%s: %zu bytes in one call", who, o);
   }
@@ -378,9 +374,7 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
     fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
     return SRSRAN_ERROR;
   }
-  auto*                           jobs  = reinterpret_cast<nrchan::ModJob*>(s.pin + o_jobs);
-  uint32_t*                       tjob  = reinterpret_cast<uint32_t*>(s.pin + o_tj);
-  uint32_t                        tile0 = 0;
+  JobList<nrchan::ModJob>         jobs(s.pin, jl.o_jobs, jl.o_tj);
   std::vector<srsran_hip_nr_tb_t> tbs(n);
   for (uint32_t i = 0; i < n; i++) {
     memcpy(s.pin + o_pay[i], data[i], cfg[i].A / 8);
@@ -388,13 +382,9 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
     tbs[i].e_offset       = (uint32_t)(o_e[i] - e0);
     tbs[i].payload_offset = (uint32_t)o_pay[i];
     tbs[i].first_cb       = 0;
-    const uint32_t nt     = ceil_div(g[i].nof_re, MODEM_TILE_SYMS);
+    const uint32_t nt     = modem::tiles_of(g[i].tb.mod, g[i].nof_re);
     const float    scale  = (g[i].scaling != 0.f && !std::isnan(g[i].scaling)) ? g[i].scaling : 1.0f;
-    jobs[i] = nrchan::ModJob{g[i].tb.mod, g[i].nof_re, g[i].seed, scale, (uint32_t)(o_e[i] - e0), (uint32_t)((o_sym[i] - s0) / sizeof(cf_t)), tile0, nt};
-    for (uint32_t t = 0; t < nt; t++) {
-      tjob[tile0 + t] = i;
-    }
-    tile0 += nt;
+    jobs.jobs[i] = nrchan::ModJob{g[i].tb.mod, g[i].nof_re, g[i].seed, scale, (uint32_t)(o_e[i] - e0), (uint32_t)((o_sym[i] - s0) / sizeof(cf_t)), jobs.append(i, nt), nt};
   }
   auto fail = [&](const char* what) {
     (void)hipStreamSynchronize(s.st);
@@ -406,7 +396,7 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
     return fail("transport blocks");
   }
   nrchan::ModParams p;
-  p.bits = s.dev + e0, p.out = reinterpret_cast<float2*>(s.pin + s0), p.table = tab, p.jobs = jobs, p.tile_job = tjob, p.n_tiles = n_tiles;
+  p.bits = s.dev + e0, p.out = reinterpret_cast<float2*>(s.pin + s0), p.table = tab, p.jobs = jobs.jobs, p.tile_job = jobs.tile_job, p.n_tiles = n_tiles;
   p.x1_bits = mp.x1_bits, p.x2_cols = mp.x2_cols;
   const hipError_t e = nrchan::launch_mod(p, s.st);
   if (e != hipSuccess) {

@@ -202,7 +202,7 @@ int rx_host(const T* input, T* output, uint32_t in_len, uint32_t cb_idx, uint32_
 
 // rm_turbo.c:276-340 builds every table of every block size here, and srsran_sch_init calls it (sch.c:166): the init-time hook of the transport-block
 // path.  All 188 sizes x 4 redundancy versions x {16-bit decoder layout, 8-bit decoder layout, transmit side} in one allocation and one upload
-// (about 40 MB, 0.1 s), then one worker's staging contexts warmed (chan_host.cpp: srsran_hip_warmup).
+// (about 40 MB, 0.1 s), then one worker's staging contexts warmed (warmup_host.cpp: srsran_hip_warmup).
 extern "C" int srsran_hip_warmup(uint32_t nof_workers);
 extern "C" void srsran_rm_turbo_gentables(void)
 {
@@ -217,7 +217,7 @@ extern "C" void srsran_rm_turbo_free_tables(void) {}
 
 namespace phyhip {
 namespace rm {
-bool build_all_tables()
+bool build_all_tables() // (declared in stage.h)
 {
   std::lock_guard<std::mutex> lk(g_pool.mu);
   if (g_pool.all) {

@@ -501,7 +501,7 @@ hipStream_t stage_stream()
 // decode_tb_cb for n transport blocks on the thread's stage: ONE upload, one de-matching and one early-stop decoder launch per block size over the code
 // blocks of ALL of them, one transport-CRC launch, one download, one host wait (a second one only when a code block failed and its combined soft bits
 // have to come back for the next transmission).  The e bits of a block are either the caller's host array (`e_bits`) or -- `front` given -- produced
-// ON THE DEVICE by the kernels `front(stream, d_e_bits)` enqueues in front of the de-matcher (chan_host.cpp: equaliser, transform de-precoding,
+// ON THE DEVICE by the kernels `front(stream, d_e_bits)` enqueues in front of the de-matcher (chan_host.cpp, txdiv_host.cpp: equaliser, transform de-precoding,
 // demodulator + descrambler never leave the device).  One call takes blocks of one soft-bit width, one iteration limit and one kind of e-bit source;
 // a mixed list is decoded piece by piece.
 static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const phyhip::sch::GroupFrontEnd* group, uint32_t base)

@@ -1,4 +1,4 @@
-// sch_stage.h -- the calling thread's transport-block stage (sch_host.cpp) as the grant-level entry points (chan_host.cpp) use it
+// sch_stage.h -- the calling thread's transport-block stage (sch_host.cpp) as the grant-level entry points (chan_host.cpp, txdiv_host.cpp) use it
 #pragma once
 #include "srsran_amd/phy_sch_abi.h"
 

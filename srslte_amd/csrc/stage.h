@@ -119,4 +119,8 @@ private:
 using DeviceBuf = StageBuf<StageMem::Device>;
 using HostImage = StageBuf<StageMem::HostImage>;
 
+namespace rm {
+bool build_all_tables(); // every rate-matching table in one allocation and one upload (rm_host.cpp): what srsran_hip_warmup (warmup_host.cpp) starts with
+}
+
 } // namespace phyhip

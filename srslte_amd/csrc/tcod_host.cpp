@@ -750,7 +750,7 @@ int phyhip::sch::encode_tbs_staged(TxItem* it, uint32_t n, const GroupBackEnd* b
   return encode_items(it, n, false, [&](hipStream_t st, const uint8_t* d_e, uint8_t*, const uint32_t* e_off) { return (*back)(st, d_e, e_off, n); });
 }
 
-// `back` given: the e bits stay on the device and the kernels back(stream, d_e_bits) enqueues consume them there (chan_host.cpp: scrambling +
+// `back` given: the e bits stay on the device and the kernels back(stream, d_e_bits) enqueues consume them there (chan_host.cpp, txdiv_host.cpp: scrambling +
 // modulation, or the UL channel interleaver) -- their results are the caller's to collect after this function's one host wait.  Otherwise they come
 // down to e_bits.
 int phyhip::sch::encode_tb_staged(srsran_softbuffer_tx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits, uint8_t* data,

@@ -370,31 +370,42 @@ def test_transmit_in_one_call(hiplib, ports, mod, tbs, nof_re):
 
 
 def test_transmit_codewords_of_a_tti_in_one_call(hiplib):
-    """srsran_hip_pdsch_encode_txdiv_multi: three codewords of mixed port counts, modulations and sizes = the three single calls"""
+    """srsran_hip_pdsch_encode_txdiv_multi: three codewords of mixed port counts, modulations and sizes = the three single calls (a job list of one entry
+    each), sentinels behind every plane included.  A second TTI has codewords of 2044, 2048 and 2052 symbols around the 2048 of a workgroup: one short of
+    full, exactly full (so the next codeword's first workgroup follows a full one: a wrong tile0 shows in it) and four symbols into a second workgroup;
+    its planes are also held to the per-stage path, which has no job list at all."""
     lib, capi = _lib()
     rng = np.random.default_rng(31)
-    ues = [(3, 18336, 5200, 2, 1.0, 0), (1, 328, 300, 4, TX_SCALINGS[1], 0), (2, 6200, 2400, 4, 0.5, 2)]  # mod, tbs, nof_re, ports, scaling, rv
-    n = len(ues)
-    grants = (capi.HipPdschTxdivTx * n)()
-    sbs, pays, outs, singles = [], [], [], []
-    for i, (mod, tbs, nof_re, ports, scaling, rv) in enumerate(ues):
-        seed = O.pdsch_seed(0x50 + i, 0, 6, 401)
-        payload = rng.integers(0, 256, tbs // 8).astype(np.uint8)
-        grants[i] = capi.HipPdschTxdivTx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, 0, 0, 2), ports, scaling)
-        one = np.full((ports, nof_re + 8), 7, np.complex64)
-        sb1, rows1 = _tx_softbuffer(capi, O.cbsegm(tbs)["C"])
-        assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(grants[i]), C.byref(sb1), O.P(payload), _planes(capi, list(one))) == 0, capi.last_error()
-        del rows1
-        singles.append(one)
-        sbs.append(_tx_softbuffer(capi, O.cbsegm(tbs)["C"]))
-        pays.append(payload)
-        outs.append(np.full((ports, nof_re + 8), 7, np.complex64))
-    planes = [_planes(capi, list(o)) for o in outs]
-    assert lib.srsran_hip_pdsch_encode_txdiv_multi(n, grants, (C.POINTER(capi.SoftbufferTx) * n)(*[C.pointer(s[0]) for s in sbs]),
-                                                   (C.c_void_p * n)(*[p.ctypes.data for p in pays]),
-                                                   (C.POINTER(C.c_void_p) * n)(*[C.cast(p, C.POINTER(C.c_void_p)) for p in planes])) == 0, capi.last_error()
-    for i in range(n):
-        assert np.array_equal(outs[i].view(np.uint32), singles[i].view(np.uint32)), i
+    ttis = [  # mod, tbs, nof_re, ports, scaling, rv
+        [(3, 18336, 5200, 2, 1.0, 0), (1, 328, 300, 4, TX_SCALINGS[1], 0), (2, 6200, 2400, 4, 0.5, 2)],
+        [(1, 328, 2044, 2, 1.0, 0), (1, 328, 2048, 4, TX_SCALINGS[1], 0), (1, 328, 2052, 2, 1.0, 0)],
+    ]
+    for t, ues in enumerate(ttis):
+        n = len(ues)
+        grants = (capi.HipPdschTxdivTx * n)()
+        sbs, pays, outs, singles = [], [], [], []
+        for i, (mod, tbs, nof_re, ports, scaling, rv) in enumerate(ues):
+            seed = O.pdsch_seed(0x50 + i, 0, 6, 401)
+            payload = rng.integers(0, 256, tbs // 8).astype(np.uint8)
+            grants[i] = capi.HipPdschTxdivTx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, 0, 0, 2), ports, scaling)
+            one = np.full((ports, nof_re + 8), 7, np.complex64)
+            sb1, rows1 = _tx_softbuffer(capi, O.cbsegm(tbs)["C"])
+            assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(grants[i]), C.byref(sb1), O.P(payload), _planes(capi, list(one))) == 0, capi.last_error()
+            if t == 1:
+                stage = _per_stage_tx(lib, capi, sb1, payload, mod, tbs, rv, nof_re, seed, ports, scaling)
+                assert np.array_equal(one[:, :nof_re].view(np.uint32), stage.view(np.uint32)), i
+            del rows1
+            singles.append(one)
+            sbs.append(_tx_softbuffer(capi, O.cbsegm(tbs)["C"]))
+            pays.append(payload)
+            outs.append(np.full((ports, nof_re + 8), 7, np.complex64))
+        planes = [_planes(capi, list(o)) for o in outs]
+        assert lib.srsran_hip_pdsch_encode_txdiv_multi(n, grants, (C.POINTER(capi.SoftbufferTx) * n)(*[C.pointer(s[0]) for s in sbs]),
+                                                       (C.c_void_p * n)(*[p.ctypes.data for p in pays]),
+                                                       (C.POINTER(C.c_void_p) * n)(*[C.cast(p, C.POINTER(C.c_void_p)) for p in planes])) == 0, capi.last_error()
+        for i, (mod, tbs, nof_re, ports, scaling, rv) in enumerate(ues):
+            assert np.array_equal(outs[i].view(np.uint32), singles[i].view(np.uint32)), (t, i)
+            assert np.all(outs[i][:, nof_re:] == 7), (t, i)
 
 
 # ---- 6. loop back

@@ -23,9 +23,14 @@
  * cell) is taken by srsran_hip_pdsch_decode_txdiv / srsran_hip_pdsch_encode_txdiv: SFBC combining over 1 or 2 receive antennas and layer de-mapping sit in
  * front of the demodulator in one kernel, the layer map and the SFBC precoder are the modulator's store.
  *
- * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD
- * (two codewords, 2x2 ZF / MMSE, PMI), CSI weighting of the soft bits (cfg->csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI only),
- * 8-bit soft bits on a grant with control information, the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the
+ * A PDSCH grant of a 2-port cell sent with large-delay CDD (TM3: two codewords) or closed-loop spatial multiplexing (TM4: a PMI, one or two codewords),
+ * received on 2 antennas, is taken by srsran_hip_pdsch_decode_mimo / srsran_hip_pdsch_encode_mimo: the precoder applied to the estimates, the 2x2 ZF / MMSE solve
+ * (or maximum-ratio combining), the demodulator and the descrambler of BOTH codewords are one kernel, and both transport blocks decode behind it in one pass.
+ *
+ * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD on 4 ports (the
+ * reference refuses them too) or with other than 2 receive antennas, PMI and condition-number selection (srsran_precoding_pmi_select, srsran_precoding_cn:
+ * reductions over a whole subframe's estimates), CSI weighting of the soft bits (cfg->csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
+ * only), 8-bit soft bits on a grant with control information, the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the
  * control bits themselves, EVM measurement.
  * The NR shared channels (pdsch_nr.c / pusch_nr.c, LDPC) have their own one-call-per-codeword entry points in phy_nr_chan_abi.h.
  */
@@ -179,6 +184,60 @@ SRSRAN_API int srsran_hip_pdsch_encode_txdiv(const srsran_hip_pdsch_txdiv_tx_t* 
 SRSRAN_API int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_pdsch_txdiv_tx_t* g, srsran_softbuffer_tx_t* const* softbuffers,
                                                    uint8_t* const* data, cf_t* const* const* symbols);
 
+/* ---- PDSCH with spatial multiplexing or large-delay CDD on a 2-port cell, 2 receive antennas: one or two codewords in ONE call (pdsch.c:788 / :1017 with
+ * tx_scheme == SRSRAN_TXSCHEME_CDD or SRSRAN_TXSCHEME_SPATIALMUX).  Taken: CDD with 2 layers and 2 codewords; spatial multiplexing with 2 layers and 2
+ * codewords (codebook_idx 0 .. 2 = pmi + 1, pdsch.c:867) or 1 layer and 1 codeword (codebook_idx 0 .. 3).  Layer mapping is the identity in all three
+ * (nof_layers == nof_tb, pdsch.c:858): codeword k is layer k.  The arithmetic, its limits and the decoder values: srsran_hip_predecoding_mimo (phy_modem_abi.h).
+ * Receive: symbols[rx], ce[port][rx] as for transmit diversity (nof_re REs each, HOST memory, only read).  One staging image (2 + 4 planes), one front-end
+ * kernel for both codewords (srsran_hip_predecoding_mimo's arithmetic -> demodulator -> descrambler per codeword; the equalised symbols never reach memory),
+ * one decoding pass over the code blocks of both transport blocks, one host wait.  softbuffers[k] == NULL skips codeword k (the reference skips a transport
+ * block whose crc is already set, pdsch.c:893): its layer is still part of the solve, res[k] = {0, 0, NAN}, data[k] is not touched.  Both res entries are
+ * initialised before anything is checked.
+ * Refused before anything is enqueued, with one line on stderr and SRSRAN_ERROR_INVALID_INPUTS: NULL arguments or a NULL plane, nof_rx != 2, a (tx_scheme,
+ * nof_layers, nof_tb) other than the three above (4 ports have no field: the reference refuses them, precoding.c:1035, :1852, :2078), a codebook_idx out of
+ * range, an odd nof_re with CDD, a decoder that is neither ZF nor MMSE, scaling 0 or not finite, a negative or non-finite noise_estimate, two codewords
+ * whose nof_re, llr_is_8bit or max_nof_iterations differ, every codeword skipped, and what every grant call refuses per codeword (modulation, tbs, rv,
+ * length).  A device-side failure returns SRSRAN_ERROR.
+ * Not taken: PMI and condition-number selection, CSI weighting of the soft bits (csi_enable), EVM, resource (de)mapping, 4 ports. */
+typedef struct SRSRAN_API {
+  srsran_hip_grant_tb_t tb[2]; /* tb[k]: codeword k; seed with q = k; tb[k].nl is taken as 1; nof_re = REs of the grant, the same in both */
+  uint32_t nof_tb;             /* 1 or 2 */
+  uint32_t nof_layers;         /* = nof_tb */
+  uint32_t tx_scheme;          /* SRSRAN_HIP_TXSCHEME_CDD or SRSRAN_HIP_TXSCHEME_SPATIALMUX */
+  uint32_t codebook_idx;       /* spatial multiplexing only */
+  uint32_t decoder;            /* SRSRAN_HIP_MIMO_DECODER_ZF or _MMSE (two layers) */
+  uint32_t nof_rx;             /* 2 */
+  float    scaling;            /* pdsch_scaling */
+  float    noise_estimate;     /* MMSE: added to the diagonal; 0 is what srsran_pdsch_decode passes for SRSRAN_MIMO_DECODER_ZF */
+} srsran_hip_pdsch_mimo_rx_t;
+SRSRAN_API int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                            srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                            srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS]);
+/* the same, and per codeword (the array or an entry may be NULL) d_out[k] <- the nof_re equalised symbols of layer k (q->d[k]; made by the per-stage kernel
+ * in this case only: same arithmetic), e_out[k] <- the nof_re * Qm descrambled soft bits (q->e[k]: int16, int8 with llr_is_8bit; not for a skipped codeword).
+ * SRSRAN_ERROR when an output that was asked for was not produced: the front end does not run for a codeword whose soft buffer has fewer rows than it has code
+ * blocks, or whose code blocks were all decoded in an earlier round. */
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
+                                                void* const e_out[SRSRAN_MAX_CODEWORDS]);
+/* Transmit: one coding launch over the code blocks of the grant's codewords, then scrambling + modulation of each codeword + srsran_hip_precoding_mimo's
+ * arithmetic in one kernel: symbols[port] <- nof_re points each (HOST memory), ready for srsran_pdsch_put per port.  data[k] == NULL: a retransmission of what
+ * softbuffers[k] holds.  Refusals as on the receive side (both soft buffers of a two-codeword grant are needed). */
+typedef struct SRSRAN_API {
+  srsran_hip_grant_tb_t tb[2]; /* as above; max_nof_iterations, llr_is_8bit unused */
+  uint32_t nof_tb;
+  uint32_t nof_layers;
+  uint32_t tx_scheme;
+  uint32_t codebook_idx;
+  float    scaling;
+} srsran_hip_pdsch_mimo_tx_t;
+SRSRAN_API int srsran_hip_pdsch_encode_mimo(const srsran_hip_pdsch_mimo_tx_t* g, srsran_softbuffer_tx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                            uint8_t* const data[SRSRAN_MAX_CODEWORDS], cf_t* const symbols[]);
+/* the grants of one TTI in ONE call: one coding launch, one modulation + precoding launch, one host wait; softbuffers[i][k], data[i][k], symbols[i][port] */
+SRSRAN_API int srsran_hip_pdsch_encode_mimo_multi(uint32_t n, const srsran_hip_pdsch_mimo_tx_t* g, srsran_softbuffer_tx_t* const (*softbuffers)[SRSRAN_MAX_CODEWORDS],
+                                                  uint8_t* const (*data)[SRSRAN_MAX_CODEWORDS], cf_t* const* const* symbols);
+
 /* ---- UL-SCH transmit without UCI (srsran_ulsch_encode, sch.c:1194-1340, with no ACK / RI / CQI configured): encode_tb -> channel
  * interleaver of 36.212 5.2.2.8 over nof_symb columns.  q_bits: nof_bits = nof_re * Qm bits, byte packed (what pusch.c:322 scrambles next). */
 SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t nof_symb, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, uint8_t* q_bits);
@@ -186,7 +245,8 @@ SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t
 /* ---- warm start.  The first grant of a process / of a worker thread otherwise pays for loading the kernels' device code, creating the thread's staging
  * context (stream, pinned and device images, decoder / encoder objects, transform plans) and building rate-matching tables: 20-28 ms where a warm
  * call takes 0.1-0.4 ms.  srsran_hip_warmup(n) builds every rate-matching table and prepares n staging contexts by running real grants (the
- * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits; one 2-port transmit-diversity grant each way) on short-lived threads; a worker
+ * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits; one 2-port transmit-diversity grant and one two-codeword
+ * spatial-multiplexing grant each way) on short-lived threads; a worker
  * thread adopts a prepared context at its first call.  srsran_rm_turbo_gentables() -- which srsran_sch_init calls (sch.c:166) -- does the same
  * for one worker, so an application that does nothing gets a warm first subframe on one thread; srsenb's pool of nof_phy_threads workers
  * wants srsran_hip_warmup(nof_phy_threads) once after its objects are created.  Idempotent; returns SRSRAN_ERROR without a device. */

@@ -117,6 +117,44 @@ SRSRAN_API int srsran_hip_layermap_diversity(const cf_t* d_d, cf_t* const d_x[SR
 SRSRAN_API int srsran_hip_layerdemap_diversity(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* d_d, uint32_t nof_layers, uint32_t nof_layer_symbols,
                                                void* stream);
 
+/* ---- spatial multiplexing and large-delay CDD on 2 ports with 2 receive antennas (TM3 / TM4; TS 36.211 6.3.4.2): the bodies srsran_predecoding_type and
+ * srsran_precoding_type dispatch to for SRSRAN_TXSCHEME_CDD and SRSRAN_TXSCHEME_SPATIALMUX (precoding.c:841-1858 receive, :2044-2211 transmit; utils/mat.c:63-109).
+ * The reference exports no name per scheme for them, and its _type dispatchers also take the schemes the entry points above have, so no reference name is
+ * claimed: the arguments are those of the _type functions plus the decoder, which the reference keeps in a process-wide variable
+ * (srsran_predecoding_set_mimo_decoder).  tx_scheme and decoder carry the values of srsran_tx_scheme_t / srsran_mimo_decoder_t (phy_common.h:273-280).
+ * Taken, all with nof_ports == 2 and nof_rxant == 2:
+ *   SRSRAN_HIP_TXSCHEME_CDD          2 layers; the precoder alternates with the parity of the RE index; nof_symbols even (the reference's loop runs past the end
+ *                                    of an odd count)
+ *   SRSRAN_HIP_TXSCHEME_SPATIALMUX   2 layers, codebook_idx 0 .. 2 (pmi + 1, pdsch.c:867); 1 layer, codebook_idx 0 .. 3 (maximum-ratio combining over both
+ *                                    receive antennas); any nof_symbols
+ * Receive: y[rx][nof_symbols], h[port][rx][nof_symbols] -> x[layer][nof_symbols].  The formulas and their operation order are those of the reference's scalar loop
+ * bodies of the _csi variants (what srsran_pdsch_decode runs), whether or not csi is given; every float operation is rounded once, nothing contracts; the
+ * reference's vector bodies use a reciprocal estimate and differ from this by up to 1.5 x 2^-12 relative.  A singular channel gets no replacement value: what
+ * the formula gives (inf / NaN) comes out.  SRSRAN_HIP_MIMO_DECODER_MMSE with noise_estimate 0 is the reference's default (pdsch.c:819 zeroes the noise for ZF
+ * and leaves the process-wide decoder at MMSE).  csi (when csi and csi[0] are non-NULL), nof_symbols floats per row, as the reference's scalar bodies write it:
+ * ZF 1.0 -- for CDD in csi[0] and csi[1], for spatial multiplexing in csi[0] ONLY, csi[1] is left untouched (:1330-1331); MMSE 1 / Re(B00) in csi[0] and
+ * 1 / Re(B11) in csi[1] (when non-NULL), B = norm (H^H H + noise I)^-1; one layer |h|^2 / norm * (float)M_SQRT1_2 in csi[0].
+ * Transmit: x[layer][nof_symbols] -> y[port][nof_symbols]; every output component is one float sum or difference times the reference's float factor
+ * (scaling / 2, or (float)(scaling * M_SQRT1_2) for one layer and codebook 0); a multiplication by +-j is a swap and a sign.
+ * HOST buffers of any alignment (the reference's vector bodies fault on planes that are not 32-byte aligned).  Return SRSRAN_SUCCESS, SRSRAN_ERROR_INVALID_INPUTS
+ * (with one line on stderr, nothing written) for anything else than the above -- 4 ports, nof_rxant != 2, other layer counts, a codebook_idx out of range, an odd
+ * nof_symbols with CDD, a decoder that is neither, scaling 0 or not finite, a negative or non-finite noise_estimate, a NULL plane -- or SRSRAN_ERROR. */
+#define SRSRAN_HIP_TXSCHEME_SPATIALMUX 2
+#define SRSRAN_HIP_TXSCHEME_CDD 3
+#define SRSRAN_HIP_MIMO_DECODER_ZF 0
+#define SRSRAN_HIP_MIMO_DECODER_MMSE 1
+SRSRAN_API int srsran_hip_predecoding_mimo(cf_t* y[SRSRAN_MAX_PORTS], cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], cf_t* x[SRSRAN_MAX_LAYERS],
+                                           float* csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_layers, int codebook_idx, int nof_symbols,
+                                           int tx_scheme, float scaling, float noise_estimate, int decoder);
+SRSRAN_API int srsran_hip_precoding_mimo(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRSRAN_MAX_PORTS], int nof_layers, int nof_ports, int codebook_idx, int nof_symbols,
+                                         float scaling, int tx_scheme);
+/* the same two on device buffers (planes 4-byte aligned), asynchronous on `stream` */
+SRSRAN_API int srsran_hip_predecoding_mimo_dev(const cf_t* const d_y[SRSRAN_MAX_PORTS], const cf_t* const d_h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                               cf_t* const d_x[SRSRAN_MAX_LAYERS], float* const d_csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_layers,
+                                               int codebook_idx, int nof_symbols, int tx_scheme, float scaling, float noise_estimate, int decoder, void* stream);
+SRSRAN_API int srsran_hip_precoding_mimo_dev(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* const d_y[SRSRAN_MAX_PORTS], int nof_layers, int nof_ports,
+                                             int codebook_idx, int nof_symbols, float scaling, int tx_scheme, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

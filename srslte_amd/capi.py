@@ -170,6 +170,18 @@ class HipPdschTxdivTx(C.Structure):  # srsran_hip_pdsch_txdiv_tx_t
     _fields_ = [("tb", HipGrantTb), ("nof_ports", C.c_uint32), ("scaling", C.c_float)]
 
 
+class HipPdschMimoRx(C.Structure):  # srsran_hip_pdsch_mimo_rx_t
+    _fields_ = [("tb", HipGrantTb * 2), ("nof_tb", C.c_uint32), ("nof_layers", C.c_uint32), ("tx_scheme", C.c_uint32), ("codebook_idx", C.c_uint32),
+                ("decoder", C.c_uint32), ("nof_rx", C.c_uint32), ("scaling", C.c_float), ("noise_estimate", C.c_float)]
+
+
+class HipPdschMimoTx(C.Structure):  # srsran_hip_pdsch_mimo_tx_t
+    _fields_ = [("tb", HipGrantTb * 2), ("nof_tb", C.c_uint32), ("nof_layers", C.c_uint32), ("tx_scheme", C.c_uint32), ("codebook_idx", C.c_uint32),
+                ("scaling", C.c_float)]
+
+
+TXSCHEME_SPATIALMUX, TXSCHEME_CDD = 2, 3  # srsran_tx_scheme_t
+MIMO_DECODER_ZF, MIMO_DECODER_MMSE = 0, 1  # srsran_mimo_decoder_t
 SRSRAN_MAX_PORTS = 4
 PlaneArray = C.c_void_p * SRSRAN_MAX_PORTS  # cf_t* [SRSRAN_MAX_PORTS]: symbols[rx], x[layer], y[port]
 PlaneMatrix = PlaneArray * SRSRAN_MAX_PORTS  # cf_t* [SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]: ce[port][rx]
@@ -552,6 +564,19 @@ def lib():
             "srsran_hip_pdsch_encode_txdiv": (i32, [C.POINTER(HipPdschTxdivTx), C.POINTER(SoftbufferTx), vp, C.POINTER(vp)]),
             "srsran_hip_pdsch_encode_txdiv_multi": (i32, [u32, C.POINTER(HipPdschTxdivTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp),
                                                           C.POINTER(C.POINTER(vp))]),
+            "srsran_hip_predecoding_mimo": (i32, [C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, C.c_float, C.c_float,
+                                                  i32]),
+            "srsran_hip_precoding_mimo": (i32, [C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, C.c_float, i32]),
+            "srsran_hip_predecoding_mimo_dev": (i32, [C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, C.c_float,
+                                                      C.c_float, i32, vp]),
+            "srsran_hip_precoding_mimo_dev": (i32, [C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, C.c_float, i32, vp]),
+            "srsran_hip_pdsch_decode_mimo": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp),
+                                                   C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_mimo_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp),
+                                                       C.POINTER(HipGrantRes), C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_hip_pdsch_encode_mimo": (i32, [C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_hip_pdsch_encode_mimo_multi": (i32, [u32, C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx) * 2), C.POINTER(vp * 2),
+                                                         C.POINTER(C.POINTER(vp))]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_modulate_bytes": (i32, [u32, vp, vp, u32, u32, u32, C.c_float]),
             "srsran_hip_sequence_nr_seed": (u32, [C.c_uint16, u32, u32]),

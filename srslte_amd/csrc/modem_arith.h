@@ -1,6 +1,6 @@
-// modem_arith.h -- the device functions the demodulating kernels share (modem_kernels.hip, nr_chan_kernels.hip, txdiv_kernels.hip): the integer soft-bit
-// arithmetic of demod_soft.c as the x86 reference evaluates it, the transmit-diversity combiner, the Gold-sequence chips of one wave, sign flips and the
-// soft-bit stores.  Device code only.
+// modem_arith.h -- the device functions the demodulating kernels share (modem_kernels.hip, nr_chan_kernels.hip, txdiv_kernels.hip, spmux_kernels.hip): the
+// integer soft-bit arithmetic of demod_soft.c as the x86 reference evaluates it, the transmit-diversity combiner, the 2x2 spatial-multiplexing / CDD
+// equalisers and precoders, the Gold-sequence chips of one wave, sign flips, the soft-bit stores and the scrambled constellation point.  Device code only.
 #pragma once
 #include "hip_common.h"
 #include "modem_device.h"
@@ -159,6 +159,191 @@ __device__ __forceinline__ void sfbc_finish(const Sfbc& a, float scaling, float 
   x0  = make_float2(sfbc_quot(a.x0r, d0), sfbc_quot(a.x0i, d0));
   x1  = make_float2(sfbc_quot(a.x1r, d1), sfbc_quot(a.x1i, d1));
   csi = PORTS == 2 ? make_float2(a.g0, a.g0) : make_float2(__fdiv_rn(d0, nof_rx), __fdiv_rn(d1, nof_rx));
+}
+
+// ---- 2x2 spatial multiplexing and large-delay CDD on 2 ports, 2 receive antennas (mimo/precoding.c:841-1812 receive, :2044-2203 transmit; utils/mat.c:63-109):
+// the one arithmetic of the per-stage kernels and the fused kernels of spmux_kernels.hip.  Operation order: that of the reference's scalar loop bodies
+// (the `for (; i < nof_symbols; ...)` tails, the _csi variants), a complex product evaluated as C does ((ar br - ai bi) + j (ar bi + ai br)), every
+// product, sum and quotient rounded by itself (rn_mul / rn_add / rn_sub / rn_div below: nothing contracts); a multiplication by +-j is a swap and a sign.  No replacement value anywhere: a
+// singular channel gives what the formula gives (inf / NaN).
+// One rounding per operation, kept HERE and not in a build flag: to this compiler __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn are the plain operators
+// (__clang_hip_math.h), which hipcc's default contraction fuses into FMAs -- differently in different kernels: the per-stage and the fused kernel of
+// spmux_kernels.hip once differed by one unit in 2 of 9600 soft bits.  The pragma takes the contract flag off these operations wherever they are inlined.
+__device__ __forceinline__ float rn_mul(float a, float b)
+{
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b)
+{
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b)
+{
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float rn_div(float a, float b)
+{
+#pragma clang fp contract(off)
+  return a / b;
+}
+__device__ __forceinline__ float2 lo(const float4 v)
+{
+  return make_float2(v.x, v.y);
+}
+__device__ __forceinline__ float2 hi(const float4 v)
+{
+  return make_float2(v.z, v.w);
+}
+__device__ __forceinline__ float2 cx_add(float2 a, float2 b)
+{
+  return make_float2(rn_add(a.x, b.x), rn_add(a.y, b.y));
+}
+__device__ __forceinline__ float2 cx_sub(float2 a, float2 b)
+{
+  return make_float2(rn_sub(a.x, b.x), rn_sub(a.y, b.y));
+}
+__device__ __forceinline__ float2 cx_mul(float2 a, float2 b)
+{
+  return make_float2(rn_sub(rn_mul(a.x, b.x), rn_mul(a.y, b.y)), rn_add(rn_mul(a.x, b.y), rn_mul(a.y, b.x)));
+}
+__device__ __forceinline__ float2 cx_conj(float2 a)
+{
+  return make_float2(a.x, -a.y);
+}
+__device__ __forceinline__ float2 cx_neg(float2 a)
+{
+  return make_float2(-a.x, -a.y);
+}
+__device__ __forceinline__ float2 cx_scale(float2 a, float s)
+{
+  return make_float2(rn_mul(a.x, s), rn_mul(a.y, s));
+}
+
+// one column of a 2-port codebook applied to the channel of one receive antenna (a: port 0, b: port 1).  kind (modem_device.h) 0: a + b, 1: a - b,
+// 2: a + j b, 3: a - j b
+__device__ __forceinline__ float2 pre_column(float2 a, float2 b, uint32_t kind)
+{
+  switch (kind) {
+    case PRE_PLUS:
+      return cx_add(a, b);
+    case PRE_MINUS:
+      return cx_sub(a, b);
+    case PRE_PLUS_J:
+      return make_float2(rn_sub(a.x, b.y), rn_add(a.y, b.x));
+    default:
+      return make_float2(rn_add(a.x, b.y), rn_sub(a.y, b.x));
+  }
+}
+// the effective channel of two layers, Heff[rx][layer], from h[port][rx] (a0 = h[0][0], b0 = h[1][0], a1 = h[0][1], b1 = h[1][1]).
+// pre (modem_device.h) 0: identity (codebook 0); 1: columns (+, -) (codebook 1, CDD on an even RE); 2: (+j, -j) (codebook 2); 3: (-, +) (CDD on an odd RE)
+struct Heff {
+  float2 h00, h01, h10, h11;
+};
+__device__ __forceinline__ Heff mimo2x2_heff(float2 a0, float2 b0, float2 a1, float2 b1, uint32_t pre)
+{
+  if (pre == HEFF_IDENT) {
+    return Heff{a0, b0, a1, b1};
+  }
+  const uint32_t k0 = pre == HEFF_PM ? PRE_PLUS : pre == HEFF_J ? PRE_PLUS_J : PRE_MINUS;
+  const uint32_t k1 = pre == HEFF_PM ? PRE_MINUS : pre == HEFF_J ? PRE_MINUS_J : PRE_PLUS;
+  return Heff{pre_column(a0, b0, k0), pre_column(a0, b0, k1), pre_column(a1, b1, k0), pre_column(a1, b1, k1)};
+}
+// zero forcing (precoding.c:905-909, :1324-1328): det = h00 h11 - h01 h10, d = conj(det) (norm / |det|^2), x0 = (h11 y0 - h01 y1) d, x1 = (-h10 y0 + h00 y1) d
+__device__ __forceinline__ void mimo2x2_zf(float2 y0, float2 y1, const Heff& h, float norm, float2& x0, float2& x1)
+{
+  const float2 det = cx_sub(cx_mul(h.h00, h.h11), cx_mul(h.h01, h.h10));
+  const float  q   = rn_div(norm, rn_add(rn_mul(det.x, det.x), rn_mul(det.y, det.y)));
+  const float2 d   = cx_scale(cx_conj(det), q);
+  x0               = cx_mul(cx_sub(cx_mul(h.h11, y0), cx_mul(h.h01, y1)), d);
+  x1               = cx_mul(cx_add(cx_mul(cx_neg(h.h10), y0), cx_mul(h.h00, y1)), d);
+}
+// MMSE, srsran_mat_2x2_mmse_csi_gen (utils/mat.c:63-109): A = H^H H + noise I, B = norm A^-1, W = B H^H, x = W y, csi_k = 1 / Re(B_kk)
+__device__ __forceinline__ void mimo2x2_mmse(float2 y0, float2 y1, const Heff& h, float noise, float norm, float2& x0, float2& x1, float& csi0, float& csi1)
+{
+  const float2 c00 = cx_conj(h.h00), c01 = cx_conj(h.h01), c10 = cx_conj(h.h10), c11 = cx_conj(h.h11);
+  float2       a00 = cx_add(cx_mul(c00, h.h00), cx_mul(c10, h.h10));
+  const float2 a01 = cx_add(cx_mul(c00, h.h01), cx_mul(c10, h.h11));
+  const float2 a10 = cx_add(cx_mul(c01, h.h00), cx_mul(c11, h.h10));
+  float2       a11 = cx_add(cx_mul(c01, h.h01), cx_mul(c11, h.h11));
+  a00.x            = rn_add(a00.x, noise);
+  a11.x            = rn_add(a11.x, noise);
+  const float2 det = cx_sub(cx_mul(a00, a11), cx_mul(a01, a10));
+  const float  dn  = rn_add(rn_mul(det.x, det.x), rn_mul(det.y, det.y));
+  const float2 nr  = cx_scale(make_float2(rn_div(det.x, dn), rn_div(-det.y, dn)), norm);
+  const float2 b00 = cx_mul(a11, nr), b01 = cx_mul(cx_neg(a01), nr), b10 = cx_mul(cx_neg(a10), nr), b11 = cx_mul(a00, nr);
+  const float2 w00 = cx_add(cx_mul(b00, c00), cx_mul(b01, c01)), w01 = cx_add(cx_mul(b00, c10), cx_mul(b01, c11));
+  const float2 w10 = cx_add(cx_mul(b10, c00), cx_mul(b11, c01)), w11 = cx_add(cx_mul(b10, c10), cx_mul(b11, c11));
+  x0               = cx_add(cx_mul(y0, w00), cx_mul(y1, w01));
+  x1               = cx_add(cx_mul(y0, w10), cx_mul(y1, w11));
+  csi0             = rn_div(1.0f, b00.x);
+  csi1             = rn_div(1.0f, b11.x);
+}
+// one layer, maximum-ratio combining over the two receive antennas (precoding.c:1805-1809): g = |h0|^2 + |h1|^2, x = (conj(h0) y0 + conj(h1) y1) (norm / g),
+// csi = g / norm * (float)M_SQRT1_2
+__device__ __forceinline__ void mrc2(float2 y0, float2 y1, float2 h0, float2 h1, float norm, float2& x, float& csi)
+{
+  const float g = rn_add(rn_add(rn_add(rn_mul(h0.x, h0.x), rn_mul(h0.y, h0.y)), rn_mul(h1.x, h1.x)), rn_mul(h1.y, h1.y));
+  x             = cx_scale(cx_add(cx_mul(cx_conj(h0), y0), cx_mul(cx_conj(h1), y1)), rn_div(norm, g));
+  csi           = rn_mul(rn_div(g, norm), 0.70710678118654752440f);
+}
+// one RE of the receive side: `layers` 2 with `pre` a HEFF_* value, or 1 with `pre` a PRE_* value (codebook_idx); x1 / c1 are written with two layers only
+__device__ __forceinline__ void mimo_equalise(uint32_t layers, uint32_t pre, bool mmse, float2 y0, float2 y1, float2 a0, float2 b0, float2 a1, float2 b1, float norm,
+                                              float noise, float2& x0, float2& x1, float& c0, float& c1)
+{
+  if (layers == 1) {
+    mrc2(y0, y1, pre_column(a0, b0, pre), pre_column(a1, b1, pre), norm, x0, c0);
+  } else {
+    const Heff h = mimo2x2_heff(a0, b0, a1, b1, pre);
+    if (mmse) {
+      mimo2x2_mmse(y0, y1, h, noise, norm, x0, x1, c0, c1);
+    } else {
+      mimo2x2_zf(y0, y1, h, norm, x0, x1);
+      c0 = c1 = 1.0f;
+    }
+  }
+}
+// one RE of the transmit side (precoding.c:2044-2053, :2097-2195): layer symbols x0, x1 -> port symbols y0, y1; `s` is the reference's float factor (host
+// evaluated: scaling / 2, or (float)(scaling * M_SQRT1_2) for one layer and for codebook 0).  kind (modem_device.h): TXPRE_CDD + (RE index & 1),
+// TXPRE_MUX2 + codebook_idx (two layers), TXPRE_MUX1 + codebook_idx (one layer, x1 unused)
+__device__ __forceinline__ void mimo_precode(uint32_t kind, float2 x0, float2 x1, float s, float2& y0, float2& y1)
+{
+  switch (kind) {
+    case TXPRE_CDD + 1: // odd RE: y1 = (-x0 + x1) s
+      y0 = cx_scale(cx_add(x0, x1), s);
+      y1 = cx_scale(cx_add(cx_neg(x0), x1), s);
+      break;
+    case TXPRE_MUX2: // codebook 0: the identity
+      y0 = cx_scale(x0, s);
+      y1 = cx_scale(x1, s);
+      break;
+    case TXPRE_MUX2 + 2: { // y1 = j (x0 - x1) s
+      const float2 d = cx_sub(x0, x1);
+      y0             = cx_scale(cx_add(x0, x1), s);
+      y1             = cx_scale(make_float2(-d.y, d.x), s);
+    } break;
+    case TXPRE_MUX1:
+      y0 = y1 = cx_scale(x0, s);
+      break;
+    case TXPRE_MUX1 + 1:
+      y0 = cx_scale(x0, s);
+      y1 = cx_scale(x0, -s);
+      break;
+    case TXPRE_MUX1 + 2:
+      y0 = cx_scale(x0, s);
+      y1 = make_float2(-y0.y, y0.x);
+      break;
+    case TXPRE_MUX1 + 3:
+      y0 = cx_scale(x0, s);
+      y1 = make_float2(y0.y, -y0.x);
+      break;
+    default: // TXPRE_CDD on an even RE, TXPRE_MUX2 + 1: y1 = (x0 - x1) s
+      y0 = cx_scale(cx_add(x0, x1), s);
+      y1 = cx_scale(cx_sub(x0, x1), s);
+      break;
+  }
 }
 
 // ---- scrambling chips of one tile -> LDS --------------------------------------------------------------------------------
@@ -320,6 +505,22 @@ __device__ __forceinline__ void store_bits_staged(T* wave_dst, const T* v, uint3
     }
   }
   __builtin_amdgcn_wave_barrier();
+}
+// ---- transmit (txdiv_kernels.hip, spmux_kernels.hip).  Symbol s of the codeword (ls: counted from the wave's first): its Qm packed bits (mod_tile of
+// modem_kernels.hip), scrambled with the wave's chips, as a constellation point
+template <int MOD>
+__device__ __forceinline__ float2 mod_point(const uint8_t* bits, uint32_t nbytes, const float2* tab, uint32_t s, uint32_t ls, const uint32_t* cbw)
+{
+  constexpr int  QM = MOD == 0 ? 1 : 2 * MOD;
+  const uint32_t b = s * QM, by = b >> 3;
+  const uint32_t hi8 = bits[by], lo8 = by + 1 < nbytes ? bits[by + 1] : 0u;
+  uint32_t       v   = (((hi8 << 8) | lo8) >> (16 - QM - (b & 7u))) & ((1u << QM) - 1u); // bit 0 of the symbol = MSB of v
+  const uint32_t c   = chips_at(cbw, ls * QM);                                           // chip i of the symbol in bit i
+#pragma unroll
+  for (int i = 0; i < QM; i++) {
+    v ^= ((c >> i) & 1u) << (QM - 1 - i);
+  }
+  return tab[v];
 }
 } // namespace
 

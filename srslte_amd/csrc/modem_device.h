@@ -17,6 +17,11 @@ enum { MOD_PASS = 5 }; // no demodulation: the input already holds LLRs of the o
 #define MODEM_TILE_SYMS 2048u    // symbols per workgroup
 #define MODEM_TILE_BITS (8u * MODEM_TILE_SYMS) // soft bits per workgroup (256-QAM: 8 per symbol)
 
+// the precoders of 2x2 spatial multiplexing and CDD as the arithmetic of modem_arith.h names them (spmux_kernels.hip; set by spmux_host.cpp)
+enum { PRE_PLUS = 0, PRE_MINUS = 1, PRE_PLUS_J = 2, PRE_MINUS_J = 3 }; // one codebook column on the two ports: a + b, a - b, a + j b, a - j b
+enum { HEFF_IDENT = 0, HEFF_PM = 1, HEFF_J = 2, HEFF_MP = 3 };         // the two columns of a two-layer precoder: identity, (+, -), (+j, -j), (-, +)
+enum { TXPRE_CDD = 0, TXPRE_MUX2 = 2, TXPRE_MUX1 = 5 };                // transmit: + RE parity, + codebook_idx (two layers), + codebook_idx (one layer)
+
 struct Job {
   uint32_t mod;     // srsran_mod_t or MOD_PASS
   uint32_t n;       // symbols (soft bits for MOD_PASS)

@@ -1,0 +1,511 @@
+// spmux_host.cpp -- spatial multiplexing and large-delay CDD on 2 ports with 2 receive antennas (include/srsran_amd/phy_modem_abi.h, phy_chan_abi.h;
+// spmux_kernels.hip): the two stages on HOST buffers (one kernel each on the calling thread's stage) and on device buffers, and the PDSCH grant of one or
+// two codewords in one call each way.
+#include "chan_internal.h"
+#include "spmux_device.h"
+
+#include <cmath>
+#include <vector>
+
+using namespace phyhip;
+using namespace phyhip::chan;
+
+namespace {
+
+// one of the three transmissions that are taken, as the kernels want it
+struct Taken {
+  spmux::Scheme rx;         // (mmse, noise: set by the receive side)
+  uint32_t      tx_kind[2]; // TXPRE_* of an even / odd RE
+  float         tx_scale;   // the reference's float factor of the precoder (precoding.c:2046, :2098, :2126, :2131, :2164)
+};
+
+// nullptr when (tx_scheme, layers, codebook_idx, n, scaling) is taken, else why not
+const char* mimo_case(int tx_scheme, int layers, int codebook_idx, int64_t n, float scaling, Taken& t)
+{
+  if (!(scaling != 0.f) || !std::isfinite(scaling)) {
+    return "scaling is 0 or not finite";
+  }
+  t = {};
+  if (tx_scheme == SRSRAN_HIP_TXSCHEME_CDD) {
+    if (layers != 2) {
+      return "CDD is taken with 2 layers";
+    }
+    if (n & 1) {
+      return "CDD needs an even number of REs";
+    }
+    t.rx       = {2, {modem::HEFF_PM, modem::HEFF_MP}, 0, 2.0f / scaling, 0.f};
+    t.tx_kind[0] = modem::TXPRE_CDD;
+    t.tx_kind[1] = modem::TXPRE_CDD + 1;
+    t.tx_scale = scaling / 2.0f;
+    return nullptr;
+  }
+  if (tx_scheme != SRSRAN_HIP_TXSCHEME_SPATIALMUX) {
+    return "the scheme is neither spatial multiplexing nor CDD";
+  }
+  if (layers == 2) {
+    if (codebook_idx < 0 || codebook_idx > 2) {
+      return "codebook_idx is 0 .. 2 with 2 layers";
+    }
+    const uint32_t pre = codebook_idx == 0 ? modem::HEFF_IDENT : codebook_idx == 1 ? modem::HEFF_PM : modem::HEFF_J;
+    t.rx = {2, {pre, pre}, 0, codebook_idx == 0 ? (float)M_SQRT2 / scaling : 2.0f / scaling, 0.f};
+    t.tx_kind[0] = t.tx_kind[1] = modem::TXPRE_MUX2 + (uint32_t)codebook_idx;
+    t.tx_scale = codebook_idx == 0 ? (float)(scaling * M_SQRT1_2) : scaling / 2.0f;
+    return nullptr;
+  }
+  if (layers == 1) {
+    if (codebook_idx < 0 || codebook_idx > 3) {
+      return "codebook_idx is 0 .. 3 with 1 layer";
+    }
+    t.rx = {1, {(uint32_t)codebook_idx, (uint32_t)codebook_idx}, 0, (float)M_SQRT2 / scaling, 0.f};
+    t.tx_kind[0] = t.tx_kind[1] = modem::TXPRE_MUX1 + (uint32_t)codebook_idx;
+    t.tx_scale = (float)(scaling * M_SQRT1_2);
+    return nullptr;
+  }
+  return "spatial multiplexing is taken with 1 or 2 layers";
+}
+
+// the receive side's own conditions on top
+const char* mimo_rx_case(int tx_scheme, int layers, int codebook_idx, int64_t n, float scaling, int nof_rx, int decoder, float noise, Taken& t)
+{
+  if (nof_rx != 2) {
+    return "2 receive antennas are taken";
+  }
+  if (decoder != SRSRAN_HIP_MIMO_DECODER_ZF && decoder != SRSRAN_HIP_MIMO_DECODER_MMSE) {
+    return "the decoder is neither ZF nor MMSE";
+  }
+  if (!(noise >= 0.f) || !std::isfinite(noise)) {
+    return "noise_estimate is negative or not finite";
+  }
+  const char* why = mimo_case(tx_scheme, layers, codebook_idx, n, scaling, t);
+  t.rx.mmse       = decoder == SRSRAN_HIP_MIMO_DECODER_MMSE ? 1u : 0u;
+  t.rx.noise      = noise;
+  return why;
+}
+
+int refuse_stage(const char* who, const char* why, int tx_scheme, int ports, int layers, int codebook_idx, int n)
+{
+  return refuse("%s: %s (scheme %d, %d ports, %d layers, codebook_idx %d, %d REs)", who, why, tx_scheme, ports, layers, codebook_idx, n);
+}
+
+inline const float* fl(const cf_t* p)
+{
+  return reinterpret_cast<const float*>(p);
+}
+inline float* fl(cf_t* p)
+{
+  return reinterpret_cast<float*>(p);
+}
+inline bool al4(const void* p)
+{
+  return (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+}
+
+spmux::EqParams eq_params(const cf_t* const* y, const cf_t* const (*h)[SRSRAN_MAX_PORTS], cf_t* const* x, float* const* csi, uint32_t n, const spmux::Scheme& s)
+{
+  spmux::EqParams p = {};
+  for (uint32_t r = 0; r < 2; r++) {
+    p.y[r] = fl(y[r]);
+    for (uint32_t k = 0; k < 2; k++) {
+      p.h[k][r] = fl(h[k][r]);
+    }
+  }
+  for (uint32_t k = 0; k < s.layers; k++) {
+    p.x[k] = fl(x[k]);
+  }
+  // what the reference's scalar bodies write: two-layer ZF spatial multiplexing gets csi[0] only (precoding.c:1330-1331)
+  const bool second = s.layers == 2 && (s.mmse || s.pre[0] != s.pre[1]);
+  p.csi[0]          = csi ? csi[0] : nullptr;
+  p.csi[1]          = (csi && csi[0] && second) ? csi[1] : nullptr;
+  p.n               = n;
+  p.s               = s;
+  return p;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------ the stages on device buffers
+
+extern "C" int srsran_hip_predecoding_mimo_dev(const cf_t* const d_y[SRSRAN_MAX_PORTS], const cf_t* const d_h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                               cf_t* const d_x[SRSRAN_MAX_LAYERS], float* const d_csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_layers,
+                                               int codebook_idx, int nof_symbols, int tx_scheme, float scaling, float noise_estimate, int decoder, void* stream)
+{
+  Taken       t;
+  const char* why = nof_ports != 2 ? "2 ports are taken" : nof_symbols < 0 ? "a negative number of REs" : (!d_y || !d_h || !d_x) ? "NULL argument" : nullptr;
+  why             = why ? why : mimo_rx_case(tx_scheme, nof_layers, codebook_idx, nof_symbols, scaling, nof_rxant, decoder, noise_estimate, t);
+  for (uint32_t r = 0; !why && nof_symbols && r < 2; r++) {
+    const bool ok = d_y[r] && al4(d_y[r]) && d_h[0][r] && al4(d_h[0][r]) && d_h[1][r] && al4(d_h[1][r]) && (r >= t.rx.layers || (d_x[r] && al4(d_x[r]))) &&
+                    (!d_csi || al4(d_csi[r]));
+    why           = ok ? nullptr : "a NULL or misaligned plane";
+  }
+  if (why) {
+    return refuse_stage("srsran_hip_predecoding_mimo", why, tx_scheme, nof_ports, nof_layers, codebook_idx, nof_symbols);
+  }
+  if (!device_available()) {
+    return SRSRAN_ERROR;
+  }
+  PHY_HIP_CHECK(spmux::launch_eq(eq_params(d_y, d_h, d_x, d_csi, (uint32_t)nof_symbols, t.rx), (hipStream_t)stream), SRSRAN_ERROR);
+  return SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_precoding_mimo_dev(const cf_t* const d_x[SRSRAN_MAX_LAYERS], cf_t* const d_y[SRSRAN_MAX_PORTS], int nof_layers, int nof_ports,
+                                             int codebook_idx, int nof_symbols, float scaling, int tx_scheme, void* stream)
+{
+  Taken       t;
+  const char* why = nof_ports != 2 ? "2 ports are taken" : nof_symbols < 0 ? "a negative number of REs" : (!d_x || !d_y) ? "NULL argument" : nullptr;
+  why             = why ? why : mimo_case(tx_scheme, nof_layers, codebook_idx, nof_symbols, scaling, t);
+  for (uint32_t k = 0; !why && nof_symbols && k < 2; k++) {
+    why = (d_y[k] && al4(d_y[k]) && (k >= t.rx.layers || (d_x[k] && al4(d_x[k])))) ? nullptr : "a NULL or misaligned plane";
+  }
+  if (why) {
+    return refuse_stage("srsran_hip_precoding_mimo", why, tx_scheme, nof_ports, nof_layers, codebook_idx, nof_symbols);
+  }
+  if (!device_available()) {
+    return SRSRAN_ERROR;
+  }
+  spmux::PrecodeParams p = {{fl(d_x[0]), t.rx.layers == 2 ? fl(d_x[1]) : nullptr}, {fl(d_y[0]), fl(d_y[1])}, (uint32_t)nof_symbols, {t.tx_kind[0], t.tx_kind[1]}, t.tx_scale};
+  PHY_HIP_CHECK(spmux::launch_precode(p, (hipStream_t)stream), SRSRAN_ERROR);
+  return SRSRAN_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------ the stages on HOST buffers
+
+extern "C" int srsran_hip_predecoding_mimo(cf_t* y[SRSRAN_MAX_PORTS], cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], cf_t* x[SRSRAN_MAX_LAYERS],
+                                           float* csi[SRSRAN_MAX_CODEWORDS], int nof_rxant, int nof_ports, int nof_layers, int codebook_idx, int nof_symbols,
+                                           int tx_scheme, float scaling, float noise_estimate, int decoder)
+{
+  Taken       t;
+  const char* why = nof_ports != 2 ? "2 ports are taken" : nof_symbols < 0 ? "a negative number of REs" : (!y || !h || !x) ? "NULL argument" : nullptr;
+  why             = why ? why : mimo_rx_case(tx_scheme, nof_layers, codebook_idx, nof_symbols, scaling, nof_rxant, decoder, noise_estimate, t);
+  for (uint32_t r = 0; !why && r < 2; r++) {
+    why = (y[r] && h[0][r] && h[1][r] && (r >= t.rx.layers || x[r])) ? nullptr : "a NULL plane";
+  }
+  if (why) {
+    return refuse_stage("srsran_hip_predecoding_mimo", why, tx_scheme, nof_ports, nof_layers, codebook_idx, nof_symbols);
+  }
+  if (nof_symbols == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  // y[rx], then h[port][rx], then the layers and the channel-state rows
+  const size_t nb = (size_t)nof_symbols * sizeof(cf_t), nc = (size_t)nof_symbols * sizeof(float);
+  PlaneGroup   grp[5] = {{y, 2, nb, true, false}, {h[0], 2, nb, true, false}, {h[1], 2, nb, true, false}, {x, t.rx.layers, nb, false, true}, {nullptr, 2, nc, false, false}};
+  float*       cp[2]  = {nullptr, nullptr};
+  const bool   ok = run_on_planes("srsran_hip_predecoding_mimo", grp, 5, [&](hipStream_t st) {
+    const cf_t* hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {{grp[1].pin[0], grp[1].pin[1]}, {grp[2].pin[0], grp[2].pin[1]}};
+    float*      cpin[2] = {reinterpret_cast<float*>(grp[4].pin[0]), reinterpret_cast<float*>(grp[4].pin[1])};
+    const spmux::EqParams ep = eq_params(grp[0].pin, hp, grp[3].pin, (csi && csi[0]) ? cpin : nullptr, (uint32_t)nof_symbols, t.rx);
+    cp[0] = ep.csi[0]; // the rows the kernel writes: only those go back to the caller (the reference leaves the others untouched)
+    cp[1] = ep.csi[1];
+    return spmux::launch_eq(ep, st);
+  });
+  for (uint32_t k = 0; ok && csi && k < 2; k++) {
+    if (cp[k] && csi[k]) {
+      memcpy(csi[k], cp[k], nc);
+    }
+  }
+  return ok ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+}
+
+extern "C" int srsran_hip_precoding_mimo(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRSRAN_MAX_PORTS], int nof_layers, int nof_ports, int codebook_idx, int nof_symbols,
+                                         float scaling, int tx_scheme)
+{
+  Taken       t;
+  const char* why = nof_ports != 2 ? "2 ports are taken" : nof_symbols < 0 ? "a negative number of REs" : (!x || !y) ? "NULL argument" : nullptr;
+  why             = why ? why : mimo_case(tx_scheme, nof_layers, codebook_idx, nof_symbols, scaling, t);
+  for (uint32_t k = 0; !why && k < 2; k++) {
+    why = (y[k] && (k >= t.rx.layers || x[k])) ? nullptr : "a NULL plane";
+  }
+  if (why) {
+    return refuse_stage("srsran_hip_precoding_mimo", why, tx_scheme, nof_ports, nof_layers, codebook_idx, nof_symbols);
+  }
+  if (nof_symbols == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  const size_t nb = (size_t)nof_symbols * sizeof(cf_t);
+  PlaneGroup   grp[2] = {{x, t.rx.layers, nb, true, false}, {y, 2, nb, false, true}};
+  const bool   ok = run_on_planes("srsran_hip_precoding_mimo", grp, 2, [&](hipStream_t st) {
+    spmux::PrecodeParams p = {{fl(grp[0].pin[0]), t.rx.layers == 2 ? fl(grp[0].pin[1]) : nullptr}, {fl(grp[1].pin[0]), fl(grp[1].pin[1])}, (uint32_t)nof_symbols,
+                              {t.tx_kind[0], t.tx_kind[1]}, t.tx_scale};
+    return spmux::launch_precode(p, st);
+  });
+  return ok ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+}
+
+// ------------------------------------------------------------------------------------------------ PDSCH grant, receive
+
+extern "C" int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                            srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                            srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS])
+{
+  return srsran_hip_pdsch_decode_mimo_dbg(g, symbols, ce, softbuffers, data, res, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
+                                                void* const e_out[SRSRAN_MAX_CODEWORDS])
+{
+  static const char* who = "srsran_hip_pdsch_decode_mimo";
+  TraceRange         trace_(who);
+  if (res) {
+    res[0] = res[1] = {0, 0.f, NAN};
+  }
+  if (!g || !symbols || !ce || !softbuffers || !data || !res) {
+    fprintf(stderr, "[srsran_phy_hip] %s: NULL argument\n", who);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t ntb = g->nof_tb;
+  if ((ntb != 1 && ntb != 2) || g->nof_layers != ntb) {
+    return refuse("%s: %u codewords on %u layers is not taken (1 on 1, or 2 on 2)", who, ntb, g->nof_layers);
+  }
+  const uint32_t nof_re = g->tb[0].nof_re;
+  Taken          t;
+  const char*    why = mimo_rx_case((int)g->tx_scheme, (int)g->nof_layers, (int)g->codebook_idx, nof_re, g->scaling, (int)g->nof_rx, (int)g->decoder, g->noise_estimate, t);
+  if (!why && (!symbols[0] || !symbols[1] || !ce[0][0] || !ce[0][1] || !ce[1][0] || !ce[1][1])) {
+    why = "a NULL plane";
+  }
+  if (!why && ntb == 2 && (g->tb[1].nof_re != nof_re || g->tb[1].llr_is_8bit != g->tb[0].llr_is_8bit || g->tb[1].max_nof_iterations != g->tb[0].max_nof_iterations)) {
+    why = "the two codewords differ in nof_re, llr_is_8bit or max_nof_iterations";
+  }
+  bool any = false;
+  for (uint32_t k = 0; !why && k < ntb; k++) {
+    any = any || softbuffers[k];
+    why = (softbuffers[k] && !data[k]) ? "a codeword without room for its payload" : nullptr;
+  }
+  if (!why && !any) {
+    why = "every codeword is skipped";
+  }
+  if (why) {
+    return refuse("%s: %s (scheme %u, %u layers, codebook_idx %u, decoder %u, %u receive antennas, %u REs, scaling %g, noise %g)", who, why, g->tx_scheme, g->nof_layers,
+                  g->codebook_idx, g->decoder, g->nof_rx, nof_re, (double)g->scaling, (double)g->noise_estimate);
+  }
+  for (uint32_t k = 0; k < ntb; k++) {
+    if (!tb_valid(g->tb[k], who)) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  ChanStage* sp = stage_for(who);
+  if (!sp) {
+    return SRSRAN_ERROR;
+  }
+  ChanStage& s = *sp;
+  // staging image: 2 symbol planes, then 2 x 2 estimate planes, each 256-byte aligned (an odd grant's last pair is read whole: the padding is there);
+  // behind them room for what _dbg hands back: the layers' symbols, then each codeword's soft bits
+  const bool   llr8 = g->tb[0].llr_is_8bit != 0;
+  const size_t nd = (size_t)nof_re * sizeof(cf_t), nb = al256(nd);
+  size_t       ne[2] = {0, 0}, o_e[2] = {0, 0};
+  const size_t o_d = 6 * nb;
+  size_t       end = o_d + 2 * nb;
+  for (uint32_t k = 0; k < ntb; k++) {
+    ne[k]  = (size_t)nof_re * qm_of(g->tb[k].mod) * (llr8 ? 1 : 2);
+    o_e[k] = end;
+    end += al256(ne[k]);
+  }
+  const bool want_d = d_out && (d_out[0] || (ntb == 2 && d_out[1]));
+  if (!s.grow(end, want_d ? 2 * nb : 0)) {
+    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
+    return SRSRAN_ERROR;
+  }
+  const cf_t *yp[SRSRAN_MAX_PORTS] = {}, *hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
+  for (uint32_t r = 0; r < 2; r++) {
+    yp[r] = reinterpret_cast<cf_t*>(s.pin + (size_t)r * nb);
+    memcpy(s.pin + (size_t)r * nb, symbols[r], nd);
+    for (uint32_t k = 0; k < 2; k++) {
+      uint8_t* at = s.pin + (2 + (size_t)k * 2 + r) * nb;
+      hp[k][r]    = reinterpret_cast<cf_t*>(at);
+      memcpy(at, ce[k][r], nd);
+    }
+  }
+  // the enabled codewords as items of one decoding pass
+  srsran_cbsegm_t       seg[2];
+  srsran_hip_sch_head_t head[2];
+  sch::TbItem           items[2];
+  uint32_t              cw_of[2] = {0, 0}, n_items = 0;
+  const sch::FrontEnd   marks_device_bits = [](hipStream_t, void*) { return false; }; // (never called: the group front end below serves both codewords)
+  for (uint32_t k = 0; k < ntb; k++) {
+    if (!softbuffers[k]) {
+      continue;
+    }
+    if (!segment(&seg[k], g->tb[k].tbs)) {
+      return SRSRAN_ERROR;
+    }
+    head[k]          = {g->tb[k].max_nof_iterations, 0.f, llr8};
+    cw_of[n_items]   = k;
+    items[n_items++] = {&head[k], softbuffers[k], &seg[k], qm_of(g->tb[k].mod), g->tb[k].rv, nof_re * qm_of(g->tb[k].mod), nullptr, &marks_device_bits, data[k], false};
+  }
+  bool                     failed = false, d_made = false, e_made[2] = {false, false};
+  const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
+    modem::Params mp;
+    if (!modem::params_for(mp, llr8 ? modem::LLR_I8 : modem::LLR_I16)) {
+      failed = true;
+      return false;
+    }
+    spmux::FrontParams fp = {};
+    for (uint32_t r = 0; r < 2; r++) {
+      fp.y[r] = reinterpret_cast<const float4*>(yp[r]);
+      for (uint32_t k = 0; k < 2; k++) {
+        fp.h[k][r] = reinterpret_cast<const float4*>(hp[k][r]);
+      }
+    }
+    for (uint32_t k = 0; k < ntb; k++) {
+      fp.mod[k]  = g->tb[k].mod;
+      fp.seed[k] = g->tb[k].seed;
+    }
+    for (uint32_t j = 0; j < m; j++) {
+      fp.out[cw_of[which[j]]] = d_e[j];
+    }
+    fp.n       = nof_re;
+    fp.s       = t.rx;
+    fp.x1_bits = mp.x1_bits;
+    fp.x2_cols = mp.x2_cols;
+    fp.k       = mp.k;
+    if (spmux::launch_front(fp, llr8, st) != hipSuccess) {
+      set_error("grant front end: spatial-multiplexing front-end launch failed");
+      failed = true;
+      return false;
+    }
+    // what the reference leaves in q->d: the symbols exist in the front end's registers only, so the per-stage kernel makes them (same arithmetic)
+    if (want_d) {
+      cf_t* xd[SRSRAN_MAX_LAYERS] = {reinterpret_cast<cf_t*>(s.dev.get()), reinterpret_cast<cf_t*>(s.dev.get() + nb)};
+      if (spmux::launch_eq(eq_params(yp, hp, xd, nullptr, nof_re, t.rx), st) != hipSuccess ||
+          hipMemcpyAsync(s.pin + o_d, s.dev, (ntb - 1) * nb + nd, hipMemcpyDeviceToHost, st) != hipSuccess) {
+        set_error("grant front end: the equalised symbols could not be produced");
+        failed = true;
+        return false;
+      }
+      d_made = true;
+    }
+    for (uint32_t j = 0; j < m; j++) {
+      const uint32_t k = cw_of[which[j]];
+      if (e_out && e_out[k]) {
+        if (hipMemcpyAsync(s.pin + o_e[k], d_e[j], ne[k], hipMemcpyDeviceToHost, st) != hipSuccess) {
+          set_error("grant front end: copy of the intermediate results failed");
+          failed = true;
+          return false;
+        }
+        e_made[k] = true;
+      }
+    }
+    return true;
+  };
+  sch::decode_tbs_staged(items, n_items, &group);
+  for (uint32_t i = 0; i < n_items; i++) {
+    const uint32_t k = cw_of[i];
+    res[k].crc_ok               = items[i].ok ? 1 : 0;
+    res[k].avg_iterations_block = head[k].avg_iterations;
+  }
+  // what _dbg was asked for and the front end did not make -- it never ran for a codeword the transport-block stage dropped (a soft buffer with fewer
+  // rows than the codeword has blocks) or whose blocks were all decoded in an earlier round -- is an error, not a silently untouched buffer
+  bool missing = false;
+  for (uint32_t k = 0; k < ntb && !failed; k++) {
+    if (d_out && d_out[k]) {
+      if (d_made) {
+        memcpy(d_out[k], s.pin + o_d + k * nb, nd);
+      } else {
+        missing = true;
+      }
+    }
+    if (e_out && e_out[k] && softbuffers[k]) {
+      if (e_made[k]) {
+        memcpy(e_out[k], s.pin + o_e[k], ne[k]);
+      } else {
+        missing = true;
+      }
+    }
+  }
+  if (missing) {
+    set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", who);
+    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+  }
+  return (failed || missing) ? SRSRAN_ERROR : SRSRAN_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------ PDSCH grant, transmit
+
+extern "C" int srsran_hip_pdsch_encode_mimo(const srsran_hip_pdsch_mimo_tx_t* g, srsran_softbuffer_tx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                            uint8_t* const data[SRSRAN_MAX_CODEWORDS], cf_t* const symbols[])
+{
+  if (!softbuffers || !data) {
+    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_encode_mimo: NULL argument\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return srsran_hip_pdsch_encode_mimo_multi(1, g, reinterpret_cast<srsran_softbuffer_tx_t* const(*)[SRSRAN_MAX_CODEWORDS]>(softbuffers),
+                                            reinterpret_cast<uint8_t* const(*)[SRSRAN_MAX_CODEWORDS]>(data), &symbols);
+}
+
+extern "C" int srsran_hip_pdsch_encode_mimo_multi(uint32_t n, const srsran_hip_pdsch_mimo_tx_t* g, srsran_softbuffer_tx_t* const (*softbuffers)[SRSRAN_MAX_CODEWORDS],
+                                                  uint8_t* const (*data)[SRSRAN_MAX_CODEWORDS], cf_t* const* const* symbols)
+{
+  static const char* who = "srsran_hip_pdsch_encode_mimo";
+  TraceRange         trace_(who);
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!g || !softbuffers || !data || !symbols) {
+    fprintf(stderr, "[srsran_phy_hip] %s: NULL argument\n", who);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  // the codewords of all grants in one list: a grant's first codeword owns its two port planes
+  std::vector<TxCodeword> cw;
+  std::vector<Taken>      taken(n);
+  std::vector<uint32_t>   first(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t ntb = g[i].nof_tb;
+    if ((ntb != 1 && ntb != 2) || g[i].nof_layers != ntb) {
+      return refuse("%s: grant %u: %u codewords on %u layers is not taken (1 on 1, or 2 on 2)", who, i, ntb, g[i].nof_layers);
+    }
+    const uint32_t nof_re = g[i].tb[0].nof_re;
+    const char*    why    = mimo_case((int)g[i].tx_scheme, (int)g[i].nof_layers, (int)g[i].codebook_idx, nof_re, g[i].scaling, taken[i]);
+    if (!why && (!symbols[i] || !symbols[i][0] || !symbols[i][1])) {
+      why = "a NULL plane";
+    }
+    if (!why && ntb == 2 && g[i].tb[1].nof_re != nof_re) {
+      why = "the two codewords differ in nof_re";
+    }
+    for (uint32_t k = 0; !why && k < ntb; k++) {
+      why = softbuffers[i][k] ? nullptr : "a codeword without a soft buffer";
+    }
+    if (why) {
+      return refuse("%s: grant %u: %s (scheme %u, %u layers, codebook_idx %u, %u REs, scaling %g)", who, i, why, g[i].tx_scheme, g[i].nof_layers, g[i].codebook_idx, nof_re,
+                    (double)g[i].scaling);
+    }
+    first[i] = (uint32_t)cw.size();
+    for (uint32_t k = 0; k < ntb; k++) {
+      if (!tb_valid(g[i].tb[k], who)) {
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+      cw.push_back({&g[i].tb[k], qm_of(g[i].tb[k].mod), k == 0 ? 2u : 0u, softbuffers[i][k], data[i][k], k == 0 ? symbols[i] : nullptr, 0});
+    }
+  }
+  ChanStage* sp = stage_for(who);
+  if (!sp) {
+    return SRSRAN_ERROR;
+  }
+  ChanStage& s = *sp;
+  return pdsch_encode_codewords<spmux::ModJob>(s, cw.data(), (uint32_t)cw.size(), [&](hipStream_t st, const uint8_t* d_e, const uint32_t* e_byte_off, JobList<spmux::ModJob>& jobs) {
+    modem::Params mp;
+    const float2* tab = modem::mod_tables();
+    if (!modem::params_for(mp, modem::LLR_I16) || !tab) {
+      return false;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t f = first[i], nof_re = g[i].tb[0].nof_re;
+      const bool     two   = g[i].nof_tb == 2;
+      const size_t   plane = al256((size_t)nof_re * sizeof(cf_t));
+      jobs.jobs[i] = {{g[i].tb[0].mod, two ? g[i].tb[1].mod : 0u},
+                      {g[i].tb[0].seed, two ? g[i].tb[1].seed : 0u},
+                      {e_byte_off[f], two ? e_byte_off[f + 1] : 0u},
+                      nof_re,
+                      g[i].nof_layers,
+                      {taken[i].tx_kind[0], taken[i].tx_kind[1]},
+                      taken[i].tx_scale,
+                      {(uint32_t)(cw[f].o_out / sizeof(cf_t)), (uint32_t)((cw[f].o_out + plane) / sizeof(cf_t))},
+                      jobs.append(i, (nof_re + MODEM_TILE_SYMS - 1) / MODEM_TILE_SYMS)};
+    }
+    spmux::ModParams p = {d_e, reinterpret_cast<float2*>(s.pin.get()), tab, jobs.jobs, jobs.tile_job, jobs.n_tiles, mp.x1_bits, mp.x2_cols};
+    if (spmux::launch_mod(p, st) != hipSuccess) {
+      set_error("spatial-multiplexing modulator launch failed");
+      return false;
+    }
+    return true;
+  });
+}

@@ -89,54 +89,6 @@ txdiv::LayerParams layer_params(const cf_t* d, const cf_t* const* x, uint32_t la
   return p;
 }
 
-// ---- a host-buffer stage: the caller's planes into the thread's pinned image (the kernels work on it directly), one kernel, one wait, planes out
-
-struct PlaneGroup { // k planes of `bytes` each, 256-byte aligned, group behind group in the image
-  cf_t* const* host;                  // the caller's planes (refused when one is NULL); nullptr: room in the image only
-  uint32_t     k;
-  size_t       bytes;
-  bool         in, out;               // copied in before / out after the kernel
-  cf_t*        pin[SRSRAN_MAX_PORTS]; // set by run_on_planes: the planes in the image
-};
-
-template <class Launch>
-bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch launch)
-{
-  size_t need = 0;
-  for (uint32_t g = 0; g < n_grp; g++) {
-    for (uint32_t i = 0; grp[g].host && i < grp[g].k; i++) {
-      if (!grp[g].host[i]) {
-        return false;
-      }
-    }
-    need += grp[g].k * al256(grp[g].bytes);
-  }
-  ChanStage*  s  = stage_for(who);
-  hipStream_t st = s ? sch::stage_stream() : nullptr;
-  if (!st || !s->grow(need, 0)) {
-    return false;
-  }
-  uint8_t* at = s->pin;
-  for (uint32_t g = 0; g < n_grp; g++) {
-    for (uint32_t i = 0; i < grp[g].k; i++, at += al256(grp[g].bytes)) {
-      grp[g].pin[i] = reinterpret_cast<cf_t*>(at);
-      if (grp[g].in) {
-        memcpy(at, grp[g].host[i], grp[g].bytes);
-      }
-    }
-  }
-  const bool launched = launch(st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
-    return false;
-  }
-  for (uint32_t g = 0; g < n_grp; g++) {
-    for (uint32_t i = 0; grp[g].out && i < grp[g].k; i++) {
-      memcpy(grp[g].host[i], grp[g].pin[i], grp[g].bytes);
-    }
-  }
-  return true;
-}
-
 } // namespace
 
 extern "C" int srsran_hip_predecoding_diversity_multi(const cf_t* const d_y[SRSRAN_MAX_PORTS], const cf_t* const d_h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],

@@ -26,15 +26,6 @@ using namespace modem;
 
 namespace {
 
-__device__ __forceinline__ float2 lo(const float4 v)
-{
-  return make_float2(v.x, v.y);
-}
-__device__ __forceinline__ float2 hi(const float4 v)
-{
-  return make_float2(v.z, v.w);
-}
-
 // ---- srsran_predecoding_diversity_multi on device planes: one lane per RE pair (2 ports) or quad (4 ports)
 template <int PORTS>
 __global__ __launch_bounds__(256) void txdiv_eq_kernel(const EqParams p)
@@ -298,22 +289,7 @@ __global__ __launch_bounds__(256) void txdiv_front_kernel(const FrontParams p)
   }
 }
 
-// ---- transmit: one tile.  Symbol s of the codeword: its Qm packed bits (mod_tile of modem_kernels.hip), scrambled, as a constellation point
-template <int MOD>
-__device__ __forceinline__ float2 mod_point(const uint8_t* bits, uint32_t nbytes, const float2* tab, uint32_t s, uint32_t ls, const uint32_t* cbw)
-{
-  constexpr int  QM = MOD == 0 ? 1 : 2 * MOD;
-  const uint32_t b = s * QM, by = b >> 3;
-  const uint32_t hi8 = bits[by], lo8 = by + 1 < nbytes ? bits[by + 1] : 0u;
-  uint32_t       v   = (((hi8 << 8) | lo8) >> (16 - QM - (b & 7u))) & ((1u << QM) - 1u); // bit 0 of the symbol = MSB of v
-  const uint32_t c   = chips_at(cbw, ls * QM);                                           // chip i of the symbol in bit i
-#pragma unroll
-  for (int i = 0; i < QM; i++) {
-    v ^= ((c >> i) & 1u) << (QM - 1 - i);
-  }
-  return tab[v];
-}
-
+// ---- transmit: one tile (a symbol of the codeword as a constellation point: mod_point of modem_arith.h)
 template <int MOD>
 __device__ __forceinline__ void mod_tile(const ModParams& p, const ModJob& job, uint32_t tile, uint32_t* cbw)
 {

@@ -5,7 +5,8 @@
 // and every (block size, redundancy version) brings its rate-matching table.  The reference does that kind of work in srsran_sch_init (sch.c:159-197:
 // allocation, srsran_tdec_init, srsran_rm_turbo_gentables) -- so does the library: srsran_rm_turbo_gentables() builds every rate-matching table in
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
-// grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits -- on a short-lived
+// grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one 2-port transmit-diversity
+// grant and one two-codeword spatial-multiplexing grant each way -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
 #include "turbo_device.h"
@@ -99,6 +100,28 @@ void warm_one_worker()
     (void)srsran_hip_pdsch_encode_txdiv(&tx, &sb.tx, data.data(), planes);
     sb.reset();
     (void)srsran_hip_pdsch_decode_txdiv_dbg(&rx, planes, est, &sb.rx, data.data(), &res, qsym.data(), nullptr);
+  }
+  // one two-codeword spatial-multiplexing grant each way on the same planes (16-QAM + QPSK, 1728 REs, one block each), so the device code of
+  // spmux_kernels.hip is loaded before the first TM3 / TM4 subframe
+  {
+    const uint32_t               nof_re = nsymb * 12 * 12;
+    const srsran_hip_grant_tb_t  tb0    = {SRSRAN_MOD_16QAM, 6144 - 24, 0, nof_re, 12345u, 1, 0, 1};
+    const srsran_hip_grant_tb_t  tb1    = {SRSRAN_MOD_QPSK, 3136 - 24, 0, nof_re, 54321u, 1, 0, 1};
+    std::vector<cf_t>            port1(nof_re), est1(nof_re, cf_t(0.f, 0.5f));
+    cf_t* const                  planes[SRSRAN_MAX_PORTS] = {sym.data(), port1.data(), nullptr, nullptr};
+    cf_t* const                  est[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {{ce.data(), est1.data()}, {est1.data(), ce.data()}};
+    HostSoftbuffers              sb1(1);
+    srsran_softbuffer_tx_t* const stx[2] = {&sb.tx, &sb1.tx};
+    srsran_softbuffer_rx_t* const srx[2] = {&sb.rx, &sb1.rx};
+    std::vector<uint8_t>         data1(3136 / 8 + 64, 0xa5);
+    uint8_t* const               pay[2] = {data.data(), data1.data()};
+    srsran_hip_pdsch_mimo_tx_t   tx = {{tb0, tb1}, 2, 2, SRSRAN_HIP_TXSCHEME_SPATIALMUX, 1, 1.0f};
+    srsran_hip_pdsch_mimo_rx_t   rx = {{tb0, tb1}, 2, 2, SRSRAN_HIP_TXSCHEME_SPATIALMUX, 1, SRSRAN_HIP_MIMO_DECODER_MMSE, 2, 1.0f, 0.01f};
+    srsran_hip_grant_res_t       res[2];
+    cf_t* const                  dd[2] = {qsym.data(), nullptr};
+    (void)srsran_hip_pdsch_encode_mimo(&tx, stx, pay, planes);
+    sb.reset();
+    (void)srsran_hip_pdsch_decode_mimo_dbg(&rx, planes, est, srx, pay, res, dd, nullptr);
   }
   // NR: one codeword through the one-call paths of phy_nr_chan_abi.h, transmit then receive -- the 8-block 256-QAM transport block of a 100 MHz
   // carrier with the reference's default decoder parameters, so a worker's first slot finds its context, decoder objects and kernels ready

@@ -29,9 +29,14 @@
  *
  * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD on 4 ports (the
  * reference refuses them too) or with other than 2 receive antennas, PMI and condition-number selection (srsran_precoding_pmi_select, srsran_precoding_cn:
- * reductions over a whole subframe's estimates), CSI weighting of the soft bits (cfg->csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
+ * reductions over a whole subframe's estimates), the PUSCH's CSI weighting (pusch_cfg.h: csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
  * only), 8-bit soft bits on a grant with control information, the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the
  * control bits themselves, EVM measurement.
+ *
+ * CSI weighting of the PDSCH's soft bits (cfg->csi_enable, which srsue turns on by default; csi_correction, pdsch.c:523-618, between the descrambler and
+ * srsran_dlsch_decode2) is taken by the _csi form of each PDSCH receive call: the front end files the equaliser's channel-state values, one more kernel finds
+ * their maximum and scales every soft bit in the reference's integer arithmetic, bit for bit (its pairwise weight swaps for QPSK and 64-QAM and the halving of
+ * its 16-bit vector body included: csi_kernels.hip), still with one host wait.
  * The NR shared channels (pdsch_nr.c / pusch_nr.c, LDPC) have their own one-call-per-codeword entry points in phy_nr_chan_abi.h.
  */
 #ifndef SRSRAN_AMD_PHY_CHAN_ABI_H
@@ -132,6 +137,18 @@ SRSRAN_API int srsran_hip_pdsch_decode(const srsran_hip_pdsch_rx_t* g, const cf_
 SRSRAN_API int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
                                            uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
 
+/* the same with cfg->csi_enable: the soft bits are weighted with the codeword's channel-state values (csi_correction, pdsch.c:523-618) in front of the transport
+ * block.  ce != NULL: the values are the equaliser's (what srsran_predecoding_single files in q->csi[0]) and `csi` must be NULL; ce == NULL: `csi` is the
+ * caller's q->csi[cw], nof_re floats of HOST memory, required -- this form keeps the weighting, the rate de-matching and the decoding on the device for the
+ * port / antenna counts the library does not equalise.  Refused like the plain call, and with one line on stderr and SRSRAN_ERROR_INVALID_INPUTS before
+ * anything is enqueued: both or neither of ce and csi, a caller's csi entry that is negative or not finite.
+ * _dbg: e_out <- the WEIGHTED soft bits (what q->e[cw] holds when srsran_pdsch_decode returns), csi_out (or NULL) <- the nof_re values that were used. */
+SRSRAN_API int srsran_hip_pdsch_decode_csi(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
+                                           srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
+SRSRAN_API int srsran_hip_pdsch_decode_csi_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
+                                               srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                               float* csi_out);
+
 /* ---- PDSCH transmit, one codeword (srsran_pdsch_codeword_encode, pdsch.c:949-1015, + the scaling of :1116-1120): payload bytes ->
  * CRC24A, segmentation, CRC24B, turbo coding, rate matching (encode_tb, sch.c:238-368) -> scrambling -> constellation points x scaling.
  * data == NULL: a retransmission of what the soft buffer holds.  symbols: nof_re points, HOST memory. */
@@ -170,6 +187,13 @@ SRSRAN_API int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* 
  * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[0]: int16, int8 with llr_is_8bit) */
 SRSRAN_API int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                                                  srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
+/* the same with cfg->csi_enable: the soft bits are weighted with the combiner's channel-state values (what srsran_predecoding_diversity_multi files in
+ * q->csi[0]); arguments and refusals of the plain calls.  _dbg: e_out <- the WEIGHTED soft bits, csi_out (or NULL) <- the nof_re values that were used. */
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_csi(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_csi_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                     srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                                     float* csi_out);
 /* Transmit: srsran_hip_pdsch_encode's coding pass, then scrambling + modulation + srsran_layermap_diversity + srsran_precoding_diversity in one kernel:
  * symbols[port] <- nof_re points each (HOST memory), ready for srsran_pdsch_put per port; no intermediate d reaches memory.  scaling: what pdsch.c:486-492
  * returns on an eNB object (rho_a sqrt 2 on a multi-port cell); the precoder's 1 / sqrt 2 is applied inside.  data == NULL: a
@@ -198,7 +222,7 @@ SRSRAN_API int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_
  * range, an odd nof_re with CDD, a decoder that is neither ZF nor MMSE, scaling 0 or not finite, a negative or non-finite noise_estimate, two codewords
  * whose nof_re, llr_is_8bit or max_nof_iterations differ, every codeword skipped, and what every grant call refuses per codeword (modulation, tbs, rv,
  * length).  A device-side failure returns SRSRAN_ERROR.
- * Not taken: PMI and condition-number selection, CSI weighting of the soft bits (csi_enable), EVM, resource (de)mapping, 4 ports. */
+ * Not taken: PMI and condition-number selection, EVM, resource (de)mapping, 4 ports. */
 typedef struct SRSRAN_API {
   srsran_hip_grant_tb_t tb[2]; /* tb[k]: codeword k; seed with q = k; tb[k].nl is taken as 1; nof_re = REs of the grant, the same in both */
   uint32_t nof_tb;             /* 1 or 2 */
@@ -221,6 +245,18 @@ SRSRAN_API int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
                                                 srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
                                                 srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
                                                 void* const e_out[SRSRAN_MAX_CODEWORDS]);
+/* the same with cfg->csi_enable: codeword k's soft bits are weighted with layer k's channel-state values (what srsran_hip_predecoding_mimo files in
+ * q->csi[k]), both codewords in one launch; arguments and refusals of the plain calls.  Two-layer zero-forcing spatial multiplexing is undefined in the
+ * reference: its equaliser writes q->csi[0] only, all 1.0 (precoding.c:1330-1331), and codeword 1 is weighted with whatever an earlier call left in q->csi[1];
+ * the library uses 1.0 for that row as well.  _dbg: e_out[k] <- the WEIGHTED soft bits, csi_out[k] (the array or an entry may be NULL; not for a skipped
+ * codeword) <- the nof_re values that were used. */
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_csi(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS]);
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_csi_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                    srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                    srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
+                                                    void* const e_out[SRSRAN_MAX_CODEWORDS], float* const csi_out[SRSRAN_MAX_CODEWORDS]);
 /* Transmit: one coding launch over the code blocks of the grant's codewords, then scrambling + modulation of each codeword + srsran_hip_precoding_mimo's
  * arithmetic in one kernel: symbols[port] <- nof_re points each (HOST memory), ready for srsran_pdsch_put per port.  data[k] == NULL: a retransmission of what
  * softbuffers[k] holds.  Refusals as on the receive side (both soft buffers of a two-codeword grant are needed). */
@@ -245,8 +281,8 @@ SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t
 /* ---- warm start.  The first grant of a process / of a worker thread otherwise pays for loading the kernels' device code, creating the thread's staging
  * context (stream, pinned and device images, decoder / encoder objects, transform plans) and building rate-matching tables: 20-28 ms where a warm
  * call takes 0.1-0.4 ms.  srsran_hip_warmup(n) builds every rate-matching table and prepares n staging contexts by running real grants (the
- * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits; one 2-port transmit-diversity grant and one two-codeword
- * spatial-multiplexing grant each way) on short-lived threads; a worker
+ * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits, one CSI-weighted grant of each width;
+ * one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way) on short-lived threads; a worker
  * thread adopts a prepared context at its first call.  srsran_rm_turbo_gentables() -- which srsran_sch_init calls (sch.c:166) -- does the same
  * for one worker, so an application that does nothing gets a warm first subframe on one thread; srsenb's pool of nof_phy_threads workers
  * wants srsran_hip_warmup(nof_phy_threads) once after its objects are created.  Idempotent; returns SRSRAN_ERROR without a device. */

@@ -548,6 +548,8 @@ def lib():
             "srsran_hip_pdsch_decode": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
             "srsran_hip_pdsch_encode": (i32, [C.POINTER(HipPdschTx), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pdsch_decode_dbg": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp]),
+            "srsran_hip_pdsch_decode_csi": (i32, [C.POINTER(HipPdschRx), vp, vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_csi_dbg": (i32, [C.POINTER(HipPdschRx), vp, vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp, vp]),
             "srsran_hip_pdsch_encode_dbg": (i32, [C.POINTER(HipPdschTx), C.POINTER(SoftbufferTx), vp, vp, vp]),
             "srsran_hip_pdsch_encode_multi": (i32, [u32, C.POINTER(HipPdschTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_predecoding_diversity_multi": (i32, [C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, C.c_float]),
@@ -561,6 +563,10 @@ def lib():
             "srsran_hip_pdsch_decode_txdiv": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
             "srsran_hip_pdsch_decode_txdiv_dbg": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp,
                                                         C.POINTER(HipGrantRes), vp, vp]),
+            "srsran_hip_pdsch_decode_txdiv_csi": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp,
+                                                        C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_txdiv_csi_dbg": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx), vp,
+                                                            C.POINTER(HipGrantRes), vp, vp, vp]),
             "srsran_hip_pdsch_encode_txdiv": (i32, [C.POINTER(HipPdschTxdivTx), C.POINTER(SoftbufferTx), vp, C.POINTER(vp)]),
             "srsran_hip_pdsch_encode_txdiv_multi": (i32, [u32, C.POINTER(HipPdschTxdivTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp),
                                                           C.POINTER(C.POINTER(vp))]),
@@ -574,6 +580,10 @@ def lib():
                                                    C.POINTER(HipGrantRes)]),
             "srsran_hip_pdsch_decode_mimo_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp),
                                                        C.POINTER(HipGrantRes), C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_hip_pdsch_decode_mimo_csi": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(C.POINTER(SoftbufferRx)),
+                                                       C.POINTER(vp), C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_mimo_csi_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(C.POINTER(SoftbufferRx)),
+                                                           C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_pdsch_encode_mimo": (i32, [C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_pdsch_encode_mimo_multi": (i32, [u32, C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx) * 2), C.POINTER(vp * 2),
                                                          C.POINTER(C.POINTER(vp))]),

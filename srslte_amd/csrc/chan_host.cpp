@@ -3,6 +3,7 @@
 // (sch.c:1194) chained on the calling thread's transport-block stream, nothing but the inputs and the results crossing the bus.
 #include "chan_device.h"
 #include "chan_internal.h"
+#include "csi_device.h"
 #include "modem_device.h"
 
 #include <algorithm>
@@ -42,16 +43,42 @@ bool phyhip::chan::tb_valid(const srsran_hip_grant_tb_t& tb, const char* who)
   return true;
 }
 
+bool phyhip::chan::enqueue_csi_weight(hipStream_t st, const CsiCodeword* cw, uint32_t n_cw, uint32_t nof_re, bool llr8)
+{
+  csi::WeightParams p = {};
+  for (uint32_t k = 0; k < n_cw && k < 2; k++) {
+    p.job[k] = {cw[k].d_e, cw[k].csi, cw[k].mod, nof_re};
+  }
+  p.n_jobs = n_cw;
+  p.tile1  = (nof_re + CSI_TILE_SYMS - 1) / CSI_TILE_SYMS;
+  if (csi::launch_weight(p, llr8, st) != hipSuccess) {
+    set_error("grant front end: CSI weighting launch failed");
+    return false;
+  }
+  return true;
+}
+
+bool phyhip::chan::csi_row_valid(const float* csi, uint32_t nof_re)
+{
+  for (uint32_t i = 0; i < nof_re; i++) {
+    if (!(csi[i] >= 0.f) || !std::isfinite(csi[i])) {
+      return false;
+    }
+  }
+  return true;
+}
+
 namespace {
 
 // the receive front end of one grant, enqueued on `st`: [equaliser] -> [transform de-precoding] -> demodulator + descrambler (+ UL channel
-// de-interleaver in its store) -> d_e.  p_sym / p_ce: the grant's REs in the pinned image; d_x / d_z: device scratch of nof_re points each.
+// de-interleaver in its store) -> d_e.  p_sym / p_ce: the grant's REs in the pinned image; d_x / d_z: device scratch of nof_re points each; d_csi: nullptr,
+// or where the equaliser files its nof_re channel-state values.
 bool enqueue_rx_front(hipStream_t st, const srsran_hip_grant_tb_t& tb, const uint8_t* p_sym, const uint8_t* p_ce, float scaling, float noise, uint32_t L_prb,
-                      uint32_t nof_symb, uint8_t* d_x, uint8_t* d_z, srsran_hip_dft_batch_t* plan, void* d_e)
+                      uint32_t nof_symb, uint8_t* d_x, uint8_t* d_z, srsran_hip_dft_batch_t* plan, void* d_e, float* d_csi = nullptr)
 {
   const uint8_t* cur = p_sym;
   if (p_ce) {
-    if (modem::launch_eq(p_sym, p_ce, d_x, nullptr, tb.nof_re, scaling, noise, st) != hipSuccess) {
+    if (modem::launch_eq(p_sym, p_ce, d_x, d_csi, tb.nof_re, scaling, noise, st) != hipSuccess) {
       set_error("grant front end: equaliser launch failed");
       return false;
     }
@@ -404,42 +431,93 @@ extern "C" int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_
 
 // ------------------------------------------------------------------------------------------------ PDSCH receive, one codeword
 
-extern "C" int srsran_hip_pdsch_decode(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
-                                       uint8_t* data, srsran_hip_grant_res_t* res)
-{
-  return srsran_hip_pdsch_decode_dbg(g, symbols, ce, softbuffer, data, res, nullptr, nullptr);
-}
-
-extern "C" int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
-                                           uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+// weight: the _csi forms (cfg->csi_enable).  ce != NULL: the equaliser files its channel-state values in device scratch; ce == NULL: the caller's row goes
+// up in the pinned image with the symbols.  One launch behind the front end weights the soft bits; the _dbg downloads come behind it.
+static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
+                            srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
 {
   TraceRange trace_("srsran_hip_pdsch_decode");
   if (!g || !symbols || !softbuffer || !data || !res) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   *res = {0, 0.f, NAN};
-  if (!tb_valid(g->tb, "srsran_hip_pdsch_decode") || (ce && !(g->scaling != 0.f))) {
+  if (!tb_valid(g->tb, who) || (ce && !(g->scaling != 0.f))) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  ChanStage* sp = stage_for("srsran_hip_pdsch_decode");
+  if (weight && (ce != nullptr) == (csi != nullptr)) {
+    return refuse("%s: %s", who, ce ? "the equaliser makes the CSI of a grant with channel estimates: csi must be NULL" : "a grant without channel estimates needs the caller's csi");
+  }
+  if (weight && csi && !csi_row_valid(csi, g->tb.nof_re)) {
+    return refuse("%s: a csi entry is negative or not finite", who);
+  }
+  ChanStage* sp = stage_for(who);
   if (!sp) {
     return SRSRAN_ERROR;
   }
   ChanStage&   s  = *sp;
   const size_t nb = al256((size_t)g->tb.nof_re * sizeof(cf_t));
   const size_t ne = (size_t)g->tb.nof_re * qm_of(g->tb.mod) * (g->tb.llr_is_8bit ? 1 : 2);
-  if (!s.grow(3 * nb + al256(ne), nb)) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode: staging allocation failed\n");
+  // behind the plain call's images: the CSI row (pinned: the caller's, or what _dbg hands back; device: the equaliser's)
+  const size_t nc = weight ? csi_plane(g->tb.nof_re) : 0, o_c = 3 * nb + al256(ne);
+  if (!s.grow(o_c + nc, nb + (ce ? nc : 0))) {
+    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
     return SRSRAN_ERROR;
   }
   memcpy(s.pin, symbols, (size_t)g->tb.nof_re * sizeof(cf_t));
   if (ce) {
     memcpy(s.pin + nb, ce, (size_t)g->tb.nof_re * sizeof(cf_t));
   }
+  if (csi) {
+    memcpy(s.pin + o_c, csi, (size_t)g->tb.nof_re * sizeof(float));
+  }
+  float*              row    = !weight ? nullptr : reinterpret_cast<float*>(ce ? s.dev + nb : s.pin + o_c);
   const sch::FrontEnd make_e = [&](hipStream_t st, void* d_e) {
-    return enqueue_rx_front(st, g->tb, s.pin, ce ? s.pin + nb : nullptr, g->scaling, g->noise_estimate, 0, 0, s.dev, nullptr, nullptr, d_e);
+    if (!enqueue_rx_front(st, g->tb, s.pin, ce ? s.pin + nb : nullptr, g->scaling, g->noise_estimate, 0, 0, s.dev, nullptr, nullptr, d_e, ce ? row : nullptr)) {
+      return false;
+    }
+    if (!weight) {
+      return true;
+    }
+    const CsiCodeword cw = {d_e, row, g->tb.mod};
+    if (!enqueue_csi_weight(st, &cw, 1, g->tb.nof_re, g->tb.llr_is_8bit != 0)) {
+      return false;
+    }
+    if (csi_out && ce && hipMemcpyAsync(s.pin + o_c, row, (size_t)g->tb.nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
+      set_error("grant front end: copy of the intermediate results failed");
+      return false;
+    }
+    return true;
   };
-  return pdsch_decode_codeword(s, g->tb, qm_rm(g->tb), make_e, (d_out && ce) ? s.dev.get() : nullptr, 2 * nb, softbuffer, data, res, d_out, e_out);
+  const int rc = pdsch_decode_codeword(s, g->tb, qm_rm(g->tb), make_e, (d_out && ce) ? s.dev.get() : nullptr, 2 * nb, softbuffer, data, res, d_out, e_out);
+  if (rc == SRSRAN_SUCCESS && weight && csi_out) {
+    memcpy(csi_out, s.pin + o_c, (size_t)g->tb.nof_re * sizeof(float));
+  }
+  return rc;
+}
+
+extern "C" int srsran_hip_pdsch_decode(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
+                                       uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_one("srsran_hip_pdsch_decode", false, g, symbols, ce, nullptr, softbuffer, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
+                                           uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+{
+  return pdsch_decode_one("srsran_hip_pdsch_decode", false, g, symbols, ce, nullptr, softbuffer, data, res, d_out, e_out, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_csi(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
+                                           srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_one("srsran_hip_pdsch_decode_csi", true, g, symbols, ce, csi, softbuffer, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_csi_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
+                                               srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                               float* csi_out)
+{
+  return pdsch_decode_one("srsran_hip_pdsch_decode_csi", true, g, symbols, ce, csi, softbuffer, data, res, d_out, e_out, csi_out);
 }
 
 int phyhip::chan::pdsch_decode_codeword(ChanStage& s, const srsran_hip_grant_tb_t& tb, uint32_t Qm, const sch::FrontEnd& make_e, const uint8_t* dev_d, size_t o_d,

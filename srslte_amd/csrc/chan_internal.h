@@ -72,6 +72,22 @@ int refuse(const char* fmt, Args... args)
 int pdsch_decode_codeword(ChanStage& s, const srsran_hip_grant_tb_t& tb, uint32_t Qm, const sch::FrontEnd& make_e, const uint8_t* dev_d, size_t o_d,
                           srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
 
+// ---- CSI weighting of the soft bits (cfg->csi_enable: csi_correction, pdsch.c:523-618; csi_kernels.hip), what the three _csi grant calls share.
+// The front end leaves the codeword's CSI row -- one float per RE -- in device scratch (or the caller's row went up in the pinned image); ONE launch
+// behind it weights the soft bits of the call's codewords in place at d_e, in front of the transport-block stage and of the _dbg downloads.
+struct CsiCodeword {
+  void*        d_e;
+  const float* csi; // device-readable
+  uint32_t     mod;
+};
+bool enqueue_csi_weight(hipStream_t st, const CsiCodeword* cw, uint32_t n_cw, uint32_t nof_re, bool llr8);
+inline size_t csi_plane(uint32_t nof_re) // a CSI row's room in a staging image
+{
+  return al256((size_t)nof_re * sizeof(float));
+}
+// a caller's row: every entry finite and >= 0 (checked before the device is looked for)
+bool csi_row_valid(const float* csi, uint32_t nof_re);
+
 // The codewords of a TTI, transmit, behind the caller's checks: one coding launch over the code blocks of all of them, one launch of the caller's
 // modulator, one host wait.  The pinned image holds, per codeword, `planes` output planes of al256(nof_re points) from o_out, then the job list;
 // `launch(stream, d_e, e_byte_off, JobList<J>&)` writes the jobs (e_byte_off[i]: codeword i's first byte in d_e) and enqueues the kernel.

@@ -120,6 +120,11 @@ __device__ __forceinline__ void demod_int(float re, float im, uint32_t idx, uint
 // symbols, replaced by 1e-4 inside the antenna loop when it is 0 (:699-701); 4 ports: (0, 2) on the first pair of a quad and (1, 3) on the second,
 // each symbol with its own gain.  Operation order (ours): every product and sum rounded by itself (nothing contracts); per antenna the two complex
 // products of a symbol are formed, added to each other, then to the accumulator; a gain's four squares are summed left to right, then added.
+// The two gains are what the grant calls file as the codeword's CSI (txdiv_front_kernel<T, true>) and what srsran_predecoding_diversity_multi files
+// (txdiv_eq_kernel): they go through rn_mul / rn_add (defined with the 2x2 section below: contraction off), so that the two kernels agree on them bit for
+// bit whatever the compiler fuses elsewhere -- with the plain operators the 4-port, 2-antenna sums came out one unit apart between the two kernels.
+__device__ __forceinline__ float rn_mul(float a, float b);
+__device__ __forceinline__ float rn_add(float a, float b);
 struct Sfbc {
   float x0r = 0.f, x0i = 0.f, x1r = 0.f, x1i = 0.f, g0 = 0.f, g1 = 0.f;
 };
@@ -138,11 +143,11 @@ __device__ __forceinline__ void sfbc_add(Sfbc& a, float2 ha, float2 hb, float2 h
   a.x0i           = __fadd_rn(a.x0i, __fadd_rn(p0i, p1i));
   a.x1r           = __fadd_rn(a.x1r, __fsub_rn(q0r, q1r));
   a.x1i           = __fadd_rn(a.x1i, __fsub_rn(q0i, q1i));
-  a.g0 = __fadd_rn(a.g0, __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(ha.x, ha.x), __fmul_rn(ha.y, ha.y)), __fmul_rn(hb.x, hb.x)), __fmul_rn(hb.y, hb.y)));
+  a.g0 = rn_add(a.g0, rn_add(rn_add(rn_add(rn_mul(ha.x, ha.x), rn_mul(ha.y, ha.y)), rn_mul(hb.x, hb.x)), rn_mul(hb.y, hb.y)));
   if (PORTS == 2) {
     a.g0 = a.g0 == 0.f ? 1e-4f : a.g0;
   } else {
-    a.g1 = __fadd_rn(a.g1, __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(hd.x, hd.x), __fmul_rn(hd.y, hd.y)), __fmul_rn(hc.x, hc.x)), __fmul_rn(hc.y, hc.y)));
+    a.g1 = rn_add(a.g1, rn_add(rn_add(rn_add(rn_mul(hd.x, hd.x), rn_mul(hd.y, hd.y)), rn_mul(hc.x, hc.x)), rn_mul(hc.y, hc.y)));
   }
 }
 // x / den * M_SQRT2 as the C expression evaluates it: float quotient, product in double, rounded once to float

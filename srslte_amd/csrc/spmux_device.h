@@ -44,6 +44,7 @@ struct FrontParams {
   const float4*   y[2];    // [rx]: n REs, 16-byte aligned, readable up to the next multiple of 2 REs
   const float4*   h[2][2]; // [port][rx]
   void*           out[2];  // [codeword]: n * Qm soft bits (int16 / int8), 16-byte aligned
+  float*          csi[2];  // [layer]: n floats, 8-byte aligned: the channel-state values of srsran_hip_predecoding_mimo; csi[0] == nullptr: not wanted
   uint32_t        mod[2], seed[2];
   uint32_t        n;
   Scheme          s;

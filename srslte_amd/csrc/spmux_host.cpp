@@ -232,17 +232,13 @@ extern "C" int srsran_hip_precoding_mimo(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRS
 
 // ------------------------------------------------------------------------------------------------ PDSCH grant, receive
 
-extern "C" int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
-                                            srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
-                                            srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS])
-{
-  return srsran_hip_pdsch_decode_mimo_dbg(g, symbols, ce, softbuffers, data, res, nullptr, nullptr);
-}
-
-extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
-                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
-                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
-                                                void* const e_out[SRSRAN_MAX_CODEWORDS])
+// weight: the _csi forms (cfg->csi_enable): the front end files each layer's channel-state values in device scratch, ONE launch behind it weights the soft
+// bits of both codewords (chan_internal.h), the _dbg downloads come behind that.  Two-layer zero-forcing spatial multiplexing: the reference's equaliser
+// writes q->csi[0] only (precoding.c:1330-1331) and weights codeword 1 with whatever an earlier call left in q->csi[1]; here that row is 1.0, as row 0 is.
+static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                             srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                             srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
+                             float* const csi_out[SRSRAN_MAX_CODEWORDS])
 {
   static const char* who = "srsran_hip_pdsch_decode_mimo";
   TraceRange         trace_(who);
@@ -300,8 +296,9 @@ extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
     o_e[k] = end;
     end += al256(ne[k]);
   }
-  const bool want_d = d_out && (d_out[0] || (ntb == 2 && d_out[1]));
-  if (!s.grow(end, want_d ? 2 * nb : 0)) {
+  const bool   want_d = d_out && (d_out[0] || (ntb == 2 && d_out[1]));
+  const size_t nc = weight ? csi_plane(nof_re) : 0, o_c = end, o_dc = want_d ? 2 * nb : 0; // the CSI rows: what _dbg hands back, device scratch
+  if (!s.grow(o_c + ntb * nc, o_dc + ntb * nc)) {
     fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
     return SRSRAN_ERROR;
   }
@@ -332,7 +329,8 @@ extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
     cw_of[n_items]   = k;
     items[n_items++] = {&head[k], softbuffers[k], &seg[k], qm_of(g->tb[k].mod), g->tb[k].rv, nof_re * qm_of(g->tb[k].mod), nullptr, &marks_device_bits, data[k], false};
   }
-  bool                     failed = false, d_made = false, e_made[2] = {false, false};
+  float* const             row[2] = {weight ? reinterpret_cast<float*>(s.dev + o_dc) : nullptr, (weight && ntb == 2) ? reinterpret_cast<float*>(s.dev + o_dc + nc) : nullptr};
+  bool                     failed = false, d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false};
   const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
     modem::Params mp;
     if (!modem::params_for(mp, llr8 ? modem::LLR_I8 : modem::LLR_I16)) {
@@ -353,6 +351,8 @@ extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
     for (uint32_t j = 0; j < m; j++) {
       fp.out[cw_of[which[j]]] = d_e[j];
     }
+    fp.csi[0]  = row[0];
+    fp.csi[1]  = row[1];
     fp.n       = nof_re;
     fp.s       = t.rx;
     fp.x1_bits = mp.x1_bits;
@@ -374,8 +374,26 @@ extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
       }
       d_made = true;
     }
+    if (weight) {
+      CsiCodeword cw[2];
+      for (uint32_t j = 0; j < m && j < 2; j++) {
+        cw[j] = {d_e[j], row[cw_of[which[j]]], g->tb[cw_of[which[j]]].mod};
+      }
+      if (!enqueue_csi_weight(st, cw, m, nof_re, llr8)) {
+        failed = true;
+        return false;
+      }
+    }
     for (uint32_t j = 0; j < m; j++) {
       const uint32_t k = cw_of[which[j]];
+      if (csi_out && csi_out[k]) {
+        if (hipMemcpyAsync(s.pin + o_c + k * nc, row[k], (size_t)nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
+          set_error("grant front end: copy of the intermediate results failed");
+          failed = true;
+          return false;
+        }
+        c_made[k] = true;
+      }
       if (e_out && e_out[k]) {
         if (hipMemcpyAsync(s.pin + o_e[k], d_e[j], ne[k], hipMemcpyDeviceToHost, st) != hipSuccess) {
           set_error("grant front end: copy of the intermediate results failed");
@@ -411,12 +429,49 @@ extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t
         missing = true;
       }
     }
+    if (weight && csi_out && csi_out[k] && softbuffers[k]) {
+      if (c_made[k]) {
+        memcpy(csi_out[k], s.pin + o_c + k * nc, (size_t)nof_re * sizeof(float));
+      } else {
+        missing = true;
+      }
+    }
   }
   if (missing) {
     set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", who);
     fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
   }
   return (failed || missing) ? SRSRAN_ERROR : SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                            srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                            srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS])
+{
+  return pdsch_decode_mimo(false, g, symbols, ce, softbuffers, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
+                                                void* const e_out[SRSRAN_MAX_CODEWORDS])
+{
+  return pdsch_decode_mimo(false, g, symbols, ce, softbuffers, data, res, d_out, e_out, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_csi(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS])
+{
+  return pdsch_decode_mimo(true, g, symbols, ce, softbuffers, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_csi_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                    srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                    srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],
+                                                    void* const e_out[SRSRAN_MAX_CODEWORDS], float* const csi_out[SRSRAN_MAX_CODEWORDS])
+{
+  return pdsch_decode_mimo(true, g, symbols, ce, softbuffers, data, res, d_out, e_out, csi_out);
 }
 
 // ------------------------------------------------------------------------------------------------ PDSCH grant, transmit

@@ -139,7 +139,9 @@ __device__ __forceinline__ void codeword_bits_of(const FrontParams& p, uint32_t 
   }
 }
 
-template <typename T>
+// CSI: the equaliser's channel-state values (what spmux_eq_kernel files; a two-layer zero-forcing solve: 1.0 in both rows) go to p.csi[layer], one float
+// per RE, for the weighting behind (csi_kernels.hip); the plain calls run the instantiations without
+template <typename T, bool CSI>
 __global__ __launch_bounds__(256) void spmux_front_kernel(const FrontParams p)
 {
   __shared__ __attribute__((aligned(16))) uint32_t cb[4][2][MODEM_TILE_BITS / 128 + 4]; // [wave][codeword]
@@ -177,10 +179,24 @@ __global__ __launch_bounds__(256) void spmux_front_kernel(const FrontParams p)
   float2 x0[PAIRS][2], x1[PAIRS][2];
 #pragma unroll
   for (int r = 0; r < PAIRS; r++) {
-    float c0, c1;
+    float c0[2], c1[2] = {0.f, 0.f};
     x1[r][0] = x1[r][1] = make_float2(0.f, 0.f);
-    mimo_equalise(p.s.layers, p.s.pre[0], p.s.mmse != 0, lo(y0[r]), lo(y1[r]), lo(a0[r]), lo(b0[r]), lo(a1[r]), lo(b1[r]), p.s.norm, p.s.noise, x0[r][0], x1[r][0], c0, c1);
-    mimo_equalise(p.s.layers, p.s.pre[1], p.s.mmse != 0, hi(y0[r]), hi(y1[r]), hi(a0[r]), hi(b0[r]), hi(a1[r]), hi(b1[r]), p.s.norm, p.s.noise, x0[r][1], x1[r][1], c0, c1);
+    mimo_equalise(p.s.layers, p.s.pre[0], p.s.mmse != 0, lo(y0[r]), lo(y1[r]), lo(a0[r]), lo(b0[r]), lo(a1[r]), lo(b1[r]), p.s.norm, p.s.noise, x0[r][0], x1[r][0], c0[0], c1[0]);
+    mimo_equalise(p.s.layers, p.s.pre[1], p.s.mmse != 0, hi(y0[r]), hi(y1[r]), hi(a0[r]), hi(b0[r]), hi(a1[r]), hi(b1[r]), p.s.norm, p.s.noise, x0[r][1], x1[r][1], c0[1], c1[1]);
+    if (CSI) {
+      const uint32_t s = w0 + 2 * (r * 64u + lane); // the pair's even RE
+      if (s + 1 < p.n) {
+        *(float2*)(p.csi[0] + s) = make_float2(c0[0], c0[1]);
+        if (p.s.layers == 2) {
+          *(float2*)(p.csi[1] + s) = make_float2(c1[0], c1[1]);
+        }
+      } else if (s < p.n) {
+        p.csi[0][s] = c0[0];
+        if (p.s.layers == 2) {
+          p.csi[1][s] = c1[0];
+        }
+      }
+    }
   }
   // the codewords one after the other: their modulations may differ
   if (want0) {
@@ -326,10 +342,20 @@ hipError_t launch_front(const FrontParams& p, bool llr8, hipStream_t stream)
     return hipErrorInvalidValue;
   }
   const dim3 grid(ceil_div(p.n, MODEM_TILE_SYMS));
+  const bool csi = p.csi[0] != nullptr;
+  if (csi && ((((uintptr_t)p.csi[0]) & 7u) || (p.s.layers == 2 && (!p.csi[1] || (((uintptr_t)p.csi[1]) & 7u))))) {
+    return hipErrorInvalidValue;
+  }
   if (llr8) {
-    hipLaunchKernelGGL(spmux_front_kernel<int8_t>, grid, dim3(256), 0, stream, p);
+    if (csi) {
+      hipLaunchKernelGGL((spmux_front_kernel<int8_t, true>), grid, dim3(256), 0, stream, p);
+    } else {
+      hipLaunchKernelGGL((spmux_front_kernel<int8_t, false>), grid, dim3(256), 0, stream, p);
+    }
+  } else if (csi) {
+    hipLaunchKernelGGL((spmux_front_kernel<int16_t, true>), grid, dim3(256), 0, stream, p);
   } else {
-    hipLaunchKernelGGL(spmux_front_kernel<int16_t>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((spmux_front_kernel<int16_t, false>), grid, dim3(256), 0, stream, p);
   }
   return hipGetLastError();
 }

@@ -42,6 +42,7 @@ struct FrontParams {
   const float4*   y[2];    // [rx]: n REs
   const float4*   h[4][2]; // [port][rx]
   void*           out;     // n * Qm soft bits (int16 / int8), 16-byte aligned
+  float*          csi;     // n floats, 16-byte aligned: the channel-state values of srsran_predecoding_diversity_multi; nullptr: not wanted
   uint32_t        mod, n, seed;
   uint32_t        ports, nof_rx;
   float           scaling;

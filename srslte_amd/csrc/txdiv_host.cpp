@@ -243,14 +243,10 @@ extern "C" int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, 
 
 // ---- PDSCH codeword with transmit diversity, receive
 
-extern "C" int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
-                                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
-{
-  return srsran_hip_pdsch_decode_txdiv_dbg(g, symbols, ce, softbuffer, data, res, nullptr, nullptr);
-}
-
-extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
-                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+// weight: the _csi forms (cfg->csi_enable): the front end files the combiner's channel-state values in device scratch, one launch behind it weights the
+// soft bits (chan_internal.h), the _dbg downloads come behind that
+static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
 {
   TraceRange trace_("srsran_hip_pdsch_decode_txdiv");
   if (res) {
@@ -286,7 +282,8 @@ extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx
   const size_t                 ne = (size_t)nof_re * qm_of(tb.mod) * (tb.llr_is_8bit ? 1 : 2);
   const size_t                 o_d = (size_t)nrx * (1 + ports) * nb;
   const bool                   want_d = d_out != nullptr;
-  if (!s.grow(o_d + nb + al256(ne), want_d ? nb : 0)) {
+  const size_t                 nc = weight ? csi_plane(nof_re) : 0, o_c = o_d + nb + al256(ne), o_dc = want_d ? nb : 0; // the CSI row: what _dbg hands back, device scratch
+  if (!s.grow(o_c + nc, o_dc + nc)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode_txdiv: staging allocation failed\n");
     return SRSRAN_ERROR;
   }
@@ -304,7 +301,8 @@ extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx
   for (uint32_t k = 0; k < ports; k++) { // the combined symbols layer-demapped: layer k's symbol i is d[ports i + k]
     xd[k] = reinterpret_cast<cf_t*>(s.dev.get()) + k;
   }
-  const txdiv::EqParams ep = eq_params(yp, hp, xd, nullptr, ports, nrx, ports, nof_re, g->scaling);
+  const txdiv::EqParams ep  = eq_params(yp, hp, xd, nullptr, ports, nrx, ports, nof_re, g->scaling);
+  float*                row = weight ? reinterpret_cast<float*>(s.dev + o_dc) : nullptr;
   const sch::FrontEnd   make_e = [&](hipStream_t st, void* d_e) {
     modem::Params mp;
     if (!modem::params_for(mp, tb.llr_is_8bit ? modem::LLR_I8 : modem::LLR_I16)) {
@@ -314,6 +312,7 @@ extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx
     memcpy(fp.y, ep.y, sizeof(fp.y));
     memcpy(fp.h, ep.h, sizeof(fp.h));
     fp.out     = d_e;
+    fp.csi     = row;
     fp.mod     = tb.mod;
     fp.n       = nof_re;
     fp.seed    = tb.seed;
@@ -332,9 +331,49 @@ extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx
       set_error("grant front end: the combined symbols could not be produced");
       return false;
     }
+    if (!weight) {
+      return true;
+    }
+    const CsiCodeword cw = {d_e, row, tb.mod};
+    if (!enqueue_csi_weight(st, &cw, 1, nof_re, tb.llr_is_8bit != 0)) {
+      return false;
+    }
+    if (csi_out && hipMemcpyAsync(s.pin + o_c, row, (size_t)nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
+      set_error("grant front end: copy of the intermediate results failed");
+      return false;
+    }
     return true;
   };
-  return pdsch_decode_codeword(s, tb, 2 * qm_of(tb.mod), make_e, want_d ? s.dev.get() : nullptr, o_d, softbuffer, data, res, d_out, e_out);
+  const int rc = pdsch_decode_codeword(s, tb, 2 * qm_of(tb.mod), make_e, want_d ? s.dev.get() : nullptr, o_d, softbuffer, data, res, d_out, e_out);
+  if (rc == SRSRAN_SUCCESS && weight && csi_out) {
+    memcpy(csi_out, s.pin + o_c, (size_t)nof_re * sizeof(float));
+  }
+  return rc;
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_txdiv(false, g, symbols, ce, softbuffer, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+{
+  return pdsch_decode_txdiv(false, g, symbols, ce, softbuffer, data, res, d_out, e_out, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_csi(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                 srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_txdiv(true, g, symbols, ce, softbuffer, data, res, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_csi_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                                     srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                                     float* csi_out)
+{
+  return pdsch_decode_txdiv(true, g, symbols, ce, softbuffer, data, res, d_out, e_out, csi_out);
 }
 
 // ---- PDSCH codeword with transmit diversity, transmit

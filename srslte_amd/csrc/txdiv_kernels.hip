@@ -141,7 +141,7 @@ __device__ __forceinline__ void pair_bits(const FrontParams& p, float2 x0, float
   store_bits<T, 2 * QM>(out + (size_t)s * QM, v, al);
 }
 
-template <typename T, int MOD, int PORTS>
+template <typename T, int MOD, int PORTS, bool CSI>
 __device__ __forceinline__ void front_tile(const FrontParams& p, uint32_t tile, uint32_t* cbw)
 {
   constexpr int  QM   = MOD == 0 ? 1 : 2 * MOD;
@@ -190,6 +190,9 @@ __device__ __forceinline__ void front_tile(const FrontParams& p, uint32_t tile, 
       }
       float2 x0, x1, c;
       sfbc_finish<2>(a, p.scaling, nrx, x0, x1, c);
+      if (CSI) {
+        *(float2*)(p.csi + s) = c;
+      }
       pair_bits<T, MOD>(p, x0, x1, s, ls, cbw, out, al);
     }
   } else {
@@ -232,16 +235,21 @@ __device__ __forceinline__ void front_tile(const FrontParams& p, uint32_t tile, 
         sfbc_add<4>(a, lo(h0[1][r]), hi(h2[1][r]), lo(h2[1][r]), hi(h0[1][r]), lo(y0[1][r]), hi(y0[1][r]));
         sfbc_add<4>(b, lo(h1[1][r]), hi(h3[1][r]), lo(h3[1][r]), hi(h1[1][r]), lo(y1[1][r]), hi(y1[1][r]));
       }
-      float2 x0, x1, x2, x3, c;
-      sfbc_finish<4>(a, p.scaling, nrx, x0, x1, c);
-      sfbc_finish<4>(b, p.scaling, nrx, x2, x3, c);
+      float2 x0, x1, x2, x3, c0, c1;
+      sfbc_finish<4>(a, p.scaling, nrx, x0, x1, c0);
+      sfbc_finish<4>(b, p.scaling, nrx, x2, x3, c1);
+      if (CSI) {
+        *(float4*)(p.csi + s) = make_float4(c0.x, c0.y, c1.x, c1.y);
+      }
       pair_bits<T, MOD>(p, x0, x1, s, ls, cbw, out, al);
       pair_bits<T, MOD>(p, x2, x3, s + 2, ls + 2, cbw, out, al);
     }
   }
 }
 
-template <typename T>
+// CSI: the combiner's channel-state values (what txdiv_eq_kernel files) go to p.csi, one float per RE, for the weighting behind (csi_kernels.hip); the
+// plain calls run the instantiations without
+template <typename T, bool CSI>
 __global__ __launch_bounds__(256) void txdiv_front_kernel(const FrontParams p)
 {
   __shared__ __attribute__((aligned(16))) uint32_t cb[4][MODEM_TILE_BITS / 128 + 4];
@@ -253,37 +261,37 @@ __global__ __launch_bounds__(256) void txdiv_front_kernel(const FrontParams p)
   if (p.ports == 2) {
     switch (p.mod) {
       case 0:
-        front_tile<T, 0, 2>(p, blockIdx.x, cbw);
+        front_tile<T, 0, 2, CSI>(p, blockIdx.x, cbw);
         break;
       case 1:
-        front_tile<T, 1, 2>(p, blockIdx.x, cbw);
+        front_tile<T, 1, 2, CSI>(p, blockIdx.x, cbw);
         break;
       case 2:
-        front_tile<T, 2, 2>(p, blockIdx.x, cbw);
+        front_tile<T, 2, 2, CSI>(p, blockIdx.x, cbw);
         break;
       case 3:
-        front_tile<T, 3, 2>(p, blockIdx.x, cbw);
+        front_tile<T, 3, 2, CSI>(p, blockIdx.x, cbw);
         break;
       default:
-        front_tile<T, 4, 2>(p, blockIdx.x, cbw);
+        front_tile<T, 4, 2, CSI>(p, blockIdx.x, cbw);
         break;
     }
   } else {
     switch (p.mod) {
       case 0:
-        front_tile<T, 0, 4>(p, blockIdx.x, cbw);
+        front_tile<T, 0, 4, CSI>(p, blockIdx.x, cbw);
         break;
       case 1:
-        front_tile<T, 1, 4>(p, blockIdx.x, cbw);
+        front_tile<T, 1, 4, CSI>(p, blockIdx.x, cbw);
         break;
       case 2:
-        front_tile<T, 2, 4>(p, blockIdx.x, cbw);
+        front_tile<T, 2, 4, CSI>(p, blockIdx.x, cbw);
         break;
       case 3:
-        front_tile<T, 3, 4>(p, blockIdx.x, cbw);
+        front_tile<T, 3, 4, CSI>(p, blockIdx.x, cbw);
         break;
       default:
-        front_tile<T, 4, 4>(p, blockIdx.x, cbw);
+        front_tile<T, 4, 4, CSI>(p, blockIdx.x, cbw);
         break;
     }
   }
@@ -428,10 +436,19 @@ hipError_t launch_front(const FrontParams& p, bool llr8, hipStream_t stream)
     return hipErrorInvalidValue;
   }
   const dim3 grid(ceil_div(p.n, MODEM_TILE_SYMS));
+  if (p.csi && (((uintptr_t)p.csi) & 15u)) {
+    return hipErrorInvalidValue;
+  }
   if (llr8) {
-    hipLaunchKernelGGL(txdiv_front_kernel<int8_t>, grid, dim3(256), 0, stream, p);
+    if (p.csi) {
+      hipLaunchKernelGGL((txdiv_front_kernel<int8_t, true>), grid, dim3(256), 0, stream, p);
+    } else {
+      hipLaunchKernelGGL((txdiv_front_kernel<int8_t, false>), grid, dim3(256), 0, stream, p);
+    }
+  } else if (p.csi) {
+    hipLaunchKernelGGL((txdiv_front_kernel<int16_t, true>), grid, dim3(256), 0, stream, p);
   } else {
-    hipLaunchKernelGGL(txdiv_front_kernel<int16_t>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((txdiv_front_kernel<int16_t, false>), grid, dim3(256), 0, stream, p);
   }
   return hipGetLastError();
 }

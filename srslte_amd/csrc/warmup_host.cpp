@@ -5,8 +5,8 @@
 // and every (block size, redundancy version) brings its rate-matching table.  The reference does that kind of work in srsran_sch_init (sch.c:159-197:
 // allocation, srsran_tdec_init, srsran_rm_turbo_gentables) -- so does the library: srsran_rm_turbo_gentables() builds every rate-matching table in
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
-// grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one 2-port transmit-diversity
-// grant and one two-codeword spatial-multiplexing grant each way -- on a short-lived
+// grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one CSI-weighted grant of each
+// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
 #include "turbo_device.h"
@@ -79,6 +79,11 @@ void warm_one_worker()
       pd.tb = tb;
       (void)srsran_hip_pdsch_decode(&pd, grid.data(), nullptr, &sb.rx, data.data(), &res);
       tb.rv = 0;
+      if (gr.L == 12) { // one CSI-weighted grant per soft-bit width (cfg->csi_enable, srsue's default): csi_kernels.hip is loaded
+        pd.tb = tb;
+        sb.reset();
+        (void)srsran_hip_pdsch_decode_csi(&pd, grid.data(), ce.data(), nullptr, &sb.rx, data.data(), &res);
+      }
       if (!llr8) { // transmit
         srsran_hip_pdsch_tx_t tx = {tb, 1.0f};
         (void)srsran_hip_pdsch_encode_dbg(&tx, &sb.tx, data.data(), sym.data(), qbits.data());

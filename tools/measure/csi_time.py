@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""Host-to-host latency of the PDSCH grant calls with and without CSI weighting of the soft bits (include/srsran_amd/phy_chan_abi.h).
+
+    plain   srsran_hip_pdsch_decode (one port, with the equaliser), srsran_hip_pdsch_decode_txdiv (2 ports, 2 receive antennas), srsran_hip_pdsch_decode_mimo
+            (two codewords, codebook 1, MMSE at noise 0)
+    csi     their _csi forms, when the library has them (a library from before they existed is timed on the plain calls alone: --lib)
+on a 25-PRB grant (3600 REs, 16-QAM, tbs 6200: 2 code blocks per codeword) and a 100-PRB grant (14400 REs, 64-QAM, tbs 75376: 13 code blocks per codeword).  The
+symbols come from the library's own transmit calls through a mild channel with noise 35 dB down, so every call decodes in the minimum of iterations.  Plain and
+_csi calls alternate call by call in one loop after a warm-up of both; soft buffers are reset outside the timed region.  Median / p90 of the timed calls in
+microseconds and, for the _csi forms, the median of the per-iteration difference to the plain call; one JSON line at the end.
+
+    python tools/measure/csi_time.py [--calls 300] [--lib PATH] [--tag NAME] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+
+import oracle_api as O
+import spmux_model as M
+from srslte_amd import capi
+
+GRANTS = [("25prb_16qam", 2, 6200, 3600), ("100prb_64qam", 3, 75376, 14400)]
+SB, ITERS, SCALING = 18600, 10, 0.8
+vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
+
+
+def pct(t, q):
+    t = sorted(t)
+    return t[min(len(t) - 1, int(len(t) * q))]
+
+
+def planes(arrs):
+    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
+
+
+def matrix(h):
+    return capi.PlaneMatrix(*[planes([h[k][r] for r in range(h.shape[1])]) for k in range(h.shape[0])])
+
+
+def rx_softbuffer(nb):
+    rows = [np.zeros(SB, np.int16) for _ in range(nb)]
+    keep = [np.zeros(SB // 8, np.uint8) for _ in range(nb)]
+    flags = np.zeros(nb, np.bool_)
+    return (capi.SoftbufferRx(nb, SB, (vp * nb)(*[r.ctypes.data for r in rows]), (vp * nb)(*[k.ctypes.data for k in keep]), flags.ctypes.data_as(C.POINTER(C.c_bool)), False),
+            rows, keep, flags)
+
+
+def tx_softbuffer(nb):
+    rows = [np.zeros(SB, np.uint8) for _ in range(nb)]
+    return capi.SoftbufferTx(nb, SB, (vp * nb)(*[r.ctypes.data for r in rows])), rows
+
+
+def load(path):
+    """the library with the argument types of the calls timed here; the _csi forms only when it exports them"""
+    L = C.CDLL(path)
+    R, T, MR = C.POINTER(capi.SoftbufferRx), C.POINTER(capi.SoftbufferTx), C.POINTER(capi.HipGrantRes)
+    sig = {"srsran_hip_device_count": [], "srsran_hip_set_device": [i32], "srsran_hip_warmup": [u32],
+           "srsran_hip_pdsch_encode": [C.POINTER(capi.HipPdschTx), T, vp, vp],
+           "srsran_hip_pdsch_encode_txdiv": [C.POINTER(capi.HipPdschTxdivTx), T, vp, C.POINTER(vp)],
+           "srsran_hip_pdsch_encode_mimo": [C.POINTER(capi.HipPdschMimoTx), C.POINTER(T), C.POINTER(vp), C.POINTER(vp)],
+           "srsran_hip_pdsch_decode": [C.POINTER(capi.HipPdschRx), vp, vp, R, vp, MR],
+           "srsran_hip_pdsch_decode_txdiv": [C.POINTER(capi.HipPdschTxdivRx), C.POINTER(vp), C.POINTER(capi.PlaneArray), R, vp, MR],
+           "srsran_hip_pdsch_decode_mimo": [C.POINTER(capi.HipPdschMimoRx), C.POINTER(vp), C.POINTER(capi.PlaneArray), C.POINTER(R), C.POINTER(vp), MR]}
+    csi = {"srsran_hip_pdsch_decode_csi": [C.POINTER(capi.HipPdschRx), vp, vp, vp, R, vp, MR],
+           "srsran_hip_pdsch_decode_txdiv_csi": sig["srsran_hip_pdsch_decode_txdiv"], "srsran_hip_pdsch_decode_mimo_csi": sig["srsran_hip_pdsch_decode_mimo"]}
+    has_csi = all(hasattr(L, n) for n in csi)
+    for name, args in list(sig.items()) + (list(csi.items()) if has_csi else []):
+        f = getattr(L, name)
+        f.restype, f.argtypes = i32, args
+    return L, has_csi
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=300)
+    ap.add_argument("--lib", default=capi.LIB_PATH)
+    ap.add_argument("--tag", default="")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    lib, has_csi = load(args.lib)
+    assert lib.srsran_hip_device_count() > 0, "no HIP device: nothing is measured without one"
+    assert lib.srsran_hip_set_device(0) == 0 and lib.srsran_hip_warmup(1) == 0
+    warm = max(30, args.calls // 10)
+    rows_out = []
+    for name, mod, tbs, n in GRANTS:
+        rng = np.random.default_rng(n)
+        nb = O.cbsegm(tbs)["C"]
+        seeds = [O.pdsch_seed(0x1234, k, 10, 301) for k in range(2)]
+        pays = [rng.integers(0, 256, tbs // 8).astype(np.uint8) for _ in range(2)]
+        sigma = 10 ** (-35 / 20) / np.sqrt(2)
+
+        def through(h, p):
+            y = np.einsum("krn,kn->rn", h.astype(np.complex128), p.astype(np.complex128))
+            return np.ascontiguousarray((y + sigma * (rng.standard_normal(y.shape) + 1j * rng.standard_normal(y.shape))).astype(np.complex64))
+
+        def tb(k, iters, nl):
+            return capi.HipGrantTb(mod, tbs, 0, n, seeds[k], iters, 0, nl)
+
+        calls = {}
+        keep = []
+        # one port
+        p = np.zeros((1, n), np.complex64)
+        sbt = tx_softbuffer(nb)
+        assert lib.srsran_hip_pdsch_encode(C.byref(capi.HipPdschTx(tb(0, 0, 1), SCALING)), C.byref(sbt[0]), O.P(pays[0]), O.P(p[0])) == 0
+        h1 = np.ascontiguousarray((0.9 + 0.1 * M.cn(rng, (1, 1, n))).astype(np.complex64))
+        y1 = through(h1, p)
+        g1 = capi.HipPdschRx(tb(0, ITERS, 1), SCALING, 0.0)
+        sb1, d1, r1 = rx_softbuffer(nb), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
+        calls["single"] = (lambda: lib.srsran_hip_pdsch_decode(C.byref(g1), O.P(y1[0]), O.P(h1[0][0]), C.byref(sb1[0]), O.P(d1), r1),
+                           lambda: lib.srsran_hip_pdsch_decode_csi(C.byref(g1), O.P(y1[0]), O.P(h1[0][0]), None, C.byref(sb1[0]), O.P(d1), r1), [sb1], [d1], r1, 1)
+        # transmit diversity, 2 ports, 2 receive antennas (taps constant over a pair)
+        p = np.zeros((2, n), np.complex64)
+        sbt = tx_softbuffer(nb)
+        assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(capi.HipPdschTxdivTx(tb(0, 0, 2), 2, SCALING)), C.byref(sbt[0]), O.P(pays[0]), planes(list(p))) == 0
+        h2 = np.ascontiguousarray(np.repeat(0.9 + 0.1 * M.cn(rng, (2, 2, n // 2)), 2, axis=2).astype(np.complex64))
+        y2 = through(h2, p)
+        g2 = capi.HipPdschTxdivRx(tb(0, ITERS, 2), 2, 2, SCALING, 0)
+        sb2, d2, r2 = rx_softbuffer(nb), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
+        py2, ph2 = planes(list(y2)), matrix(h2)
+        calls["txdiv"] = (lambda: lib.srsran_hip_pdsch_decode_txdiv(C.byref(g2), py2, ph2, C.byref(sb2[0]), O.P(d2), r2),
+                          lambda: lib.srsran_hip_pdsch_decode_txdiv_csi(C.byref(g2), py2, ph2, C.byref(sb2[0]), O.P(d2), r2), [sb2], [d2], r2, 1)
+        # spatial multiplexing, two codewords
+        p = np.zeros((2, n), np.complex64)
+        sbt2 = [tx_softbuffer(nb) for _ in range(2)]
+        gt = capi.HipPdschMimoTx((capi.HipGrantTb * 2)(tb(0, 0, 1), tb(1, 0, 1)), 2, 2, capi.TXSCHEME_SPATIALMUX, 1, SCALING)
+        assert lib.srsran_hip_pdsch_encode_mimo(C.byref(gt), (C.POINTER(capi.SoftbufferTx) * 2)(*[C.pointer(s[0]) for s in sbt2]), (vp * 2)(*[a.ctypes.data for a in pays]),
+                                                planes(list(p))) == 0
+        h3 = M.channel(rng, n)
+        y3 = through(h3, p)
+        g3 = capi.HipPdschMimoRx((capi.HipGrantTb * 2)(tb(0, ITERS, 1), tb(1, ITERS, 1)), 2, 2, capi.TXSCHEME_SPATIALMUX, 1, capi.MIMO_DECODER_MMSE, 2, SCALING, 0.0)
+        sb3 = [rx_softbuffer(nb) for _ in range(2)]
+        d3, r3 = [np.zeros(tbs // 8 + 16, np.uint8) for _ in range(2)], (capi.HipGrantRes * 2)()
+        py3, ph3 = planes(list(y3)), matrix(h3)
+        sbp3, dp3 = (C.POINTER(capi.SoftbufferRx) * 2)(*[C.pointer(s[0]) for s in sb3]), (vp * 2)(*[a.ctypes.data for a in d3])
+        calls["mimo"] = (lambda: lib.srsran_hip_pdsch_decode_mimo(C.byref(g3), py3, ph3, sbp3, dp3, r3),
+                         lambda: lib.srsran_hip_pdsch_decode_mimo_csi(C.byref(g3), py3, ph3, sbp3, dp3, r3), sb3, d3, r3, 2)
+        keep.append((sbt, sbt2))
+        for path, (plain, weighted, sbs, data, res, ncw) in calls.items():
+            tm = {"plain": [], "csi": []}
+            for i in range(warm + args.calls):
+                for what, fn in (("plain", plain), ("csi", weighted)):
+                    if what == "csi" and not has_csi:
+                        continue
+                    for sb, rows, _, flags in sbs:  # (outside the timed region: a fresh soft buffer)
+                        flags[:] = False
+                        sb.tb_crc = False
+                        for r in rows:
+                            r[:] = 0
+                    t0 = time.perf_counter()
+                    rc = fn()
+                    dt = (time.perf_counter() - t0) * 1e6
+                    assert rc == 0, (name, path, what, rc)
+                    for k in range(ncw):
+                        assert res[k].crc_ok == 1 and np.array_equal(data[k][:tbs // 8], pays[k]), (name, path, what, k)
+                    if i >= warm:
+                        tm[what].append(dt)
+            row = dict(grant=name, path=path, nof_re=n, tbs=tbs, nof_cb=nb * ncw, calls=args.calls, plain_p50_us=round(pct(tm["plain"], 0.5), 1),
+                       plain_p90_us=round(pct(tm["plain"], 0.9), 1))
+            txt = "%-6s %-13s %-7s nof_re %5d (%2d blocks)   plain p50 %6.1f p90 %6.1f us" % (args.tag, name, path, n, nb * ncw, row["plain_p50_us"], row["plain_p90_us"])
+            if has_csi:
+                row.update(csi_p50_us=round(pct(tm["csi"], 0.5), 1), csi_p90_us=round(pct(tm["csi"], 0.9), 1),
+                           csi_minus_plain_p50_us=round(pct([b - a for a, b in zip(tm["plain"], tm["csi"])], 0.5), 1))
+                txt += " | _csi p50 %6.1f p90 %6.1f us | _csi - plain, call by call, p50 %+5.1f us" % (row["csi_p50_us"], row["csi_p90_us"], row["csi_minus_plain_p50_us"])
+            rows_out.append(row)
+            print(txt, flush=True)
+    line = json.dumps({"tool": "csi_time", "tag": args.tag, "unit": "us, host to host", "rows": rows_out})
+    print(line)
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

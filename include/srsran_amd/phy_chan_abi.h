@@ -133,7 +133,10 @@ SRSRAN_API int srsran_hip_pdsch_decode(const srsran_hip_pdsch_rx_t* g, const cf_
                                        uint8_t* data, srsran_hip_grant_res_t* res);
 /* the same, and the intermediate results the reference leaves in the PDSCH object where its callers can see them (lib/test/phy/phy_dl_test.c:253-298 compares
  * both with the transmitter's): d_out (or NULL) <- the nof_re equalised symbols (q->d[cw]; only written when ce != NULL -- otherwise they are `symbols`),
- * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[cw]: int16, int8 with llr_is_8bit).  Each costs a device -> host copy. */
+ * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[cw]: int16, int8 with llr_is_8bit).  Each costs a device -> host copy.
+ * SRSRAN_ERROR when an output that was asked for was not produced: the front end does not run for a codeword whose soft buffer has fewer rows than it has code
+ * blocks, or whose code blocks were all decoded in an earlier round.  That output is left untouched; *res is filled as usual.  (d_out with ce == NULL is
+ * never written and is not such an output.)  A device-side failure returns SRSRAN_ERROR, in this and in the plain call. */
 SRSRAN_API int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
                                            uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
 
@@ -142,7 +145,8 @@ SRSRAN_API int srsran_hip_pdsch_decode_dbg(const srsran_hip_pdsch_rx_t* g, const
  * caller's q->csi[cw], nof_re floats of HOST memory, required -- this form keeps the weighting, the rate de-matching and the decoding on the device for the
  * port / antenna counts the library does not equalise.  Refused like the plain call, and with one line on stderr and SRSRAN_ERROR_INVALID_INPUTS before
  * anything is enqueued: both or neither of ce and csi, a caller's csi entry that is negative or not finite.
- * _dbg: e_out <- the WEIGHTED soft bits (what q->e[cw] holds when srsran_pdsch_decode returns), csi_out (or NULL) <- the nof_re values that were used. */
+ * _dbg: e_out <- the WEIGHTED soft bits (what q->e[cw] holds when srsran_pdsch_decode returns), csi_out (or NULL) <- the nof_re values that were used;
+ * SRSRAN_ERROR, as in srsran_hip_pdsch_decode_dbg, when one of them was asked for and not produced. */
 SRSRAN_API int srsran_hip_pdsch_decode_csi(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
                                            srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
 SRSRAN_API int srsran_hip_pdsch_decode_csi_dbg(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
@@ -184,7 +188,8 @@ typedef struct SRSRAN_API {
 SRSRAN_API int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
 /* the same, and d_out (or NULL) <- the nof_re combined, layer-demapped symbols (q->d[0]; made by the per-stage kernels in this case only: same arithmetic),
- * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[0]: int16, int8 with llr_is_8bit) */
+ * e_out (or NULL) <- the nof_re * Qm descrambled soft bits (q->e[0]: int16, int8 with llr_is_8bit).  SRSRAN_ERROR, as in srsran_hip_pdsch_decode_dbg, when an
+ * output that was asked for was not produced (here and in _csi_dbg). */
 SRSRAN_API int srsran_hip_pdsch_decode_txdiv_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                                                  srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
 /* the same with cfg->csi_enable: the soft bits are weighted with the combiner's channel-state values (what srsran_predecoding_diversity_multi files in
@@ -240,7 +245,7 @@ SRSRAN_API int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g,
 /* the same, and per codeword (the array or an entry may be NULL) d_out[k] <- the nof_re equalised symbols of layer k (q->d[k]; made by the per-stage kernel
  * in this case only: same arithmetic), e_out[k] <- the nof_re * Qm descrambled soft bits (q->e[k]: int16, int8 with llr_is_8bit; not for a skipped codeword).
  * SRSRAN_ERROR when an output that was asked for was not produced: the front end does not run for a codeword whose soft buffer has fewer rows than it has code
- * blocks, or whose code blocks were all decoded in an earlier round. */
+ * blocks, or whose code blocks were all decoded in an earlier round.  That output is left untouched; res[] is filled as usual. */
 SRSRAN_API int srsran_hip_pdsch_decode_mimo_dbg(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                                                 srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
                                                 srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS],

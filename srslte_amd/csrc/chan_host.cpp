@@ -350,10 +350,13 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
     }
     return true;
   };
-  sch::decode_tbs_staged(items.data(), n, (n > 1 || uci) ? &group : nullptr);
+  const bool device_ok = sch::decode_tbs_staged(items.data(), n, (n > 1 || uci) ? &group : nullptr);
   for (uint32_t i = 0; i < n; i++) {
     res[i].crc_ok               = items[i].ok ? 1 : 0;
     res[i].avg_iterations_block = pl[i].head.avg_iterations;
+  }
+  if (!device_ok) { // not a CRC failure: the caller must not take it for a NACK
+    return SRSRAN_ERROR;
   }
   for (uint32_t i = 0; uci && i < n; i++) {
     const srsran_hip_pusch_uci_t& u = uci[i];
@@ -432,7 +435,7 @@ extern "C" int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_
 // ------------------------------------------------------------------------------------------------ PDSCH receive, one codeword
 
 // weight: the _csi forms (cfg->csi_enable).  ce != NULL: the equaliser files its channel-state values in device scratch; ce == NULL: the caller's row goes
-// up in the pinned image with the symbols.  One launch behind the front end weights the soft bits; the _dbg downloads come behind it.
+// up in the pinned image with the symbols, and `symbols` are the equalised symbols already (no d is made).
 static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
 {
@@ -450,49 +453,14 @@ static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch
   if (weight && csi && !csi_row_valid(csi, g->tb.nof_re)) {
     return refuse("%s: a csi entry is negative or not finite", who);
   }
-  ChanStage* sp = stage_for(who);
-  if (!sp) {
-    return SRSRAN_ERROR;
-  }
-  ChanStage&   s  = *sp;
-  const size_t nb = al256((size_t)g->tb.nof_re * sizeof(cf_t));
-  const size_t ne = (size_t)g->tb.nof_re * qm_of(g->tb.mod) * (g->tb.llr_is_8bit ? 1 : 2);
-  // behind the plain call's images: the CSI row (pinned: the caller's, or what _dbg hands back; device: the equaliser's)
-  const size_t nc = weight ? csi_plane(g->tb.nof_re) : 0, o_c = 3 * nb + al256(ne);
-  if (!s.grow(o_c + nc, nb + (ce ? nc : 0))) {
-    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
-    return SRSRAN_ERROR;
-  }
-  memcpy(s.pin, symbols, (size_t)g->tb.nof_re * sizeof(cf_t));
-  if (ce) {
-    memcpy(s.pin + nb, ce, (size_t)g->tb.nof_re * sizeof(cf_t));
-  }
-  if (csi) {
-    memcpy(s.pin + o_c, csi, (size_t)g->tb.nof_re * sizeof(float));
-  }
-  float*              row    = !weight ? nullptr : reinterpret_cast<float*>(ce ? s.dev + nb : s.pin + o_c);
-  const sch::FrontEnd make_e = [&](hipStream_t st, void* d_e) {
-    if (!enqueue_rx_front(st, g->tb, s.pin, ce ? s.pin + nb : nullptr, g->scaling, g->noise_estimate, 0, 0, s.dev, nullptr, nullptr, d_e, ce ? row : nullptr)) {
-      return false;
-    }
-    if (!weight) {
-      return true;
-    }
-    const CsiCodeword cw = {d_e, row, g->tb.mod};
-    if (!enqueue_csi_weight(st, &cw, 1, g->tb.nof_re, g->tb.llr_is_8bit != 0)) {
-      return false;
-    }
-    if (csi_out && ce && hipMemcpyAsync(s.pin + o_c, row, (size_t)g->tb.nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
-      set_error("grant front end: copy of the intermediate results failed");
-      return false;
-    }
-    return true;
-  };
-  const int rc = pdsch_decode_codeword(s, g->tb, qm_rm(g->tb), make_e, (d_out && ce) ? s.dev.get() : nullptr, 2 * nb, softbuffer, data, res, d_out, e_out);
-  if (rc == SRSRAN_SUCCESS && weight && csi_out) {
-    memcpy(csi_out, s.pin + o_c, (size_t)g->tb.nof_re * sizeof(float));
-  }
-  return rc;
+  cf_t *const  y[1] = {const_cast<cf_t*>(symbols)}, *const h[1] = {const_cast<cf_t*>(ce)};
+  const size_t nd   = (size_t)g->tb.nof_re * sizeof(cf_t);
+  PlaneGroup   in[2] = {{y, 1, nd, true, false}, {h, ce ? 1u : 0u, nd, true, false}};
+  RxGrant      gr = {who, in, 2, csi, {{&g->tb, qm_rm(g->tb), softbuffer, data, res, d_out, e_out, csi_out}}, 1, ce ? 1u : 0u, ce != nullptr, weight};
+  return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
+    return enqueue_rx_front(st, g->tb, reinterpret_cast<uint8_t*>(in[0].pin[0]), reinterpret_cast<uint8_t*>(in[1].pin[0]), g->scaling, g->noise_estimate, 0, 0, d_d, nullptr,
+                            nullptr, d_e[0], ce ? row[0] : nullptr);
+  });
 }
 
 extern "C" int srsran_hip_pdsch_decode(const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
@@ -520,36 +488,119 @@ extern "C" int srsran_hip_pdsch_decode_csi_dbg(const srsran_hip_pdsch_rx_t* g, c
   return pdsch_decode_one("srsran_hip_pdsch_decode_csi", true, g, symbols, ce, csi, softbuffer, data, res, d_out, e_out, csi_out);
 }
 
-int phyhip::chan::pdsch_decode_codeword(ChanStage& s, const srsran_hip_grant_tb_t& tb, uint32_t Qm, const sch::FrontEnd& make_e, const uint8_t* dev_d, size_t o_d,
-                                        srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out)
+// ------------------------------------------------------------------------------------------------ PDSCH receive, the frame of every grant call
+
+int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
 {
-  srsran_cbsegm_t seg;
-  if (!segment(&seg, tb.tbs)) { // (behind the caller's staging: it cannot fail for a grant tb_valid has passed)
+  ChanStage* sp = stage_for(g.who);
+  if (!sp) {
     return SRSRAN_ERROR;
   }
-  const size_t          nd = (size_t)tb.nof_re * sizeof(cf_t), ne = (size_t)tb.nof_re * qm_of(tb.mod) * (tb.llr_is_8bit ? 1 : 2);
-  srsran_hip_sch_head_t head = {tb.max_nof_iterations, 0.f, tb.llr_is_8bit != 0};
-  uint8_t *             p_d = s.pin + o_d, *p_e = p_d + al256(nd);
-  const sch::FrontEnd   front = [&](hipStream_t st, void* d_e) {
-    if (!make_e(st, d_e)) {
+  ChanStage&     s      = *sp;
+  const uint32_t nof_re = g.cw[0].tb->nof_re;
+  const bool     llr8   = g.cw[0].tb->llr_is_8bit != 0;
+  const size_t   nd = (size_t)nof_re * sizeof(cf_t), nb = al256(nd), nr = (size_t)nof_re * sizeof(float), nc = g.weight ? csi_plane(nof_re) : 0;
+  bool           want_d = false;
+  for (uint32_t k = 0; k < g.n_cw; k++) {
+    want_d = want_d || (g.d_planes && g.cw[k].d_out);
+  }
+  // pinned: the planes, the equalised symbols, each codeword's soft bits, each codeword's CSI row; device: the equalised symbols, the front end's CSI rows
+  const size_t o_d = plane_room(g.in, g.n_in);
+  size_t       ne[2] = {0, 0}, o_e[2] = {0, 0}, o_c = o_d + g.d_planes * nb;
+  for (uint32_t k = 0; k < g.n_cw; k++) {
+    ne[k]  = (size_t)nof_re * qm_of(g.cw[k].tb->mod) * (llr8 ? 1 : 2);
+    o_e[k] = o_c;
+    o_c += al256(ne[k]);
+  }
+  const bool   dev_rows = g.weight && !g.csi;
+  const size_t o_dc     = (want_d || g.d_scratch) ? g.d_planes * nb : 0;
+  if (!s.grow(o_c + g.n_cw * nc, o_dc + (dev_rows ? g.n_cw * nc : 0))) {
+    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", g.who);
+    return SRSRAN_ERROR;
+  }
+  place_planes(s.pin, g.in, g.n_in);
+  if (g.csi) {
+    memcpy(s.pin + o_c, g.csi, nr);
+  }
+  // the enabled codewords as items of one decoding pass
+  static const sch::FrontEnd device_made = [](hipStream_t, void*) { return false; }; // (never called: the group front end below serves the call's codewords)
+  srsran_cbsegm_t            seg[2];
+  srsran_hip_sch_head_t      head[2];
+  sch::TbItem                items[2];
+  uint32_t                   cw_of[2] = {0, 0}, n_items = 0;
+  float*                     row[2] = {nullptr, nullptr};
+  for (uint32_t k = 0; k < g.n_cw; k++) {
+    const RxCodeword& c = g.cw[k];
+    if (g.weight) {
+      row[k] = reinterpret_cast<float*>(dev_rows ? s.dev + o_dc + k * nc : s.pin + o_c + k * nc);
+    }
+    if (!c.sb) {
+      continue;
+    }
+    if (!segment(&seg[k], c.tb->tbs)) { // (behind the caller's checks: it cannot fail for a grant tb_valid has passed)
+      return SRSRAN_ERROR;
+    }
+    head[k]          = {c.tb->max_nof_iterations, 0.f, llr8};
+    cw_of[n_items]   = k;
+    items[n_items++] = {&head[k], c.sb, &seg[k], c.Qm, c.tb->rv, nof_re * qm_of(c.tb->mod), nullptr, &device_made, c.data, false};
+  }
+  // what the front end actually made: it does not run for a codeword the transport-block stage drops
+  bool                     d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false};
+  const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
+    void*       de[2] = {nullptr, nullptr};
+    CsiCodeword wj[2];
+    for (uint32_t j = 0; j < m && j < 2; j++) {
+      const uint32_t k = cw_of[which[j]];
+      de[k] = d_e[j];
+      wj[j] = {d_e[j], row[k], g.cw[k].tb->mod};
+    }
+    if (!front(st, de, row, o_dc ? s.dev.get() : nullptr) || (g.weight && !enqueue_csi_weight(st, wj, m, nof_re, llr8))) {
       return false;
     }
-    if ((dev_d && hipMemcpyAsync(p_d, dev_d, nd, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (e_out && hipMemcpyAsync(p_e, d_e, ne, hipMemcpyDeviceToHost, st) != hipSuccess)) {
+    bool copied = !want_d || hipMemcpyAsync(s.pin + o_d, s.dev, (g.d_planes - 1) * nb + nd, hipMemcpyDeviceToHost, st) == hipSuccess;
+    d_made      = want_d && copied;
+    for (uint32_t j = 0; copied && j < m; j++) {
+      const uint32_t k = cw_of[which[j]];
+      if (g.weight && g.cw[k].csi_out) { // (the caller's row is in the image already)
+        copied = c_made[k] = !dev_rows || hipMemcpyAsync(s.pin + o_c + k * nc, row[k], nr, hipMemcpyDeviceToHost, st) == hipSuccess;
+      }
+      if (copied && g.cw[k].e_out) {
+        copied = e_made[k] = hipMemcpyAsync(s.pin + o_e[k], d_e[j], ne[k], hipMemcpyDeviceToHost, st) == hipSuccess;
+      }
+    }
+    if (!copied) {
       set_error("grant front end: copy of the intermediate results failed");
-      return false;
     }
-    return true;
+    return copied;
   };
-  const bool ok = sch::decode_tb_staged(&head, softbuffer, &seg, Qm, tb.rv, tb.nof_re * qm_of(tb.mod), nullptr, &front, data);
-  if (dev_d) {
-    memcpy(d_out, p_d, nd);
+  const bool device_ok = sch::decode_tbs_staged(items, n_items, &group);
+  for (uint32_t i = 0; i < n_items; i++) {
+    const RxCodeword& c = g.cw[cw_of[i]];
+    c.res->crc_ok               = items[i].ok ? 1 : 0;
+    c.res->avg_iterations_block = head[cw_of[i]].avg_iterations;
   }
-  if (e_out) {
-    memcpy(e_out, p_e, ne);
+  if (!device_ok) {
+    return SRSRAN_ERROR;
   }
-  res->crc_ok               = ok ? 1 : 0;
-  res->avg_iterations_block = head.avg_iterations;
+  // what _dbg was asked for and the front end did not make is an error, not a silently untouched buffer
+  bool missing = false;
+  const auto hand_back = [&](void* out, bool made, size_t off, size_t bytes) {
+    if (out && made) {
+      memcpy(out, s.pin + off, bytes);
+    }
+    missing = missing || (out && !made);
+  };
+  for (uint32_t k = 0; k < g.n_cw; k++) {
+    const RxCodeword& c = g.cw[k];
+    hand_back(g.d_planes ? c.d_out : nullptr, d_made, o_d + k * nb, nd);
+    hand_back(c.sb ? c.e_out : nullptr, e_made[k], o_e[k], ne[k]);
+    hand_back(c.sb && g.weight ? c.csi_out : nullptr, c_made[k], o_c + k * nc, nr);
+  }
+  if (missing) {
+    set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", g.who);
+    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+    return SRSRAN_ERROR;
+  }
   return SRSRAN_SUCCESS;
 }
 

@@ -1,5 +1,6 @@
 // chan_internal.h -- what the grant-level entry points share (chan_host.cpp: one port; txdiv_host.cpp: transmit diversity; spmux_host.cpp: spatial
-// multiplexing and CDD): the calling thread's staging context, the grant checks, the two codeword paths that exist once -- PDSCH receive of one codeword, PDSCH
+// multiplexing and CDD): the calling thread's staging context, the grant checks, the two grant frames that exist once -- PDSCH receive of a grant's one or two
+// codewords (pdsch_decode_grant: staging, transport-block stage, CSI weighting, the _dbg outputs and their bookkeeping; a scheme adds its kernels), PDSCH
 // transmit of a TTI's codewords -- and the frame of a per-stage call on host planes.
 #pragma once
 #include "hip_common.h"
@@ -66,12 +67,6 @@ int refuse(const char* fmt, Args... args)
   return SRSRAN_ERROR_INVALID_INPUTS;
 }
 
-// One PDSCH codeword, receive, behind the caller's checks and staging: `make_e` enqueues the front end that leaves the soft bits at d_e; the frame adds
-// the downloads of what the reference leaves in q->d / q->e for its callers to look at (d from `dev_d` when the caller wants it, else nullptr; through
-// the pinned image: d at o_d, e one plane behind it), segments and runs the transport block (`Qm`: the rate matcher's), copies out and fills *res.
-int pdsch_decode_codeword(ChanStage& s, const srsran_hip_grant_tb_t& tb, uint32_t Qm, const sch::FrontEnd& make_e, const uint8_t* dev_d, size_t o_d,
-                          srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out);
-
 // ---- CSI weighting of the soft bits (cfg->csi_enable: csi_correction, pdsch.c:523-618; csi_kernels.hip), what the three _csi grant calls share.
 // The front end leaves the codeword's CSI row -- one float per RE -- in device scratch (or the caller's row went up in the pinned image); ONE launch
 // behind it weights the soft bits of the call's codewords in place at d_e, in front of the transport-block stage and of the _dbg downloads.
@@ -137,34 +132,26 @@ int pdsch_encode_codewords(ChanStage& s, TxCodeword* cw, uint32_t n, Launch laun
   return SRSRAN_SUCCESS;
 }
 
-// ---- a host-buffer stage: the caller's planes into the thread's pinned image (the kernels work on it directly), one kernel, one wait, planes out
+// ---- planes in the thread's pinned image (the kernels work on it directly)
 
 struct PlaneGroup { // k planes of `bytes` each, 256-byte aligned, group behind group in the image
   cf_t* const* host;                  // the caller's planes (refused when one is NULL); nullptr: room in the image only
   uint32_t     k;
   size_t       bytes;
   bool         in, out;               // copied in before / out after the kernel
-  cf_t*        pin[SRSRAN_MAX_PORTS]; // set by run_on_planes: the planes in the image
+  cf_t*        pin[SRSRAN_MAX_PORTS]; // set by place_planes: the planes in the image
 };
-
-template <class Launch>
-bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch launch)
+inline size_t plane_room(const PlaneGroup* grp, uint32_t n_grp)
 {
   size_t need = 0;
   for (uint32_t g = 0; g < n_grp; g++) {
-    for (uint32_t i = 0; grp[g].host && i < grp[g].k; i++) {
-      if (!grp[g].host[i]) {
-        return false;
-      }
-    }
     need += grp[g].k * al256(grp[g].bytes);
   }
-  ChanStage*  s  = stage_for(who);
-  hipStream_t st = s ? sch::stage_stream() : nullptr;
-  if (!st || !s->grow(need, 0)) {
-    return false;
-  }
-  uint8_t* at = s->pin;
+  return need;
+}
+// the groups' planes from the image's start (plane_room bytes), the `in` ones filled from the caller's
+inline void place_planes(uint8_t* at, PlaneGroup* grp, uint32_t n_grp)
+{
   for (uint32_t g = 0; g < n_grp; g++) {
     for (uint32_t i = 0; i < grp[g].k; i++, at += al256(grp[g].bytes)) {
       grp[g].pin[i] = reinterpret_cast<cf_t*>(at);
@@ -173,6 +160,25 @@ bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch laun
       }
     }
   }
+}
+
+// a host-buffer stage: the caller's planes into the image, one kernel, one wait, planes out
+template <class Launch>
+bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch launch)
+{
+  for (uint32_t g = 0; g < n_grp; g++) {
+    for (uint32_t i = 0; grp[g].host && i < grp[g].k; i++) {
+      if (!grp[g].host[i]) {
+        return false;
+      }
+    }
+  }
+  ChanStage*  s  = stage_for(who);
+  hipStream_t st = s ? sch::stage_stream() : nullptr;
+  if (!st || !s->grow(plane_room(grp, n_grp), 0)) {
+    return false;
+  }
+  place_planes(s->pin, grp, n_grp);
   const bool launched = launch(st) == hipSuccess;
   if (hipStreamSynchronize(st) != hipSuccess || !launched) {
     return false;
@@ -184,6 +190,42 @@ bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch laun
   }
   return true;
 }
+
+// ---- one PDSCH grant, receive, behind the caller's checks: the frame around a scheme's front-end kernels.  It stages the planes, runs the grant's one or two
+// codewords as ONE pass of the transport-block stage (sch::decode_tbs_staged) whose front end is `front` and, with `weight`, one CSI weighting launch behind it
+// (csi_kernels.hip), downloads what _dbg asked for, copies out and fills every codeword's res.  The codewords share nof_re, llr_is_8bit and max_nof_iterations.
+// Pinned image: the planes, d_planes planes for the equalised symbols, every codeword's soft bits, every codeword's CSI row (the caller's, or what _dbg hands
+// back); device scratch: the equalised symbols (when somebody wants them), the CSI rows the front end files.  Everything on a 256-byte boundary, a plane's
+// padding behind it (the MIMO kernels read an odd grant's last pair whole).
+// SRSRAN_ERROR when a device-side step failed, and -- one line on stderr -- when a _dbg output that was asked for was not produced: the front end does not run for a
+// codeword the transport-block stage drops (a soft buffer with fewer rows than code blocks) or whose blocks were all decoded in an earlier round.  Such an
+// output is left untouched; res is filled in both cases.
+struct RxCodeword {
+  const srsran_hip_grant_tb_t* tb;
+  uint32_t                     Qm; // the rate matcher's
+  srsran_softbuffer_rx_t*      sb; // nullptr: skipped (its layer is still part of the front end)
+  uint8_t*                     data;
+  srsran_hip_grant_res_t*      res;
+  cf_t*                        d_out; // _dbg, or nullptr: equalised symbols, soft bits, the CSI row that was used
+  void*                        e_out;
+  float*                       csi_out;
+};
+struct RxGrant {
+  const char*  who;
+  PlaneGroup*  in; // staged: symbols [nof_rx], then estimates [port][nof_rx]
+  uint32_t     n_in;
+  const float* csi; // the caller's CSI row in place of the front end's (one port without estimates), or nullptr
+  RxCodeword   cw[SRSRAN_MAX_CODEWORDS];
+  uint32_t     n_cw;
+  uint32_t     d_planes;  // planes of nof_re points the equalised symbols take: 1, one per layer with MIMO; 0: the front end makes none
+  bool         d_scratch; // the front end needs that room whether or not d_out asks for it
+  bool         weight;
+};
+// enqueues the scheme's kernels on the stage's stream, reading g.in[].pin: codeword k's soft bits to d_e[k] and, with weight, its CSI values to row[k]
+// (d_e[k] == nullptr: not called for that codeword; row[k] is device-readable); the equalised symbols to d_d, plane behind plane of al256(nof_re points) --
+// nullptr when nobody asked for them
+using RxFront = std::function<bool(hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d)>;
+int pdsch_decode_grant(RxGrant& g, const RxFront& front);
 
 } // namespace chan
 } // namespace phyhip

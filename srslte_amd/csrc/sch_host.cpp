@@ -503,8 +503,9 @@ hipStream_t stage_stream()
 // have to come back for the next transmission).  The e bits of a block are either the caller's host array (`e_bits`) or -- `front` given -- produced
 // ON THE DEVICE by the kernels `front(stream, d_e_bits)` enqueues in front of the de-matcher (chan_host.cpp, txdiv_host.cpp: equaliser, transform de-precoding,
 // demodulator + descrambler never leave the device).  One call takes blocks of one soft-bit width, one iteration limit and one kind of e-bit source;
-// a mixed list is decoded piece by piece.
-static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const phyhip::sch::GroupFrontEnd* group, uint32_t base)
+// a mixed list is decoded piece by piece.  false: a device-side step failed (the stage, a staging allocation, a copy, the front end, the decoder, a stream wait);
+// an item that is dropped -- a soft buffer with fewer rows than code blocks, a foreign segmentation -- or does not decode is not one.
+static bool tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const phyhip::sch::GroupFrontEnd* group, uint32_t base)
 {
   TraceRange trace_("decode_tb_cb (staged)");
   using phyhip::sch::TbItem;
@@ -514,7 +515,7 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
   TbStage& s = tb_stage();
   if (!s.ready()) {
     fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: %s (there is no CPU fallback)\n", get_error());
-    return;
+    return false;
   }
   auto*        q0   = static_cast<srsran_hip_sch_head_t*>(it[0].q);
   const bool   llr8 = q0->llr_is_8bit;
@@ -578,11 +579,11 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
   }
   const size_t total = off;
   if (slots == 0) {
-    return;
+    return true;
   }
   if (!s.grow(total)) {
     fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: staging allocation failed\n");
-    return;
+    return false;
   }
   std::vector<srsran_hip_tb_t>        tbs;
   std::vector<srsran_hip_tb_result_t> res;
@@ -635,7 +636,7 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
       if (hipMemcpyAsync(s.dev + o_soft + p.first * row, s.pin + o_soft + p.first * row, (p.last - p.first) * row + p.span[p.last] * es,
                          hipMemcpyHostToDevice, s.st) != hipSuccess) {
         (void)hipStreamSynchronize(s.st);
-        return;
+        return false;
       }
     } else {
       rv |= SRSRAN_HIP_TB_NEW_DATA; // every row is still zero: the de-matcher writes the rows instead of accumulating into them
@@ -653,11 +654,11 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
     who.push_back(t);
   }
   if (tbs.empty()) {
-    return;
+    return true;
   }
   if (any_data_up && hipMemcpyAsync(s.dev + o_data0, s.pin + o_data0, total - o_data0, hipMemcpyHostToDevice, s.st) != hipSuccess) {
     (void)hipStreamSynchronize(s.st);
-    return;
+    return false;
   }
   if (dev_e && group) {
     std::vector<uint32_t> idx;
@@ -669,14 +670,14 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
     if (!(*group)(s.st, idx.data(), de.data(), (uint32_t)idx.size())) {
       (void)hipStreamSynchronize(s.st);
       fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: %s\n", get_error());
-      return;
+      return false;
     }
   } else if (dev_e) {
     for (uint32_t t : who) {
       if (!(*it[t].front)(s.st, s.dev + pl[t].o_e)) {
         (void)hipStreamSynchronize(s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
         fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: %s\n", get_error());
-        return;
+        return false;
       }
     }
   }
@@ -687,7 +688,7 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
   if (rc != SRSRAN_SUCCESS) {
     (void)hipStreamSynchronize(s.st);
     fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: %s\n", get_error());
-    return;
+    return false;
   }
   // still undecoded: their rows are the HARQ state the next transmission combines into
   bool second = false;
@@ -706,14 +707,14 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
                          hipMemcpyDeviceToHost, s.st) != hipSuccess) {
         (void)hipStreamSynchronize(s.st);
         fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: download of the soft buffer rows failed\n");
-        return;
+        return false;
       }
       second = true;
     }
   }
   if (second && hipStreamSynchronize(s.st) != hipSuccess) {
     fprintf(stderr, "[srsran_phy_hip] decode_tb_cb: download of the soft buffer rows failed\n");
-    return;
+    return false;
   }
   // host side effects of sch.c:424-486
   for (size_t k = 0; k < who.size(); k++) {
@@ -749,10 +750,12 @@ static void tbs_staged_homogeneous(phyhip::sch::TbItem* it, uint32_t n, const ph
     static_cast<srsran_hip_sch_head_t*>(x.q)->avg_iterations = res[k].avg_iterations;
     x.ok = all_ok;
   }
+  return true;
 }
 
-void phyhip::sch::decode_tbs_staged(TbItem* it, uint32_t n, const GroupFrontEnd* group)
+bool phyhip::sch::decode_tbs_staged(TbItem* it, uint32_t n, const GroupFrontEnd* group)
 {
+  bool device_ok = true;
   // validate, then cut the list into runs of blocks that can share a launch
   for (uint32_t t = 0; t < n; t++) {
     TbItem& x = it[t];
@@ -780,9 +783,10 @@ void phyhip::sch::decode_tbs_staged(TbItem* it, uint32_t n, const GroupFrontEnd*
       }
       b++;
     }
-    tbs_staged_homogeneous(it + a, b - a, group, a);
+    device_ok = tbs_staged_homogeneous(it + a, b - a, group, a) && device_ok;
     a = b;
   }
+  return device_ok;
 }
 
 bool phyhip::sch::decode_tb_staged(void* qv, srsran_softbuffer_rx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits,

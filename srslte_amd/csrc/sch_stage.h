@@ -29,7 +29,8 @@ struct TbItem {
 using GroupFrontEnd = std::function<bool(hipStream_t stream, const uint32_t* which, void* const* d_e_bits, uint32_t n)>;
 
 hipStream_t stage_stream();
-void decode_tbs_staged(TbItem* items, uint32_t n, const GroupFrontEnd* group = nullptr);
+// false: a device-side step failed (not: an item was dropped or did not decode -- that is its `ok`)
+bool decode_tbs_staged(TbItem* items, uint32_t n, const GroupFrontEnd* group = nullptr);
 bool decode_tb_staged(void* q, srsran_softbuffer_rx_t* softbuffer, srsran_cbsegm_t* cb_segm, uint32_t Qm, uint32_t rv, uint32_t nof_e_bits, const void* e_bits,
                       const FrontEnd* front, uint8_t* data);
 

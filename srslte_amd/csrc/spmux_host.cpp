@@ -232,8 +232,8 @@ extern "C" int srsran_hip_precoding_mimo(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRS
 
 // ------------------------------------------------------------------------------------------------ PDSCH grant, receive
 
-// weight: the _csi forms (cfg->csi_enable): the front end files each layer's channel-state values in device scratch, ONE launch behind it weights the soft
-// bits of both codewords (chan_internal.h), the _dbg downloads come behind that.  Two-layer zero-forcing spatial multiplexing: the reference's equaliser
+// weight: the _csi forms (cfg->csi_enable): the front end files each layer's channel-state values in the rows the frame (chan_internal.h) weights both
+// codewords with in one launch.  Two-layer zero-forcing spatial multiplexing: the reference's equaliser
 // writes q->csi[0] only (precoding.c:1330-1331) and weights codeword 1 with whatever an earlier call left in q->csi[1]; here that row is 1.0, as row 0 is.
 static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                              srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
@@ -279,67 +279,23 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
   }
-  ChanStage* sp = stage_for(who);
-  if (!sp) {
-    return SRSRAN_ERROR;
-  }
-  ChanStage& s = *sp;
-  // staging image: 2 symbol planes, then 2 x 2 estimate planes, each 256-byte aligned (an odd grant's last pair is read whole: the padding is there);
-  // behind them room for what _dbg hands back: the layers' symbols, then each codeword's soft bits
+  // staged: 2 symbol planes, then 2 x 2 estimate planes; codeword k is layer k
   const bool   llr8 = g->tb[0].llr_is_8bit != 0;
-  const size_t nd = (size_t)nof_re * sizeof(cf_t), nb = al256(nd);
-  size_t       ne[2] = {0, 0}, o_e[2] = {0, 0};
-  const size_t o_d = 6 * nb;
-  size_t       end = o_d + 2 * nb;
+  const size_t nd   = (size_t)nof_re * sizeof(cf_t);
+  PlaneGroup   in[3] = {{symbols, 2, nd, true, false}, {ce[0], 2, nd, true, false}, {ce[1], 2, nd, true, false}};
+  RxGrant      gr = {who, in, 3, nullptr, {}, ntb, ntb, false, weight};
   for (uint32_t k = 0; k < ntb; k++) {
-    ne[k]  = (size_t)nof_re * qm_of(g->tb[k].mod) * (llr8 ? 1 : 2);
-    o_e[k] = end;
-    end += al256(ne[k]);
+    gr.cw[k] = {&g->tb[k], qm_of(g->tb[k].mod), softbuffers[k], data[k], &res[k], d_out ? d_out[k] : nullptr, e_out ? e_out[k] : nullptr, csi_out ? csi_out[k] : nullptr};
   }
-  const bool   want_d = d_out && (d_out[0] || (ntb == 2 && d_out[1]));
-  const size_t nc = weight ? csi_plane(nof_re) : 0, o_c = end, o_dc = want_d ? 2 * nb : 0; // the CSI rows: what _dbg hands back, device scratch
-  if (!s.grow(o_c + ntb * nc, o_dc + ntb * nc)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
-    return SRSRAN_ERROR;
-  }
-  const cf_t *yp[SRSRAN_MAX_PORTS] = {}, *hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
-  for (uint32_t r = 0; r < 2; r++) {
-    yp[r] = reinterpret_cast<cf_t*>(s.pin + (size_t)r * nb);
-    memcpy(s.pin + (size_t)r * nb, symbols[r], nd);
-    for (uint32_t k = 0; k < 2; k++) {
-      uint8_t* at = s.pin + (2 + (size_t)k * 2 + r) * nb;
-      hp[k][r]    = reinterpret_cast<cf_t*>(at);
-      memcpy(at, ce[k][r], nd);
-    }
-  }
-  // the enabled codewords as items of one decoding pass
-  srsran_cbsegm_t       seg[2];
-  srsran_hip_sch_head_t head[2];
-  sch::TbItem           items[2];
-  uint32_t              cw_of[2] = {0, 0}, n_items = 0;
-  const sch::FrontEnd   marks_device_bits = [](hipStream_t, void*) { return false; }; // (never called: the group front end below serves both codewords)
-  for (uint32_t k = 0; k < ntb; k++) {
-    if (!softbuffers[k]) {
-      continue;
-    }
-    if (!segment(&seg[k], g->tb[k].tbs)) {
-      return SRSRAN_ERROR;
-    }
-    head[k]          = {g->tb[k].max_nof_iterations, 0.f, llr8};
-    cw_of[n_items]   = k;
-    items[n_items++] = {&head[k], softbuffers[k], &seg[k], qm_of(g->tb[k].mod), g->tb[k].rv, nof_re * qm_of(g->tb[k].mod), nullptr, &marks_device_bits, data[k], false};
-  }
-  float* const             row[2] = {weight ? reinterpret_cast<float*>(s.dev + o_dc) : nullptr, (weight && ntb == 2) ? reinterpret_cast<float*>(s.dev + o_dc + nc) : nullptr};
-  bool                     failed = false, d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false};
-  const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
+  return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
     modem::Params mp;
     if (!modem::params_for(mp, llr8 ? modem::LLR_I8 : modem::LLR_I16)) {
-      failed = true;
       return false;
     }
+    const cf_t*        hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {{in[1].pin[0], in[1].pin[1]}, {in[2].pin[0], in[2].pin[1]}};
     spmux::FrontParams fp = {};
     for (uint32_t r = 0; r < 2; r++) {
-      fp.y[r] = reinterpret_cast<const float4*>(yp[r]);
+      fp.y[r] = reinterpret_cast<const float4*>(in[0].pin[r]);
       for (uint32_t k = 0; k < 2; k++) {
         fp.h[k][r] = reinterpret_cast<const float4*>(hp[k][r]);
       }
@@ -347,12 +303,9 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
     for (uint32_t k = 0; k < ntb; k++) {
       fp.mod[k]  = g->tb[k].mod;
       fp.seed[k] = g->tb[k].seed;
+      fp.out[k]  = d_e[k];
+      fp.csi[k]  = row[k];
     }
-    for (uint32_t j = 0; j < m; j++) {
-      fp.out[cw_of[which[j]]] = d_e[j];
-    }
-    fp.csi[0]  = row[0];
-    fp.csi[1]  = row[1];
     fp.n       = nof_re;
     fp.s       = t.rx;
     fp.x1_bits = mp.x1_bits;
@@ -360,88 +313,18 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
     fp.k       = mp.k;
     if (spmux::launch_front(fp, llr8, st) != hipSuccess) {
       set_error("grant front end: spatial-multiplexing front-end launch failed");
-      failed = true;
       return false;
     }
     // what the reference leaves in q->d: the symbols exist in the front end's registers only, so the per-stage kernel makes them (same arithmetic)
-    if (want_d) {
-      cf_t* xd[SRSRAN_MAX_LAYERS] = {reinterpret_cast<cf_t*>(s.dev.get()), reinterpret_cast<cf_t*>(s.dev.get() + nb)};
-      if (spmux::launch_eq(eq_params(yp, hp, xd, nullptr, nof_re, t.rx), st) != hipSuccess ||
-          hipMemcpyAsync(s.pin + o_d, s.dev, (ntb - 1) * nb + nd, hipMemcpyDeviceToHost, st) != hipSuccess) {
+    if (d_d) {
+      cf_t* xd[SRSRAN_MAX_LAYERS] = {reinterpret_cast<cf_t*>(d_d), reinterpret_cast<cf_t*>(d_d + al256(nd))};
+      if (spmux::launch_eq(eq_params(in[0].pin, hp, xd, nullptr, nof_re, t.rx), st) != hipSuccess) {
         set_error("grant front end: the equalised symbols could not be produced");
-        failed = true;
         return false;
-      }
-      d_made = true;
-    }
-    if (weight) {
-      CsiCodeword cw[2];
-      for (uint32_t j = 0; j < m && j < 2; j++) {
-        cw[j] = {d_e[j], row[cw_of[which[j]]], g->tb[cw_of[which[j]]].mod};
-      }
-      if (!enqueue_csi_weight(st, cw, m, nof_re, llr8)) {
-        failed = true;
-        return false;
-      }
-    }
-    for (uint32_t j = 0; j < m; j++) {
-      const uint32_t k = cw_of[which[j]];
-      if (csi_out && csi_out[k]) {
-        if (hipMemcpyAsync(s.pin + o_c + k * nc, row[k], (size_t)nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
-          set_error("grant front end: copy of the intermediate results failed");
-          failed = true;
-          return false;
-        }
-        c_made[k] = true;
-      }
-      if (e_out && e_out[k]) {
-        if (hipMemcpyAsync(s.pin + o_e[k], d_e[j], ne[k], hipMemcpyDeviceToHost, st) != hipSuccess) {
-          set_error("grant front end: copy of the intermediate results failed");
-          failed = true;
-          return false;
-        }
-        e_made[k] = true;
       }
     }
     return true;
-  };
-  sch::decode_tbs_staged(items, n_items, &group);
-  for (uint32_t i = 0; i < n_items; i++) {
-    const uint32_t k = cw_of[i];
-    res[k].crc_ok               = items[i].ok ? 1 : 0;
-    res[k].avg_iterations_block = head[k].avg_iterations;
-  }
-  // what _dbg was asked for and the front end did not make -- it never ran for a codeword the transport-block stage dropped (a soft buffer with fewer
-  // rows than the codeword has blocks) or whose blocks were all decoded in an earlier round -- is an error, not a silently untouched buffer
-  bool missing = false;
-  for (uint32_t k = 0; k < ntb && !failed; k++) {
-    if (d_out && d_out[k]) {
-      if (d_made) {
-        memcpy(d_out[k], s.pin + o_d + k * nb, nd);
-      } else {
-        missing = true;
-      }
-    }
-    if (e_out && e_out[k] && softbuffers[k]) {
-      if (e_made[k]) {
-        memcpy(e_out[k], s.pin + o_e[k], ne[k]);
-      } else {
-        missing = true;
-      }
-    }
-    if (weight && csi_out && csi_out[k] && softbuffers[k]) {
-      if (c_made[k]) {
-        memcpy(csi_out[k], s.pin + o_c + k * nc, (size_t)nof_re * sizeof(float));
-      } else {
-        missing = true;
-      }
-    }
-  }
-  if (missing) {
-    set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", who);
-    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
-  }
-  return (failed || missing) ? SRSRAN_ERROR : SRSRAN_SUCCESS;
+  });
 }
 
 extern "C" int srsran_hip_pdsch_decode_mimo(const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],

@@ -243,8 +243,7 @@ extern "C" int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, 
 
 // ---- PDSCH codeword with transmit diversity, receive
 
-// weight: the _csi forms (cfg->csi_enable): the front end files the combiner's channel-state values in device scratch, one launch behind it weights the
-// soft bits (chan_internal.h), the _dbg downloads come behind that
+// weight: the _csi forms (cfg->csi_enable): the front end files the combiner's channel-state values in the row the frame (chan_internal.h) weights with
 static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                               srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
 {
@@ -271,48 +270,33 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
     return refuse("srsran_hip_pdsch_decode_txdiv: %u ports, %u receive antennas, %u REs, scaling %g%s is not a transmit-diversity grant", ports, nrx, nof_re, (double)g->scaling,
                   (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2) && !planes ? ", a NULL plane" : "");
   }
-  ChanStage* sp = stage_for("srsran_hip_pdsch_decode_txdiv");
-  if (!sp) {
-    return SRSRAN_ERROR;
-  }
-  ChanStage& s = *sp;
-  // staging image: nof_rx symbol planes, then nof_ports x nof_rx estimate planes, each 256-byte aligned; behind them room for what _dbg hands back
+  // staged: nof_rx symbol planes, then nof_ports x nof_rx estimate planes
   const srsran_hip_grant_tb_t& tb = g->tb;
-  const size_t                 nb = al256((size_t)nof_re * sizeof(cf_t));
-  const size_t                 ne = (size_t)nof_re * qm_of(tb.mod) * (tb.llr_is_8bit ? 1 : 2);
-  const size_t                 o_d = (size_t)nrx * (1 + ports) * nb;
-  const bool                   want_d = d_out != nullptr;
-  const size_t                 nc = weight ? csi_plane(nof_re) : 0, o_c = o_d + nb + al256(ne), o_dc = want_d ? nb : 0; // the CSI row: what _dbg hands back, device scratch
-  if (!s.grow(o_c + nc, o_dc + nc)) {
-    fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode_txdiv: staging allocation failed\n");
-    return SRSRAN_ERROR;
+  const size_t                 nd = (size_t)nof_re * sizeof(cf_t);
+  PlaneGroup                   in[1 + SRSRAN_MAX_PORTS] = {{symbols, nrx, nd, true, false}};
+  for (uint32_t k = 0; k < ports; k++) {
+    in[1 + k] = {ce[k], nrx, nd, true, false};
   }
-  const cf_t *yp[SRSRAN_MAX_PORTS] = {}, *hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
-  for (uint32_t r = 0; r < nrx; r++) {
-    yp[r] = reinterpret_cast<cf_t*>(s.pin + (size_t)r * nb);
-    memcpy(s.pin + (size_t)r * nb, symbols[r], (size_t)nof_re * sizeof(cf_t));
+  RxGrant gr = {"srsran_hip_pdsch_decode_txdiv", in, 1 + ports, nullptr, {{&tb, 2 * qm_of(tb.mod), softbuffer, data, res, d_out, e_out, csi_out}}, 1, 1, false, weight};
+  return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
+    const cf_t* hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
+    cf_t*       xd[SRSRAN_MAX_LAYERS]                  = {};
     for (uint32_t k = 0; k < ports; k++) {
-      uint8_t* at = s.pin + ((size_t)nrx + (size_t)k * nrx + r) * nb;
-      hp[k][r]    = reinterpret_cast<cf_t*>(at);
-      memcpy(at, ce[k][r], (size_t)nof_re * sizeof(cf_t));
+      for (uint32_t r = 0; r < nrx; r++) {
+        hp[k][r] = in[1 + k].pin[r];
+      }
+      xd[k] = d_d ? reinterpret_cast<cf_t*>(d_d) + k : nullptr; // the combined symbols layer-demapped: layer k's symbol i is d[ports i + k]
     }
-  }
-  cf_t*          xd[SRSRAN_MAX_LAYERS] = {};
-  for (uint32_t k = 0; k < ports; k++) { // the combined symbols layer-demapped: layer k's symbol i is d[ports i + k]
-    xd[k] = reinterpret_cast<cf_t*>(s.dev.get()) + k;
-  }
-  const txdiv::EqParams ep  = eq_params(yp, hp, xd, nullptr, ports, nrx, ports, nof_re, g->scaling);
-  float*                row = weight ? reinterpret_cast<float*>(s.dev + o_dc) : nullptr;
-  const sch::FrontEnd   make_e = [&](hipStream_t st, void* d_e) {
-    modem::Params mp;
+    const txdiv::EqParams ep = eq_params(in[0].pin, hp, xd, nullptr, ports, nrx, ports, nof_re, g->scaling);
+    modem::Params         mp;
     if (!modem::params_for(mp, tb.llr_is_8bit ? modem::LLR_I8 : modem::LLR_I16)) {
       return false;
     }
     txdiv::FrontParams fp = {};
     memcpy(fp.y, ep.y, sizeof(fp.y));
     memcpy(fp.h, ep.h, sizeof(fp.h));
-    fp.out     = d_e;
-    fp.csi     = row;
+    fp.out     = d_e[0];
+    fp.csi     = row[0];
     fp.mod     = tb.mod;
     fp.n       = nof_re;
     fp.seed    = tb.seed;
@@ -327,28 +311,12 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
       return false;
     }
     // what the reference leaves in q->d: the symbols exist in the front end's registers only, so the per-stage kernel makes them (same arithmetic)
-    if (want_d && txdiv::launch_eq(ep, st) != hipSuccess) {
+    if (d_d && txdiv::launch_eq(ep, st) != hipSuccess) {
       set_error("grant front end: the combined symbols could not be produced");
       return false;
     }
-    if (!weight) {
-      return true;
-    }
-    const CsiCodeword cw = {d_e, row, tb.mod};
-    if (!enqueue_csi_weight(st, &cw, 1, nof_re, tb.llr_is_8bit != 0)) {
-      return false;
-    }
-    if (csi_out && hipMemcpyAsync(s.pin + o_c, row, (size_t)nof_re * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) {
-      set_error("grant front end: copy of the intermediate results failed");
-      return false;
-    }
     return true;
-  };
-  const int rc = pdsch_decode_codeword(s, tb, 2 * qm_of(tb.mod), make_e, want_d ? s.dev.get() : nullptr, o_d, softbuffer, data, res, d_out, e_out);
-  if (rc == SRSRAN_SUCCESS && weight && csi_out) {
-    memcpy(csi_out, s.pin + o_c, (size_t)nof_re * sizeof(float));
-  }
-  return rc;
+  });
 }
 
 extern "C" int srsran_hip_pdsch_decode_txdiv(const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],

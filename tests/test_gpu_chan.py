@@ -26,24 +26,10 @@ import numpy as np
 import pytest
 
 import oracle_api as O
+from grant_helpers import SB, _rx_softbuffer, _tx_softbuffer
 
 pytestmark = pytest.mark.gpu
-SB = 18600
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _rx_softbuffer(capi, max_cb, dt):
-    rows = [np.zeros(SB, dt) for _ in range(max_cb)]
-    keep = [np.zeros(SB // 8, np.uint8) for _ in range(max_cb)]
-    flags = np.zeros(max_cb, np.bool_)
-    sb = capi.SoftbufferRx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows]), (C.c_void_p * max_cb)(*[k.ctypes.data for k in keep]),
-                           flags.ctypes.data_as(C.POINTER(C.c_bool)), False)
-    return sb, rows, keep, flags
-
-
-def _tx_softbuffer(capi, max_cb):
-    rows = [np.zeros(SB, np.uint8) for _ in range(max_cb)]
-    return capi.SoftbufferTx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows])), rows
 
 
 def _oracle_tx_bits(tbs, Qm, nof_bits, rv, payload_bits):

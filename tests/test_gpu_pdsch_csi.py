@@ -22,9 +22,9 @@ import pytest
 import csi_model as CM
 import oracle_api as O
 import spmux_model as M
+from grant_helpers import SB, _lib, _matrix, _planes, _rx_softbuffer, _tx_softbuffer
 
 pytestmark = pytest.mark.gpu
-SB = 18600
 ITERS = 10
 SCALING = 0.8
 MUX, CDD = M.TXSCHEME_SPATIALMUX, M.TXSCHEME_CDD
@@ -45,37 +45,8 @@ PATHS = {
 }
 
 
-def _lib():
-    import srslte_amd as S
-    from srslte_amd import capi
-
-    return S.lib(), capi
-
-
 def _seed(k):
     return O.pdsch_seed(0x1234, k, 10, 301)
-
-
-def _planes(capi, arrs):
-    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
-
-
-def _matrix(capi, h):
-    return capi.PlaneMatrix(*[capi.PlaneArray(*[h[k][r].ctypes.data for r in range(h.shape[1])]) for k in range(h.shape[0])])
-
-
-def _rx_softbuffer(capi, max_cb, dt):
-    rows = [np.zeros(SB, dt) for _ in range(max_cb)]
-    keep = [np.zeros(SB // 8, np.uint8) for _ in range(max_cb)]
-    flags = np.zeros(max_cb, np.bool_)
-    sb = capi.SoftbufferRx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows]), (C.c_void_p * max_cb)(*[k.ctypes.data for k in keep]),
-                           flags.ctypes.data_as(C.POINTER(C.c_bool)), False)
-    return sb, rows, keep, flags
-
-
-def _tx_softbuffer(capi, max_cb):
-    rows = [np.zeros(SB, np.uint8) for _ in range(max_cb)]
-    return capi.SoftbufferTx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows])), rows
 
 
 def _call(lib, capi, path, weight, dbg, y, h, csi_in, tbm, nof_re, llr8, rv=0, sbs=None, iters=ITERS):

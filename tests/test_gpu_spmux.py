@@ -22,43 +22,14 @@ import pytest
 
 import oracle_api as O
 import spmux_model as M
+from grant_helpers import SB, _lib, _matrix, _planes, _rx_softbuffer, _tx_softbuffer
 
 pytestmark = pytest.mark.gpu
-SB = 18600
 ITERS = 10
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MUX, CDD = M.TXSCHEME_SPATIALMUX, M.TXSCHEME_CDD
 CASE_IDS = ["cdd", "mux2_cb0", "mux2_cb1", "mux2_cb2", "mux1_cb0", "mux1_cb1", "mux1_cb2", "mux1_cb3"]
 SENT = -7.0
-
-
-def _lib():
-    import srslte_amd as S
-    from srslte_amd import capi
-
-    return S.lib(), capi
-
-
-def _planes(capi, arrs):
-    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
-
-
-def _matrix(capi, h):
-    return capi.PlaneMatrix(*[capi.PlaneArray(*[h[k][r].ctypes.data for r in range(2)]) for k in range(2)])
-
-
-def _rx_softbuffer(capi, max_cb, dt):
-    rows = [np.zeros(SB, dt) for _ in range(max_cb)]
-    keep = [np.zeros(SB // 8, np.uint8) for _ in range(max_cb)]
-    flags = np.zeros(max_cb, np.bool_)
-    sb = capi.SoftbufferRx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows]), (C.c_void_p * max_cb)(*[k.ctypes.data for k in keep]),
-                           flags.ctypes.data_as(C.POINTER(C.c_bool)), False)
-    return sb, rows, keep, flags
-
-
-def _tx_softbuffer(capi, max_cb):
-    rows = [np.zeros(SB, np.uint8) for _ in range(max_cb)]
-    return capi.SoftbufferTx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows])), rows
 
 
 def _predecode(lib, capi, y, h, scheme, layers, cb, dec, noise, scaling, want_csi=True):

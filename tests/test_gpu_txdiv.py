@@ -21,41 +21,12 @@ import numpy as np
 import pytest
 
 import oracle_api as O
+from grant_helpers import SB, _lib, _matrix, _planes, _rx_softbuffer, _tx_softbuffer
 
 pytestmark = pytest.mark.gpu
-SB = 18600
 ITERS = 10
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 EPS = 2.0 ** -24
-
-
-def _lib():
-    import srslte_amd as S
-    from srslte_amd import capi
-
-    return S.lib(), capi
-
-
-def _planes(capi, arrs):
-    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
-
-
-def _matrix(capi, h, ports, nrx):
-    return capi.PlaneMatrix(*[capi.PlaneArray(*[h[k][r].ctypes.data for r in range(nrx)]) for k in range(ports)])
-
-
-def _rx_softbuffer(capi, max_cb, dt):
-    rows = [np.zeros(SB, dt) for _ in range(max_cb)]
-    keep = [np.zeros(SB // 8, np.uint8) for _ in range(max_cb)]
-    flags = np.zeros(max_cb, np.bool_)
-    sb = capi.SoftbufferRx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows]), (C.c_void_p * max_cb)(*[k.ctypes.data for k in keep]),
-                           flags.ctypes.data_as(C.POINTER(C.c_bool)), False)
-    return sb, rows, keep, flags
-
-
-def _tx_softbuffer(capi, max_cb):
-    rows = [np.zeros(SB, np.uint8) for _ in range(max_cb)]
-    return capi.SoftbufferTx(max_cb, SB, (C.c_void_p * max_cb)(*[r.ctypes.data for r in rows])), rows
 
 
 def _taps(rng, ports, nrx, n, group):
@@ -70,7 +41,7 @@ def _predecode(lib, capi, y, h, scaling, want_csi=True):
     x = np.full((ports, n // ports + 2), 7, np.complex64)
     csi = np.full(n + 4, 7, np.float32)
     cp = (C.c_void_p * 2)(csi.ctypes.data if want_csi else None, None)
-    assert lib.srsran_predecoding_diversity_multi(_planes(capi, list(y)), _matrix(capi, h, ports, nrx), _planes(capi, list(x)), cp, nrx, ports, n, scaling) == n // ports
+    assert lib.srsran_predecoding_diversity_multi(_planes(capi, list(y)), _matrix(capi, h), _planes(capi, list(x)), cp, nrx, ports, n, scaling) == n // ports
     assert np.all(x[:, n // ports:] == 7) and np.all(csi[n:] == 7) and (want_csi or np.all(csi == 7))
     return np.ascontiguousarray(x[:, :n // ports]), (csi[:n].copy() if want_csi else None)
 
@@ -266,7 +237,7 @@ def _decode_one(lib, capi, case, mod, tbs, nof_re, ports, nrx, llr8, dbg):
     sb, rows, keep, flags = _rx_softbuffer(capi, case["C"], dt)
     data = np.zeros(tbs // 8 + 16, np.uint8)
     res = capi.HipGrantRes(7, 7.0, 7.0)
-    sym, ce = _planes(capi, list(case["y"])), _matrix(capi, case["h"], ports, nrx)
+    sym, ce = _planes(capi, list(case["y"])), _matrix(capi, case["h"])
     if not dbg:
         assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(g), sym, ce, C.byref(sb), O.P(data), C.byref(res)) == 0, capi.last_error()
         return res.crc_ok, res.avg_iterations_block, data, None, None
@@ -314,7 +285,7 @@ def test_grant_that_cannot_decode(hiplib):
         g = capi.HipPdschTxdivRx(capi.HipGrantTb(mod, tbs, rv, nof_re, seed, ITERS, 0, 2), ports, nrx, SCALING, 0)
         data = np.full(tbs // 8 + 16, 0xA5, np.uint8)
         res = capi.HipGrantRes(7, 7.0, 7.0)
-        assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(g), _planes(capi, list(y)), _matrix(capi, h, ports, nrx), C.byref(sb), O.P(data), C.byref(res)) == 0, capi.last_error()
+        assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(g), _planes(capi, list(y)), _matrix(capi, h), C.byref(sb), O.P(data), C.byref(res)) == 0, capi.last_error()
         llr, _ = _per_stage_bits(lib, capi, y, h, mod, seed, 0, SCALING)
         ret, _, avg = O.sch_decode_tb(tbs, 2 * Qm, rv, llr, soft, crc, ITERS)
         assert ret == -1 and not crc.any(), (rv, ret, crc)  # the precondition: every row comes back
@@ -431,7 +402,7 @@ def test_loop_back(hiplib, ports, nrx):
     sbr, rows, keep, flags = _rx_softbuffer(capi, nb, np.int16)
     data = np.zeros(tbs // 8 + 16, np.uint8)
     res = capi.HipGrantRes()
-    assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(gr), _planes(capi, list(y)), _matrix(capi, h, ports, nrx), C.byref(sbr), O.P(data), C.byref(res)) == 0, capi.last_error()
+    assert lib.srsran_hip_pdsch_decode_txdiv(C.byref(gr), _planes(capi, list(y)), _matrix(capi, h), C.byref(sbr), O.P(data), C.byref(res)) == 0, capi.last_error()
     assert res.crc_ok == 1 and np.array_equal(data[:tbs // 8], payload)
     assert res.avg_iterations_block == 1.0
 

@@ -25,37 +25,17 @@ import numpy as np
 
 import oracle_api as O
 import spmux_model as M
+from grant_helpers import _matrix, _planes, _rx_softbuffer, _tx_softbuffer
 from srslte_amd import capi
 
 GRANTS = [("25prb_16qam", 2, 6200, 3600), ("100prb_64qam", 3, 75376, 14400)]
-SB, ITERS, SCALING = 18600, 10, 0.8
+ITERS, SCALING = 10, 0.8
 vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
 
 
 def pct(t, q):
     t = sorted(t)
     return t[min(len(t) - 1, int(len(t) * q))]
-
-
-def planes(arrs):
-    return capi.PlaneArray(*[a.ctypes.data for a in arrs])
-
-
-def matrix(h):
-    return capi.PlaneMatrix(*[planes([h[k][r] for r in range(h.shape[1])]) for k in range(h.shape[0])])
-
-
-def rx_softbuffer(nb):
-    rows = [np.zeros(SB, np.int16) for _ in range(nb)]
-    keep = [np.zeros(SB // 8, np.uint8) for _ in range(nb)]
-    flags = np.zeros(nb, np.bool_)
-    return (capi.SoftbufferRx(nb, SB, (vp * nb)(*[r.ctypes.data for r in rows]), (vp * nb)(*[k.ctypes.data for k in keep]), flags.ctypes.data_as(C.POINTER(C.c_bool)), False),
-            rows, keep, flags)
-
-
-def tx_softbuffer(nb):
-    rows = [np.zeros(SB, np.uint8) for _ in range(nb)]
-    return capi.SoftbufferTx(nb, SB, (vp * nb)(*[r.ctypes.data for r in rows])), rows
 
 
 def load(path):
@@ -108,37 +88,37 @@ def main():
         keep = []
         # one port
         p = np.zeros((1, n), np.complex64)
-        sbt = tx_softbuffer(nb)
+        sbt = _tx_softbuffer(capi, nb)
         assert lib.srsran_hip_pdsch_encode(C.byref(capi.HipPdschTx(tb(0, 0, 1), SCALING)), C.byref(sbt[0]), O.P(pays[0]), O.P(p[0])) == 0
         h1 = np.ascontiguousarray((0.9 + 0.1 * M.cn(rng, (1, 1, n))).astype(np.complex64))
         y1 = through(h1, p)
         g1 = capi.HipPdschRx(tb(0, ITERS, 1), SCALING, 0.0)
-        sb1, d1, r1 = rx_softbuffer(nb), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
+        sb1, d1, r1 = _rx_softbuffer(capi, nb, np.int16), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
         calls["single"] = (lambda: lib.srsran_hip_pdsch_decode(C.byref(g1), O.P(y1[0]), O.P(h1[0][0]), C.byref(sb1[0]), O.P(d1), r1),
                            lambda: lib.srsran_hip_pdsch_decode_csi(C.byref(g1), O.P(y1[0]), O.P(h1[0][0]), None, C.byref(sb1[0]), O.P(d1), r1), [sb1], [d1], r1, 1)
         # transmit diversity, 2 ports, 2 receive antennas (taps constant over a pair)
         p = np.zeros((2, n), np.complex64)
-        sbt = tx_softbuffer(nb)
-        assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(capi.HipPdschTxdivTx(tb(0, 0, 2), 2, SCALING)), C.byref(sbt[0]), O.P(pays[0]), planes(list(p))) == 0
+        sbt = _tx_softbuffer(capi, nb)
+        assert lib.srsran_hip_pdsch_encode_txdiv(C.byref(capi.HipPdschTxdivTx(tb(0, 0, 2), 2, SCALING)), C.byref(sbt[0]), O.P(pays[0]), _planes(capi, list(p))) == 0
         h2 = np.ascontiguousarray(np.repeat(0.9 + 0.1 * M.cn(rng, (2, 2, n // 2)), 2, axis=2).astype(np.complex64))
         y2 = through(h2, p)
         g2 = capi.HipPdschTxdivRx(tb(0, ITERS, 2), 2, 2, SCALING, 0)
-        sb2, d2, r2 = rx_softbuffer(nb), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
-        py2, ph2 = planes(list(y2)), matrix(h2)
+        sb2, d2, r2 = _rx_softbuffer(capi, nb, np.int16), np.zeros(tbs // 8 + 16, np.uint8), (capi.HipGrantRes * 2)()
+        py2, ph2 = _planes(capi, list(y2)), _matrix(capi, h2)
         calls["txdiv"] = (lambda: lib.srsran_hip_pdsch_decode_txdiv(C.byref(g2), py2, ph2, C.byref(sb2[0]), O.P(d2), r2),
                           lambda: lib.srsran_hip_pdsch_decode_txdiv_csi(C.byref(g2), py2, ph2, C.byref(sb2[0]), O.P(d2), r2), [sb2], [d2], r2, 1)
         # spatial multiplexing, two codewords
         p = np.zeros((2, n), np.complex64)
-        sbt2 = [tx_softbuffer(nb) for _ in range(2)]
+        sbt2 = [_tx_softbuffer(capi, nb) for _ in range(2)]
         gt = capi.HipPdschMimoTx((capi.HipGrantTb * 2)(tb(0, 0, 1), tb(1, 0, 1)), 2, 2, capi.TXSCHEME_SPATIALMUX, 1, SCALING)
         assert lib.srsran_hip_pdsch_encode_mimo(C.byref(gt), (C.POINTER(capi.SoftbufferTx) * 2)(*[C.pointer(s[0]) for s in sbt2]), (vp * 2)(*[a.ctypes.data for a in pays]),
-                                                planes(list(p))) == 0
+                                                _planes(capi, list(p))) == 0
         h3 = M.channel(rng, n)
         y3 = through(h3, p)
         g3 = capi.HipPdschMimoRx((capi.HipGrantTb * 2)(tb(0, ITERS, 1), tb(1, ITERS, 1)), 2, 2, capi.TXSCHEME_SPATIALMUX, 1, capi.MIMO_DECODER_MMSE, 2, SCALING, 0.0)
-        sb3 = [rx_softbuffer(nb) for _ in range(2)]
+        sb3 = [_rx_softbuffer(capi, nb, np.int16) for _ in range(2)]
         d3, r3 = [np.zeros(tbs // 8 + 16, np.uint8) for _ in range(2)], (capi.HipGrantRes * 2)()
-        py3, ph3 = planes(list(y3)), matrix(h3)
+        py3, ph3 = _planes(capi, list(y3)), _matrix(capi, h3)
         sbp3, dp3 = (C.POINTER(capi.SoftbufferRx) * 2)(*[C.pointer(s[0]) for s in sb3]), (vp * 2)(*[a.ctypes.data for a in d3])
         calls["mimo"] = (lambda: lib.srsran_hip_pdsch_decode_mimo(C.byref(g3), py3, ph3, sbp3, dp3, r3),
                          lambda: lib.srsran_hip_pdsch_decode_mimo_csi(C.byref(g3), py3, ph3, sbp3, dp3, r3), sb3, d3, r3, 2)

@@ -10,14 +10,17 @@
  *                                                            srsran_dlsch_decode2 (sch.c:579); single port: srsran_predecoding_single in front
  *   srsran_pdsch_encode   lib/src/phy/phch/pdsch.c:1017-1144 (per codeword, :949-1015) srsran_dlsch_encode2 -> srsran_sequence_pdsch_apply_pack ->
  *                                                            srsran_mod_modulate_bytes (-> power scaling, :1119)
- *   srsran_ulsch_encode   lib/src/phy/phch/sch.c:1194-1340   (without UCI) encode_tb -> channel interleaver
+ *   srsran_ulsch_encode   lib/src/phy/phch/sch.c:1194-1340   encode_tb -> [CQI / RI / ACK multiplexing] -> channel interleaver
+ *   srsran_pusch_encode   lib/src/phy/phch/pusch.c:259-354   srsran_ulsch_encode -> srsran_sequence_pusch_apply_pack -> placeholder / repetition fix-up ->
+ *                                                            srsran_mod_modulate_bytes -> srsran_dft_precoding -> pusch_put
  * Through the per-stage handle API a grant costs four host <-> device round trips; here it costs one: symbols and channel estimates go up
  * (the kernels read them from the pinned staging image), the payload and the verdict come down.  Soft-buffer handling (HARQ combining
  * across calls, stored code blocks) is srsran_hip_decode_tb_cb's (phy_sch_abi.h).
  *
  * A PUSCH grant that carries control information (HARQ-ACK, RI, CQI multiplexed into it by TS 36.212 5.2.2.8) is taken by srsran_hip_pusch_decode_uci:
  * the de-multiplexer is part of the demodulator's store, the few soft bits of the control fields come down with the payload, and the caller runs the
- * reference's own small decoders (uci.c) on them.
+ * reference's own small decoders (uci.c) on them.  The UE's transmit side is srsran_hip_pusch_encode: the caller runs the reference's small encoders and
+ * hands over the types of the ACK / RI bits and the coded CQI bits; multiplexer, scrambler, fix-up and modulator are one kernel, the transform follows.
  *
  * A PDSCH codeword of a 2- or 4-port cell sent with transmit diversity (SRSRAN_TXSCHEME_DIVERSITY: TM2, the common channels and the TM3 / TM4 fallback of such a
  * cell) is taken by srsran_hip_pdsch_decode_txdiv / srsran_hip_pdsch_encode_txdiv: SFBC combining over 1 or 2 receive antennas and layer de-mapping sit in
@@ -30,8 +33,8 @@
  * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD on 4 ports (the
  * reference refuses them too) or with other than 2 receive antennas, PMI and condition-number selection (srsran_precoding_pmi_select, srsran_precoding_cn:
  * reductions over a whole subframe's estimates), the PUSCH's CSI weighting (pusch_cfg.h: csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
- * only), 8-bit soft bits on a grant with control information, the UE's transmit side with control information (srsran_ulsch_encode with UCI), decoding the
- * control bits themselves, EVM measurement.
+ * only; in both directions), 8-bit soft bits on a grant with control information, the block codes of the control information themselves (srsran_uci_encode_ack_ri,
+ * srsran_uci_encode_cqi_pusch, srsran_cqi_value_pack and their decoders), EVM measurement.
  *
  * CSI weighting of the PDSCH's soft bits (cfg->csi_enable, which srsue turns on by default; csi_correction, pdsch.c:523-618, between the descrambler and
  * srsran_dlsch_decode2) is taken by the _csi form of each PDSCH receive call: the front end files the equaliser's channel-state values, one more kernel finds
@@ -283,11 +286,55 @@ SRSRAN_API int srsran_hip_pdsch_encode_mimo_multi(uint32_t n, const srsran_hip_p
  * interleaver of 36.212 5.2.2.8 over nof_symb columns.  q_bits: nof_bits = nof_re * Qm bits, byte packed (what pusch.c:322 scrambles next). */
 SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t nof_symb, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, uint8_t* q_bits);
 
+/* ---- PUSCH transmit, with or without control information: all of srsran_pusch_encode (pusch.c:259-354) in one call.  The transport block is coded for
+ * G Qm bits, G = H' - Q_prime_ri - Q_prime_cqi (H' = tb.nof_re); ONE kernel then does srsran_ulsch_encode's multiplexing (sch.c:1194-1337: the CQI code word in
+ * front of the data stream, the channel interleaver around the RI positions, RI and ACK bits at the positions of uci.c:364-416, computed in closed form as on
+ * the receive side), srsran_sequence_pusch_apply_pack, the placeholder / repetition fix-up of pusch.c:315-331 and the modulator; one transform launch over
+ * 12 L_prb points per SC-FDMA symbol follows, and after the call's ONE host wait the precoded rows are copied to their places in sf_symbols (pusch_put,
+ * pusch.c:48-100: every symbol but each slot's reference symbol and, when shortened, the last).  The block codes are NOT built here: the caller runs the
+ * reference's srsran_uci_encode_ack_ri / srsran_uci_encode_cqi_pusch and hands over what they leave -- the .type of every ACK / RI bit (a bit of type 1 is sent
+ * as 1, every other type as 0; after scrambling a placeholder becomes 1 and a repetition at position p > 1 the bit at p - 1, in the order of the reference's
+ * list: RI first) and the coded CQI bits.
+ * Refused before anything is enqueued, with one line on stderr and SRSRAN_ERROR_INVALID_INPUTS: a NULL argument (uci may be NULL: no control information; in
+ * may be NULL when all counts are 0; data may be NULL: a retransmission of what the soft buffer holds), an allocation that is not a PUSCH allocation (as on the
+ * receive side), a modulation outside QPSK .. 64-QAM, Q_prime_ack or Q_prime_ri above 4 * 12 * L_prb, Q_prime_ri + Q_prime_cqi >= H', a NULL array for a
+ * non-zero count, a type byte above 3, a cqi_bits byte above 1, tbs == 0 (CQI only: stays with the caller, as on the receive side).  A device-side failure
+ * returns SRSRAN_ERROR. */
+typedef struct SRSRAN_API {
+  srsran_hip_grant_tb_t tb;  /* nof_re = nof_symb * 12 * L_prb; max_nof_iterations, llr_is_8bit unused */
+  uint32_t cell_nof_prb;     /* width of the grid */
+  uint32_t cp_nsymb;         /* 7 or 6 */
+  uint32_t n_prb_tilde[2];   /* first PRB of the allocation in each slot */
+  uint32_t L_prb;            /* srsran_dft_precoding_valid_prb */
+  uint32_t shortened;        /* last symbol left to SRS */
+} srsran_hip_pusch_tx_t;
+
+/* what the reference's encoders leave, caller's HOST memory; a pointer may be NULL when its count is 0 */
+typedef struct SRSRAN_API {
+  const uint8_t* ack_type; /* Q_prime_ack * Qm entries: ack_ri_bits[Q_prime_ri*Qm + i].type (0, 1, 2 = repetition, 3 = placeholder) */
+  const uint8_t* ri_type;  /* Q_prime_ri  * Qm entries: ack_ri_bits[i].type */
+  const uint8_t* cqi_bits; /* Q_prime_cqi * Qm coded CQI bits, one bit per byte (q->temp_g_bits as srsran_uci_encode_cqi_pusch fills it) */
+} srsran_hip_pusch_uci_in_t;
+
+/* sf_symbols: the caller's subframe grid, 2 cp_nsymb x 12 cell_nof_prb points of HOST memory; only the allocation's REs are written */
+SRSRAN_API int srsran_hip_pusch_encode(const srsran_hip_pusch_tx_t* g, const srsran_hip_pusch_uci_t* uci, const srsran_hip_pusch_uci_in_t* in,
+                                       srsran_softbuffer_tx_t* softbuffer, uint8_t* data, cf_t* sf_symbols);
+/* the same, and what the reference leaves in the PUSCH object (each may be NULL; each costs a device -> host copy): q_out <- the byte-packed bits after
+ * scrambling and the fix-up (q->q, nof_re * Qm / 8 bytes), d_out <- the nof_re constellation points (q->d), z_out <- the nof_re precoded points (q->z) */
+SRSRAN_API int srsran_hip_pusch_encode_dbg(const srsran_hip_pusch_tx_t* g, const srsran_hip_pusch_uci_t* uci, const srsran_hip_pusch_uci_in_t* in,
+                                           srsran_softbuffer_tx_t* softbuffer, uint8_t* data, cf_t* sf_symbols, uint8_t* q_out, cf_t* d_out, cf_t* z_out);
+/* srsran_ulsch_encode alone with control information: q_bits <- the unscrambled interleaved bits, nof_re * Qm bits byte packed, placeholder and repetition
+ * bits written as 0 as the reference leaves them.  nof_symb columns, rows = nof_re / nof_symb (4 rows' worth of ACK / RI symbols at most; ACK or RI needs
+ * nof_symb >= 9).  All counts 0 (or uci == NULL): byte for byte what srsran_hip_ulsch_encode gives.  Refusals as above. */
+SRSRAN_API int srsran_hip_ulsch_encode_uci(const srsran_hip_grant_tb_t* tb, uint32_t nof_symb, const srsran_hip_pusch_uci_t* uci,
+                                           const srsran_hip_pusch_uci_in_t* in, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, uint8_t* q_bits);
+
 /* ---- warm start.  The first grant of a process / of a worker thread otherwise pays for loading the kernels' device code, creating the thread's staging
  * context (stream, pinned and device images, decoder / encoder objects, transform plans) and building rate-matching tables: 20-28 ms where a warm
  * call takes 0.1-0.4 ms.  srsran_hip_warmup(n) builds every rate-matching table and prepares n staging contexts by running real grants (the
  * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits, one CSI-weighted grant of each width;
- * one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way) on short-lived threads; a worker
+ * one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PUSCH transmit grant with control information) on
+ * short-lived threads; a worker
  * thread adopts a prepared context at its first call.  srsran_rm_turbo_gentables() -- which srsran_sch_init calls (sch.c:166) -- does the same
  * for one worker, so an application that does nothing gets a warm first subframe on one thread; srsenb's pool of nof_phy_threads workers
  * wants srsran_hip_warmup(nof_phy_threads) once after its objects are created.  Idempotent; returns SRSRAN_ERROR without a device. */

@@ -154,6 +154,15 @@ class HipPuschUciOut(C.Structure):  # srsran_hip_pusch_uci_out_t
                 ("cqi_llr", C.c_void_p)]
 
 
+class HipPuschTx(C.Structure):  # srsran_hip_pusch_tx_t
+    _fields_ = [("tb", HipGrantTb), ("cell_nof_prb", C.c_uint32), ("cp_nsymb", C.c_uint32), ("n_prb_tilde", C.c_uint32 * 2), ("L_prb", C.c_uint32),
+                ("shortened", C.c_uint32)]
+
+
+class HipPuschUciIn(C.Structure):  # srsran_hip_pusch_uci_in_t
+    _fields_ = [("ack_type", C.c_void_p), ("ri_type", C.c_void_p), ("cqi_bits", C.c_void_p)]
+
+
 class HipPdschRx(C.Structure):
     _fields_ = [("tb", HipGrantTb), ("scaling", C.c_float), ("noise_estimate", C.c_float)]
 
@@ -588,6 +597,10 @@ def lib():
             "srsran_hip_pdsch_encode_mimo_multi": (i32, [u32, C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx) * 2), C.POINTER(vp * 2),
                                                          C.POINTER(C.POINTER(vp))]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
+            "srsran_hip_pusch_encode": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp]),
+            "srsran_hip_pusch_encode_dbg": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp, vp, vp,
+                                                  vp]),
+            "srsran_hip_ulsch_encode_uci": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_modulate_bytes": (i32, [u32, vp, vp, u32, u32, u32, C.c_float]),
             "srsran_hip_sequence_nr_seed": (u32, [C.c_uint16, u32, u32]),
             "srsran_hip_nr_cw_decode": (i32, [C.POINTER(HipNrCwRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult)]),

@@ -30,24 +30,29 @@ struct ChanStage {
   HostImage pin;
   DeviceBuf dev;
   std::map<uint32_t, srsran_hip_dft_batch_t*> idft; // L_prb -> backward, normalised plan of 12 L_prb points (srsran_dft_precoding_init_rx)
+  std::map<uint32_t, srsran_hip_dft_batch_t*> fdft; // L_prb -> forward, normalised plan (srsran_dft_precoding_init_tx): PUSCH transmit
   ~ChanStage()
   {
     for (auto& kv : idft) {
       srsran_hip_dft_batch_free(kv.second);
     }
+    for (auto& kv : fdft) {
+      srsran_hip_dft_batch_free(kv.second);
+    }
   }
   bool grow(size_t need_pin, size_t need_dev) { return pin.grow(need_pin, need_pin / 2) && dev.grow(need_dev, need_dev / 2); }
-  srsran_hip_dft_batch_t* plan(uint32_t L_prb)
+  srsran_hip_dft_batch_t* plan(uint32_t L_prb, bool tx = false)
   {
-    auto it = idft.find(L_prb);
-    if (it != idft.end()) {
+    auto& plans = tx ? fdft : idft;
+    auto  it    = plans.find(L_prb);
+    if (it != plans.end()) {
       return it->second;
     }
     srsran_hip_dft_batch_t* h = nullptr;
-    if (srsran_hip_dft_batch_create(&h, (int)(12 * L_prb), SRSRAN_DFT_BACKWARD, false, false, true) != SRSRAN_SUCCESS) {
+    if (srsran_hip_dft_batch_create(&h, (int)(12 * L_prb), tx ? SRSRAN_DFT_FORWARD : SRSRAN_DFT_BACKWARD, false, false, true) != SRSRAN_SUCCESS) {
       return nullptr;
     }
-    idft[L_prb] = h;
+    plans[L_prb] = h;
     return h;
   }
 };

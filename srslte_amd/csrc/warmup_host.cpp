@@ -6,7 +6,7 @@
 // allocation, srsran_tdec_init, srsran_rm_turbo_gentables) -- so does the library: srsran_rm_turbo_gentables() builds every rate-matching table in
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
 // grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one CSI-weighted grant of each
-// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way -- on a short-lived
+// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PUSCH transmit grant with control information -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
 #include "turbo_device.h"
@@ -90,6 +90,16 @@ void warm_one_worker()
         (void)srsran_hip_ulsch_encode(&tb, nsymb, &sb.tx, data.data(), qbits.data());
       }
     }
+  }
+  // one PUSCH transmit grant with control information (the one-block 16-QAM grant, 12 PRB: ACK, RI and CQI symbols), so the device code of
+  // pusch_tx_kernels.hip and the forward transform plan are there before a UE worker's first uplink subframe
+  {
+    const uint32_t                  L = 12, nof_re = nsymb * 12 * L, Qm = 4;
+    const srsran_hip_pusch_tx_t     tx  = {{SRSRAN_MOD_16QAM, 6144 - 24, 0, nof_re, 12345u, 1, 0, 1}, nof_prb, 7, {0, 0}, L, 0};
+    const srsran_hip_pusch_uci_t    uci = {24, 5, 60};
+    const std::vector<uint8_t>      types((24 + 5) * Qm, 1), cqi(60 * Qm, 1);
+    const srsran_hip_pusch_uci_in_t in  = {types.data(), types.data() + 24 * Qm, cqi.data()};
+    (void)srsran_hip_pusch_encode(&tx, &uci, &in, &sb.tx, data.data(), grid.data());
   }
   // one 2-port transmit-diversity codeword each way (the one-block 16-QAM grant above: 1728 REs on two layers), so the device code of txdiv_kernels.hip
   // is loaded before the first subframe of a 2-port cell

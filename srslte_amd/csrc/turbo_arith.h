@@ -53,6 +53,8 @@ struct Ar16 {
   static __device__ __forceinline__ s2 clean(s2 v) { return v; }
   static __device__ __forceinline__ s2 sub(s2 a, s2 b) { return __builtin_elementwise_sub_sat(a, b); }
   static __device__ __forceinline__ bool norm_at(uint32_t k) { return (k & 1) == 0 && k != 0; }
+  // norm_at(k) for any k > 0 with k = j modulo 8: the schedule inside a block that is not the first, as a compile-time constant
+  static constexpr bool norm_in_block(int j) { return (j & 1) == 0; }
   // turbodecoder_win.h:480-498 (normalize_period 2; caller checks the step index)
   static __device__ __forceinline__ void normalize(s2 (&o)[8])
   {
@@ -91,6 +93,7 @@ struct Ar8 {
   static __device__ __forceinline__ s2 clean(s2 v) { return from_u(to_u(v) & 0xff00ff00u); }
   static __device__ __forceinline__ s2 sub(s2 a, s2 b) { return fix_hi(__builtin_elementwise_sub_sat(a, b)); }
   static __device__ __forceinline__ bool norm_at(uint32_t k) { return k != 0; }
+  static constexpr bool norm_in_block(int) { return true; } // (see Ar16)
   static __device__ __forceinline__ void normalize(s2 (&o)[8])
   {
     s2 m = vmax(o[0], o[1]);

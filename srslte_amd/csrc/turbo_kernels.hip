@@ -610,11 +610,56 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           }
         }
       };
-      for (int b = ((int)nblk - 1) | 3; b >= 0; b -= 4) {
-        block(b, nx3, cur);
-        block(b - 1, nx2, nx3);
-        block(b - 2, nxt, nx2);
-        block(b - 3, cur, nxt);
+      // The whole-block body: a block of a group of four whose top block b (b = 3 mod 4) has 7 <= b <= nblk - 5.  Every block of such a group
+      // is a whole one fetched from HBM (b <= top), its request is a real block (b - 6 >= 1), none of its steps is step 0, so the schedule of
+      // the normalisation is the step's position in the block; the check-point is stored by the even blocks, second and fourth of the group.
+      auto whole_block = [&](auto ck_store, int b, const Ops& c, Ops& tgt) {
+        s2 xs[8], ys[8], ap[8];
+        taken(c);
+        prep(c, xs, ys, ap);
+        issue(b - 3, tgt);
+#pragma unroll
+        for (int j = 7; j >= 0; j--) {
+          beta_step<AR>(o, xs[j], ys[j]);
+          if constexpr (ck_store.value) {
+            if (j == 0) {
+              uint32_t ck[8];
+#pragma unroll
+              for (int i = 0; i < 8; i++) {
+                ck[i] = to_u(o[i]);
+              }
+              store_block_v<AR::kIs8>(CK, ((uint32_t)b & m_own()) * 64 + lane, ck);
+            }
+          }
+          if (AR::norm_in_block(j)) {
+            AR::normalize(o);
+          }
+        }
+      };
+      constexpr std::integral_constant<bool, true>  kStore{};
+      constexpr std::integral_constant<bool, false> kNoStore{};
+      // Two bodies, each emitted once, never two arms of one loop trip (at a merge the compiler counts the arm with the fewest loads in
+      // flight): the general loop runs the groups above the whole-block range in the first trip of the outer loop and the group below it
+      // (blocks 3 ... 0) in the second; the whole-block loop has groups only in the first.  Every way into either loop carries what its back
+      // edge carries: the requests of the next three blocks.
+      int b = ((int)nblk - 1) | 3;
+#pragma nounroll
+      for (int trip = 0; trip < 2; trip++) {
+        const int above = trip == 0 && nblk > 4 ? (int)nblk - 5 : -1; // (never below -1: the general loop ends with block 0, as the one loop it replaces did)
+#pragma nounroll
+        for (; b > above; b -= 4) {
+          block(b, nx3, cur);
+          block(b - 1, nx2, nx3);
+          block(b - 2, nxt, nx2);
+          block(b - 3, cur, nxt);
+        }
+#pragma nounroll
+        for (; b >= 7; b -= 4) {
+          whole_block(kNoStore, b, nx3, cur);
+          whole_block(kStore, b - 1, nx2, nx3);
+          whole_block(kNoStore, b - 2, nxt, nx2);
+          whole_block(kStore, b - 3, cur, nxt);
+        }
       }
     } else {
       // (8-step check-points: the 8-bit and the early-stop kernels.  With four rotating sets the int16 early-stop kernels spill -- their forward
@@ -680,6 +725,12 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
     const bool sign_rows = bit_rows && n + 1 == p.n_end;
 
+    // The forward main pass has two bodies.  The general one takes any block: ragged, the last one, one that is not there.  The whole-block one (16-step
+    // form only) takes a whole block that is neither the first nor the last of its sub-block and whose walks do not start from the sub-block's end: its
+    // length is 8, the block above it exists, no step is step 0 and no stored value is the one at the sub-block's end, so the schedule of the normalisation is
+    // the step's position in the block and a block's steps are straight-line code.
+    constexpr std::integral_constant<bool, true>  kWhole{};
+    constexpr std::integral_constant<bool, false> kGeneral{};
     // one block of the main pass, in two parts (between them the 16-step form requests its next check-point).
     // rederive: beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the value at the block's upper boundary into
     // this lane's private LDS slots (registers are needed for the prefetched operands)
@@ -693,12 +744,12 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       Bl[top][0][lane] = make_uint4(ckv[0], ckv[1], ckv[2], ckv[3]);
       Bl[top][1][lane] = make_uint4(ckv[4], ckv[5], ckv[6], ckv[7]);
     };
-    auto rederive_rest = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], s2(&st)[8]) {
+    auto rederive_rest = [&](auto whole, uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], s2(&st)[8]) {
 #pragma unroll
       for (int j = 6; j >= 0; j--) {
-        if (j <= len - 2) {
+        if (whole.value || j <= len - 2) {
           uint32_t idx = b * 8 + j + 2; // index of the stored value we start from
-          if (idx != long_sb && AR::norm_at(idx)) {
+          if (whole.value ? AR::norm_in_block(j + 2) : (idx != long_sb && AR::norm_at(idx))) {
             AR::normalize(st);
           }
           beta_step<AR>(st, xs[j + 1], ys[j + 1]);
@@ -708,19 +759,19 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
     };
     // emit: the forward steps, their outputs, the exchange
-    auto emit = [&](uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const s2(&ap)[8], const uint32_t(&tr)[8], auto&& ck_taken) {
+    auto emit = [&](auto whole, uint32_t b, int len, const s2(&xs)[8], const s2(&ys)[8], const s2(&ap)[8], const uint32_t(&tr)[8], auto&& ck_taken) {
       uint32_t outv[8], rawv[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         outv[j] = 0;
         rawv[j] = 0;
-        if (j < len) {
+        if (whole.value || j < len) {
           const uint4 b0 = Bl[j][0][lane], b1 = Bl[j][1][lane];
           const s2    B[8] = {from_u(b0.x), from_u(b0.y), from_u(b0.z), from_u(b0.w),
                               from_u(b1.x), from_u(b1.y), from_u(b1.z), from_u(b1.w)};
           s2       llr = alpha_step<AR, true>(o, B, xs[j], ys[j]);
           uint32_t k   = b * 8 + j;
-          if (AR::norm_at(k)) {
+          if (whole.value ? AR::norm_in_block(j) : AR::norm_at(k)) {
             AR::normalize(o);
           }
           s2 proc = llr;
@@ -746,10 +797,23 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       }
       // the hot store phase: per step the exchange and one row store, nothing else
       if (!sign_rows) {
+        if constexpr (whole.value) {
+          // all of the block's exchanges are requested before the first one is waited for: one LDS round trip per block, not one per step
+          uint32_t xv[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          if (j < len) {
-            store_xch_row<AR::kIs8>(dst, tr[j], m_own(), lane, permute_pair(outv[j], tr[j], xbase));
+          for (int j = 0; j < 8; j++) {
+            xv[j] = permute_pair(outv[j], tr[j], xbase);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; j++) {
+            store_xch_row<AR::kIs8>(dst, tr[j], m_own(), lane, xv[j]);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; j++) {
+            if (j < len) {
+              store_xch_row<AR::kIs8>(dst, tr[j], m_own(), lane, permute_pair(outv[j], tr[j], xbase));
+            }
           }
         }
       }
@@ -757,7 +821,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       if (last) {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-          if (j < len) {
+          if (whole.value || j < len) {
             if (sign_rows) {
               // the values tdec_decision_byte reads (below), reduced to "> 0": one 16-byte row per step, stored by one lane
               const s2       v  = from_u(dec1 ? rawv[j] : permute_pair(rawv[j], tr[j], xbase));
@@ -800,8 +864,8 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         block_values<AR::kIs8>(ck, ckv);
         s2 st[8];
         rederive_start(len, ckv, st);
-        rederive_rest(b, len, xs, ys, st);
-        emit(b, len, xs, ys, ap, tr, [] {});
+        rederive_rest(kGeneral, b, len, xs, ys, st);
+        emit(kGeneral, b, len, xs, ys, ap, tr, [] {});
         cur = nxt;
         nxt = nx2;
 #pragma unroll
@@ -838,15 +902,17 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       // b may lie behind the last block (the loop below goes over four blocks whatever the count): such a block has no steps, len = 0.  It makes
       // its requests and goes the same way as every other: an arm of its own, or one around the others' work, is a way on which the compiler
       // sees the table entries and the check-point still open, and its wait for them, placed behind the row stores, reaches into the request.
-      auto block = [&](auto even, uint32_t b, const Ops& c, const Ops& held, Ops& tgt) {
+      // (whole: the block is one of a whole-block group.  What stays clamped there: the block that is requested and the check-point of the next pair may
+      // lie behind the last block, b + 6 against b + 5 <= nblk.)
+      auto block = [&](auto whole, auto even, uint32_t b, const Ops& c, const Ops& held, Ops& tgt) {
         const int rem = (int)long_sb - (int)b * 8;
-        const int len = rem < 0 ? 0 : rem < 8 ? rem : 8;
+        const int len = whole.value ? 8 : rem < 0 ? 0 : rem < 8 ? rem : 8;
         s2         xs[8], ys[8], ap[8], st[8];
         uint32_t   ckv[8];
         auto       ck_taken = [&] { asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7])); };
         ck_taken();
         block_values<AR::kIs8>(ck, ckv);
-        load_lut(lut, (b < nblk ? b : nblk - 1) * LPC + pl, tr);
+        load_lut(lut, (whole.value || b < nblk ? b : nblk - 1) * LPC + pl, tr);
         taken(c);
         if constexpr (even.value) {
           taken(held); // (also where there is no block b + 1: the set was requested all the same)
@@ -861,23 +927,23 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         }
         {
           if constexpr (even.value) {
-            const bool paired = b + 1 < nblk;
+            const bool paired = whole.value || b + 1 < nblk;
             s2        x1[8], y1[8], a1[8];
             if (paired) {
               prep(held, x1, y1, a1);
             }
             prep(c, xs, ys, ap);
             if (paired) {
-              const int len1 = (long_sb - (b + 1) * 8) < 8 ? (int)(long_sb - (b + 1) * 8) : 8;
+              const int len1 = whole.value ? 8 : (long_sb - (b + 1) * 8) < 8 ? (int)(long_sb - (b + 1) * 8) : 8;
 #pragma unroll
               for (int i = 0; i < 8; i++) {
                 st[i] = from_u(ckv[i]);
               }
 #pragma unroll
               for (int j = 7; j >= 0; j--) {
-                if (j < len1) {
+                if (whole.value || j < len1) {
                   uint32_t idx = (b + 1) * 8 + j + 1; // index of the value we start from
-                  if (idx != long_sb && AR::norm_at(idx)) {
+                  if (whole.value ? AR::norm_in_block(j + 1) : (idx != long_sb && AR::norm_at(idx))) {
                     AR::normalize(st);
                   }
                   beta_step<AR>(st, x1[j], y1[j]);
@@ -890,19 +956,36 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
             }
             rederive_start(len, ckv, st);
           }
-          rederive_rest(b, len, xs, ys, st);
-          emit(b, len, xs, ys, ap, tr, ck_taken);
+          rederive_rest(whole, b, len, xs, ys, st);
+          emit(whole, b, len, xs, ys, ap, tr, ck_taken);
         }
       };
       constexpr std::integral_constant<bool, true>  kEven{};
       constexpr std::integral_constant<bool, false> kOdd{};
       // (one way out, at the bottom: a `break` behind each block is routed through the loop's latch, and the waits at the loop's top are
       // then counted as if a block's own request could still be open there; a block skipped as a whole is an arm without requests)
-      for (uint32_t b = 0; b < nblk; b += 4) {
-        block(kEven, b, q0, q1, q3);
-        block(kOdd, b + 1, q1, q2, q0);
-        block(kEven, b + 2, q2, q3, q1);
-        block(kOdd, b + 3, q3, q0, q2);
+      // A group of four starting at b takes the whole-block body when 4 <= b and b + 5 <= nblk: blocks b ... b + 3 are whole (b + 3 <= nblk - 2), none is the
+      // last one, and the pairs' check-points are those of boundaries b + 2 and b + 4 <= nblk - 1, not the sub-block's end.  As in the backward pass the two bodies are
+      // two loops, each emitted once: the general loop runs blocks 0 ... 3 in the first trip of the outer loop and the groups behind the whole-block range in the
+      // second, the whole-block loop has groups only in the first; every way into either loop carries one request in flight, as its back edge does.
+      uint32_t b = 0;
+#pragma nounroll
+      for (int trip = 0; trip < 2; trip++) {
+        const uint32_t gend = trip == 0 ? 4u : nblk;
+#pragma nounroll
+        for (; b < gend; b += 4) {
+          block(kGeneral, kEven, b, q0, q1, q3);
+          block(kGeneral, kOdd, b + 1, q1, q2, q0);
+          block(kGeneral, kEven, b + 2, q2, q3, q1);
+          block(kGeneral, kOdd, b + 3, q3, q0, q2);
+        }
+#pragma nounroll
+        for (; b + 5 <= nblk; b += 4) {
+          block(kWhole, kEven, b, q0, q1, q3);
+          block(kWhole, kOdd, b + 1, q1, q2, q0);
+          block(kWhole, kEven, b + 2, q2, q3, q1);
+          block(kWhole, kOdd, b + 3, q3, q0, q2);
+        }
       }
     }
     __syncthreads();

@@ -30,7 +30,11 @@
  * received on 2 antennas, is taken by srsran_hip_pdsch_decode_mimo / srsran_hip_pdsch_encode_mimo: the precoder applied to the estimates, the 2x2 ZF / MMSE solve
  * (or maximum-ratio combining), the demodulator and the descrambler of BOTH codewords are one kernel, and both transport blocks decode behind it in one pass.
  *
- * What is NOT taken here and stays with the caller: resource (de)mapping other than the PUSCH's rectangular one, spatial multiplexing and CDD on 4 ports (the
+ * The PDSCH's resource DE-mapping (srsran_pdsch_get: the gather around reference signals, PSS / SSS and PBCH) is taken by the _sf form of each PDSCH receive
+ * call, which starts at srsran_pdsch_decode's own signature: subframe grids and the channel estimator's grids in, one more launch, still one host wait.
+ *
+ * What is NOT taken here and stays with the caller: the PDSCH's resource mapping on transmit (srsran_pdsch_put: the caller's grid holds other channels' REs),
+ * spatial multiplexing and CDD on 4 ports (the
  * reference refuses them too) or with other than 2 receive antennas, PMI and condition-number selection (srsran_precoding_pmi_select, srsran_precoding_cn:
  * reductions over a whole subframe's estimates), the PUSCH's CSI weighting (pusch_cfg.h: csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
  * only; in both directions), 8-bit soft bits on a grant with control information, the block codes of the control information themselves (srsran_uci_encode_ack_ri,
@@ -230,7 +234,7 @@ SRSRAN_API int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_
  * range, an odd nof_re with CDD, a decoder that is neither ZF nor MMSE, scaling 0 or not finite, a negative or non-finite noise_estimate, two codewords
  * whose nof_re, llr_is_8bit or max_nof_iterations differ, every codeword skipped, and what every grant call refuses per codeword (modulation, tbs, rv,
  * length).  A device-side failure returns SRSRAN_ERROR.
- * Not taken: PMI and condition-number selection, EVM, resource (de)mapping, 4 ports. */
+ * Not taken: PMI and condition-number selection, EVM, resource mapping on transmit (de-mapping: the _sf form below), 4 ports. */
 typedef struct SRSRAN_API {
   srsran_hip_grant_tb_t tb[2]; /* tb[k]: codeword k; seed with q = k; tb[k].nl is taken as 1; nof_re = REs of the grant, the same in both */
   uint32_t nof_tb;             /* 1 or 2 */
@@ -281,6 +285,60 @@ SRSRAN_API int srsran_hip_pdsch_encode_mimo(const srsran_hip_pdsch_mimo_tx_t* g,
 /* the grants of one TTI in ONE call: one coding launch, one modulation + precoding launch, one host wait; softbuffers[i][k], data[i][k], symbols[i][port] */
 SRSRAN_API int srsran_hip_pdsch_encode_mimo_multi(uint32_t n, const srsran_hip_pdsch_mimo_tx_t* g, srsran_softbuffer_tx_t* const (*softbuffers)[SRSRAN_MAX_CODEWORDS],
                                                   uint8_t* const (*data)[SRSRAN_MAX_CODEWORDS], cf_t* const* const* symbols);
+
+/* ---- PDSCH receive from the subframe grids: RE de-mapping on the device.  The _sf form of each receive call starts where srsran_pdsch_decode does
+ * (pdsch.c:788): it takes the subframe grids (sf_symbols[rx]) and the channel estimator's grids (channel->ce[port][rx]), HOST memory, (nof_symb_slot[0] +
+ * nof_symb_slot[1]) * 12 * cell_nof_prb points each, where its twin takes the nof_re REs srsran_pdsch_get (pdsch.c:246; srsran_pdsch_cp :136-220) extracts
+ * from them.  The host copies the used rows of every grid into the staging image (symbol lstart to the grant's last symbol; whole rows, or the span from the
+ * lowest to the highest allocated PRB), ONE more launch de-maps all nof_rx * (1 + nof_ports) planes into device scratch around the reference signals, PSS / SSS
+ * and PBCH (half PRBs on a cell with an odd PRB count), and the twin's kernels run on those planes unchanged: one launch more than the twin, still one host
+ * wait.  apply_power_allocation (pdsch.c:809) stays with the caller, as for the twins.  The transmit direction (srsran_pdsch_put) is not taken. */
+typedef struct SRSRAN_API {
+  uint32_t cell_nof_prb;     /* 6 .. 110: width of the grids */
+  uint32_t cell_nof_ports;   /* 1, 2 or 4: decides the CRS pattern */
+  uint32_t cell_id;          /* 0 .. 503 */
+  uint32_t cp_nsymb;         /* 7 or 6 */
+  uint32_t frame_type;       /* 0 FDD, 1 TDD */
+  uint32_t sf_idx;           /* sf->tti % 10 */
+  uint32_t lstart;           /* SRSRAN_NOF_CTRL_SYMBOLS(cell, cfi) */
+  uint32_t nof_symb_slot[2]; /* grant->nof_symb_slot */
+  uint32_t csi_enable;       /* cfg->csi_enable */
+  uint8_t  prb_idx[2][110];  /* grant->prb_idx (bool [2][SRSRAN_MAX_PRB]) */
+} srsran_hip_pdsch_sf_t;
+/* host only: the count srsran_pdsch_get would return for this description, or -1 for an invalid one (a field outside the ranges above, nof_symb_slot[s] >
+ * cp_nsymb, lstart >= nof_symb_slot[0], csi_enable above 1, a prb_idx byte above 1, an empty allocation) */
+SRSRAN_API int srsran_hip_pdsch_nof_re(const srsran_hip_pdsch_sf_t* sf);
+/* the stage by itself on HOST buffers: symbols[p] <- the nof_re REs of grids[p], p < n_planes, all planes in ONE launch.  Returns nof_re, or -1 (an invalid
+ * description, a NULL pointer, no device) */
+SRSRAN_API int srsran_hip_pdsch_get(const srsran_hip_pdsch_sf_t* sf, uint32_t n_planes, const cf_t* const* grids, cf_t* const* symbols);
+/* the grant calls.  Arguments of the twin with `sf` behind `g` and grids where the planes went; sf->csi_enable selects what the _csi twin does.  (The one-port
+ * call needs ce: the "already equalised" form has no grid.)  Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS,
+ * *res = {0, 0, NAN} and nothing else written: everything the twin refuses, a NULL sf, what srsran_hip_pdsch_nof_re refuses, csi_enable above 1, a
+ * cell_nof_ports that is not the call's (1; nof_ports; 2), and srsran_hip_pdsch_nof_re(sf) != tb.nof_re (the reference's "expecting %d symbols but got %d",
+ * pdsch.c:834).
+ * _sf_dbg: the outputs of the _csi_dbg twin (csi_out is only written with csi_enable) and the extracted planes, sym_out[rx] <- q->symbols[rx], ce_out[port][rx]
+ * <- q->ce[port][rx], nof_re points each; either array, or any entry of it, may be NULL.  They cost one device -> host copy. */
+SRSRAN_API int srsran_hip_pdsch_decode_sf(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const cf_t* sf_symbols, const cf_t* ce,
+                                          srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res);
+SRSRAN_API int srsran_hip_pdsch_decode_sf_dbg(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const cf_t* sf_symbols, const cf_t* ce,
+                                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                              float* csi_out, cf_t* sym_out, cf_t* ce_out);
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_sf(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                                srsran_hip_grant_res_t* res);
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_sf_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                    cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                                    srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out, cf_t* const sym_out[],
+                                                    cf_t* const (*ce_out)[SRSRAN_MAX_PORTS]);
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_sf(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                               cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                               uint8_t* const data[SRSRAN_MAX_CODEWORDS], srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS]);
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_sf_dbg(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                   cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                                   uint8_t* const data[SRSRAN_MAX_CODEWORDS], srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS],
+                                                   cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
+                                                   float* const csi_out[SRSRAN_MAX_CODEWORDS], cf_t* const sym_out[],
+                                                   cf_t* const (*ce_out)[SRSRAN_MAX_PORTS]);
 
 /* ---- UL-SCH transmit without UCI (srsran_ulsch_encode, sch.c:1194-1340, with no ACK / RI / CQI configured): encode_tb -> channel
  * interleaver of 36.212 5.2.2.8 over nof_symb columns.  q_bits: nof_bits = nof_re * Qm bits, byte packed (what pusch.c:322 scrambles next). */
@@ -333,7 +391,8 @@ SRSRAN_API int srsran_hip_ulsch_encode_uci(const srsran_hip_grant_tb_t* tb, uint
  * context (stream, pinned and device images, decoder / encoder objects, transform plans) and building rate-matching tables: 20-28 ms where a warm
  * call takes 0.1-0.4 ms.  srsran_hip_warmup(n) builds every rate-matching table and prepares n staging contexts by running real grants (the
  * largest of a 100-PRB cell, a one-block and a scalar-decoder one; receive and transmit side; 16- and 8-bit soft bits, one CSI-weighted grant of each width;
- * one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PUSCH transmit grant with control information) on
+ * one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PDSCH grant from the subframe grids, one PUSCH transmit
+ * grant with control information) on
  * short-lived threads; a worker
  * thread adopts a prepared context at its first call.  srsran_rm_turbo_gentables() -- which srsran_sch_init calls (sch.c:166) -- does the same
  * for one worker, so an application that does nothing gets a warm first subframe on one thread; srsenb's pool of nof_phy_threads workers

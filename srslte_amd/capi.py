@@ -189,6 +189,11 @@ class HipPdschMimoTx(C.Structure):  # srsran_hip_pdsch_mimo_tx_t
                 ("scaling", C.c_float)]
 
 
+class HipPdschSf(C.Structure):  # srsran_hip_pdsch_sf_t
+    _fields_ = [(n, C.c_uint32) for n in ("cell_nof_prb", "cell_nof_ports", "cell_id", "cp_nsymb", "frame_type", "sf_idx", "lstart")] + [
+        ("nof_symb_slot", C.c_uint32 * 2), ("csi_enable", C.c_uint32), ("prb_idx", (C.c_uint8 * 110) * 2)]
+
+
 TXSCHEME_SPATIALMUX, TXSCHEME_CDD = 2, 3  # srsran_tx_scheme_t
 MIMO_DECODER_ZF, MIMO_DECODER_MMSE = 0, 1  # srsran_mimo_decoder_t
 SRSRAN_MAX_PORTS = 4
@@ -596,6 +601,20 @@ def lib():
             "srsran_hip_pdsch_encode_mimo": (i32, [C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx)), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_pdsch_encode_mimo_multi": (i32, [u32, C.POINTER(HipPdschMimoTx), C.POINTER(C.POINTER(SoftbufferTx) * 2), C.POINTER(vp * 2),
                                                          C.POINTER(C.POINTER(vp))]),
+            "srsran_hip_pdsch_nof_re": (i32, [C.POINTER(HipPdschSf)]),
+            "srsran_hip_pdsch_get": (i32, [C.POINTER(HipPdschSf), u32, C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_hip_pdsch_decode_sf": (i32, [C.POINTER(HipPdschRx), C.POINTER(HipPdschSf), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_sf_dbg": (i32, [C.POINTER(HipPdschRx), C.POINTER(HipPdschSf), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp,
+                                                     vp, vp, vp]),
+            "srsran_hip_pdsch_decode_txdiv_sf": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(HipPdschSf), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx),
+                                                       vp, C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_txdiv_sf_dbg": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(HipPdschSf), C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(SoftbufferRx),
+                                                           vp, C.POINTER(HipGrantRes), vp, vp, vp, C.POINTER(vp), C.POINTER(PlaneArray)]),
+            "srsran_hip_pdsch_decode_mimo_sf": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(HipPdschSf), C.POINTER(vp), C.POINTER(PlaneArray),
+                                                      C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes)]),
+            "srsran_hip_pdsch_decode_mimo_sf_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(HipPdschSf), C.POINTER(vp), C.POINTER(PlaneArray),
+                                                          C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(vp), C.POINTER(vp),
+                                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(PlaneArray)]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pusch_encode": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pusch_encode_dbg": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp, vp, vp,

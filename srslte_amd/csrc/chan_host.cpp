@@ -5,6 +5,7 @@
 #include "chan_internal.h"
 #include "csi_device.h"
 #include "modem_device.h"
+#include "pdsch_map_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -436,8 +437,10 @@ extern "C" int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_
 
 // weight: the _csi forms (cfg->csi_enable).  ce != NULL: the equaliser files its channel-state values in device scratch; ce == NULL: the caller's row goes
 // up in the pinned image with the symbols, and `symbols` are the equalised symbols already (no d is made).
+// map: the _sf forms -- symbols and ce are grids.
 static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
-                            srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
+                            srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out,
+                            const SfMap* map = nullptr)
 {
   TraceRange trace_("srsran_hip_pdsch_decode");
   if (!g || !symbols || !softbuffer || !data || !res) {
@@ -453,10 +456,13 @@ static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch
   if (weight && csi && !csi_row_valid(csi, g->tb.nof_re)) {
     return refuse("%s: a csi entry is negative or not finite", who);
   }
+  if (map && !sf_valid(who, map->sf, 1, g->tb.nof_re)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
   cf_t *const  y[1] = {const_cast<cf_t*>(symbols)}, *const h[1] = {const_cast<cf_t*>(ce)};
   const size_t nd   = (size_t)g->tb.nof_re * sizeof(cf_t);
   PlaneGroup   in[2] = {{y, 1, nd, true, false}, {h, ce ? 1u : 0u, nd, true, false}};
-  RxGrant      gr = {who, in, 2, csi, {{&g->tb, qm_rm(g->tb), softbuffer, data, res, d_out, e_out, csi_out}}, 1, ce ? 1u : 0u, ce != nullptr, weight};
+  RxGrant      gr = {who, in, 2, map, csi, {{&g->tb, qm_rm(g->tb), softbuffer, data, res, d_out, e_out, csi_out}}, 1, ce ? 1u : 0u, ce != nullptr, weight};
   return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
     return enqueue_rx_front(st, g->tb, reinterpret_cast<uint8_t*>(in[0].pin[0]), reinterpret_cast<uint8_t*>(in[1].pin[0]), g->scaling, g->noise_estimate, 0, 0, d_d, nullptr,
                             nullptr, d_e[0], ce ? row[0] : nullptr);
@@ -488,6 +494,103 @@ extern "C" int srsran_hip_pdsch_decode_csi_dbg(const srsran_hip_pdsch_rx_t* g, c
   return pdsch_decode_one("srsran_hip_pdsch_decode_csi", true, g, symbols, ce, csi, softbuffer, data, res, d_out, e_out, csi_out);
 }
 
+// ------------------------------------------------------------------------------------------------ PDSCH receive from the subframe grids
+
+bool phyhip::chan::sf_valid(const char* who, const srsran_hip_pdsch_sf_t* sf, uint32_t ports, uint32_t nof_re)
+{
+  const char* why = !sf ? "NULL sf" : pdsch_map::invalid(*sf);
+  if (!why && sf->cell_nof_ports != ports) {
+    why = "cell_nof_ports is not the call's";
+  }
+  if (why) {
+    refuse("%s: subframe description: %s", who, why);
+    return false;
+  }
+  const uint32_t n = pdsch_map::nof_re(*sf);
+  if (n != nof_re) {
+    refuse("%s: expecting %u symbols but got %u", who, nof_re, n); // pdsch.c:834
+    return false;
+  }
+  return true;
+}
+
+extern "C" int srsran_hip_pdsch_nof_re(const srsran_hip_pdsch_sf_t* sf)
+{
+  return (!sf || pdsch_map::invalid(*sf)) ? -1 : (int)pdsch_map::nof_re(*sf);
+}
+
+extern "C" int srsran_hip_pdsch_get(const srsran_hip_pdsch_sf_t* sf, uint32_t n_planes, const cf_t* const* grids, cf_t* const* symbols)
+{
+  static const char* who = "srsran_hip_pdsch_get";
+  const char*        why = !sf ? "NULL sf" : pdsch_map::invalid(*sf);
+  why                    = why ? why : (!grids || !symbols || n_planes > 65535u) ? "NULL argument or more than 65535 planes" : nullptr;
+  for (uint32_t i = 0; !why && i < n_planes; i++) {
+    why = (grids[i] && symbols[i]) ? nullptr : "a NULL plane";
+  }
+  if (why) {
+    refuse("%s: %s", who, why);
+    return -1;
+  }
+  const pdsch_map::Window w = pdsch_map::window(*sf);
+  if (w.nof_re == 0 || n_planes == 0) {
+    return (int)w.nof_re;
+  }
+  ChanStage*  s  = stage_for(who);
+  hipStream_t st = s ? sch::stage_stream() : nullptr;
+  // pinned: the staged rows of every grid, the table, the planes
+  const size_t sb = al256((size_t)w.staged_points() * sizeof(cf_t)), nd = (size_t)w.nof_re * sizeof(cf_t), nb = al256(nd);
+  const size_t o_tab = n_planes * sb, o_out = o_tab + al256(w.n_seg * sizeof(pdsch_map::Seg));
+  if (!st || !s->grow(o_out + n_planes * nb, 0)) {
+    return -1;
+  }
+  for (uint32_t i = 0; i < n_planes; i++) {
+    stage_grid(s->pin + i * sb, grids[i], *sf, w);
+  }
+  pdsch_map::fill_table(*sf, w, reinterpret_cast<pdsch_map::Seg*>(s->pin + o_tab));
+  const pdsch_map::DemapParams dp = {reinterpret_cast<const float2*>(s->pin.get()), reinterpret_cast<float2*>(s->pin + o_out), reinterpret_cast<const pdsch_map::Seg*>(s->pin + o_tab),
+                                     w.n_seg, n_planes, (uint32_t)(sb / sizeof(cf_t)), w.staged_points(), (uint32_t)(nb / sizeof(cf_t)), w.nof_re};
+  const bool launched = pdsch_map::launch_demap(dp, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+    return -1;
+  }
+  for (uint32_t i = 0; i < n_planes; i++) {
+    memcpy(symbols[i], s->pin + o_out + i * nb, nd);
+  }
+  return (int)w.nof_re;
+}
+
+// the one-port call: a line on stderr for every refusal, then the twin's path with the grids in the planes' place
+static int pdsch_decode_one_sf(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const cf_t* sf_symbols, const cf_t* ce, srsran_softbuffer_rx_t* softbuffer,
+                               uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out, cf_t* sym_out, cf_t* ce_out)
+{
+  static const char* who = "srsran_hip_pdsch_decode_sf";
+  if (res) {
+    *res = {0, 0.f, NAN};
+  }
+  if (!g || !sf || !sf_symbols || !ce || !softbuffer || !data || !res) {
+    return refuse("%s: NULL argument (the call needs the estimates' grid: there is no grid of equalised symbols)", who);
+  }
+  if (!(g->scaling != 0.f)) {
+    return refuse("%s: scaling is 0", who);
+  }
+  const SfMap map    = {sf, {sym_out, ce_out}};
+  const bool  weight = sf->csi_enable != 0;
+  return pdsch_decode_one(who, weight, g, sf_symbols, ce, nullptr, softbuffer, data, res, d_out, e_out, weight ? csi_out : nullptr, &map);
+}
+
+extern "C" int srsran_hip_pdsch_decode_sf(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const cf_t* sf_symbols, const cf_t* ce,
+                                          srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_one_sf(g, sf, sf_symbols, ce, softbuffer, data, res, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_sf_dbg(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const cf_t* sf_symbols, const cf_t* ce,
+                                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out,
+                                              float* csi_out, cf_t* sym_out, cf_t* ce_out)
+{
+  return pdsch_decode_one_sf(g, sf, sf_symbols, ce, softbuffer, data, res, d_out, e_out, csi_out, sym_out, ce_out);
+}
+
 // ------------------------------------------------------------------------------------------------ PDSCH receive, the frame of every grant call
 
 int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
@@ -505,7 +608,14 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     want_d = want_d || (g.d_planes && g.cw[k].d_out);
   }
   // pinned: the planes, the equalised symbols, each codeword's soft bits, each codeword's CSI row; device: the equalised symbols, the front end's CSI rows
-  const size_t o_d = plane_room(g.in, g.n_in);
+  // (with g.map: the staged rows of every grid and the segment table where the planes would be)
+  const pdsch_map::Window w = g.map ? pdsch_map::window(*g.map->sf) : pdsch_map::Window{};
+  uint32_t                n_pl = 0;
+  for (uint32_t i = 0; i < g.n_in; i++) {
+    n_pl += g.in[i].k;
+  }
+  const size_t sb = al256((size_t)w.staged_points() * sizeof(cf_t)), o_tab = n_pl * sb;
+  const size_t o_d = g.map ? o_tab + al256(w.n_seg * sizeof(pdsch_map::Seg)) : plane_room(g.in, g.n_in);
   size_t       ne[2] = {0, 0}, o_e[2] = {0, 0}, o_c = o_d + g.d_planes * nb;
   for (uint32_t k = 0; k < g.n_cw; k++) {
     ne[k]  = (size_t)nof_re * qm_of(g.cw[k].tb->mod) * (llr8 ? 1 : 2);
@@ -514,11 +624,28 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
   }
   const bool   dev_rows = g.weight && !g.csi;
   const size_t o_dc     = (want_d || g.d_scratch) ? g.d_planes * nb : 0;
-  if (!s.grow(o_c + g.n_cw * nc, o_dc + (dev_rows ? g.n_cw * nc : 0))) {
+  // the de-mapped planes: device scratch behind the CSI rows; pinned room behind everything else for the ones _sf_dbg asked for
+  bool want_m = false;
+  for (uint32_t i = 0; g.map && i < n_pl; i++) {
+    want_m = want_m || g.map->out[i];
+  }
+  const size_t o_dm = o_dc + (dev_rows ? g.n_cw * nc : 0), o_m = o_c + g.n_cw * nc;
+  if (n_pl > PDSCH_MAX_RX_PLANES || !s.grow(o_m + (want_m ? n_pl * nb : 0), o_dm + (g.map ? n_pl * nb : 0))) {
     fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", g.who);
     return SRSRAN_ERROR;
   }
-  place_planes(s.pin, g.in, g.n_in);
+  if (g.map) {
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < g.n_in; i++) {
+      for (uint32_t k = 0; k < g.in[i].k; k++, at++) {
+        stage_grid(s.pin + at * sb, g.in[i].host[k], *g.map->sf, w);
+        g.in[i].pin[k] = reinterpret_cast<cf_t*>(s.dev + o_dm + at * nb);
+      }
+    }
+    pdsch_map::fill_table(*g.map->sf, w, reinterpret_cast<pdsch_map::Seg*>(s.pin + o_tab));
+  } else {
+    place_planes(s.pin, g.in, g.n_in);
+  }
   if (g.csi) {
     memcpy(s.pin + o_c, g.csi, nr);
   }
@@ -545,7 +672,7 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     items[n_items++] = {&head[k], c.sb, &seg[k], c.Qm, c.tb->rv, nof_re * qm_of(c.tb->mod), nullptr, &device_made, c.data, false};
   }
   // what the front end actually made: it does not run for a codeword the transport-block stage drops
-  bool                     d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false};
+  bool                     d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false}, m_made = false;
   const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
     void*       de[2] = {nullptr, nullptr};
     CsiCodeword wj[2];
@@ -554,11 +681,22 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
       de[k] = d_e[j];
       wj[j] = {d_e[j], row[k], g.cw[k].tb->mod};
     }
+    if (g.map) {
+      const pdsch_map::DemapParams dp = {reinterpret_cast<const float2*>(s.pin.get()), reinterpret_cast<float2*>(s.dev + o_dm), reinterpret_cast<const pdsch_map::Seg*>(s.pin + o_tab),
+                                         w.n_seg, n_pl, (uint32_t)(sb / sizeof(cf_t)), w.staged_points(), (uint32_t)(nb / sizeof(cf_t)), nof_re};
+      if (pdsch_map::launch_demap(dp, st) != hipSuccess) {
+        set_error("grant front end: RE de-mapping launch failed");
+        return false;
+      }
+    }
     if (!front(st, de, row, o_dc ? s.dev.get() : nullptr) || (g.weight && !enqueue_csi_weight(st, wj, m, nof_re, llr8))) {
       return false;
     }
     bool copied = !want_d || hipMemcpyAsync(s.pin + o_d, s.dev, (g.d_planes - 1) * nb + nd, hipMemcpyDeviceToHost, st) == hipSuccess;
     d_made      = want_d && copied;
+    if (copied && want_m) {
+      copied = m_made = hipMemcpyAsync(s.pin + o_m, s.dev + o_dm, (n_pl - 1) * nb + nd, hipMemcpyDeviceToHost, st) == hipSuccess;
+    }
     for (uint32_t j = 0; copied && j < m; j++) {
       const uint32_t k = cw_of[which[j]];
       if (g.weight && g.cw[k].csi_out) { // (the caller's row is in the image already)
@@ -595,6 +733,9 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     hand_back(g.d_planes ? c.d_out : nullptr, d_made, o_d + k * nb, nd);
     hand_back(c.sb ? c.e_out : nullptr, e_made[k], o_e[k], ne[k]);
     hand_back(c.sb && g.weight ? c.csi_out : nullptr, c_made[k], o_c + k * nc, nr);
+  }
+  for (uint32_t i = 0; g.map && i < n_pl; i++) {
+    hand_back(g.map->out[i], m_made, o_m + i * nb, nd);
   }
   if (missing) {
     set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", g.who);

@@ -5,6 +5,7 @@
 #pragma once
 #include "hip_common.h"
 #include "joblist.h"
+#include "pdsch_map.h"
 #include "sch_stage.h"
 #include "stage.h"
 #include "srsran_amd/phy_chan_abi.h"
@@ -202,6 +203,8 @@ bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch laun
 // Pinned image: the planes, d_planes planes for the equalised symbols, every codeword's soft bits, every codeword's CSI row (the caller's, or what _dbg hands
 // back); device scratch: the equalised symbols (when somebody wants them), the CSI rows the front end files.  Everything on a 256-byte boundary, a plane's
 // padding behind it (the MIMO kernels read an odd grant's last pair whole).
+// With g.map (the _sf calls) the planes' place in the pinned image holds the used rows of the grids and the segment table instead; ONE launch in front of the
+// scheme's de-maps all planes into device scratch behind the CSI rows, and `front` reads them there (g.in[].pin); _sf_dbg's planes come down in one copy.
 // SRSRAN_ERROR when a device-side step failed, and -- one line on stderr -- when a _dbg output that was asked for was not produced: the front end does not run for a
 // codeword the transport-block stage drops (a soft buffer with fewer rows than code blocks) or whose blocks were all decoded in an earlier round.  Such an
 // output is left untouched; res is filled in both cases.
@@ -215,10 +218,34 @@ struct RxCodeword {
   void*                        e_out;
   float*                       csi_out;
 };
+
+// ---- the _sf calls: the planes handed in are subframe grids, de-mapped on the device (pdsch_map.h, pdsch_map_kernels.hip)
+#define PDSCH_MAX_RX_PLANES 10 // nof_rx * (1 + nof_ports) of the largest grant taken: 2 * (1 + 4)
+struct SfMap {
+  const srsran_hip_pdsch_sf_t* sf;
+  cf_t*                        out[PDSCH_MAX_RX_PLANES]; // _sf_dbg, or nullptr: where the extracted plane goes, in the order the planes are staged
+};
+// one line on stderr and false for what the _sf calls refuse on top of their twins: a NULL or invalid description, a cell_nof_ports other than `ports`,
+// another RE count than the grant's
+bool sf_valid(const char* who, const srsran_hip_pdsch_sf_t* sf, uint32_t ports, uint32_t nof_re);
+// the used rows of a grid into a plane's staged image of window w: whole rows in one copy, or the span of the allocation row by row
+inline void stage_grid(uint8_t* at, const cf_t* grid, const srsran_hip_pdsch_sf_t& sf, const pdsch_map::Window& w)
+{
+  const size_t row = (size_t)12 * sf.cell_nof_prb, span = (size_t)12 * w.prbs;
+  if (w.prbs == sf.cell_nof_prb) {
+    memcpy(at, grid + w.row0 * row, w.rows * row * sizeof(cf_t));
+    return;
+  }
+  for (uint32_t r = 0; r < w.rows; r++) {
+    memcpy(at + r * span * sizeof(cf_t), grid + (w.row0 + r) * row + (size_t)12 * w.prb0, span * sizeof(cf_t));
+  }
+}
+
 struct RxGrant {
   const char*  who;
   PlaneGroup*  in; // staged: symbols [nof_rx], then estimates [port][nof_rx]
   uint32_t     n_in;
+  const SfMap* map; // nullptr: `in` are the grant's extracted REs; else they are grids (PlaneGroup::bytes is still a PLANE's) and pin[] will be device scratch
   const float* csi; // the caller's CSI row in place of the front end's (one port without estimates), or nullptr
   RxCodeword   cw[SRSRAN_MAX_CODEWORDS];
   uint32_t     n_cw;

@@ -238,8 +238,10 @@ extern "C" int srsran_hip_precoding_mimo(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* y[SRS
 static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                              srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
                              srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
-                             float* const csi_out[SRSRAN_MAX_CODEWORDS])
+                             float* const csi_out[SRSRAN_MAX_CODEWORDS], bool sf_form = false, const srsran_hip_pdsch_sf_t* sf = nullptr,
+                             cf_t* const sym_out[] = nullptr, cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr)
 {
+  // sf_form: the _sf calls -- symbols and ce are grids, sf describes them (weight is its csi_enable), sym_out / ce_out take the extracted planes
   static const char* who = "srsran_hip_pdsch_decode_mimo";
   TraceRange         trace_(who);
   if (res) {
@@ -279,11 +281,21 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
   }
+  if (sf_form && !sf_valid("srsran_hip_pdsch_decode_mimo_sf", sf, 2, nof_re)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
   // staged: 2 symbol planes, then 2 x 2 estimate planes; codeword k is layer k
   const bool   llr8 = g->tb[0].llr_is_8bit != 0;
   const size_t nd   = (size_t)nof_re * sizeof(cf_t);
   PlaneGroup   in[3] = {{symbols, 2, nd, true, false}, {ce[0], 2, nd, true, false}, {ce[1], 2, nd, true, false}};
-  RxGrant      gr = {who, in, 3, nullptr, {}, ntb, ntb, false, weight};
+  SfMap        map = {sf, {}};
+  for (uint32_t r = 0; r < 2; r++) {
+    map.out[r] = sym_out ? sym_out[r] : nullptr;
+    for (uint32_t k = 0; k < 2; k++) {
+      map.out[2 + 2 * k + r] = ce_out ? ce_out[k][r] : nullptr;
+    }
+  }
+  RxGrant      gr = {who, in, 3, sf_form ? &map : nullptr, nullptr, {}, ntb, ntb, false, weight};
   for (uint32_t k = 0; k < ntb; k++) {
     gr.cw[k] = {&g->tb[k], qm_of(g->tb[k].mod), softbuffers[k], data[k], &res[k], d_out ? d_out[k] : nullptr, e_out ? e_out[k] : nullptr, csi_out ? csi_out[k] : nullptr};
   }
@@ -355,6 +367,24 @@ extern "C" int srsran_hip_pdsch_decode_mimo_csi_dbg(const srsran_hip_pdsch_mimo_
                                                     void* const e_out[SRSRAN_MAX_CODEWORDS], float* const csi_out[SRSRAN_MAX_CODEWORDS])
 {
   return pdsch_decode_mimo(true, g, symbols, ce, softbuffers, data, res, d_out, e_out, csi_out);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_sf(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                               cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                               uint8_t* const data[SRSRAN_MAX_CODEWORDS], srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS])
+{
+  return pdsch_decode_mimo(sf && sf->csi_enable, g, sf_symbols, ce, softbuffers, data, res, nullptr, nullptr, nullptr, true, sf);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_sf_dbg(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                   cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                                   uint8_t* const data[SRSRAN_MAX_CODEWORDS], srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS],
+                                                   cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
+                                                   float* const csi_out[SRSRAN_MAX_CODEWORDS], cf_t* const sym_out[],
+                                                   cf_t* const (*ce_out)[SRSRAN_MAX_PORTS])
+{
+  const bool weight = sf && sf->csi_enable;
+  return pdsch_decode_mimo(weight, g, sf_symbols, ce, softbuffers, data, res, d_out, e_out, weight ? csi_out : nullptr, true, sf, sym_out, ce_out);
 }
 
 // ------------------------------------------------------------------------------------------------ PDSCH grant, transmit

@@ -244,8 +244,11 @@ extern "C" int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, 
 // ---- PDSCH codeword with transmit diversity, receive
 
 // weight: the _csi forms (cfg->csi_enable): the front end files the combiner's channel-state values in the row the frame (chan_internal.h) weights with
+// sf_form: the _sf calls -- symbols and ce are grids, sf describes them (weight is its csi_enable), sym_out / ce_out take the extracted planes
 static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
-                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out)
+                              srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out,
+                              bool sf_form = false, const srsran_hip_pdsch_sf_t* sf = nullptr, cf_t* const sym_out[] = nullptr,
+                              cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr)
 {
   TraceRange trace_("srsran_hip_pdsch_decode_txdiv");
   if (res) {
@@ -270,14 +273,24 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
     return refuse("srsran_hip_pdsch_decode_txdiv: %u ports, %u receive antennas, %u REs, scaling %g%s is not a transmit-diversity grant", ports, nrx, nof_re, (double)g->scaling,
                   (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2) && !planes ? ", a NULL plane" : "");
   }
+  if (sf_form && !sf_valid("srsran_hip_pdsch_decode_txdiv_sf", sf, ports, nof_re)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
   // staged: nof_rx symbol planes, then nof_ports x nof_rx estimate planes
   const srsran_hip_grant_tb_t& tb = g->tb;
   const size_t                 nd = (size_t)nof_re * sizeof(cf_t);
   PlaneGroup                   in[1 + SRSRAN_MAX_PORTS] = {{symbols, nrx, nd, true, false}};
+  SfMap                        map = {sf, {}};
+  for (uint32_t r = 0; r < nrx; r++) {
+    map.out[r] = sym_out ? sym_out[r] : nullptr;
+  }
   for (uint32_t k = 0; k < ports; k++) {
     in[1 + k] = {ce[k], nrx, nd, true, false};
+    for (uint32_t r = 0; r < nrx; r++) {
+      map.out[nrx + k * nrx + r] = ce_out ? ce_out[k][r] : nullptr;
+    }
   }
-  RxGrant gr = {"srsran_hip_pdsch_decode_txdiv", in, 1 + ports, nullptr, {{&tb, 2 * qm_of(tb.mod), softbuffer, data, res, d_out, e_out, csi_out}}, 1, 1, false, weight};
+  RxGrant gr = {"srsran_hip_pdsch_decode_txdiv", in, 1 + ports, sf_form ? &map : nullptr, nullptr, {{&tb, 2 * qm_of(tb.mod), softbuffer, data, res, d_out, e_out, csi_out}}, 1, 1, false, weight};
   return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
     const cf_t* hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
     cf_t*       xd[SRSRAN_MAX_LAYERS]                  = {};
@@ -342,6 +355,22 @@ extern "C" int srsran_hip_pdsch_decode_txdiv_csi_dbg(const srsran_hip_pdsch_txdi
                                                      float* csi_out)
 {
   return pdsch_decode_txdiv(true, g, symbols, ce, softbuffer, data, res, d_out, e_out, csi_out);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_sf(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                                srsran_hip_grant_res_t* res)
+{
+  return pdsch_decode_txdiv(sf && sf->csi_enable, g, sf_symbols, ce, softbuffer, data, res, nullptr, nullptr, nullptr, true, sf);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_sf_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, cf_t* const sf_symbols[],
+                                                    cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                                    srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out, cf_t* const sym_out[],
+                                                    cf_t* const (*ce_out)[SRSRAN_MAX_PORTS])
+{
+  const bool weight = sf && sf->csi_enable;
+  return pdsch_decode_txdiv(weight, g, sf_symbols, ce, softbuffer, data, res, d_out, e_out, weight ? csi_out : nullptr, true, sf, sym_out, ce_out);
 }
 
 // ---- PDSCH codeword with transmit diversity, transmit

@@ -6,7 +6,8 @@
 // allocation, srsran_tdec_init, srsran_rm_turbo_gentables) -- so does the library: srsran_rm_turbo_gentables() builds every rate-matching table in
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
 // grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one CSI-weighted grant of each
-// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PUSCH transmit grant with control information -- on a short-lived
+// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PDSCH grant from the subframe grids, one PUSCH
+// transmit grant with control information -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
 #include "turbo_device.h"
@@ -100,6 +101,19 @@ void warm_one_worker()
     const std::vector<uint8_t>      types((24 + 5) * Qm, 1), cqi(60 * Qm, 1);
     const srsran_hip_pusch_uci_in_t in  = {types.data(), types.data() + 24 * Qm, cqi.data()};
     (void)srsran_hip_pusch_encode(&tx, &uci, &in, &sb.tx, data.data(), grid.data());
+  }
+  // one PDSCH grant from the subframe grids (12 PRB of the 100-PRB cell, subframe 1, one control symbol: 1800 REs; CSI-weighted), so the device code of
+  // pdsch_map_kernels.hip is loaded before a UE worker's first srsran_pdsch_decode
+  {
+    srsran_hip_pdsch_sf_t sf = {nof_prb, 1, 1, 7, 0, 1, 1, {7, 7}, 1, {}};
+    for (uint32_t n = 40; n < 52; n++) {
+      sf.prb_idx[0][n] = sf.prb_idx[1][n] = 1;
+    }
+    const int                   nof_re = srsran_hip_pdsch_nof_re(&sf);
+    const srsran_hip_pdsch_rx_t pd     = {{SRSRAN_MOD_16QAM, 6144 - 24, 0, (uint32_t)(nof_re > 0 ? nof_re : 0), 12345u, 1, 0, 1}, 1.0f, 0.01f};
+    srsran_hip_grant_res_t      res;
+    sb.reset();
+    (void)srsran_hip_pdsch_decode_sf(&pd, &sf, grid.data(), ce.data(), &sb.rx, data.data(), &res);
   }
   // one 2-port transmit-diversity codeword each way (the one-block 16-QAM grant above: 1728 REs on two layers), so the device code of txdiv_kernels.hip
   // is loaded before the first subframe of a 2-port cell

@@ -33,7 +33,11 @@
  * The PDSCH's resource DE-mapping (srsran_pdsch_get: the gather around reference signals, PSS / SSS and PBCH) is taken by the _sf form of each PDSCH receive
  * call, which starts at srsran_pdsch_decode's own signature: subframe grids and the channel estimator's grids in, one more launch, still one host wait.
  *
- * What is NOT taken here and stays with the caller: the PDSCH's resource mapping on transmit (srsran_pdsch_put: the caller's grid holds other channels' REs),
+ * The PUSCH's channel estimator (srsran_chest_ul_estimate_pusch, the first of the two calls of srsran_enb_ul_get_pusch, enb_ul.c:272-281) is taken by
+ * srsran_hip_chest_ul_estimate_pusch and, in front of the equaliser of the same call, by srsran_hip_pusch_decode_est{,_multi}: the grid and the grant's DMRS
+ * row in, the payload and the estimator's six measurements out, one more launch, still one host wait.
+ *
+ * What is NOT taken here and stays with the caller: the PUCCH and SRS channel estimators, generating the DMRS rows (refsignal_ul.c), the PDSCH's resource mapping on transmit (srsran_pdsch_put: the caller's grid holds other channels' REs),
  * spatial multiplexing and CDD on 4 ports (the
  * reference refuses them too) or with other than 2 receive antennas, PMI and condition-number selection (srsran_precoding_pmi_select, srsran_precoding_cn:
  * reductions over a whole subframe's estimates), the PUSCH's CSI weighting (pusch_cfg.h: csi_enable), PMCH, a PUSCH without a transport block (tbs == 0: CQI
@@ -127,6 +131,50 @@ SRSRAN_API int srsran_hip_pusch_decode_uci(const srsran_hip_pusch_rx_t* g, const
 SRSRAN_API int srsran_hip_pusch_decode_uci_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* const* sf_symbols,
                                                  const cf_t* const* ce, srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data,
                                                  srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out);
+
+/* ---- PUSCH channel estimation on the device (srsran_chest_ul_estimate_pusch, chest_ul.c:370-404): with it the PUSCH grant calls start at the level of
+ * srsran_enb_ul_get_pusch (enb_ul.c:272-281) -- subframe grid in, payload and the estimator's measurements out, no ce grid and no noise estimate from the
+ * caller.  Per slot, with n = 12 L_prb and L(slot) = (slot + 1) cp_nsymb - 4: the received references are symbol L(slot) of the grid at sub-carriers
+ * 12 n_prb_tilde[slot] + k; ls = rx conj(r); with filter_len 3 the estimate is srsran_conv_same_cf(ls, filter) (the virtual neighbour in front of element 0
+ * is 3 ls[1] - 2 ls[0], the one behind the last 3 ls[n-1] - 2 ls[n-2]) and noise_estimate the calibrated mean |estimate - ls|^2 (chest_ul.c:200-221, the
+ * calibration from filter[0]); with filter_len 0 the estimate is ls, noise_estimate 0 and snr NAN.  The slot's row is the estimate of every symbol of the slot
+ * (no time interpolation: the reference compiles none in).  cfo_hz, ta_us (0 unless meas_ta_en), snr and the dB values as chest_ul.c:300-326, :358-367.
+ * Intra-subframe hopping (n_prb_tilde[0] != n_prb_tilde[1]) is taken: each slot is estimated where the UE sent it.  The reference's estimator logs an error
+ * there and places its rows by n_prb (chest_ul.c:329-331), so the record the library is tested against (tests/golden/chest_ul_ref.npz) has no such case.
+ * Not taken: generating the DMRS rows (the caller's pregen table is handed over), the PUCCH and SRS estimators, filters longer than 3 taps, rsrp / epre of
+ * srsran_chest_ul_res_t (the PUSCH estimator does not set them). */
+typedef struct SRSRAN_API {
+  uint32_t    filter_len;  /* 3: {w, 1-2w, w} in filter[] (the reference's default: w = 0.3333f); 0: no smoothing */
+  float       filter[3];
+  uint32_t    meas_ta_en;
+  const cf_t* r;           /* the grant's DMRS row, dmrs_pregen.r[n_dmrs][tti % 10][L_prb]: 2 x 12 L_prb points, HOST memory */
+} srsran_hip_chest_ul_t;
+
+typedef struct SRSRAN_API {   /* what srsran_chest_ul_estimate_pusch leaves in srsran_chest_ul_res_t */
+  float noise_estimate, noise_estimate_dbm, snr, snr_db, cfo_hz, ta_us;
+} srsran_hip_chest_ul_res_t;
+/* the stage by itself.  Of g only the geometry is read: cell_nof_prb, cp_nsymb, n_prb_tilde[], L_prb.  sf_symbols: the subframe grid, HOST memory.  ce: a
+ * full grid of HOST memory -- only the grant's columns of all 2 cp_nsymb symbols are written -- or NULL for the measurements only.  One launch (one
+ * workgroup per grant), one host wait.  Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *out zeroed and
+ * nothing else written: a NULL g, est, est->r, sf_symbols or out, a geometry that is not a PUSCH allocation (as srsran_hip_pusch_decode), filter_len other
+ * than 0 or 3, a filter tap that is not finite. */
+SRSRAN_API int srsran_hip_chest_ul_estimate_pusch(const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const cf_t* sf_symbols, cf_t* ce,
+                                                  srsran_hip_chest_ul_res_t* out);
+/* arrays of n entries (ce, or any ce[i], may be NULL) */
+SRSRAN_API int srsran_hip_chest_ul_estimate_pusch_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est,
+                                                        const cf_t* const* sf_symbols, cf_t* const* ce, srsran_hip_chest_ul_res_t* out);
+/* the grant calls: srsran_hip_pusch_decode_uci{,_multi} without the ce argument.  g->noise_estimate is not read: the estimator's kernel runs ahead of the
+ * equaliser on the same stream and hands it the rows and the noise estimate on the device; est_out[i] is filled after the call's ONE host wait.  uci may
+ * be NULL, or uci[i] all zero for a grant without control information (uci_out[i] is then not looked at); the rules are those of srsran_hip_pusch_decode_uci.
+ * The single call is the multi call with n = 1.  Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, every res[i]
+ * = {0, 0, NAN}, every est_out[i] zeroed and nothing else written: everything srsran_hip_pusch_decode_uci refuses, a NULL est, est[i].r or est_out,
+ * filter_len other than 0 or 3, a filter tap that is not finite. */
+SRSRAN_API int srsran_hip_pusch_decode_est(const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const srsran_hip_pusch_uci_t* uci,
+                                           const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res,
+                                           srsran_hip_pusch_uci_out_t* uci_out, srsran_hip_chest_ul_res_t* est_out);
+SRSRAN_API int srsran_hip_pusch_decode_est_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const srsran_hip_pusch_uci_t* uci,
+                                                 const cf_t* const* sf_symbols, srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data,
+                                                 srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* uci_out, srsran_hip_chest_ul_res_t* est_out);
 
 /* ---- PDSCH receive, one codeword: `symbols` are the grant's nof_re extracted REs (srsran_pdsch_get) of HOST memory.  ce != NULL: single
  * port, single receive antenna -- the zero-forcing / MMSE equaliser srsran_predecoding_single(symbols, ce, ., NULL, nof_re, scaling,

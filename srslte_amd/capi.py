@@ -154,6 +154,15 @@ class HipPuschUciOut(C.Structure):  # srsran_hip_pusch_uci_out_t
                 ("cqi_llr", C.c_void_p)]
 
 
+class HipChestUl(C.Structure):  # srsran_hip_chest_ul_t
+    _fields_ = [("filter_len", C.c_uint32), ("filter", C.c_float * 3), ("meas_ta_en", C.c_uint32), ("r", C.c_void_p)]
+
+
+class HipChestUlRes(C.Structure):  # srsran_hip_chest_ul_res_t
+    _fields_ = [("noise_estimate", C.c_float), ("noise_estimate_dbm", C.c_float), ("snr", C.c_float), ("snr_db", C.c_float), ("cfo_hz", C.c_float),
+                ("ta_us", C.c_float)]
+
+
 class HipPuschTx(C.Structure):  # srsran_hip_pusch_tx_t
     _fields_ = [("tb", HipGrantTb), ("cell_nof_prb", C.c_uint32), ("cp_nsymb", C.c_uint32), ("n_prb_tilde", C.c_uint32 * 2), ("L_prb", C.c_uint32),
                 ("shortened", C.c_uint32)]
@@ -559,6 +568,14 @@ def lib():
                                                   C.POINTER(HipPuschUciOut)]),
             "srsran_hip_pusch_decode_uci_multi": (i32, [u32, C.POINTER(HipPuschRx), C.POINTER(HipPuschUci), C.POINTER(vp), C.POINTER(vp),
                                                         C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(HipPuschUciOut)]),
+            "srsran_hip_chest_ul_estimate_pusch": (i32, [C.POINTER(HipPuschRx), C.POINTER(HipChestUl), vp, vp, C.POINTER(HipChestUlRes)]),
+            "srsran_hip_chest_ul_estimate_pusch_multi": (i32, [u32, C.POINTER(HipPuschRx), C.POINTER(HipChestUl), C.POINTER(vp), C.POINTER(vp),
+                                                               C.POINTER(HipChestUlRes)]),
+            "srsran_hip_pusch_decode_est": (i32, [C.POINTER(HipPuschRx), C.POINTER(HipChestUl), C.POINTER(HipPuschUci), vp, C.POINTER(SoftbufferRx), vp,
+                                                  C.POINTER(HipGrantRes), C.POINTER(HipPuschUciOut), C.POINTER(HipChestUlRes)]),
+            "srsran_hip_pusch_decode_est_multi": (i32, [u32, C.POINTER(HipPuschRx), C.POINTER(HipChestUl), C.POINTER(HipPuschUci), C.POINTER(vp),
+                                                        C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(HipPuschUciOut),
+                                                        C.POINTER(HipChestUlRes)]),
             "srsran_hip_pdsch_decode": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes)]),
             "srsran_hip_pdsch_encode": (i32, [C.POINTER(HipPdschTx), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pdsch_decode_dbg": (i32, [C.POINTER(HipPdschRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), vp, vp]),

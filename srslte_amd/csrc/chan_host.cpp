@@ -3,6 +3,7 @@
 // (sch.c:1194) chained on the calling thread's transport-block stream, nothing but the inputs and the results crossing the bus.
 #include "chan_device.h"
 #include "chan_internal.h"
+#include "chest_ul_device.h"
 #include "csi_device.h"
 #include "modem_device.h"
 #include "pdsch_map_device.h"
@@ -73,13 +74,16 @@ namespace {
 
 // the receive front end of one grant, enqueued on `st`: [equaliser] -> [transform de-precoding] -> demodulator + descrambler (+ UL channel
 // de-interleaver in its store) -> d_e.  p_sym / p_ce: the grant's REs in the pinned image; d_x / d_z: device scratch of nof_re points each; d_csi: nullptr,
-// or where the equaliser files its nof_re channel-state values.
+// or where the equaliser files its nof_re channel-state values.  d_eqj: nullptr, or the grant's equaliser job in DEVICE memory, which the channel estimator's
+// kernel ahead on the stream fills with the noise estimate (`noise` is then not looked at; nof_re is even).
 bool enqueue_rx_front(hipStream_t st, const srsran_hip_grant_tb_t& tb, const uint8_t* p_sym, const uint8_t* p_ce, float scaling, float noise, uint32_t L_prb,
-                      uint32_t nof_symb, uint8_t* d_x, uint8_t* d_z, srsran_hip_dft_batch_t* plan, void* d_e, float* d_csi = nullptr)
+                      uint32_t nof_symb, uint8_t* d_x, uint8_t* d_z, srsran_hip_dft_batch_t* plan, void* d_e, float* d_csi = nullptr,
+                      const modem::EqJob* d_eqj = nullptr)
 {
   const uint8_t* cur = p_sym;
   if (p_ce) {
-    if (modem::launch_eq(p_sym, p_ce, d_x, d_csi, tb.nof_re, scaling, noise, st) != hipSuccess) {
+    if ((d_eqj ? modem::launch_eq_jobs(p_sym, p_ce, d_x, d_eqj, 1, tb.nof_re / 2, scaling, st) : modem::launch_eq(p_sym, p_ce, d_x, d_csi, tb.nof_re, scaling, noise, st)) !=
+        hipSuccess) {
       set_error("grant front end: equaliser launch failed");
       return false;
     }
@@ -125,11 +129,40 @@ struct PuschPlan { // one grant of a (multi-)call
   srsran_hip_dft_batch_t* plan = nullptr;
   sch::FrontEnd           front;
   size_t                  o_uci = 0; // the grant's control image in the pinned image (modem_device.h: uci_image_*)
+  size_t                  o_refs = 0; // with an estimator: the grant's reference rows in the pinned image (stage_refs)
 };
 
 inline bool has_uci(const srsran_hip_pusch_uci_t& u)
 {
   return (u.Q_prime_ack | u.Q_prime_ri | u.Q_prime_cqi) != 0;
+}
+
+// the geometry of a PUSCH allocation (what the channel estimator reads of a grant)
+inline bool alloc_valid(const srsran_hip_pusch_rx_t& x)
+{
+  return (x.cp_nsymb == 7 || x.cp_nsymb == 6) && x.L_prb != 0 && srsran_dft_precoding_valid_prb(x.L_prb) && x.n_prb_tilde[0] + x.L_prb <= x.cell_nof_prb &&
+         x.n_prb_tilde[1] + x.L_prb <= x.cell_nof_prb;
+}
+
+// the estimator's input of one grant into the pinned image at byte `at`: the two received reference rows (srsran_refsignal_dmrs_pusch_get,
+// refsignal_ul.c:209-224: symbol (slot + 1) cp_nsymb - 4 of each slot), then the grant's DMRS row -- 4 n points.  Returns the job but for its output rows.
+chest_ul::Job stage_refs(uint8_t* pin, size_t at, const srsran_hip_pusch_rx_t& x, const srsran_hip_chest_ul_t& e, const cf_t* grid)
+{
+  const uint32_t n = 12 * x.L_prb;
+  for (uint32_t slot = 0; slot < 2; slot++) {
+    const size_t idx = ((size_t)((slot + 1) * x.cp_nsymb - 4) * x.cell_nof_prb + x.n_prb_tilde[slot]) * 12;
+    memcpy(pin + at + (size_t)slot * n * sizeof(cf_t), grid + idx, n * sizeof(cf_t));
+  }
+  memcpy(pin + at + (size_t)2 * n * sizeof(cf_t), e.r, (size_t)2 * n * sizeof(cf_t));
+  chest_ul::Job j = {};
+  j.n          = n;
+  j.o_rx       = (uint32_t)(at / sizeof(cf_t));
+  j.o_r        = j.o_rx + 2 * n;
+  j.filter_len = e.filter_len;
+  for (uint32_t i = 0; i < e.filter_len && i < 3; i++) {
+    j.filter[i] = e.filter[i];
+  }
+  return j;
 }
 
 } // namespace
@@ -138,32 +171,40 @@ inline bool has_uci(const srsran_hip_pusch_uci_t& u)
 
 // the grants of a call.  uci == nullptr: srsran_hip_pusch_decode{,_multi}; else uci[i] / out[i] are grant i's control-information counts and outputs
 // (srsran_hip_pusch_decode_uci{,_multi}) and the 16-bit grants' demodulator launch is the de-multiplexing one (modem::launch_uci).
+// est != nullptr: srsran_hip_pusch_decode_est{,_multi} -- there is no ce; est[i] describes grant i's channel estimator, whose kernel runs ahead of the equaliser
+// and hands it the rows and the noise estimate on the device; est_out[i] <- its measurements.  Every refusal of those calls comes before the device is
+// looked for, with one line on stderr.
 static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_pusch_uci_t* uci, const cf_t* const* sf_symbols, const cf_t* const* ce,
-                               srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out)
+                               srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data, srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* out,
+                               const srsran_hip_chest_ul_t* est = nullptr, srsran_hip_chest_ul_res_t* est_out = nullptr)
 {
   TraceRange trace_("srsran_hip_pusch_decode");
   if (n == 0) {
     return SRSRAN_SUCCESS;
   }
-  if (!g || !sf_symbols || !ce || !softbuffers || !data || !res) {
-    return SRSRAN_ERROR_INVALID_INPUTS;
+  if (!g || !sf_symbols || (!ce && !est) || !softbuffers || !data || !res) {
+    return est ? refuse("srsran_hip_pusch_decode_est: NULL argument") : SRSRAN_ERROR_INVALID_INPUTS;
   }
-  ChanStage* sp = stage_for("srsran_hip_pusch_decode");
-  if (!sp) {
+  ChanStage* sp = est ? nullptr : stage_for("srsran_hip_pusch_decode");
+  if (!sp && !est) {
     return SRSRAN_ERROR;
   }
-  ChanStage&             s = *sp;
   std::vector<PuschPlan> pl(n);
   size_t                 pin_need = 0, dev_need = 0;
   for (uint32_t i = 0; i < n; i++) {
     const srsran_hip_pusch_rx_t& x = g[i];
     res[i] = {0, 0.f, NAN};
-    if (!tb_valid(x.tb, "srsran_hip_pusch_decode") || !sf_symbols[i] || !ce[i] || !softbuffers[i] || !data[i]) {
+    if (!tb_valid(x.tb, "srsran_hip_pusch_decode")) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
+    if (!sf_symbols[i] || (!est && !ce[i]) || !softbuffers[i] || !data[i]) {
+      return est ? refuse("srsran_hip_pusch_decode_est: grant %u: NULL argument", i) : SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (est && chest_ul::invalid(&est[i])) {
+      return refuse("srsran_hip_pusch_decode_est: grant %u: %s", i, chest_ul::invalid(&est[i]));
+    }
     const uint32_t nsymb = 2 * (x.cp_nsymb - 1) - (x.shortened ? 1u : 0u);
-    if ((x.cp_nsymb != 7 && x.cp_nsymb != 6) || x.L_prb == 0 || !srsran_dft_precoding_valid_prb(x.L_prb) || x.n_prb_tilde[0] + x.L_prb > x.cell_nof_prb ||
-        x.n_prb_tilde[1] + x.L_prb > x.cell_nof_prb || x.tb.nof_re != nsymb * 12 * x.L_prb || x.tb.mod < SRSRAN_MOD_QPSK || x.tb.mod > SRSRAN_MOD_64QAM) {
+    if (!alloc_valid(x) || x.tb.nof_re != nsymb * 12 * x.L_prb || x.tb.mod < SRSRAN_MOD_QPSK || x.tb.mod > SRSRAN_MOD_64QAM) {
       return refuse("srsran_hip_pusch_decode: grant %u: allocation (%u PRB at %u / %u of %u, %u REs, mod %u) is not a PUSCH allocation", i, x.L_prb, x.n_prb_tilde[0],
                     x.n_prb_tilde[1], x.cell_nof_prb, x.tb.nof_re, x.tb.mod);
     }
@@ -190,8 +231,17 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
     if (!segment(&p.seg, x.tb.tbs)) {
       return SRSRAN_ERROR;
     }
-    p.plan = s.plan(x.L_prb);
-    if (!p.plan) {
+  }
+  if (est) {
+    sp = stage_for("srsran_hip_pusch_decode_est");
+    if (!sp) {
+      return SRSRAN_ERROR;
+    }
+  }
+  ChanStage& s = *sp;
+  for (uint32_t i = 0; i < n; i++) {
+    pl[i].plan = s.plan(g[i].L_prb);
+    if (!pl[i].plan) {
       return SRSRAN_ERROR;
     }
   }
@@ -212,13 +262,14 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
   }
   const size_t region = al256(tot);
   for (uint32_t i = 0; i < n; i++) {
-    pl[i].o_ce = region + pl[i].o_sym;
+    pl[i].o_ce = (est ? 2 * region : region) + pl[i].o_sym; // (est: in the device image)
     pl[i].o_z  = region + pl[i].o_x;
   }
-  const size_t        o_eqj = 2 * region;
-  const JobListLayout jl    = job_list_layout(al256(o_eqj + n * sizeof(modem::EqJob)), n * sizeof(modem::Job), tiles);
+  // (with an estimator the estimates' region and the equaliser's job list are DEVICE memory behind the other two regions: the estimator's kernel writes both)
+  const size_t        o_eqj = est ? region : 2 * region;
+  const JobListLayout jl    = job_list_layout(al256(o_eqj + (est ? 0 : n * sizeof(modem::EqJob))), n * sizeof(modem::Job), tiles);
   pin_need = jl.end;
-  dev_need = 2 * region;
+  dev_need = est ? 3 * region + al256(n * sizeof(modem::EqJob)) : 2 * region;
   // with control information: the de-multiplexing demodulator's job list behind the others, then every grant's control image (the kernel stores the
   // control soft bits and chips straight into the pinned image: they are there after the call's one host wait).  Its workgroups are listed in the
   // one tile table: a 16-bit grant of such a call is in this list, an 8-bit one in the other
@@ -230,10 +281,33 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
       pin_need    = al256(pin_need + modem::uci_image_bytes(uci[i].Q_prime_ack, uci[i].Q_prime_ri, uci[i].Q_prime_cqi, qm_of(g[i].tb.mod)));
     }
   }
+  // with an estimator: its job list, its records and every grant's four reference rows behind everything else
+  const size_t o_cj = al256(pin_need), o_rec = al256(o_cj + (est ? n * sizeof(chest_ul::Job) : 0));
+  if (est) {
+    pin_need = al256(o_rec + n * sizeof(chest_ul::Record));
+    for (uint32_t i = 0; i < n; i++) {
+      pl[i].o_refs = pin_need;
+      pin_need += (size_t)4 * 12 * g[i].L_prb * sizeof(cf_t);
+    }
+  }
   if (!s.grow(pin_need, dev_need)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_hip_pusch_decode: staging allocation failed\n");
     return SRSRAN_ERROR;
   }
+  // the estimator's launch: job k is the k-th grant of the layout, as the equaliser's; it stores the slot's row to every data symbol of the slot in the
+  // layout the equaliser reads (pusch_get order) and the equaliser's job k -- end of the grant's run of symbol pairs, noise estimate -- next to it
+  auto*      cjobs = reinterpret_cast<chest_ul::Job*>(s.pin + o_cj);
+  const auto enqueue_chest = [&](hipStream_t st) {
+    const chest_ul::Params cp = {reinterpret_cast<const float2*>(s.pin.get()), reinterpret_cast<float2*>(s.dev + 2 * region), cjobs,
+                                 reinterpret_cast<chest_ul::Record*>(s.pin + o_rec), reinterpret_cast<modem::EqJob*>(s.dev + 3 * region), n,
+                                 (uint32_t)(pin_need / sizeof(cf_t)), (uint32_t)(tot / sizeof(cf_t))};
+    if (chest_ul::launch(cp, st) != hipSuccess) {
+      set_error("grant front end: channel estimator launch failed");
+      return false;
+    }
+    return true;
+  };
+  bool front_done = false; // the front end of the call has been enqueued
   std::vector<sch::TbItem> items(n);
   for (uint32_t i = 0; i < n; i++) {
     const srsran_hip_pusch_rx_t& x = g[i];
@@ -250,7 +324,9 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
         }
         const size_t idx = ((size_t)(l + slot * x.cp_nsymb) * x.cell_nof_prb + x.n_prb_tilde[slot]) * 12;
         memcpy(s.pin + p.o_sym + at, sf_symbols[i] + idx, wid);
-        memcpy(s.pin + p.o_ce + at, ce[i] + idx, wid);
+        if (!est) {
+          memcpy(s.pin + p.o_ce + at, ce[i] + idx, wid);
+        }
         at += wid;
       }
     }
@@ -259,30 +335,52 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
     }
     p.head = {x.tb.max_nof_iterations, 0.f, x.tb.llr_is_8bit != 0};
     const srsran_hip_grant_tb_t tb = x.tb;
-    const uint8_t *psym = s.pin + p.o_sym, *pce = s.pin + p.o_ce;
+    const uint8_t *psym = s.pin + p.o_sym, *pce = est ? nullptr : s.pin + p.o_ce;
     uint8_t *      dx = s.dev + p.o_x, *dz = s.dev + p.o_z;
     const float    noise = x.noise_estimate;
     const uint32_t L_prb = x.L_prb, nsymb = p.nof_symb;
     auto*          plan  = p.plan;
-    p.front = [=](hipStream_t st, void* d_e) { return enqueue_rx_front(st, tb, psym, pce, 1.0f, noise, L_prb, nsymb, dx, dz, plan, d_e); };
+    if (est) { // the estimator's launch ahead, and the equaliser takes its rows and its noise estimate from the device image (pce is not looked at)
+      const uint8_t*      dh  = s.dev + p.o_ce;
+      const modem::EqJob* eqj = reinterpret_cast<const modem::EqJob*>(s.dev + 3 * region);
+      p.front = [=, &enqueue_chest, &front_done](hipStream_t st, void* d_e) {
+        front_done = true;
+        return enqueue_chest(st) && enqueue_rx_front(st, tb, psym, dh, 1.0f, 0.f, L_prb, nsymb, dx, dz, plan, d_e, nullptr, eqj);
+      };
+    } else {
+      p.front = [=](hipStream_t st, void* d_e) { return enqueue_rx_front(st, tb, psym, pce, 1.0f, noise, L_prb, nsymb, dx, dz, plan, d_e); };
+    }
     // (with control information the transport block's e bits are what RI and CQI leave: G = H' - Q'ri - Q'cqi symbols, sch.c:1184-1190)
     const uint32_t G = uci ? x.tb.nof_re - uci[i].Q_prime_ri - uci[i].Q_prime_cqi : x.tb.nof_re;
     items[i] = {&p.head, softbuffers[i], &p.seg, qm_rm(x.tb), x.tb.rv, G * qm_of(x.tb.mod), nullptr, &p.front, data[i], false};
   }
   if (uci) { // a grant that does not reach the launch (sch_host.cpp refuses its soft buffer) leaves zeros
-    memset(s.pin + pl[0].o_uci, 0, pin_need - pl[0].o_uci);
+    memset(s.pin + pl[0].o_uci, 0, (est ? o_cj : pin_need) - pl[0].o_uci);
   }
-  // the front end of all grants at once (n > 1)
-  bool                     front_done = false;
+  for (uint32_t k = 0; est && k < n; k++) {
+    const srsran_hip_pusch_rx_t& x = g[ord[k]];
+    chest_ul::Job&               j = cjobs[k];
+    j          = stage_refs(s.pin, pl[ord[k]].o_refs, x, est[ord[k]], sf_symbols[ord[k]]);
+    j.o_out    = (uint32_t)(pl[ord[k]].o_sym / sizeof(cf_t));
+    j.row0[1]  = x.cp_nsymb - 1;
+    j.rows[0]  = x.cp_nsymb - 1;
+    j.rows[1]  = x.cp_nsymb - 1 - (x.shortened ? 1u : 0u);
+    j.end_pair = (uint32_t)((pl[ord[k]].o_sym + (size_t)x.tb.nof_re * sizeof(cf_t)) / (2 * sizeof(cf_t)));
+  }
+  // the front end of all grants at once (n > 1 or control information)
   size_t                   job_cur = 0, tile_cur = 0;
   const sch::GroupFrontEnd group   = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
     if (!front_done) {
-      auto* ej = reinterpret_cast<modem::EqJob*>(s.pin + o_eqj);
-      for (uint32_t k = 0; k < n; k++) {
+      auto*          ej = reinterpret_cast<modem::EqJob*>(est ? s.dev + 3 * region : s.pin + o_eqj);
+      const uint8_t* h  = est ? s.dev + 2 * region : s.pin + region;
+      if (est && !enqueue_chest(st)) {
+        return false;
+      }
+      for (uint32_t k = 0; !est && k < n; k++) {
         const srsran_hip_pusch_rx_t& x = g[ord[k]];
         ej[k] = {(uint32_t)((pl[ord[k]].o_sym + (size_t)x.tb.nof_re * sizeof(cf_t)) / (2 * sizeof(cf_t))), x.noise_estimate, x.noise_estimate > 0.f ? 1u : 0u};
       }
-      if (modem::launch_eq_jobs(s.pin, s.pin + region, s.dev, ej, n, (uint32_t)(tot / (2 * sizeof(cf_t))), 1.0f, st) != hipSuccess) {
+      if (modem::launch_eq_jobs(s.pin, h, s.dev, ej, n, (uint32_t)(tot / (2 * sizeof(cf_t))), 1.0f, st) != hipSuccess) {
         set_error("grant front end: equaliser launch failed");
         return false;
       }
@@ -359,6 +457,18 @@ static int pusch_decode_grants(uint32_t n, const srsran_hip_pusch_rx_t* g, const
   if (!device_ok) { // not a CRC failure: the caller must not take it for a NACK
     return SRSRAN_ERROR;
   }
+  if (est) {
+    if (!front_done) { // no grant reached the launch (sch_host.cpp dropped every soft buffer): the measurements are still the call's
+      hipStream_t st = sch::stage_stream();
+      if (!st || !enqueue_chest(st) || hipStreamSynchronize(st) != hipSuccess) {
+        return SRSRAN_ERROR;
+      }
+    }
+    const auto* rec = reinterpret_cast<const chest_ul::Record*>(s.pin + o_rec);
+    for (uint32_t k = 0; k < n; k++) {
+      chest_ul::finish(rec[k], est[ord[k]].meas_ta_en != 0, &est_out[ord[k]]);
+    }
+  }
   for (uint32_t i = 0; uci && i < n; i++) {
     const srsran_hip_pusch_uci_t& u = uci[i];
     if (!has_uci(u)) {
@@ -431,6 +541,107 @@ extern "C" int srsran_hip_pusch_decode(const srsran_hip_pusch_rx_t* g, const cf_
                                        uint8_t* data, srsran_hip_grant_res_t* res)
 {
   return srsran_hip_pusch_decode_multi(1, g, &sf_symbols, &ce, &softbuffer, &data, res);
+}
+
+// ------------------------------------------------------------------------------------------------ PUSCH channel estimation
+
+extern "C" int srsran_hip_pusch_decode_est_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const srsran_hip_pusch_uci_t* uci,
+                                                 const cf_t* const* sf_symbols, srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* data,
+                                                 srsran_hip_grant_res_t* res, const srsran_hip_pusch_uci_out_t* uci_out, srsran_hip_chest_ul_res_t* est_out)
+{
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  bool any = false;
+  for (uint32_t i = 0; i < n; i++) { // every result, before anything is checked
+    if (res) {
+      res[i] = {0, 0.f, NAN};
+    }
+    if (est_out) {
+      est_out[i] = {};
+    }
+    any = any || (uci && has_uci(uci[i]));
+  }
+  if (!g || !est || !res || !est_out) {
+    return refuse("srsran_hip_pusch_decode_est: NULL argument");
+  }
+  return pusch_decode_grants(n, g, any ? uci : nullptr, sf_symbols, nullptr, softbuffers, data, res, uci_out, est, est_out);
+}
+
+extern "C" int srsran_hip_pusch_decode_est(const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const srsran_hip_pusch_uci_t* uci,
+                                           const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res,
+                                           srsran_hip_pusch_uci_out_t* uci_out, srsran_hip_chest_ul_res_t* est_out)
+{
+  return srsran_hip_pusch_decode_est_multi(1, g, est, uci, &sf_symbols, &softbuffer, &data, res, uci_out, est_out);
+}
+
+// the stage by itself: the kernel's rows come down in the pinned image, one per slot, and are copied to the grant's columns of every symbol of the slot
+extern "C" int srsran_hip_chest_ul_estimate_pusch_multi(uint32_t n, const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est,
+                                                        const cf_t* const* sf_symbols, cf_t* const* ce, srsran_hip_chest_ul_res_t* out)
+{
+  static const char* who = "srsran_hip_chest_ul_estimate_pusch";
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  for (uint32_t i = 0; out && i < n; i++) {
+    out[i] = {};
+  }
+  if (!g || !est || !sf_symbols || !out) {
+    return refuse("%s: NULL argument", who);
+  }
+  size_t points = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const srsran_hip_pusch_rx_t& x = g[i];
+    if (!sf_symbols[i] || chest_ul::invalid(&est[i])) {
+      return refuse("%s: grant %u: %s", who, i, sf_symbols[i] ? chest_ul::invalid(&est[i]) : "NULL sf_symbols");
+    }
+    if (!alloc_valid(x)) {
+      return refuse("%s: grant %u: allocation (%u PRB at %u / %u of %u, %u symbols per slot) is not a PUSCH allocation", who, i, x.L_prb, x.n_prb_tilde[0],
+                    x.n_prb_tilde[1], x.cell_nof_prb, x.cp_nsymb);
+    }
+    points += (size_t)12 * x.L_prb;
+  }
+  ChanStage*  s  = stage_for(who);
+  hipStream_t st = s ? sch::stage_stream() : nullptr;
+  // pinned: every grant's four input rows, every grant's two output rows, the jobs, the records
+  const size_t o_out = al256(4 * points * sizeof(cf_t)), o_cj = al256(o_out + 2 * points * sizeof(cf_t)), o_rec = al256(o_cj + n * sizeof(chest_ul::Job));
+  const size_t need  = o_rec + n * sizeof(chest_ul::Record);
+  if (!st || !s->grow(need, 0)) {
+    return SRSRAN_ERROR;
+  }
+  auto*  jobs = reinterpret_cast<chest_ul::Job*>(s->pin + o_cj);
+  size_t at   = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    jobs[i]         = stage_refs(s->pin, 4 * at * sizeof(cf_t), g[i], est[i], sf_symbols[i]);
+    jobs[i].o_out   = (uint32_t)(2 * at);
+    jobs[i].row0[1] = 1;
+    jobs[i].rows[0] = jobs[i].rows[1] = 1;
+    at += (size_t)12 * g[i].L_prb;
+  }
+  const auto*            rec = reinterpret_cast<const chest_ul::Record*>(s->pin + o_rec);
+  const chest_ul::Params cp  = {reinterpret_cast<const float2*>(s->pin.get()), reinterpret_cast<float2*>(s->pin + o_out), jobs,
+                                reinterpret_cast<chest_ul::Record*>(s->pin + o_rec), nullptr, n, (uint32_t)(4 * points), (uint32_t)(2 * points)};
+  const bool launched = chest_ul::launch(cp, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+    set_error("%s: channel estimator launch failed", who);
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const srsran_hip_pusch_rx_t& x   = g[i];
+    const size_t                 wid = (size_t)12 * x.L_prb * sizeof(cf_t);
+    for (uint32_t l = 0; ce && ce[i] && l < 2 * x.cp_nsymb; l++) {
+      const uint32_t slot = l / x.cp_nsymb;
+      memcpy(ce[i] + ((size_t)l * x.cell_nof_prb + x.n_prb_tilde[slot]) * 12, s->pin + o_out + (size_t)jobs[i].o_out * sizeof(cf_t) + slot * wid, wid);
+    }
+    chest_ul::finish(rec[i], est[i].meas_ta_en != 0, &out[i]);
+  }
+  return SRSRAN_SUCCESS;
+}
+
+extern "C" int srsran_hip_chest_ul_estimate_pusch(const srsran_hip_pusch_rx_t* g, const srsran_hip_chest_ul_t* est, const cf_t* sf_symbols, cf_t* ce,
+                                                  srsran_hip_chest_ul_res_t* out)
+{
+  return srsran_hip_chest_ul_estimate_pusch_multi(1, g, est, &sf_symbols, &ce, out);
 }
 
 // ------------------------------------------------------------------------------------------------ PDSCH receive, one codeword

@@ -388,6 +388,128 @@ SRSRAN_API int srsran_hip_pdsch_decode_mimo_sf_dbg(const srsran_hip_pdsch_mimo_r
                                                    float* const csi_out[SRSRAN_MAX_CODEWORDS], cf_t* const sym_out[],
                                                    cf_t* const (*ce_out)[SRSRAN_MAX_PORTS]);
 
+/* ---- Downlink channel estimation on the device (srsran_chest_dl_estimate_cfg, chest_dl.c:1004, with estimate_port, average_pilots, interpolate_pilots, the
+ * three noise estimators, chest_dl_rssi, chest_estimate_cfo and fill_res, srsran_conv_same_cf, srsran_interp_linear_offset and srsran_interp_linear_vector{,2}),
+ * restated AS WRITTEN: with it the PDSCH receive calls start at the level of srsran_ue_dl_decode_fft_estimate / srsran_pdsch_decode.  One launch, one
+ * workgroup per (rx antenna, port) pair, one host wait; a call gives the same bits every time.  Kept as the reference has them: estimate_noise_pilots
+ * returns the last CRS symbol's power only; get_rsrp walks ports with an antenna counter; srsran_conv_same_cf's uneven end extrapolation; the AVERAGE path
+ * interpolates every port with offset id % 3 and, without a filter, reads the first 4 nof_prb raw estimates as one row; ports 2 and 3 extrapolate the symbols
+ * behind their second CRS symbol from the first; time interpolation is a chain of additions; automatic Gauss taps from a noise estimate of 0 give a filter of
+ * length 0 and a ce of zeros.  One difference: ce is computed whether or not the caller takes it, so the PSS / EMPTY noise estimates do not depend on a NULL
+ * ce (the reference skips them then).
+ * Taken: SRSRAN_SF_NORM subframes with the full CRS pattern; 1, 2 and 4 ports; 1 .. 4 receive antennas; both cyclic prefixes; 6 .. 110 PRB; AVERAGE and
+ * INTERPOLATE; filters NONE, TRIANGLE and GAUSS (fixed taps: order filter_coef[0] <= 8, i.e. at most 9 taps; automatic taps with filter_coef[0] <= 0: order 4,
+ * std 200 x the pair's noise estimate -- this call's with REFS, the state's otherwise); noise algorithms REFS, PSS and EMPTY; rsrp_neighbour; the CFO estimate
+ * on cells of 1 or 2 ports.
+ * State is the caller's: the reference's object keeps noise_estimate[rx][port] and cfo between subframes (PSS / EMPTY estimates change in subframes 0 and 5
+ * only, cfo in the subframes of the mask only); the caller hands them in (all zero at start) and takes them from res->state.  rsrp_corr without
+ * rsrp_neighbour and sync_err are 0 (a fresh object's).
+ * Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *res zeroed and nothing else written: NULL cfg, state, grids
+ * or res, a NULL grid or pilot row that the call reads, a field out of range, estimator_alg WIENER, sf_type MBSFN, a TDD special subframe, sync_error_enable
+ * (it rewrites the caller's grid), more than 9 taps or a non-finite coefficient that is read, cfo_estimate_enable on a 4-port cell (the reference reads the
+ * previous port's stale estimates there), noise_alg PSS without pss_signal, a negative or non-finite state. */
+#define SRSRAN_HIP_ESTIMATOR_ALG_AVERAGE 0 /* srsran_chest_dl_estimator_alg_t */
+#define SRSRAN_HIP_ESTIMATOR_ALG_INTERPOLATE 1
+#define SRSRAN_HIP_ESTIMATOR_ALG_WIENER 2 /* refused */
+#define SRSRAN_HIP_NOISE_ALG_REFS 0 /* srsran_chest_dl_noise_alg_t */
+#define SRSRAN_HIP_NOISE_ALG_PSS 1
+#define SRSRAN_HIP_NOISE_ALG_EMPTY 2
+#define SRSRAN_HIP_CHEST_FILTER_GAUSS 0 /* srsran_chest_filter_t */
+#define SRSRAN_HIP_CHEST_FILTER_TRIANGLE 1
+#define SRSRAN_HIP_CHEST_FILTER_NONE 2
+#define SRSRAN_HIP_CHEST_DL_MAX_TAPS 9
+typedef struct SRSRAN_API {
+  uint32_t nof_prb;              /* cell: 6 .. 110 */
+  uint32_t nof_ports;            /* 1, 2 or 4 */
+  uint32_t id;                   /* 0 .. 503 */
+  uint32_t cp_nsymb;             /* 7 or 6 */
+  uint32_t nof_rx;               /* q->nof_rx_antennas: 1 .. 4 */
+  uint32_t sf_idx;               /* sf->tti % 10 */
+  uint32_t sf_type;              /* sf->sf_type: 0 (SRSRAN_SF_NORM); 1 (MBSFN) is refused */
+  uint32_t tdd_special;          /* 1: a TDD special subframe (srsran_sfidx_tdd_type(...) == SRSRAN_TDD_SF_S) -- refused */
+  uint32_t estimator_alg;        /* cfg->estimator_alg */
+  uint32_t noise_alg;            /* cfg->noise_alg */
+  uint32_t filter_type;          /* cfg->filter_type */
+  float    filter_coef[2];       /* cfg->filter_coef */
+  uint32_t rsrp_neighbour;       /* cfg->rsrp_neighbour */
+  uint32_t cfo_estimate_enable;  /* cfg->cfo_estimate_enable */
+  uint32_t cfo_estimate_sf_mask; /* cfg->cfo_estimate_sf_mask */
+  uint32_t sync_error_enable;    /* cfg->sync_error_enable: 1 is refused */
+  uint32_t decoder_zf;           /* read by srsran_hip_pdsch_decode_est only: 1 = cfg->decoder_type is SRSRAN_MIMO_DECODER_ZF, the equaliser gets 0 in place of
+                                    get_noise() (pdsch.c:819); 0 or 1 */
+  const cf_t* pilots[2];         /* q->csr_refs.pilots[p][sf_idx]: 8 nof_prb points (ports 0, 1) and 4 nof_prb points (ports 2, 3; read on a 4-port cell), HOST
+                                    memory.  The library does not generate the CRS rows */
+  const cf_t* pss_signal;        /* q->pss_signal, 62 points: read with noise_alg PSS, may be NULL otherwise */
+} srsran_hip_chest_dl_t;
+typedef struct SRSRAN_API { /* what the reference's object carries from subframe to subframe */
+  float noise_estimate[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]; /* [rx][port] */
+  float cfo;
+} srsran_hip_chest_dl_state_t;
+typedef struct SRSRAN_API { /* srsran_chest_dl_res_t behind fill_res (entries it does not set are 0), the object's per-pair values, the state out */
+  float noise_estimate;
+  float noise_estimate_dbm;
+  float snr_db;
+  float snr_ant_port_db[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS];
+  float rsrp;
+  float rsrp_dbm;
+  float rsrp_neigh;
+  float rsrp_port_dbm[SRSRAN_MAX_PORTS];
+  float rsrp_ant_port_dbm[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS];
+  float rsrq;
+  float rsrq_db;
+  float rsrq_ant_port_db[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS];
+  float rssi_dbm;
+  float cfo;
+  float sync_error;                                    /* 0 */
+  float rsrp_pair[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS];      /* q->rsrp[rx][port] */
+  float rssi_pair[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS];      /* q->rssi[rx][port] */
+  float rsrp_corr_pair[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]; /* q->rsrp_corr[rx][port] */
+  srsran_hip_chest_dl_state_t state;                   /* hand it to the next subframe's call */
+} srsran_hip_chest_dl_res_t;
+/* the stage by itself -- also what a UE binding calls ahead of PCFICH / PDCCH / PHICH, which stay on the host and need the grids.  sf_symbols[rx]: the
+ * received grids, 2 cp_nsymb x 12 nof_prb points each, HOST memory, only read.  ce: NULL (the measurements only), or what a caller passes res->ce as
+ * (cf_t* ce[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = [port][rx]); a NULL entry is not written.  The measurements do not depend on which entries are there. */
+SRSRAN_API int srsran_hip_chest_dl_estimate(const srsran_hip_chest_dl_t* cfg, const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
+                                            cf_t* const (*ce)[SRSRAN_MAX_PORTS], srsran_hip_chest_dl_res_t* res);
+
+/* the grant calls from the grids alone: the arguments of the _sf twin without ce, and the estimator's description, the state and est_out (what the stage
+ * returns) in their place.  The caller's noise_estimate is not read: the equaliser takes get_noise() of this subframe's estimates (chest_dl.c:868-878), averaged
+ * on the device, or 0 when the grant asks for zero forcing (pdsch.c:819: est->decoder_zf on one port, g->decoder with MIMO; diversity combining takes none).
+ * Inside the one receive frame the host stages the received grids only (whole: the estimator reads every CRS symbol), the estimator's kernel writes the ce
+ * grids into device scratch, the de-mapping kernel reads them there, and the twin's front-end kernels run unchanged: one launch more than the _sf twin, still
+ * one host wait.  The call re-estimates rather than taking a handle from the stage call: between the two the UE decodes the PDCCH on the host.
+ * Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *res = {0, 0, NAN}, *est_out zeroed and nothing else written:
+ * everything the _sf twin refuses, everything srsran_hip_chest_dl_estimate refuses, an estimator description whose cell, subframe or antenna count is not
+ * the call's, a grant that does not span both whole slots (nof_symb_slot[s] != cp_nsymb: the estimator's grids), decoder_zf above 1.
+ * SRSRAN_ERROR with est_out left zeroed when the front end did not run (every code block decoded in an earlier round, or a soft buffer with too few rows).
+ * _est_dbg: the outputs of the _sf_dbg twin and ce_grid_out[port][rx] (the array or an entry may be NULL) <- the pair's whole ce grid. */
+SRSRAN_API int srsran_hip_pdsch_decode_est(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                           const srsran_hip_chest_dl_state_t* state_in, const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                           srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out);
+SRSRAN_API int srsran_hip_pdsch_decode_est_dbg(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                               const srsran_hip_chest_dl_state_t* state_in, const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                               srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out, cf_t* d_out, void* e_out, float* csi_out, cf_t* sym_out,
+                                               cf_t* ce_out, cf_t* ce_grid_out);
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_est(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                 const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* softbuffer,
+                                                 uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out);
+SRSRAN_API int srsran_hip_pdsch_decode_txdiv_est_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                     const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* softbuffer,
+                                                     uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out, cf_t* d_out, void* e_out,
+                                                     float* csi_out, cf_t* const sym_out[], cf_t* const (*ce_out)[SRSRAN_MAX_PORTS],
+                                                     cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS]);
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_est(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], srsran_hip_chest_dl_res_t* est_out);
+SRSRAN_API int srsran_hip_pdsch_decode_mimo_est_dbg(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                    const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
+                                                    srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                    srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], srsran_hip_chest_dl_res_t* est_out,
+                                                    cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
+                                                    float* const csi_out[SRSRAN_MAX_CODEWORDS], cf_t* const sym_out[], cf_t* const (*ce_out)[SRSRAN_MAX_PORTS],
+                                                    cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS]);
+
 /* ---- UL-SCH transmit without UCI (srsran_ulsch_encode, sch.c:1194-1340, with no ACK / RI / CQI configured): encode_tb -> channel
  * interleaver of 36.212 5.2.2.8 over nof_symb columns.  q_bits: nof_bits = nof_re * Qm bits, byte packed (what pusch.c:322 scrambles next). */
 SRSRAN_API int srsran_hip_ulsch_encode(const srsran_hip_grant_tb_t* tb, uint32_t nof_symb, srsran_softbuffer_tx_t* softbuffer, uint8_t* data, uint8_t* q_bits);

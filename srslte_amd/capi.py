@@ -163,6 +163,24 @@ class HipChestUlRes(C.Structure):  # srsran_hip_chest_ul_res_t
                 ("ta_us", C.c_float)]
 
 
+class HipChestDl(C.Structure):  # srsran_hip_chest_dl_t
+    _fields_ = ([(n, C.c_uint32) for n in ("nof_prb", "nof_ports", "id", "cp_nsymb", "nof_rx", "sf_idx", "sf_type", "tdd_special", "estimator_alg", "noise_alg",
+                                           "filter_type")] + [("filter_coef", C.c_float * 2)] +
+                [(n, C.c_uint32) for n in ("rsrp_neighbour", "cfo_estimate_enable", "cfo_estimate_sf_mask", "sync_error_enable", "decoder_zf")] +
+                [("pilots", C.c_void_p * 2), ("pss_signal", C.c_void_p)])
+
+
+class HipChestDlState(C.Structure):  # srsran_hip_chest_dl_state_t
+    _fields_ = [("noise_estimate", C.c_float * 4 * 4), ("cfo", C.c_float)]
+
+
+class HipChestDlRes(C.Structure):  # srsran_hip_chest_dl_res_t
+    _fields_ = [("noise_estimate", C.c_float), ("noise_estimate_dbm", C.c_float), ("snr_db", C.c_float), ("snr_ant_port_db", C.c_float * 4 * 4), ("rsrp", C.c_float),
+                ("rsrp_dbm", C.c_float), ("rsrp_neigh", C.c_float), ("rsrp_port_dbm", C.c_float * 4), ("rsrp_ant_port_dbm", C.c_float * 4 * 4), ("rsrq", C.c_float),
+                ("rsrq_db", C.c_float), ("rsrq_ant_port_db", C.c_float * 4 * 4), ("rssi_dbm", C.c_float), ("cfo", C.c_float), ("sync_error", C.c_float),
+                ("rsrp_pair", C.c_float * 4 * 4), ("rssi_pair", C.c_float * 4 * 4), ("rsrp_corr_pair", C.c_float * 4 * 4), ("state", HipChestDlState)]
+
+
 class HipPuschTx(C.Structure):  # srsran_hip_pusch_tx_t
     _fields_ = [("tb", HipGrantTb), ("cell_nof_prb", C.c_uint32), ("cp_nsymb", C.c_uint32), ("n_prb_tilde", C.c_uint32 * 2), ("L_prb", C.c_uint32),
                 ("shortened", C.c_uint32)]
@@ -632,6 +650,24 @@ def lib():
             "srsran_hip_pdsch_decode_mimo_sf_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(HipPdschSf), C.POINTER(vp), C.POINTER(PlaneArray),
                                                           C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes), C.POINTER(vp), C.POINTER(vp),
                                                           C.POINTER(vp), C.POINTER(vp), C.POINTER(PlaneArray)]),
+            "srsran_hip_chest_dl_estimate": (i32, [C.POINTER(HipChestDl), C.POINTER(HipChestDlState), C.POINTER(vp), C.POINTER(PlaneArray),
+                                                   C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pdsch_decode_est": (i32, [C.POINTER(HipPdschRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp,
+                                                  C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pdsch_decode_est_dbg": (i32, [C.POINTER(HipPdschRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp,
+                                                      C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), C.POINTER(HipChestDlRes), vp, vp, vp, vp, vp, vp]),
+            "srsran_hip_pdsch_decode_txdiv_est": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState),
+                                                        C.POINTER(vp), C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pdsch_decode_txdiv_est_dbg": (i32, [C.POINTER(HipPdschTxdivRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState),
+                                                            C.POINTER(vp), C.POINTER(SoftbufferRx), vp, C.POINTER(HipGrantRes), C.POINTER(HipChestDlRes), vp, vp, vp,
+                                                            C.POINTER(vp), C.POINTER(PlaneArray), C.POINTER(PlaneArray)]),
+            "srsran_hip_pdsch_decode_mimo_est": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState),
+                                                       C.POINTER(vp), C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes),
+                                                       C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pdsch_decode_mimo_est_dbg": (i32, [C.POINTER(HipPdschMimoRx), C.POINTER(HipPdschSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState),
+                                                           C.POINTER(vp), C.POINTER(C.POINTER(SoftbufferRx)), C.POINTER(vp), C.POINTER(HipGrantRes),
+                                                           C.POINTER(HipChestDlRes), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                           C.POINTER(PlaneArray), C.POINTER(PlaneArray)]),
             "srsran_hip_ulsch_encode": (i32, [C.POINTER(HipGrantTb), u32, C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pusch_encode": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp]),
             "srsran_hip_pusch_encode_dbg": (i32, [C.POINTER(HipPuschTx), C.POINTER(HipPuschUci), C.POINTER(HipPuschUciIn), C.POINTER(SoftbufferTx), vp, vp, vp, vp,

@@ -3,6 +3,7 @@
 // (sch.c:1194) chained on the calling thread's transport-block stream, nothing but the inputs and the results crossing the bus.
 #include "chan_device.h"
 #include "chan_internal.h"
+#include "chest_dl_device.h"
 #include "chest_ul_device.h"
 #include "csi_device.h"
 #include "modem_device.h"
@@ -78,11 +79,12 @@ namespace {
 // kernel ahead on the stream fills with the noise estimate (`noise` is then not looked at; nof_re is even).
 bool enqueue_rx_front(hipStream_t st, const srsran_hip_grant_tb_t& tb, const uint8_t* p_sym, const uint8_t* p_ce, float scaling, float noise, uint32_t L_prb,
                       uint32_t nof_symb, uint8_t* d_x, uint8_t* d_z, srsran_hip_dft_batch_t* plan, void* d_e, float* d_csi = nullptr,
-                      const modem::EqJob* d_eqj = nullptr)
+                      const modem::EqJob* d_eqj = nullptr, const modem::NoiseAvg* dev_noise = nullptr)
 {
   const uint8_t* cur = p_sym;
   if (p_ce) {
-    if ((d_eqj ? modem::launch_eq_jobs(p_sym, p_ce, d_x, d_eqj, 1, tb.nof_re / 2, scaling, st) : modem::launch_eq(p_sym, p_ce, d_x, d_csi, tb.nof_re, scaling, noise, st)) !=
+    if ((d_eqj ? modem::launch_eq_jobs(p_sym, p_ce, d_x, d_eqj, 1, tb.nof_re / 2, scaling, st)
+               : modem::launch_eq(p_sym, p_ce, d_x, d_csi, tb.nof_re, scaling, noise, st, dev_noise)) !=
         hipSuccess) {
       set_error("grant front end: equaliser launch failed");
       return false;
@@ -651,18 +653,19 @@ extern "C" int srsran_hip_chest_ul_estimate_pusch(const srsran_hip_pusch_rx_t* g
 // map: the _sf forms -- symbols and ce are grids.
 static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch_rx_t* g, const cf_t* symbols, const cf_t* ce, const float* csi,
                             srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out,
-                            const SfMap* map = nullptr)
+                            const SfMap* map = nullptr, EstMap* est = nullptr)
 {
   TraceRange trace_("srsran_hip_pdsch_decode");
   if (!g || !symbols || !softbuffer || !data || !res) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   *res = {0, 0.f, NAN};
-  if (!tb_valid(g->tb, who) || (ce && !(g->scaling != 0.f))) {
+  const bool eq = ce != nullptr || est != nullptr; // est: the estimates are made on the device (the _est calls)
+  if (!tb_valid(g->tb, who) || (eq && !(g->scaling != 0.f))) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (weight && (ce != nullptr) == (csi != nullptr)) {
-    return refuse("%s: %s", who, ce ? "the equaliser makes the CSI of a grant with channel estimates: csi must be NULL" : "a grant without channel estimates needs the caller's csi");
+  if (weight && eq == (csi != nullptr)) {
+    return refuse("%s: %s", who, eq ? "the equaliser makes the CSI of a grant with channel estimates: csi must be NULL" : "a grant without channel estimates needs the caller's csi");
   }
   if (weight && csi && !csi_row_valid(csi, g->tb.nof_re)) {
     return refuse("%s: a csi entry is negative or not finite", who);
@@ -670,13 +673,22 @@ static int pdsch_decode_one(const char* who, bool weight, const srsran_hip_pdsch
   if (map && !sf_valid(who, map->sf, 1, g->tb.nof_re)) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
+  if (est && !est_valid(who, est, map ? map->sf : nullptr, 1)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
   cf_t *const  y[1] = {const_cast<cf_t*>(symbols)}, *const h[1] = {const_cast<cf_t*>(ce)};
   const size_t nd   = (size_t)g->tb.nof_re * sizeof(cf_t);
-  PlaneGroup   in[2] = {{y, 1, nd, true, false}, {h, ce ? 1u : 0u, nd, true, false}};
-  RxGrant      gr = {who, in, 2, map, csi, {{&g->tb, qm_rm(g->tb), softbuffer, data, res, d_out, e_out, csi_out}}, 1, ce ? 1u : 0u, ce != nullptr, weight};
+  PlaneGroup   in[2] = {{y, 1, nd, true, false}, {est ? nullptr : h, eq ? 1u : 0u, nd, true, false}};
+  RxGrant      gr = {who, in, 2, map, csi, {{&g->tb, qm_rm(g->tb), softbuffer, data, res, d_out, e_out, csi_out}}, 1, eq ? 1u : 0u, eq, weight, est};
+  // (the _est calls: get_noise() of this subframe's estimates, averaged on the device, or 0 for zero forcing; the caller's noise_estimate is not read)
+  const bool dev_noise = est && !est->cfg->decoder_zf;
   return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
-    return enqueue_rx_front(st, g->tb, reinterpret_cast<uint8_t*>(in[0].pin[0]), reinterpret_cast<uint8_t*>(in[1].pin[0]), g->scaling, g->noise_estimate, 0, 0, d_d, nullptr,
-                            nullptr, d_e[0], ce ? row[0] : nullptr);
+    if (!est) {
+      return enqueue_rx_front(st, g->tb, reinterpret_cast<uint8_t*>(in[0].pin[0]), reinterpret_cast<uint8_t*>(in[1].pin[0]), g->scaling, g->noise_estimate, 0, 0, d_d, nullptr,
+                              nullptr, d_e[0], eq ? row[0] : nullptr);
+    }
+    return enqueue_rx_front(st, g->tb, reinterpret_cast<uint8_t*>(in[0].pin[0]), reinterpret_cast<uint8_t*>(in[1].pin[0]), g->scaling, 0.f, 0, 0, d_d, nullptr, nullptr,
+                            d_e[0], row[0], nullptr, dev_noise ? &est->noise : nullptr);
   });
 }
 
@@ -802,6 +814,45 @@ extern "C" int srsran_hip_pdsch_decode_sf_dbg(const srsran_hip_pdsch_rx_t* g, co
   return pdsch_decode_one_sf(g, sf, sf_symbols, ce, softbuffer, data, res, d_out, e_out, csi_out, sym_out, ce_out);
 }
 
+// the one-port call from the grids alone: the _sf call's path with the estimator's kernel in front (chest_dl_kernels.hip)
+static int pdsch_decode_one_est(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est, const srsran_hip_chest_dl_state_t* state_in,
+                                const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out,
+                                cf_t* d_out, void* e_out, float* csi_out, cf_t* sym_out, cf_t* ce_out, cf_t* ce_grid_out)
+{
+  static const char* who = "srsran_hip_pdsch_decode_est";
+  if (res) {
+    *res = {0, 0.f, NAN};
+  }
+  if (est_out) {
+    *est_out = {};
+  }
+  if (!g || !sf || !est || !state_in || !sf_symbols || !softbuffer || !data || !res || !est_out) {
+    return refuse("%s: NULL argument", who);
+  }
+  if (!(g->scaling != 0.f)) {
+    return refuse("%s: scaling is 0", who);
+  }
+  const SfMap map    = {sf, {sym_out, ce_out}};
+  EstMap      em     = {est, state_in, est_out, {{ce_grid_out}}, {}};
+  const bool  weight = sf->csi_enable != 0;
+  return pdsch_decode_one(who, weight, g, sf_symbols, nullptr, nullptr, softbuffer, data, res, d_out, e_out, weight ? csi_out : nullptr, &map, &em);
+}
+
+extern "C" int srsran_hip_pdsch_decode_est(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                           const srsran_hip_chest_dl_state_t* state_in, const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                           srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out)
+{
+  return pdsch_decode_one_est(g, sf, est, state_in, sf_symbols, softbuffer, data, res, est_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_est_dbg(const srsran_hip_pdsch_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                               const srsran_hip_chest_dl_state_t* state_in, const cf_t* sf_symbols, srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                               srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out, cf_t* d_out, void* e_out, float* csi_out, cf_t* sym_out,
+                                               cf_t* ce_out, cf_t* ce_grid_out)
+{
+  return pdsch_decode_one_est(g, sf, est, state_in, sf_symbols, softbuffer, data, res, est_out, d_out, e_out, csi_out, sym_out, ce_out, ce_grid_out);
+}
+
 // ------------------------------------------------------------------------------------------------ PDSCH receive, the frame of every grant call
 
 int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
@@ -825,7 +876,11 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
   for (uint32_t i = 0; i < g.n_in; i++) {
     n_pl += g.in[i].k;
   }
-  const size_t sb = al256((size_t)w.staged_points() * sizeof(cf_t)), o_tab = n_pl * sb;
+  // (with g.est: the estimator's input first -- whole grids, one behind the other -- and the table over whole grids)
+  const chest_dl::Layout el      = g.est ? chest_dl::layout_of(*g.est->cfg) : chest_dl::Layout{};
+  const uint32_t         n_pairs = g.est ? g.est->cfg->nof_rx * g.est->cfg->nof_ports : 0;
+  const size_t           gb      = (size_t)el.grid_points * sizeof(cf_t);
+  const size_t sb = g.est ? gb : al256((size_t)w.staged_points() * sizeof(cf_t)), o_tab = g.est ? al256((size_t)el.in_points * sizeof(cf_t)) : n_pl * sb;
   const size_t o_d = g.map ? o_tab + al256(w.n_seg * sizeof(pdsch_map::Seg)) : plane_room(g.in, g.n_in);
   size_t       ne[2] = {0, 0}, o_e[2] = {0, 0}, o_c = o_d + g.d_planes * nb;
   for (uint32_t k = 0; k < g.n_cw; k++) {
@@ -841,11 +896,36 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     want_m = want_m || g.map->out[i];
   }
   const size_t o_dm = o_dc + (dev_rows ? g.n_cw * nc : 0), o_m = o_c + g.n_cw * nc;
-  if (n_pl > PDSCH_MAX_RX_PLANES || !s.grow(o_m + (want_m ? n_pl * nb : 0), o_dm + (g.map ? n_pl * nb : 0))) {
+  // the estimator's jobs and records, and pinned room for the ce grids _est_dbg asked for; device: its ce grids behind the planes, the pairs' noise estimates
+  bool want_g = false;
+  for (uint32_t i = 0; i < n_pairs; i++) {
+    want_g = want_g || g.est->grid_out[i % g.est->cfg->nof_ports][i / g.est->cfg->nof_ports];
+  }
+  const size_t o_ej = al256(o_m + (want_m ? n_pl * nb : 0)), o_er = al256(o_ej + n_pairs * sizeof(chest_dl::Job));
+  const size_t o_eg = al256(o_er + n_pairs * sizeof(chest_dl::Record)), pin_need = g.est ? o_eg + (want_g ? n_pairs * gb : 0) : o_m + (want_m ? n_pl * nb : 0);
+  const size_t o_dg = al256(o_dm + (g.map ? n_pl * nb : 0)), o_dn = o_dg + al256(n_pairs * gb), dev_need = g.est ? o_dn + 256 : o_dm + (g.map ? n_pl * nb : 0);
+  if (n_pl > PDSCH_MAX_RX_PLANES || (g.est && !g.map) || !s.grow(pin_need, dev_need)) {
     fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", g.who);
     return SRSRAN_ERROR;
   }
-  if (g.map) {
+  auto* ejobs = reinterpret_cast<chest_dl::Job*>(s.pin + o_ej);
+  if (g.est) {
+    const srsran_hip_chest_dl_t& c = *g.est->cfg;
+    chest_dl::stage_input(reinterpret_cast<cf_t*>(s.pin.get()), c, el, g.in[0].host);
+    chest_dl::make_jobs(ejobs, c, *g.est->state, el);
+    for (uint32_t i = 0; i < n_pairs; i++) { // the ce grids in the order of the planes: [port][rx]
+      ejobs[i].o_ce = ((i % c.nof_ports) * c.nof_rx + i / c.nof_ports) * el.grid_points;
+    }
+    for (uint32_t at = 0; at < n_pl; at++) {
+      uint32_t i = 0, k = at;
+      for (; k >= g.in[i].k; k -= g.in[i].k, i++) {
+      }
+      g.in[i].pin[k] = reinterpret_cast<cf_t*>(s.dev + o_dm + at * nb);
+    }
+    const pdsch_map::Window whole = {0, 2 * c.cp_nsymb, 0, c.nof_prb, w.n_seg, w.nof_re};
+    pdsch_map::fill_table(*g.map->sf, whole, reinterpret_cast<pdsch_map::Seg*>(s.pin + o_tab));
+    g.est->noise = {reinterpret_cast<const float*>(s.dev + o_dn), c.nof_rx, c.nof_ports};
+  } else if (g.map) {
     uint32_t at = 0;
     for (uint32_t i = 0; i < g.n_in; i++) {
       for (uint32_t k = 0; k < g.in[i].k; k++, at++) {
@@ -883,7 +963,7 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     items[n_items++] = {&head[k], c.sb, &seg[k], c.Qm, c.tb->rv, nof_re * qm_of(c.tb->mod), nullptr, &device_made, c.data, false};
   }
   // what the front end actually made: it does not run for a codeword the transport-block stage drops
-  bool                     d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false}, m_made = false;
+  bool                     d_made = false, e_made[2] = {false, false}, c_made[2] = {false, false}, m_made = false, est_made = false, g_made = false;
   const sch::GroupFrontEnd group  = [&](hipStream_t st, const uint32_t* which, void* const* d_e, uint32_t m) -> bool {
     void*       de[2] = {nullptr, nullptr};
     CsiCodeword wj[2];
@@ -892,9 +972,22 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
       de[k] = d_e[j];
       wj[j] = {d_e[j], row[k], g.cw[k].tb->mod};
     }
+    if (g.est) {
+      const chest_dl::Params cp = {reinterpret_cast<const float2*>(s.pin.get()), reinterpret_cast<float2*>(s.dev + o_dg), ejobs, reinterpret_cast<chest_dl::Record*>(s.pin + o_er),
+                                   reinterpret_cast<float*>(s.dev + o_dn), n_pairs, el.in_points, n_pairs * el.grid_points};
+      if (chest_dl::launch(cp, st) != hipSuccess) {
+        set_error("grant front end: channel estimator launch failed");
+        return false;
+      }
+      est_made = true;
+    }
     if (g.map) {
-      const pdsch_map::DemapParams dp = {reinterpret_cast<const float2*>(s.pin.get()), reinterpret_cast<float2*>(s.dev + o_dm), reinterpret_cast<const pdsch_map::Seg*>(s.pin + o_tab),
-                                         w.n_seg, n_pl, (uint32_t)(sb / sizeof(cf_t)), w.staged_points(), (uint32_t)(nb / sizeof(cf_t)), nof_re};
+      pdsch_map::DemapParams dp = {reinterpret_cast<const float2*>(s.pin.get()), reinterpret_cast<float2*>(s.dev + o_dm), reinterpret_cast<const pdsch_map::Seg*>(s.pin + o_tab),
+                                   w.n_seg, n_pl, (uint32_t)(sb / sizeof(cf_t)), g.est ? el.grid_points : w.staged_points(), (uint32_t)(nb / sizeof(cf_t)), nof_re};
+      if (g.est) { // the received grids from the pinned image, the ce grids from where the estimator left them
+        dp.in_b     = reinterpret_cast<const float2*>(s.dev + o_dg);
+        dp.planes_a = g.est->cfg->nof_rx;
+      }
       if (pdsch_map::launch_demap(dp, st) != hipSuccess) {
         set_error("grant front end: RE de-mapping launch failed");
         return false;
@@ -907,6 +1000,9 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
     d_made      = want_d && copied;
     if (copied && want_m) {
       copied = m_made = hipMemcpyAsync(s.pin + o_m, s.dev + o_dm, (n_pl - 1) * nb + nd, hipMemcpyDeviceToHost, st) == hipSuccess;
+    }
+    if (copied && want_g) {
+      copied = g_made = hipMemcpyAsync(s.pin + o_eg, s.dev + o_dg, n_pairs * gb, hipMemcpyDeviceToHost, st) == hipSuccess;
     }
     for (uint32_t j = 0; copied && j < m; j++) {
       const uint32_t k = cw_of[which[j]];
@@ -947,6 +1043,16 @@ int phyhip::chan::pdsch_decode_grant(RxGrant& g, const RxFront& front)
   }
   for (uint32_t i = 0; g.map && i < n_pl; i++) {
     hand_back(g.map->out[i], m_made, o_m + i * nb, nd);
+  }
+  if (g.est) { // the measurements from the pairs' records (behind the host wait); the front end did not run: they stay zeroed
+    const srsran_hip_chest_dl_t& c = *g.est->cfg;
+    if (est_made) {
+      chest_dl::finish(c, *g.est->state, reinterpret_cast<const chest_dl::Record*>(s.pin + o_er), srsran_symbol_sz(c.nof_prb), g.est->out);
+    }
+    missing = missing || !est_made;
+    for (uint32_t i = 0; i < n_pairs; i++) {
+      hand_back(g.est->grid_out[i % c.nof_ports][i / c.nof_ports], g_made, o_eg + (size_t)ejobs[i].o_ce * sizeof(cf_t), gb);
+    }
   }
   if (missing) {
     set_error("%s: an intermediate result that was asked for was not produced (the front end did not run for that codeword)", g.who);

@@ -203,6 +203,8 @@ bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch laun
 // Pinned image: the planes, d_planes planes for the equalised symbols, every codeword's soft bits, every codeword's CSI row (the caller's, or what _dbg hands
 // back); device scratch: the equalised symbols (when somebody wants them), the CSI rows the front end files.  Everything on a 256-byte boundary, a plane's
 // padding behind it (the MIMO kernels read an odd grant's last pair whole).
+// With g.est (the _est calls) the pinned image starts with the estimator's input -- the whole received grids, the pilot rows, the PSS -- and ONE more launch in
+// front of the de-mapping makes the ce grids in device scratch; the pairs' records come down in the pinned image and are finished after the host wait.
 // With g.map (the _sf calls) the planes' place in the pinned image holds the used rows of the grids and the segment table instead; ONE launch in front of the
 // scheme's de-maps all planes into device scratch behind the CSI rows, and `front` reads them there (g.in[].pin); _sf_dbg's planes come down in one copy.
 // SRSRAN_ERROR when a device-side step failed, and -- one line on stderr -- when a _dbg output that was asked for was not produced: the front end does not run for a
@@ -241,6 +243,19 @@ inline void stage_grid(uint8_t* at, const cf_t* grid, const srsran_hip_pdsch_sf_
   }
 }
 
+// ---- the _est calls: the channel estimates are made on the device from the received grids (chest_dl.h, chest_dl_kernels.hip), in the same frame
+struct EstMap {
+  const srsran_hip_chest_dl_t*       cfg;
+  const srsran_hip_chest_dl_state_t* state;
+  srsran_hip_chest_dl_res_t*         out;
+  cf_t*                              grid_out[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]; // _est_dbg, or nullptr: where the pair's whole ce grid goes, [port][rx]
+  modem::NoiseAvg                    noise; // set by the frame before `front` runs: the pairs' noise estimates in device memory (get_noise's order)
+};
+// one line on stderr and false for what the _est calls refuse on top of their _sf twins: a NULL description, state or est_out, what srsran_hip_chest_dl_estimate
+// refuses, a cell or subframe that is not `sf`'s, another antenna count than the call's, a grant that does not span both whole slots (the estimator's grid).
+// *est->out is zeroed first.
+bool est_valid(const char* who, EstMap* est, const srsran_hip_pdsch_sf_t* sf, uint32_t nof_rx);
+
 struct RxGrant {
   const char*  who;
   PlaneGroup*  in; // staged: symbols [nof_rx], then estimates [port][nof_rx]
@@ -252,6 +267,8 @@ struct RxGrant {
   uint32_t     d_planes;  // planes of nof_re points the equalised symbols take: 1, one per layer with MIMO; 0: the front end makes none
   bool         d_scratch; // the front end needs that room whether or not d_out asks for it
   bool         weight;
+  EstMap*      est; // nullptr, or (with map) the estimate planes have no host planes: the estimator's kernel runs ahead of the de-mapping on the whole received
+                    // grids, its ce grids stay in device scratch and the de-mapping reads them there
 };
 // enqueues the scheme's kernels on the stage's stream, reading g.in[].pin: codeword k's soft bits to d_e[k] and, with weight, its CSI values to row[k]
 // (d_e[k] == nullptr: not called for that codeword; row[k] is device-readable); the equalised symbols to d_d, plane behind plane of al256(nof_re points) --

@@ -139,8 +139,30 @@ struct UciParams {
 };
 hipError_t launch_uci(const UciParams& p, hipStream_t stream);
 
-// srsran_predecoding_single on device buffers (y, h, x: cf_t, 16-byte aligned; csi optional)
-hipError_t launch_eq(const void* y, const void* h, void* x, float* csi, uint32_t n, float scaling, float noise, hipStream_t stream);
+// a noise estimate that a kernel ahead on the stream leaves in device memory (the downlink channel estimator's per-pair values, chest_dl_kernels.hip):
+// get_noise (chest_dl.c:868-878) over v[a * nof_ports + p] -- the mean over the ports of every antenna, then over the antennas, in that order; at most 16
+// floats.  v == nullptr: the launch's own noise argument holds.
+struct NoiseAvg {
+  const float* v;
+  uint32_t     nof_rx, nof_ports;
+};
+__device__ __forceinline__ float noise_avg(const NoiseAvg& a)
+{
+  float n = 0.f;
+  for (uint32_t i = 0; i < a.nof_rx; i++) {
+    float acc = 0.f;
+    for (uint32_t p = 0; p < a.nof_ports; p++) {
+      acc = __fadd_rn(acc, a.v[i * a.nof_ports + p]);
+    }
+    n = __fadd_rn(n, __fdiv_rn(acc, (float)a.nof_ports));
+  }
+  return __fdiv_rn(n, (float)a.nof_rx);
+}
+
+// srsran_predecoding_single on device buffers (y, h, x: cf_t, 16-byte aligned; csi optional).  dev_noise: nullptr, or the noise estimate is made on the
+// device (`noise` is then not looked at)
+hipError_t launch_eq(const void* y, const void* h, void* x, float* csi, uint32_t n, float scaling, float noise, hipStream_t stream,
+                     const NoiseAvg* dev_noise = nullptr);
 
 // the same for several grants at once: job j covers the symbol pairs [jobs[j - 1].end_pair, jobs[j].end_pair) of the three arrays with its own noise
 // estimate (add_noise as launch_eq derives it: noise > 0); `jobs` must be readable by the device (device memory or a pinned image)

@@ -458,11 +458,15 @@ __global__ __launch_bounds__(256) void scramble_packed_kernel(const uint32_t* in
 // ---- single-antenna ZF / MMSE equaliser: srsran_predecoding_single (mimo/precoding.c:196-392), the float formulas of its AVX
 // body: x = (y conj(h)) / (|h|^2 + noise) * (1 / scaling); two symbols (one dwordx4 of y and of h) per lane
 __global__ __launch_bounds__(256) void eq_kernel(const float4* y, const float4* h, float4* x, float2* csi, uint32_t n, float inv_scaling,
-                                                 float noise, int add_noise)
+                                                 float noise, int add_noise, const NoiseAvg dev_noise)
 {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x; // pair index
   if (2 * i >= n) {
     return;
+  }
+  if (dev_noise.v) { // (uniform; launch_eq's rule for add_noise)
+    noise     = noise_avg(dev_noise);
+    add_noise = (csi != nullptr || noise > 0.f) ? 1 : 0;
   }
   float4 yy, hh;
   if (2 * i + 1 < n) {
@@ -534,13 +538,13 @@ __global__ __launch_bounds__(256) void eq_jobs_kernel(const float4* y, const flo
 
 } // namespace
 
-hipError_t launch_eq(const void* y, const void* h, void* x, float* csi, uint32_t n, float scaling, float noise, hipStream_t stream)
+hipError_t launch_eq(const void* y, const void* h, void* x, float* csi, uint32_t n, float scaling, float noise, hipStream_t stream, const NoiseAvg* dev_noise)
 {
   if (n == 0) {
     return hipSuccess;
   }
   hipLaunchKernelGGL(eq_kernel, dim3(ceil_div(ceil_div(n, 2u), 256u)), dim3(256), 0, stream, (const float4*)y, (const float4*)h, (float4*)x,
-                     (float2*)csi, n, 1.0f / scaling, noise, (csi != nullptr || noise > 0.f) ? 1 : 0);
+                     (float2*)csi, n, 1.0f / scaling, noise, (csi != nullptr || noise > 0.f) ? 1 : 0, dev_noise ? *dev_noise : NoiseAvg{nullptr, 0, 0});
   return hipGetLastError();
 }
 

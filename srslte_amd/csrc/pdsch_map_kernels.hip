@@ -22,7 +22,7 @@ namespace {
 __global__ __launch_bounds__(12 * PDSCH_DEMAP_SEGS) void pdsch_demap_kernel(const DemapParams p)
 {
   const uint32_t plane = blockIdx.y;
-  const float2*  in    = p.in + (size_t)plane * p.in_stride;
+  const float2*  in    = (p.in_b && plane >= p.planes_a) ? p.in_b + (size_t)(plane - p.planes_a) * p.in_stride : p.in + (size_t)plane * p.in_stride;
   float2*        out   = p.out + (size_t)plane * p.out_stride;
   const uint32_t e     = blockIdx.x * PDSCH_DEMAP_SEGS + threadIdx.x / 12u;
   const uint32_t k     = threadIdx.x % 12u;

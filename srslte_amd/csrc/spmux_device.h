@@ -13,6 +13,7 @@ struct Scheme {
   uint32_t pre[2];
   uint32_t mmse;
   float    norm, noise;
+  modem::NoiseAvg dev_noise; // v != nullptr: the noise estimate is made on the device ahead on the stream (`noise` is then not looked at)
 };
 
 // ---- per-stage kernels (srsran_hip_predecoding_mimo / srsran_hip_precoding_mimo on device planes): one lane per RE, planes of any 4-byte alignment

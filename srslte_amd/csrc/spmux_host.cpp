@@ -239,15 +239,20 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
                              srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
                              srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
                              float* const csi_out[SRSRAN_MAX_CODEWORDS], bool sf_form = false, const srsran_hip_pdsch_sf_t* sf = nullptr,
-                             cf_t* const sym_out[] = nullptr, cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr)
+                             cf_t* const sym_out[] = nullptr, cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr, EstMap* est = nullptr)
 {
+  // est: the _est calls -- there is no ce and g->noise_estimate is not read: the estimator's kernel makes the grids on the device in front of the de-mapping,
+  // and the MMSE equaliser averages get_noise() from the pairs' estimates there
   // sf_form: the _sf calls -- symbols and ce are grids, sf describes them (weight is its csi_enable), sym_out / ce_out take the extracted planes
   static const char* who = "srsran_hip_pdsch_decode_mimo";
   TraceRange         trace_(who);
   if (res) {
     res[0] = res[1] = {0, 0.f, NAN};
   }
-  if (!g || !symbols || !ce || !softbuffers || !data || !res) {
+  if (est && est->out) {
+    *est->out = {};
+  }
+  if (!g || !symbols || (!ce && !est) || !softbuffers || !data || !res) {
     fprintf(stderr, "[srsran_phy_hip] %s: NULL argument\n", who);
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
@@ -257,8 +262,8 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
   }
   const uint32_t nof_re = g->tb[0].nof_re;
   Taken          t;
-  const char*    why = mimo_rx_case((int)g->tx_scheme, (int)g->nof_layers, (int)g->codebook_idx, nof_re, g->scaling, (int)g->nof_rx, (int)g->decoder, g->noise_estimate, t);
-  if (!why && (!symbols[0] || !symbols[1] || !ce[0][0] || !ce[0][1] || !ce[1][0] || !ce[1][1])) {
+  const char*    why = mimo_rx_case((int)g->tx_scheme, (int)g->nof_layers, (int)g->codebook_idx, nof_re, g->scaling, (int)g->nof_rx, (int)g->decoder, est ? 0.f : g->noise_estimate, t);
+  if (!why && (!symbols[0] || !symbols[1] || (!est && (!ce[0][0] || !ce[0][1] || !ce[1][0] || !ce[1][1])))) {
     why = "a NULL plane";
   }
   if (!why && ntb == 2 && (g->tb[1].nof_re != nof_re || g->tb[1].llr_is_8bit != g->tb[0].llr_is_8bit || g->tb[1].max_nof_iterations != g->tb[0].max_nof_iterations)) {
@@ -281,13 +286,16 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
   }
-  if (sf_form && !sf_valid("srsran_hip_pdsch_decode_mimo_sf", sf, 2, nof_re)) {
+  if (sf_form && !sf_valid(est ? "srsran_hip_pdsch_decode_mimo_est" : "srsran_hip_pdsch_decode_mimo_sf", sf, 2, nof_re)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (est && !est_valid("srsran_hip_pdsch_decode_mimo_est", est, sf, 2)) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   // staged: 2 symbol planes, then 2 x 2 estimate planes; codeword k is layer k
   const bool   llr8 = g->tb[0].llr_is_8bit != 0;
   const size_t nd   = (size_t)nof_re * sizeof(cf_t);
-  PlaneGroup   in[3] = {{symbols, 2, nd, true, false}, {ce[0], 2, nd, true, false}, {ce[1], 2, nd, true, false}};
+  PlaneGroup   in[3] = {{symbols, 2, nd, true, false}, {est ? nullptr : ce[0], 2, nd, true, false}, {est ? nullptr : ce[1], 2, nd, true, false}};
   SfMap        map = {sf, {}};
   for (uint32_t r = 0; r < 2; r++) {
     map.out[r] = sym_out ? sym_out[r] : nullptr;
@@ -295,7 +303,7 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
       map.out[2 + 2 * k + r] = ce_out ? ce_out[k][r] : nullptr;
     }
   }
-  RxGrant      gr = {who, in, 3, sf_form ? &map : nullptr, nullptr, {}, ntb, ntb, false, weight};
+  RxGrant      gr = {who, in, 3, sf_form ? &map : nullptr, nullptr, {}, ntb, ntb, false, weight, est};
   for (uint32_t k = 0; k < ntb; k++) {
     gr.cw[k] = {&g->tb[k], qm_of(g->tb[k].mod), softbuffers[k], data[k], &res[k], d_out ? d_out[k] : nullptr, e_out ? e_out[k] : nullptr, csi_out ? csi_out[k] : nullptr};
   }
@@ -317,6 +325,9 @@ static int pdsch_decode_mimo(bool weight, const srsran_hip_pdsch_mimo_rx_t* g, c
       fp.seed[k] = g->tb[k].seed;
       fp.out[k]  = d_e[k];
       fp.csi[k]  = row[k];
+    }
+    if (est && t.rx.mmse) { // (zero forcing: 0, as pdsch.c:819 passes)
+      t.rx.dev_noise = est->noise;
     }
     fp.n       = nof_re;
     fp.s       = t.rx;
@@ -476,4 +487,48 @@ extern "C" int srsran_hip_pdsch_encode_mimo_multi(uint32_t n, const srsran_hip_p
     }
     return true;
   });
+}
+
+// the same from the grids alone (chest_dl_kernels.hip in front of the de-mapping)
+static int pdsch_decode_mimo_est(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                 const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS],
+                                 uint8_t* const data[SRSRAN_MAX_CODEWORDS], srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], srsran_hip_chest_dl_res_t* est_out,
+                                 cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS], float* const csi_out[SRSRAN_MAX_CODEWORDS],
+                                 cf_t* const sym_out[], cf_t* const (*ce_out)[SRSRAN_MAX_PORTS], cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS])
+{
+  if (res) {
+    res[0] = res[1] = {0, 0.f, NAN};
+  }
+  if (est_out) {
+    *est_out = {};
+  }
+  if (!sf || !est || !state_in || !est_out) {
+    return refuse("srsran_hip_pdsch_decode_mimo_est: NULL argument");
+  }
+  EstMap em = {est, state_in, est_out, {}, {}};
+  for (uint32_t k = 0; ce_grid_out && k < SRSRAN_MAX_PORTS; k++) {
+    for (uint32_t r = 0; r < SRSRAN_MAX_PORTS; r++) {
+      em.grid_out[k][r] = ce_grid_out[k][r];
+    }
+  }
+  return pdsch_decode_mimo(sf->csi_enable != 0, g, sf_symbols, nullptr, softbuffers, data, res, d_out, e_out, csi_out, true, sf, sym_out, ce_out, &em);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_est(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
+                                                srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], srsran_hip_chest_dl_res_t* est_out)
+{
+  return pdsch_decode_mimo_est(g, sf, est, state_in, sf_symbols, softbuffers, data, res, est_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_mimo_est_dbg(const srsran_hip_pdsch_mimo_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                    const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
+                                                    srsran_softbuffer_rx_t* const softbuffers[SRSRAN_MAX_CODEWORDS], uint8_t* const data[SRSRAN_MAX_CODEWORDS],
+                                                    srsran_hip_grant_res_t res[SRSRAN_MAX_CODEWORDS], srsran_hip_chest_dl_res_t* est_out,
+                                                    cf_t* const d_out[SRSRAN_MAX_CODEWORDS], void* const e_out[SRSRAN_MAX_CODEWORDS],
+                                                    float* const csi_out[SRSRAN_MAX_CODEWORDS], cf_t* const sym_out[], cf_t* const (*ce_out)[SRSRAN_MAX_PORTS],
+                                                    cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS])
+{
+  return pdsch_decode_mimo_est(g, sf, est, state_in, sf_symbols, softbuffers, data, res, est_out, d_out, e_out, csi_out, sym_out, ce_out, ce_grid_out);
 }

@@ -49,8 +49,9 @@ __global__ __launch_bounds__(256) void spmux_eq_kernel(const EqParams p)
   }
   float2 x0, x1 = make_float2(0.f, 0.f);
   float  c0, c1 = 0.f;
+  const float noise = p.s.dev_noise.v ? modem::noise_avg(p.s.dev_noise) : p.s.noise; // (uniform)
   mimo_equalise(p.s.layers, p.s.pre[i & 1u], p.s.mmse != 0, point_at(p.y[0], i), point_at(p.y[1], i), point_at(p.h[0][0], i), point_at(p.h[1][0], i),
-                point_at(p.h[0][1], i), point_at(p.h[1][1], i), p.s.norm, p.s.noise, x0, x1, c0, c1);
+                point_at(p.h[0][1], i), point_at(p.h[1][1], i), p.s.norm, noise, x0, x1, c0, c1);
   point_to(p.x[0], i, x0);
   if (p.csi[0]) {
     p.csi[0][i] = c0;
@@ -177,12 +178,13 @@ __global__ __launch_bounds__(256) void spmux_front_kernel(const FrontParams p)
     codeword_chips(p.x1_bits, p.x2_cols, p.seed[1], p.mod[1], w0, p.n, cbw[1]);
   }
   float2 x0[PAIRS][2], x1[PAIRS][2];
+  const float noise = p.s.dev_noise.v ? modem::noise_avg(p.s.dev_noise) : p.s.noise; // (uniform)
 #pragma unroll
   for (int r = 0; r < PAIRS; r++) {
     float c0[2], c1[2] = {0.f, 0.f};
     x1[r][0] = x1[r][1] = make_float2(0.f, 0.f);
-    mimo_equalise(p.s.layers, p.s.pre[0], p.s.mmse != 0, lo(y0[r]), lo(y1[r]), lo(a0[r]), lo(b0[r]), lo(a1[r]), lo(b1[r]), p.s.norm, p.s.noise, x0[r][0], x1[r][0], c0[0], c1[0]);
-    mimo_equalise(p.s.layers, p.s.pre[1], p.s.mmse != 0, hi(y0[r]), hi(y1[r]), hi(a0[r]), hi(b0[r]), hi(a1[r]), hi(b1[r]), p.s.norm, p.s.noise, x0[r][1], x1[r][1], c0[1], c1[1]);
+    mimo_equalise(p.s.layers, p.s.pre[0], p.s.mmse != 0, lo(y0[r]), lo(y1[r]), lo(a0[r]), lo(b0[r]), lo(a1[r]), lo(b1[r]), p.s.norm, noise, x0[r][0], x1[r][0], c0[0], c1[0]);
+    mimo_equalise(p.s.layers, p.s.pre[1], p.s.mmse != 0, hi(y0[r]), hi(y1[r]), hi(a0[r]), hi(b0[r]), hi(a1[r]), hi(b1[r]), p.s.norm, noise, x0[r][1], x1[r][1], c0[1], c1[1]);
     if (CSI) {
       const uint32_t s = w0 + 2 * (r * 64u + lane); // the pair's even RE
       if (s + 1 < p.n) {

@@ -248,13 +248,17 @@ extern "C" int srsran_layerdemap_diversity(cf_t* x[SRSRAN_MAX_LAYERS], cf_t* d, 
 static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g, cf_t* const symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                               srsran_softbuffer_rx_t* softbuffer, uint8_t* data, srsran_hip_grant_res_t* res, cf_t* d_out, void* e_out, float* csi_out,
                               bool sf_form = false, const srsran_hip_pdsch_sf_t* sf = nullptr, cf_t* const sym_out[] = nullptr,
-                              cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr)
+                              cf_t* const (*ce_out)[SRSRAN_MAX_PORTS] = nullptr, EstMap* est = nullptr)
 {
+  // est: the _est calls -- there is no ce: the estimator's kernel makes the grids on the device in front of the de-mapping
   TraceRange trace_("srsran_hip_pdsch_decode_txdiv");
   if (res) {
     *res = {0, 0.f, NAN};
   }
-  if (!g || !symbols || !ce || !softbuffer || !data || !res) {
+  if (est && est->out) {
+    *est->out = {};
+  }
+  if (!g || !symbols || (!ce && !est) || !softbuffer || !data || !res) {
     fprintf(stderr, "[srsran_phy_hip] srsran_hip_pdsch_decode_txdiv: NULL argument\n");
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
@@ -265,7 +269,7 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
   bool           planes = (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2);
   for (uint32_t r = 0; planes && r < nrx; r++) {
     planes = symbols[r] != nullptr;
-    for (uint32_t k = 0; planes && k < ports; k++) {
+    for (uint32_t k = 0; planes && !est && k < ports; k++) {
       planes = ce[k][r] != nullptr;
     }
   }
@@ -273,7 +277,10 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
     return refuse("srsran_hip_pdsch_decode_txdiv: %u ports, %u receive antennas, %u REs, scaling %g%s is not a transmit-diversity grant", ports, nrx, nof_re, (double)g->scaling,
                   (ports == 2 || ports == 4) && (nrx == 1 || nrx == 2) && !planes ? ", a NULL plane" : "");
   }
-  if (sf_form && !sf_valid("srsran_hip_pdsch_decode_txdiv_sf", sf, ports, nof_re)) {
+  if (sf_form && !sf_valid(est ? "srsran_hip_pdsch_decode_txdiv_est" : "srsran_hip_pdsch_decode_txdiv_sf", sf, ports, nof_re)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (est && !est_valid("srsran_hip_pdsch_decode_txdiv_est", est, sf, nrx)) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   // staged: nof_rx symbol planes, then nof_ports x nof_rx estimate planes
@@ -285,12 +292,12 @@ static int pdsch_decode_txdiv(bool weight, const srsran_hip_pdsch_txdiv_rx_t* g,
     map.out[r] = sym_out ? sym_out[r] : nullptr;
   }
   for (uint32_t k = 0; k < ports; k++) {
-    in[1 + k] = {ce[k], nrx, nd, true, false};
+    in[1 + k] = {est ? nullptr : ce[k], nrx, nd, true, false};
     for (uint32_t r = 0; r < nrx; r++) {
       map.out[nrx + k * nrx + r] = ce_out ? ce_out[k][r] : nullptr;
     }
   }
-  RxGrant gr = {"srsran_hip_pdsch_decode_txdiv", in, 1 + ports, sf_form ? &map : nullptr, nullptr, {{&tb, 2 * qm_of(tb.mod), softbuffer, data, res, d_out, e_out, csi_out}}, 1, 1, false, weight};
+  RxGrant gr = {"srsran_hip_pdsch_decode_txdiv", in, 1 + ports, sf_form ? &map : nullptr, nullptr, {{&tb, 2 * qm_of(tb.mod), softbuffer, data, res, d_out, e_out, csi_out}}, 1, 1, false, weight, est};
   return pdsch_decode_grant(gr, [&](hipStream_t st, void* const* d_e, float* const* row, uint8_t* d_d) {
     const cf_t* hp[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};
     cf_t*       xd[SRSRAN_MAX_LAYERS]                  = {};
@@ -435,4 +442,44 @@ extern "C" int srsran_hip_pdsch_encode_txdiv_multi(uint32_t n, const srsran_hip_
     }
     return true;
   });
+}
+
+// the same from the grids alone: the estimator's kernel (chest_dl_kernels.hip) in front of the de-mapping; diversity combining takes no noise estimate
+static int pdsch_decode_txdiv_est(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                  const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* softbuffer, uint8_t* data,
+                                  srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out, cf_t* d_out, void* e_out, float* csi_out, cf_t* const sym_out[],
+                                  cf_t* const (*ce_out)[SRSRAN_MAX_PORTS], cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS])
+{
+  if (res) {
+    *res = {0, 0.f, NAN};
+  }
+  if (est_out) {
+    *est_out = {};
+  }
+  if (!sf || !est || !state_in || !est_out) {
+    return refuse("srsran_hip_pdsch_decode_txdiv_est: NULL argument");
+  }
+  EstMap em = {est, state_in, est_out, {}, {}};
+  for (uint32_t k = 0; ce_grid_out && k < SRSRAN_MAX_PORTS; k++) {
+    for (uint32_t r = 0; r < SRSRAN_MAX_PORTS; r++) {
+      em.grid_out[k][r] = ce_grid_out[k][r];
+    }
+  }
+  return pdsch_decode_txdiv(sf->csi_enable != 0, g, sf_symbols, nullptr, softbuffer, data, res, d_out, e_out, csi_out, true, sf, sym_out, ce_out, &em);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_est(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                 const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* softbuffer,
+                                                 uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out)
+{
+  return pdsch_decode_txdiv_est(g, sf, est, state_in, sf_symbols, softbuffer, data, res, est_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int srsran_hip_pdsch_decode_txdiv_est_dbg(const srsran_hip_pdsch_txdiv_rx_t* g, const srsran_hip_pdsch_sf_t* sf, const srsran_hip_chest_dl_t* est,
+                                                     const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[], srsran_softbuffer_rx_t* softbuffer,
+                                                     uint8_t* data, srsran_hip_grant_res_t* res, srsran_hip_chest_dl_res_t* est_out, cf_t* d_out, void* e_out,
+                                                     float* csi_out, cf_t* const sym_out[], cf_t* const (*ce_out)[SRSRAN_MAX_PORTS],
+                                                     cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS])
+{
+  return pdsch_decode_txdiv_est(g, sf, est, state_in, sf_symbols, softbuffer, data, res, est_out, d_out, e_out, csi_out, sym_out, ce_out, ce_grid_out);
 }

@@ -6,7 +6,7 @@
 // allocation, srsran_tdec_init, srsran_rm_turbo_gentables) -- so does the library: srsran_rm_turbo_gentables() builds every rate-matching table in
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
 // grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one CSI-weighted grant of each
-// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PDSCH grant from the subframe grids, one PUSCH
+// width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PDSCH grant from the subframe grids with and without the channel estimator in front, one PUSCH
 // transmit grant with control information -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
@@ -114,6 +114,22 @@ void warm_one_worker()
     srsran_hip_grant_res_t      res;
     sb.reset();
     (void)srsran_hip_pdsch_decode_sf(&pd, &sf, grid.data(), ce.data(), &sb.rx, data.data(), &res);
+    // and the same grant from the received grid alone (srsue's default estimator), so the device code of chest_dl_kernels.hip is loaded as well; `ce` serves
+    // as the pilot row (8 nof_prb points of it are read)
+    srsran_hip_chest_dl_t est = {};
+    est.nof_prb = nof_prb;
+    est.nof_ports = est.nof_rx = est.id = est.sf_idx = 1;
+    est.cp_nsymb       = 7;
+    est.estimator_alg  = SRSRAN_HIP_ESTIMATOR_ALG_AVERAGE;
+    est.noise_alg      = SRSRAN_HIP_NOISE_ALG_REFS;
+    est.filter_type    = SRSRAN_HIP_CHEST_FILTER_GAUSS;
+    est.filter_coef[0] = 4.0f;
+    est.filter_coef[1] = 1.0f;
+    est.pilots[0]      = ce.data();
+    const srsran_hip_chest_dl_state_t state = {};
+    srsran_hip_chest_dl_res_t         est_out;
+    sb.reset();
+    (void)srsran_hip_pdsch_decode_est(&pd, &sf, &est, &state, grid.data(), &sb.rx, data.data(), &res, &est_out);
   }
   // one 2-port transmit-diversity codeword each way (the one-block 16-QAM grant above: 1728 REs on two layers), so the device code of txdiv_kernels.hip
   // is loaded before the first subframe of a 2-port cell

@@ -13,8 +13,12 @@
  * codeword costs four host <-> device round trips and four passes over its nof_re points; here it costs one round trip, and one kernel
  * equalises, demodulates, changes the sign and descrambles with the equalised symbols in registers only.
  *
- * NOT taken: control information on the PUSCH (pusch_nr_gen_mux_uci), RE extraction with DMRS patterns (srsran_pdsch_nr_get / _put), more than
- * one layer in the equaliser (N_L only reaches the rate matcher), EVM (pdsch_nr.c:460-464).
+ * The _grid calls further down start one step earlier, at the received slot grid: srsran_dmrs_sch_estimate (dmrs_sch.c:763-986) and srsran_pdsch_nr_get /
+ * srsran_pusch_nr_get (pdsch_nr.c:225-288, pusch_nr.c:274-336) run on the device in front of the codeword.
+ *
+ * NOT taken: control information on the PUSCH (pusch_nr_gen_mux_uci), transmit-side mapping (srsran_pdsch_nr_put, srsran_dmrs_sch_put_sf), mapping type B,
+ * more than one layer or port in the estimator and the equaliser (delta > 0; N_L only reaches the rate matcher), transform precoding, PT-RS,
+ * EVM (pdsch_nr.c:460-464).
  */
 #ifndef SRSRAN_AMD_PHY_NR_CHAN_ABI_H
 #define SRSRAN_AMD_PHY_NR_CHAN_ABI_H
@@ -66,6 +70,74 @@ SRSRAN_API int srsran_hip_nr_cw_decode_dbg(const srsran_hip_nr_cw_rx_t* g, const
  * (SRSRAN_ERROR_INVALID_INPUTS) before anything is enqueued.  The code blocks of all entries together must fit the staging context (160). */
 SRSRAN_API int srsran_hip_nr_cw_decode_multi(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* symbols, const cf_t* const* ce,
                                              srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res);
+
+/* ---- receive from the slot grid: DMRS channel estimation and RE extraction on the device
+ * The grant, restated with plain fields.  What the reference derives from its carrier and configuration structs is resolved by the caller:
+ *   slot_idx  SRSRAN_SLOT_NR_MOD(carrier.scs, slot->idx)
+ *   n_id      dmrs_sch.c:520-528: scrambling_id0 / scrambling_id1 where present for the grant's n_scid, else carrier.pci
+ * lte_CRS_to_match_around with additional_DMRS_DL_Alt (l1 = 12, dmrs_sch.c:281-285) is not described: l1 = 11. */
+#define SRSRAN_HIP_NR_MAX_PRB 275      /* SRSRAN_MAX_PRB_NR */
+#define SRSRAN_HIP_NR_MAX_RVD_PATTERNS 4 /* SRSRAN_RE_PATTERN_LIST_SIZE */
+typedef struct SRSRAN_API {
+  uint32_t rb_begin, rb_end, rb_stride; /* srsran_re_pattern_t: PRBs rb_begin, rb_begin + rb_stride, ... below rb_end (<= 275); rb_stride >= 1 */
+  uint16_t sc;                          /* bit k: subcarrier k of such a PRB is reserved (12 bits) */
+  uint16_t symbol;                      /* bit l: on symbol l of the slot (14 bits) */
+} srsran_hip_nr_re_pattern_t;
+typedef struct SRSRAN_API {
+  uint32_t nof_prb;        /* carrier: <= 275 */
+  uint32_t scs;            /* carrier: numerology 0 .. 4 */
+  uint32_t slot_idx;       /* already reduced modulo the slots of a frame */
+  uint32_t mapping;        /* 0: type A; 1: type B, refused as the reference refuses it (dmrs_sch.c:429-431) */
+  uint32_t S, L;           /* grant: symbols S .. S + L - 1 */
+  uint32_t dmrs_type;      /* 0: type 1, 1: type 2 */
+  uint32_t typeA_pos;      /* 2 or 3 */
+  uint32_t additional_pos; /* 0 .. 3 */
+  uint32_t length;         /* 1: single, 2: double */
+  uint32_t n_id, n_scid;   /* DMRS scrambling (n_scid 0 or 1) */
+  uint32_t nof_dmrs_cdm_groups_without_data; /* 1 .. 3 */
+  float    beta_dmrs;      /* not normal (0, NaN ...): 1 */
+  uint32_t nof_rvd;        /* <= 4 */
+  srsran_hip_nr_re_pattern_t rvd[SRSRAN_HIP_NR_MAX_RVD_PATTERNS];
+  uint8_t  prb_idx[SRSRAN_HIP_NR_MAX_PRB + 1]; /* grant->prb_idx: 0 / 1 per carrier PRB (the last byte is padding) */
+} srsran_hip_nr_grid_t;
+
+/* what srsran_dmrs_sch_estimate leaves in srsran_chest_dl_res_t */
+typedef struct SRSRAN_API {
+  float    noise_estimate, noise_estimate_dbm;
+  float    rsrp, rsrp_dbm;
+  float    snr_db;
+  float    cfo;        /* Hz */
+  float    sync_error; /* s */
+  uint32_t nof_re;
+} srsran_hip_nr_chest_res_t;
+
+/* REs the grant takes: the count srsran_pdsch_nr_get returns and srsran_dmrs_sch_estimate leaves in nof_re.  Pure host arithmetic: needs no device.
+ * 0 for a grid description the calls below refuse. */
+SRSRAN_API uint32_t srsran_hip_nr_sch_nof_re(const srsran_hip_nr_grid_t* grid);
+/* the de-mapping stage by itself: symbols <- the srsran_hip_nr_sch_nof_re(grid) REs of sf_symbols (HOST memory, 14 * 12 * nof_prb points, symbol l at
+ * 12 * nof_prb * l) in the order of srsran_pdsch_nr_cp.  Returns the count, or a negative error. */
+SRSRAN_API int srsran_hip_nr_sch_get(const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols, cf_t* symbols);
+/* the estimator stage by itself: srsran_dmrs_sch_estimate on one port and one layer (delta = 0).  ce (HOST memory, may be NULL: measurements only)
+ * receives the nof_re extracted estimates the reference leaves in chest_res->ce[0][0]. */
+SRSRAN_API int srsran_hip_dmrs_sch_estimate(const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols, cf_t* ce, srsran_hip_nr_chest_res_t* res);
+
+/* srsran_hip_nr_cw_decode from the grid alone: the estimator and the de-mapper run in front of the codeword's front end, which reads their output and the
+ * noise estimate from device memory.  Two launches more than srsran_hip_nr_cw_decode and no host wait more.  g->nof_re must equal
+ * srsran_hip_nr_sch_nof_re(grid); g->noise_estimate is ignored.  chest (may be NULL) receives the estimator's measurements.
+ * Refused like srsran_hip_nr_cw_decode (one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *res and *chest zeroed, nothing else written, nothing enqueued),
+ * also for: mapping type B; additional_pos 3 with typeA_pos 3; S + L of 3 or 4 with typeA_pos 3; S + L below the DMRS length's minimum (3 / 4) or above
+ * 14; additional_pos 3 with double-length DMRS; cdm groups outside 1 .. 3; no PRB set; nof_prb > 275; scs > 4; rb_end > 275, rb_stride == 0 or more than
+ * 4 patterns; an nof_re mismatch. */
+SRSRAN_API int srsran_hip_nr_cw_decode_grid(const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols,
+                                            srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, srsran_hip_nr_tb_result_t* res,
+                                            srsran_hip_nr_chest_res_t* chest);
+SRSRAN_API int srsran_hip_nr_cw_decode_grid_dbg(const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols,
+                                                srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, srsran_hip_nr_tb_result_t* res,
+                                                srsran_hip_nr_chest_res_t* chest, int8_t* e_out);
+/* the codewords of one slot, each with its own grant, all on ONE grid (staged once): arrays of n entries */
+SRSRAN_API int srsran_hip_nr_cw_decode_grid_multi(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grids, const cf_t* sf_symbols,
+                                                  srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res,
+                                                  srsran_hip_nr_chest_res_t* chest);
 
 /* ---- transmit, one codeword: payload bytes -> sch_nr_encode (sch_nr.c:375-520) -> scrambling -> constellation points x scaling.  Stateless like
  * srsran_hip_sch_nr_encode_tb.  symbols: nof_re points, HOST memory. */

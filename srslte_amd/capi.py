@@ -271,6 +271,20 @@ class HipNrCwTx(C.Structure):  # srsran_hip_nr_cw_tx_t
     _fields_ = [("tb", HipNrTb), ("nof_re", C.c_uint32), ("seed", C.c_uint32), ("scaling", C.c_float), ("reserved", C.c_uint32)]
 
 
+class HipNrRePattern(C.Structure):  # srsran_hip_nr_re_pattern_t
+    _fields_ = [("rb_begin", C.c_uint32), ("rb_end", C.c_uint32), ("rb_stride", C.c_uint32), ("sc", C.c_uint16), ("symbol", C.c_uint16)]
+
+
+class HipNrGrid(C.Structure):  # srsran_hip_nr_grid_t
+    _fields_ = [(n, C.c_uint32) for n in ("nof_prb", "scs", "slot_idx", "mapping", "S", "L", "dmrs_type", "typeA_pos", "additional_pos", "length", "n_id",
+                                          "n_scid", "nof_dmrs_cdm_groups_without_data")] + \
+               [("beta_dmrs", C.c_float), ("nof_rvd", C.c_uint32), ("rvd", HipNrRePattern * 4), ("prb_idx", C.c_uint8 * 276)]
+
+
+class HipNrChestRes(C.Structure):  # srsran_hip_nr_chest_res_t
+    _fields_ = [(n, C.c_float) for n in ("noise_estimate", "noise_estimate_dbm", "rsrp", "rsrp_dbm", "snr_db", "cfo", "sync_error")] + [("nof_re", C.c_uint32)]
+
+
 class HipCell(C.Structure):
     _fields_ = [("peak_pos", C.c_int32), ("peak_value", C.c_float), ("psr", C.c_float), ("sss_available", C.c_int32),
                 ("m0", C.c_uint32), ("m1", C.c_uint32), ("m0_value", C.c_float), ("m1_value", C.c_float), ("N_id_1", C.c_int32),
@@ -679,6 +693,15 @@ def lib():
             "srsran_hip_nr_cw_decode_dbg": (i32, [C.POINTER(HipNrCwRx), vp, vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult), vp]),
             "srsran_hip_nr_cw_decode_multi": (i32, [u32, C.POINTER(HipNrCwRx), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.POINTER(SoftbufferRx)),
                                                     C.POINTER(vp), C.POINTER(HipNrTbResult)]),
+            "srsran_hip_nr_sch_nof_re": (u32, [C.POINTER(HipNrGrid)]),
+            "srsran_hip_nr_sch_get": (i32, [C.POINTER(HipNrGrid), vp, vp]),
+            "srsran_hip_dmrs_sch_estimate": (i32, [C.POINTER(HipNrGrid), vp, vp, C.POINTER(HipNrChestRes)]),
+            "srsran_hip_nr_cw_decode_grid": (i32, [C.POINTER(HipNrCwRx), C.POINTER(HipNrGrid), vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult),
+                                                   C.POINTER(HipNrChestRes)]),
+            "srsran_hip_nr_cw_decode_grid_dbg": (i32, [C.POINTER(HipNrCwRx), C.POINTER(HipNrGrid), vp, C.POINTER(SoftbufferRx), vp, C.POINTER(HipNrTbResult),
+                                                       C.POINTER(HipNrChestRes), vp]),
+            "srsran_hip_nr_cw_decode_grid_multi": (i32, [u32, C.POINTER(HipNrCwRx), C.POINTER(HipNrGrid), vp, C.POINTER(C.POINTER(SoftbufferRx)),
+                                                         C.POINTER(vp), C.POINTER(HipNrTbResult), C.POINTER(HipNrChestRes)]),
             "srsran_hip_nr_cw_encode": (i32, [C.POINTER(HipNrCwTx), vp, vp]),
             "srsran_hip_nr_cw_encode_multi": (i32, [u32, C.POINTER(HipNrCwTx), C.POINTER(vp), C.POINTER(vp)]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),

@@ -31,6 +31,7 @@ struct FrontParams {
   const uint32_t* x1_bits;
   const uint32_t* x2_cols;
   modem::Consts   k;
+  const float*    noise_dev = nullptr; // nullptr, or DEVICE memory, one float per job: replaces FrontJob::noise / add_noise (nr_dmrs_est_kernel writes it)
 };
 hipError_t launch_front(const FrontParams& p, hipStream_t stream);
 

@@ -12,6 +12,7 @@
 #include "hip_common.h"
 #include "joblist.h"
 #include "nr_chan_device.h"
+#include "nr_chest_device.h"
 #include "sch_nr_internal.h"
 #include "srsran_amd/phy_nr_chan_abi.h"
 #include <algorithm>
@@ -61,27 +62,48 @@ struct RxCw { // one codeword of a receive call
   uint8_t  flags_in[NrTbStage::MAX_CB];
 };
 
+// grids == nullptr: the codewords come as extracted REs (symbols, ce).  Else symbols and ce are not looked at: codeword i is described by grids[i] on the
+// one slot grid sf_symbols, the estimator and the de-mapper (nr_chest_kernels.hip) run in front of the front end and leave its inputs in the device
+// buffer; chest (may be nullptr) receives the estimator's measurements.
 int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* symbols, const cf_t* const* ce, srsran_softbuffer_rx_t* const* softbuffers,
-                 uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res, int8_t* e_out)
+                 uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res, int8_t* e_out, const srsran_hip_nr_grid_t* grids = nullptr,
+                 const cf_t* sf_symbols = nullptr, srsran_hip_nr_chest_res_t* chest = nullptr)
 {
-  static const char* who = "nr_cw_decode";
-  TraceRange         trace_("srsran_hip_nr_cw_decode");
+  const char* who = grids ? "nr_cw_decode_grid" : "nr_cw_decode";
+  TraceRange  trace_("srsran_hip_nr_cw_decode");
   if (res) {
     memset(res, 0, (size_t)n * sizeof(*res)); // every result is initialised before anything is checked
+  }
+  if (chest) {
+    memset(chest, 0, (size_t)n * sizeof(*chest));
   }
   if (n == 0) {
     return SRSRAN_SUCCESS;
   }
-  if (!g || !symbols || !softbuffers || !payloads || !res) {
+  if (!g || (!grids && !symbols) || (grids && !sf_symbols) || !softbuffers || !payloads || !res) {
     NR_CW_REFUSE("%s: NULL argument", who);
   }
   // ---- validation: nothing is enqueued and nothing of the caller's is written before every entry has passed
   std::vector<RxCw> cw(n);
-  uint32_t          n_cb = 0, sb_stride = 0, data_stride = 0;
+  uint32_t          n_cb = 0, sb_stride = 0, data_stride = 0, n_seg_total = 0, n_prbs_total = 0;
   for (uint32_t i = 0; i < n; i++) {
     const srsran_softbuffer_rx_t* sb = softbuffers[i];
-    if (!symbols[i] || !sb || !payloads[i] || !sb->buffer_f || !sb->data || !sb->cb_crc) {
+    if ((!grids && !symbols[i]) || !sb || !payloads[i] || !sb->buffer_f || !sb->data || !sb->cb_crc) {
       NR_CW_REFUSE("%s: codeword %u: NULL symbols, soft buffer or payload", who, i);
+    }
+    if (grids) {
+      if (const char* why = nr_map::invalid(grids[i])) {
+        NR_CW_REFUSE("%s: codeword %u: %s", who, i, why);
+      }
+      if (grids[i].nof_prb != grids[0].nof_prb) {
+        NR_CW_REFUSE("%s: codeword %u: nof_prb %u on a grid of %u", who, i, grids[i].nof_prb, grids[0].nof_prb);
+      }
+      const uint32_t nof_re = nr_map::nof_re(grids[i]);
+      if (nof_re != g[i].nof_re) {
+        NR_CW_REFUSE("%s: codeword %u: nof_re %u, the grant takes %u", who, i, g[i].nof_re, nof_re);
+      }
+      n_seg_total += nr_map::nof_seg(grids[i]);
+      n_prbs_total += nr_map::granted_prbs(grids[i]);
     }
     TbCfg& c = cw[i].c;
     if (check_tb(who, i, g[i].tb, g[i].nof_re, &c) != SRSRAN_SUCCESS) {
@@ -117,7 +139,7 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     cw[i].o_sym = o;
     o           = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
     cw[i].o_ce  = o;
-    if (ce && ce[i]) {
+    if (grids || (ce && ce[i])) {
       o = al256(o + (size_t)g[i].nof_re * sizeof(cf_t));
     }
     n_tiles += modem::tiles_of(g[i].tb.mod, g[i].nof_re);
@@ -135,6 +157,15 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
   const size_t        pay_bytes = o - o_pay;
   const JobListLayout jl        = job_list_layout(o, (size_t)n * sizeof(nrchan::FrontJob), n_tiles);
   o                             = jl.end;
+  // grid calls: [grid | tables | granted PRBs | estimator jobs | de-mapper jobs] staged in the pinned image and uploaded in one copy, the records in the pinned
+  // image (the estimator writes them there), the noise estimates in the device buffer
+  const uint32_t grid_points = grids ? nr_map::NSYMB * 12 * grids[0].nof_prb : 0;
+  const size_t   o_grid = al256(o), o_tab = al256(o_grid + (size_t)grid_points * sizeof(cf_t)), o_prbs = al256(o_tab + (size_t)n_seg_total * sizeof(nr_map::Seg));
+  const size_t   o_ej = al256(o_prbs + (size_t)n_prbs_total * sizeof(uint16_t)), o_dj = al256(o_ej + (size_t)n * sizeof(nr_chest::EstJob));
+  const size_t   o_rec = al256(o_dj + (size_t)n * sizeof(nr_chest::DemapJob)), o_noise = al256(o_rec + (size_t)n * sizeof(nr_chest::Record));
+  if (grids) {
+    o = al256(o_noise + (size_t)n * sizeof(float));
+  }
   if (o - o_in > 0xffffffffull) {
     NR_CW_REFUSE("%s: %zu bytes of symbols and soft bits in one call", who, o - o_in);
   }
@@ -144,13 +175,16 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
   }
   JobList<nrchan::FrontJob> jobs(s.pin, jl.o_jobs, jl.o_tj);
   nrchan::FrontParams       fp;
+  const uint32_t *          mp_x1 = nullptr, *mp_x2 = nullptr;
   {
     modem::Params mp;
     if (!modem::params_for(mp, modem::LLR_I8)) {
       fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
       return SRSRAN_ERROR;
     }
-    fp.in       = reinterpret_cast<const float2*>(s.pin + o_in);
+    fp.in       = grids ? reinterpret_cast<const float2*>(s.dev + o_in) : reinterpret_cast<const float2*>(s.pin + o_in);
+    fp.noise_dev = grids ? reinterpret_cast<const float*>(s.dev + o_noise) : nullptr;
+    mp_x1 = mp.x1_bits, mp_x2 = mp.x2_cols;
     fp.out      = reinterpret_cast<int8_t*>(s.dev + o_e);
     fp.jobs     = jobs.jobs;
     fp.tile_job = jobs.tile_job;
@@ -165,10 +199,12 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     const TbCfg&                  c  = w.c;
     const srsran_softbuffer_rx_t* sb = softbuffers[i];
     const size_t                  nb = (size_t)g[i].nof_re * sizeof(cf_t);
-    const bool                    eq = ce && ce[i];
-    memcpy(s.pin + w.o_sym, symbols[i], nb);
-    if (eq) {
-      memcpy(s.pin + w.o_ce, ce[i], nb);
+    const bool                    eq = grids || (ce && ce[i]);
+    if (!grids) {
+      memcpy(s.pin + w.o_sym, symbols[i], nb);
+      if (eq) {
+        memcpy(s.pin + w.o_ce, ce[i], nb);
+      }
     }
     const uint32_t nt = modem::tiles_of(g[i].tb.mod, g[i].nof_re);
     jobs.jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
@@ -215,6 +251,40 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
     return SRSRAN_ERROR;
   };
+  nr_chest::Record* rec = reinterpret_cast<nr_chest::Record*>(s.pin + o_rec);
+  if (grids) { // the grid is staged once; every codeword has its own table and its own workgroup of the estimator
+    memcpy(s.pin + o_grid, sf_symbols, (size_t)grid_points * sizeof(cf_t));
+    nr_map::Seg*        tab  = reinterpret_cast<nr_map::Seg*>(s.pin + o_tab);
+    uint16_t*           prbs = reinterpret_cast<uint16_t*>(s.pin + o_prbs);
+    nr_chest::EstJob*   ej   = reinterpret_cast<nr_chest::EstJob*>(s.pin + o_ej);
+    nr_chest::DemapJob* dj   = reinterpret_cast<nr_chest::DemapJob*>(s.pin + o_dj);
+    uint32_t            t0 = 0, p0 = 0, max_seg = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t ns = nr_map::fill_table(grids[i], tab + t0);
+      nr_chest::fill_job(grids[i], &ej[i], prbs + p0);
+      ej[i].o_prb = p0, ej[i].o_tab = t0, ej[i].n_seg = ns, ej[i].o_ce = (uint32_t)((cw[i].o_ce - o_in) / sizeof(cf_t)), ej[i].nof_re = g[i].nof_re;
+      dj[i]   = nr_chest::DemapJob{t0, ns, (uint32_t)((cw[i].o_sym - o_in) / sizeof(cf_t)), g[i].nof_re};
+      max_seg = std::max(max_seg, ns);
+      t0 += ns, p0 += ej[i].n_prbs;
+    }
+    // one upload of the grid, the tables and the jobs: every codeword's workgroups read them, the estimator's several times
+    PHY_HIP_CHECK(hipMemcpyAsync(s.dev + o_grid, s.pin + o_grid, o_rec - o_grid, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+    const float2*             d_grid = reinterpret_cast<const float2*>(s.dev + o_grid);
+    const nr_map::Seg*        d_tab  = reinterpret_cast<const nr_map::Seg*>(s.dev + o_tab);
+    const uint32_t            io_points = (uint32_t)((o_e - o_in) / sizeof(cf_t));
+    nr_chest::DemapParams dp{d_grid, grid_points, reinterpret_cast<const nr_chest::DemapJob*>(s.dev + o_dj), n, max_seg, d_tab, n_seg_total,
+                             reinterpret_cast<float2*>(s.dev + o_in), io_points};
+    nr_chest::EstParams   ep{d_grid, grid_points, reinterpret_cast<const nr_chest::EstJob*>(s.dev + o_ej), reinterpret_cast<const uint16_t*>(s.dev + o_prbs), n_prbs_total,
+                           d_tab, n_seg_total, reinterpret_cast<float2*>(s.dev + o_in), io_points, rec, reinterpret_cast<float*>(s.dev + o_noise), n, max_seg, mp_x1, mp_x2};
+    hipError_t            e = nr_chest::launch_demap(dp, s.st);
+    if (e == hipSuccess) {
+      e = nr_chest::launch_est(ep, s.st);
+    }
+    if (e != hipSuccess) {
+      set_error("nr_demap_kernel / nr_dmrs_est_kernel: %s", hipGetErrorString(e));
+      return fail("estimator");
+    }
+  }
   {
     const hipError_t e = nrchan::launch_front(fp, s.st);
     if (e != hipSuccess) {
@@ -304,6 +374,9 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     }
     if (e_out && i == 0) {
       memcpy(e_out, s.pin + w.o_e, g[i].tb.nof_bits);
+    }
+    if (grids && chest) {
+      nr_chest::finish(rec[i], g[i].nof_re, &chest[i]);
     }
   }
   return SRSRAN_SUCCESS;
@@ -433,6 +506,40 @@ extern "C" int srsran_hip_nr_cw_decode(const srsran_hip_nr_cw_rx_t* g, const cf_
                                        uint8_t* payload, srsran_hip_nr_tb_result_t* res)
 {
   return nr_cw_decode(1, g, &symbols, &ce, &softbuffer, &payload, res, nullptr);
+}
+
+extern "C" int srsran_hip_nr_cw_decode_grid_multi(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grids, const cf_t* sf_symbols,
+                                                  srsran_softbuffer_rx_t* const* softbuffers, uint8_t* const* payloads, srsran_hip_nr_tb_result_t* res,
+                                                  srsran_hip_nr_chest_res_t* chest)
+{
+  if (n && !grids) {
+    if (res) {
+      memset(res, 0, (size_t)n * sizeof(*res));
+    }
+    if (chest) {
+      memset(chest, 0, (size_t)n * sizeof(*chest));
+    }
+    fprintf(stderr, "[srsran_phy_hip] nr_cw_decode_grid: NULL argument\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return nr_cw_decode(n, g, nullptr, nullptr, softbuffers, payloads, res, nullptr, grids, sf_symbols, chest);
+}
+
+extern "C" int srsran_hip_nr_cw_decode_grid_dbg(const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols,
+                                                srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, srsran_hip_nr_tb_result_t* res,
+                                                srsran_hip_nr_chest_res_t* chest, int8_t* e_out)
+{
+  if (!grid) {
+    return srsran_hip_nr_cw_decode_grid_multi(1, g, nullptr, sf_symbols, &softbuffer, &payload, res, chest);
+  }
+  return nr_cw_decode(1, g, nullptr, nullptr, &softbuffer, &payload, res, e_out, grid, sf_symbols, chest);
+}
+
+extern "C" int srsran_hip_nr_cw_decode_grid(const srsran_hip_nr_cw_rx_t* g, const srsran_hip_nr_grid_t* grid, const cf_t* sf_symbols,
+                                            srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, srsran_hip_nr_tb_result_t* res,
+                                            srsran_hip_nr_chest_res_t* chest)
+{
+  return srsran_hip_nr_cw_decode_grid_dbg(g, grid, sf_symbols, softbuffer, payload, res, chest, nullptr);
 }
 
 extern "C" int srsran_hip_nr_cw_encode_multi(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* const* data, cf_t* const* symbols)

@@ -104,7 +104,11 @@ __global__ __launch_bounds__(256) void nr_front_kernel(const FrontParams p)
     cb[threadIdx.x >> 6][MODEM_TILE_BITS / 128] = 0; // chips_at reads one word past the last one
   }
   __syncthreads();
-  const FrontJob job  = sjob;
+  FrontJob job = sjob;
+  if (p.noise_dev) { // the estimator in front of this launch left the codeword's noise estimate on the device
+    job.noise     = p.noise_dev[p.tile_job[blockIdx.x]];
+    job.add_noise = job.noise > 0.f ? 1u : 0u;
+  }
   const uint32_t tile = blockIdx.x - job.tile0;
   if (tile >= job.ntiles) {
     return;

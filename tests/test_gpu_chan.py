@@ -86,8 +86,9 @@ def _pusch_grid(rng, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, q, rnti, t
     return np.ascontiguousarray(grid.reshape(-1)), np.ascontiguousarray(ce.reshape(-1)), seed
 
 
-def _per_stage_pusch_llrs(lib, capi, grid, ce, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, rnti, tti, cell_id, noise, llr8):
-    """pusch.c:383-443 one reference-named call at a time on the library (four device round trips): returns the q soft bits"""
+def _per_stage_pusch_llrs(lib, capi, grid, ce, nof_prb, cp_nsymb, n_prb, L_prb, shortened, mod, rnti, tti, cell_id, noise, llr8, symbols_out=None):
+    """pusch.c:383-443 one reference-named call at a time on the library (four device round trips): returns the q soft bits.  symbols_out: a list that gets the
+    symbols the demodulator was given"""
     nsymb = 2 * (cp_nsymb - 1) - (1 if shortened else 0)
     nsc = 12 * L_prb
     nof_re = nsymb * nsc
@@ -114,6 +115,8 @@ def _per_stage_pusch_llrs(lib, capi, grid, ce, nof_prb, cp_nsymb, n_prb, L_prb, 
     llr = np.zeros(nof_re * Qm, dt)
     assert (lib.srsran_demod_soft_demodulate_b if llr8 else lib.srsran_demod_soft_demodulate_s)(mod, O.P(d), O.P(llr), nof_re) == 0
     assert np.array_equal(llr, O.demod_soft(mod, d, "b" if llr8 else "s"))  # the demodulator against the oracle on the device's own symbols
+    if symbols_out is not None:
+        symbols_out.append(d)
     out = np.zeros_like(llr)
     (lib.srsran_sequence_pusch_apply_c if llr8 else lib.srsran_sequence_pusch_apply_s)(O.P(llr), O.P(out), rnti, 2 * (tti % 10), cell_id, llr.size)
     return out, avg_power(y)

@@ -17,7 +17,9 @@ oracle fails every block (a case that cannot show its rows is a failed case).
 The shapes are the smallest allocations that still cross every boundary of the kernels (a tile is 2048 symbols, a wave's share 512, a pass 64): 144 .. 2160
 symbols, all three modulations, 16- and 8-bit stores, 12 / 11 / 10 / 9 columns (both column sets of the de-multiplexer's rank), puncturing and repetition
 in the de-matcher, Q'ri not a multiple of 4, the counts at their cap of four columns, one and two blocks, four cell widths, hopping, the cell's top edge,
-zero forcing.  The expected side of a case (literal de-multiplexer included) takes 1 to 15 ms on the CPU."""
+zero forcing; two 8-bit allocations with an odd L_prb x columns (132 and 540 symbols, 16-QAM and 64-QAM), the only ones whose last 4 symbols take the 8-bit
+demodulator's scalar tail -- which truncates where the vector body rounds: each asserts that the tail rule does change soft bits of its own input (_Ue.tail_is_seen).
+The PDSCH paths get the same treatment in tests/test_gpu_pdsch_softbits.py.  The expected side of a case (literal de-multiplexer included) takes 1 to 15 ms on the CPU."""
 import ctypes as C
 
 import numpy as np
@@ -31,6 +33,7 @@ pytestmark = pytest.mark.gpu
 SB = T.SB
 ITERS = 2  # half iterations: nothing is meant to decode
 CELL_ID = 211
+GROUP = {False: 4, True: 8}  # symbols per iteration of the demodulator's 16-QAM / 64-QAM vector bodies, by llr8: the last H % GROUP symbols take the scalar tail
 
 # the allocations: cell_nof_prb, cp_nsymb, shortened, n_prb_tilde, L_prb, mod, tbs, llr8, noise_estimate, snr_db
 GRANTS = {
@@ -44,6 +47,9 @@ GRANTS = {
     "64qam_L15": (100, 7, 0, (85, 85), 15, 3, 6712, False, 0.01, 25.0),  # 2160 symbols: a second tile; two blocks (K 3392 / 3328); the top edge of 100 PRB
     "16qam_L16_srs_8bit": (100, 7, 1, (10, 60), 16, 2, 6200, True, 0.02, 17.0),  # 2112 symbols: a second tile with one pass; 4-byte stores; two blocks
     "16qam_L16_srs": (25, 7, 1, (9, 0), 16, 2, 6200, False, 0.01, 17.0),
+    # 8 bit with L_prb x columns odd: the only allocations whose count is no multiple of 8, so that the 8-bit demodulator's last 4 symbols take its scalar tail
+    "16qam_L1_srs_8bit": (25, 7, 1, (7, 7), 1, 2, 328, True, 0.01, 17.0),  # 132 symbols, 11 columns: all in one wave, 132 % 8 == 4
+    "64qam_L5_ext_srs_8bit": (25, 6, 1, (20, 3), 5, 3, 1544, True, 0.02, 25.0),  # 540 symbols, 9 columns: the tail in a second wave, 540 % 8 == 4; hopping
 }
 
 # single grants: (allocation, (Q'ack, Q'ri, Q'cqi)); all zero = the plain call
@@ -55,15 +61,17 @@ SINGLE = [
     ("qpsk_L5_ext_srs_8bit", (0, 0, 0)), ("qpsk_L5_ext_srs", (9, 2, 31)),
     ("64qam_L15", (0, 0, 0)), ("64qam_L15", (24, 5, 60)), ("64qam_L15", (720, 720, 100)),
     ("16qam_L16_srs_8bit", (0, 0, 0)), ("16qam_L16_srs", (30, 7, 44)),
+    ("16qam_L1_srs_8bit", (0, 0, 0)), ("64qam_L5_ext_srs_8bit", (0, 0, 0)),
 ]
 
 # the grants of a TTI, all inside a 100-PRB grid: (allocation, n_prb_tilde, counts for the call with control information).  Two grants of one PRB with a
 # three-PRB one between them in list order (the host sorts by L_prb and runs one transform launch per size: 12 + 10 + 10 rows of 12 points in one, two
-# column counts in it), the same for 5 and 16 PRB; all three 8-bit grants; hopping; the top edge.
+# column counts in it), the same for 5 and 16 PRB; all five 8-bit grants; hopping; the top edge.
 TTI = [
     ("64qam_L15", (0, 0), (24, 5, 60)), ("qpsk_L1", (15, 99), (0, 2, 1)), ("16qam_L16_srs", (16, 16), (30, 7, 44)), ("16qam_L3_srs", (32, 32), (0, 0, 0)),
     ("64qam_L1_ext_8bit", (35, 35), (0, 0, 0)), ("qpsk_L5_ext_srs_8bit", (36, 59), (0, 0, 0)), ("16qam_L4_srs", (41, 41), (13, 6, 0)),
     ("16qam_L16_srs_8bit", (45, 84), (0, 0, 0)), ("qpsk_L5_ext_srs", (61, 36), (9, 2, 31)), ("64qam_L1_ext", (99, 66), (48, 48, 5)),
+    ("16qam_L1_srs_8bit", (67, 67), (0, 0, 0)), ("64qam_L5_ext_srs_8bit", (68, 73), (0, 0, 0)),
 ]
 TTI_SUBFRAME = 7
 
@@ -116,8 +124,11 @@ class _Ue:
 
     def expect(self, lib):
         """the oracle's side of the transmission: self.soft / self.crc move on, returns what the call must report"""
+        d = []
         q, _ = T._per_stage_pusch_llrs(lib, self.capi, self.grid, self.ce, self.cell, self.cp, self.n_prb, self.L, self.short, self.mod, self.rnti, TTI_SUBFRAME,
-                                       CELL_ID, self.noise, self.llr8)
+                                       CELL_ID, self.noise, self.llr8, symbols_out=d)
+        if self.mod in (2, 3) and self.H % GROUP[self.llr8]:
+            self.tail_is_seen(lib, d[0], q)
         ctl = None
         if any(self.counts):
             ack, ackp, ri, rip, cqi, e, gbits = U._literal_demux(q, self.H, self.cols, self.Qm, *self.counts)
@@ -129,6 +140,19 @@ class _Ue:
         # the precondition: no block decodes, so every row comes back
         assert ret == -1 and not self.crc.any(), (self.name, self.counts, self.rv, ret, self.crc)
         return avg, ctl
+
+    def tail_is_seen(self, lib, d, q):
+        """the demodulator's symbols with 16 more behind them, on the oracle: the q soft bits must change, and only in the symbols its scalar tail covers (the last
+        H % 8 of 8-bit 16-QAM / 64-QAM; 16 bit: H % 4, which no allocation has).  A grant that cannot show this is a failed case"""
+        more = O.qam_symbols(self.mod, 16, self.H, snr_db=self.snr)
+        llr = O.demod_soft(self.mod, np.concatenate([d, more]), "b" if self.llr8 else "s")[:q.size]
+        body = np.zeros_like(llr)
+        (lib.srsran_sequence_pusch_apply_c if self.llr8 else lib.srsran_sequence_pusch_apply_s)(O.P(llr), O.P(body), self.rnti, 2 * (TTI_SUBFRAME % 10), CELL_ID, llr.size)
+        diff = np.flatnonzero(body != q)
+        tag = (self.name, self.counts, self.rv)
+        assert diff.size > 0, tag + ("the tail rule changes no soft bit of this grant",)
+        assert diff[0] >= (self.H - self.H % GROUP[self.llr8]) * self.Qm, tag + (int(diff[0]),)
+        print("%s rv %d: %d soft bits that the tail rule decides" % (self.name, self.rv, diff.size))
 
     def spans(self):
         return [3 * ((self.seg["K1"] if i < self.seg["C1"] else self.seg["K2"]) + 32) + 12 for i in range(self.nb)]

@@ -12,7 +12,8 @@ Which test holds what to what:
                                                csi_model's output
 Shapes of the first two: nof_re = 2 (4 on 4 ports), 254 / 258 around one wave's stride of the reduction, 2046 / 2050 around one tile, 4100 = two tiles and a bit, and
 301 / 2051 (the left-over symbol of QPSK / 64-QAM) on the paths that take an odd nof_re.  The transport block of these is a single small code block that does not
-decode (random symbols, one iteration): only the soft bits are looked at."""
+decode (random symbols, one iteration): only the soft bits are looked at.  The first test holds the weighted soft bits to the plain call's; the plain call's own
+soft bits, and the weighted ones through them, are held to the oracle's demodulator in tests/test_gpu_pdsch_softbits.py."""
 import ctypes as C
 import functools
 

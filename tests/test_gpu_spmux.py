@@ -10,6 +10,9 @@ Which test holds what to what:
   test_grant_that_cannot_decode              every soft-buffer row of both codewords over two transmissions
   test_transmit_*                            the fused transmit call to srsran_hip_pdsch_encode per codeword + srsran_hip_precoding_mimo, equal as numbers
   test_loop_back, test_worker_threads        transmit into receive; four threads at once
+test_codewords_in_one_call and test_grant_that_cannot_decode take their expected soft bits and rows from the library's own srsran_hip_pdsch_decode_dbg, at sizes that
+are multiples of 4: they hold the fused call to its per-stage twin.  What holds this path's soft bits to the ORACLE's demodulator, at sizes that leave its scalar tail
+something to decide (n % 4, n % 8 != 0), is tests/test_gpu_pdsch_softbits.py.
 The received planes of the codeword tests come from the oracle's transmit bits through the oracle's modulator, the float64 precoder of spmux_model.py, a
 well-conditioned channel and noise 30 dB below the signal."""
 import ctypes as C

@@ -10,6 +10,9 @@ Which test holds what to what:
   test_grant_that_cannot_decode            every soft-buffer row over two transmissions (placement of every soft bit, HARQ combining)
   test_transmit_*                          the fused transmit call to srsran_hip_pdsch_encode + layer map + precoder one call at a time, bit for bit
   test_loop_back, test_worker_threads      transmit into receive; four threads at once
+The two receive comparisons above take their soft bits from the library's own demodulator, at sizes that are multiples of 4: they hold the fused call to its per-stage
+twin.  What holds this path's soft bits to the ORACLE's demodulator, at sizes that leave its scalar tail something to decide (n % 4, n % 8 != 0), is
+tests/test_gpu_pdsch_softbits.py.
 The received planes of the codeword tests come from the oracle's transmit bits through the oracle's modulator and an SFBC precoder written here in numpy,
 a channel that is constant over each RE pair / quad, and noise."""
 import ctypes as C

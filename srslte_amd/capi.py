@@ -285,6 +285,25 @@ class HipNrChestRes(C.Structure):  # srsran_hip_nr_chest_res_t
     _fields_ = [(n, C.c_float) for n in ("noise_estimate", "noise_estimate_dbm", "rsrp", "rsrp_dbm", "snr_db", "cfo", "sync_error")] + [("nof_re", C.c_uint32)]
 
 
+SRSRAN_VITERBI_37 = 2  # srsran_viterbi_type_t (phy_conv_abi.h)
+HIP_DCI_ROW = 144  # SRSRAN_HIP_DCI_MAX_BITS + 16: payload bytes of a result
+HIP_DCI_SYMS = 3 * HIP_DCI_ROW  # values per candidate in the _dbg rows
+
+
+class Viterbi(C.Structure):  # srsran_viterbi_t
+    _fields_ = [("ptr", C.c_void_p), ("R", C.c_uint32), ("K", C.c_uint32), ("framebits", C.c_uint32), ("tail_biting", C.c_bool), ("gain_quant", C.c_float),
+                ("gain_quant_s", C.c_int16), ("decode", C.c_void_p), ("decode_s", C.c_void_p), ("decode_f", C.c_void_p), ("free", C.c_void_p), ("tmp", C.c_void_p),
+                ("tmp_s", C.c_void_p), ("symbols_uc", C.c_void_p), ("symbols_us", C.c_void_p)]
+
+
+class HipPdcchCand(C.Structure):  # srsran_hip_pdcch_cand_t
+    _fields_ = [("ncce", C.c_uint32), ("L", C.c_uint32), ("nof_bits", C.c_uint32)]
+
+
+class HipPdcchRes(C.Structure):  # srsran_hip_pdcch_res_t
+    _fields_ = [("payload", C.c_uint8 * HIP_DCI_ROW), ("crc_rem", C.c_uint16), ("decoded", C.c_uint16), ("mean", C.c_float)]
+
+
 class HipCell(C.Structure):
     _fields_ = [("peak_pos", C.c_int32), ("peak_value", C.c_float), ("psr", C.c_float), ("sss_available", C.c_int32),
                 ("m0", C.c_uint32), ("m1", C.c_uint32), ("m0_value", C.c_float), ("m1_value", C.c_float), ("N_id_1", C.c_int32),
@@ -704,6 +723,17 @@ def lib():
                                                          C.POINTER(vp), C.POINTER(HipNrTbResult), C.POINTER(HipNrChestRes)]),
             "srsran_hip_nr_cw_encode": (i32, [C.POINTER(HipNrCwTx), vp, vp]),
             "srsran_hip_nr_cw_encode_multi": (i32, [u32, C.POINTER(HipNrCwTx), C.POINTER(vp), C.POINTER(vp)]),
+            "srsran_viterbi_init": (i32, [C.POINTER(Viterbi), i32, C.POINTER(C.c_int), u32, C.c_bool]),
+            "srsran_viterbi_free": (None, [C.POINTER(Viterbi)]),
+            "srsran_viterbi_set_gain_quant": (None, [C.POINTER(Viterbi), C.c_float]),
+            "srsran_viterbi_set_gain_quant_s": (None, [C.POINTER(Viterbi), C.c_int16]),
+            "srsran_viterbi_decode_f": (i32, [C.POINTER(Viterbi), vp, vp, u32]),
+            "srsran_viterbi_decode_s": (i32, [C.POINTER(Viterbi), vp, vp, u32]),
+            "srsran_viterbi_decode_us": (i32, [C.POINTER(Viterbi), vp, vp, u32]),
+            "srsran_viterbi_decode_uc": (i32, [C.POINTER(Viterbi), vp, vp, u32]),
+            "srsran_hip_viterbi_decode_us_multi": (i32, [C.POINTER(Viterbi), u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]),
+            "srsran_hip_pdcch_dci_decode_multi": (i32, [vp, u32, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes)]),
+            "srsran_hip_pdcch_dci_decode_multi_dbg": (i32, [vp, u32, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), vp, vp]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

@@ -7,11 +7,12 @@
 // one allocation and warms ONE worker's contexts; srsran_hip_warmup(n) makes that n.  A warm context is made by running real calls -- the largest
 // grant of a 100-PRB cell, a one-block grant and a scalar-decoder grant, receive and transmit side, 16- and 8-bit soft bits, one CSI-weighted grant of each
 // width, one 2-port transmit-diversity grant and one two-codeword spatial-multiplexing grant each way, one PDSCH grant from the subframe grids with and without the channel estimator in front, one PUSCH
-// transmit grant with control information -- on a short-lived
+// transmit grant with control information, one small PDCCH candidate call -- on a short-lived
 // thread whose contexts go back to the pools (hip_common.h: StagePool) when it ends.
 #include "stage.h"
 #include "turbo_device.h"
 #include "srsran_amd/phy_chan_abi.h"
+#include "srsran_amd/phy_conv_abi.h"
 #include "srsran_amd/phy_nr_chan_abi.h"
 
 #include <algorithm>
@@ -187,6 +188,14 @@ void warm_one_worker()
     srsran_hip_nr_tb_result_t nres;
     (void)srsran_hip_nr_cw_encode(&ntx, npay.data(), nsym.data());
     (void)srsran_hip_nr_cw_decode(&nrx, nsym.data(), nce.data(), &nsb, npay.data(), &nres);
+  }
+  // two PDCCH candidates of a 6-CCE control region (conv_host.cpp), so the device code of conv_kernels.hip is loaded and the context's images exist
+  // before a UE worker's first blind search
+  {
+    const std::vector<float>      llr(6 * 72, 1.0f);
+    const srsran_hip_pdcch_cand_t cand[2] = {{0, 0, 27}, {2, 2, 43}};
+    srsran_hip_pdcch_res_t        pres[2];
+    (void)srsran_hip_pdcch_dci_decode_multi(llr.data(), (uint32_t)llr.size(), 2, cand, pres);
   }
 }
 

@@ -64,6 +64,16 @@ struct Ar16 {
     }
     o[0] = splat(0);
   }
+  // normalize() behind a mask that is 0 or ~0 in every lane, without a branch: the subtrahend is o[0] & m.  m = ~0: o[0] - o[0] = 0 and
+  // every other state loses o[0] through the same saturating sub, which is normalize(); m = 0: o[i] - 0 = o[i], also at either bound.
+  static __device__ __forceinline__ void normalize_if(s2 (&o)[8], uint32_t m)
+  {
+    const s2 z = from_u(to_u(o[0]) & m);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      o[i] = sub(o[i], z);
+    }
+  }
   static __device__ __forceinline__ s2 llr(s2 m1, s2 m0) { return sub(m1, m0); }
   static __device__ __forceinline__ short tadd(short a, short b) { return (short)(a + b); } // tail trellis, plain adds
   static __device__ __forceinline__ short conv_in(int v) { return (short)v; }

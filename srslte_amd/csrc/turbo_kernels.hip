@@ -114,6 +114,22 @@ __device__ __forceinline__ void kept_ops(const uint4 (&Bl)[8][2][64], uint32_t s
   ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
 }
 
+// What the whole-block bodies of the main passes (tdec_win_unit, 16-step form) hand Ar16::normalize_if where a group lies at an end of the sub-block: 0 or
+// ~0, the same in every lane, and opaque like sub_x there (a mask known to be 0 or ~0 is turned back into two arms).
+__device__ __forceinline__ uint32_t norm_mask(bool on)
+{
+  uint32_t m = __builtin_amdgcn_readfirstlane(on ? ~0u : 0u); // (an "s" operand wants a value the compiler knows to be uniform)
+  asm("" : "+s"(m)); // (not volatile: that would be a barrier for the LDS traffic of the steps around it)
+  return m;
+}
+
+// Which body of the forward main pass a block takes (tdec_win_unit): the general one, or the whole-block one at place POS of its group of four.
+template <bool WHOLE, int POS>
+struct FwdBody {
+  static constexpr bool value = WHOLE;
+  static constexpr int  pos   = POS;
+};
+
 // ------------------------------------------------------------------------------------------------
 // Windowed decoder kernel: one wave per 64/LPC code blocks, whole srsran_tdec_run_all in one launch.
 //
@@ -147,6 +163,9 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
   constexpr int  CPW = 64 / LPC;
   constexpr bool NT  = !ES && !AR::kIs8; // non-temporal workspace loads (see ws_load16)
   static_assert(CKS == 8 || CKS == 16, "check-points every 8 or every 16 steps");
+  static_assert(CKS == 8 || !AR::kIs8, "the 16-step form's whole-block bodies use Ar16's masked normalisation");
+  // the arithmetic of the whole-block bodies: AR, and where they are discarded (they are generic lambdas' arms) a type that has normalize_if all the same
+  using ARW = std::conditional_t<CKS == 16, AR, Ar16>;
   const int     pl   = lane % LPC;
   const uint32_t xbase = xch_group_base<LPC>(lane); // of the exchange across the lanes of a code block (permute_pair)
   const int     cb_raw = (int)wb * CPW + lane / LPC;
@@ -610,14 +629,18 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           }
         }
       };
-      // The whole-block body: a block of a group of four whose top block b (b = 3 mod 4) has 7 <= b <= nblk - 5.  Every block of such a group
-      // is a whole one fetched from HBM (b <= top), its request is a real block (b - 6 >= 1), none of its steps is step 0, so the schedule of
-      // the normalisation is the step's position in the block; the check-point is stored by the even blocks, second and fourth of the group.
-      auto whole_block = [&](auto ck_store, int b, const Ops& c, Ops& tgt) {
+      // The whole-block body: a block of a group of four whose top block b (b = 3 mod 4) has 3 <= b <= nblk - 5.  Every block of such a group
+      // is a whole one fetched from HBM (b <= top), so the schedule of the normalisation is the step's position in the block; the check-point
+      // is stored by the even blocks, second and fourth of the group.  The bottom group (blocks 3 ... 0) differs from the others in three
+      // things, none of them an arm: the requests of blocks 2 ... 0 run off the array's start and go to its first 16 bytes, like every request
+      // that is not needed (issue); step 0 is not followed by a normalisation, so the fourth block's last one is masked (`bottom`); and the
+      // check-point the fourth block files is, for block 0, slot 0 of CK, which exists and which no pass reads (the forward passes start at slot
+      // 2 or, with 8-step check-points, at slot 1) -- a branch around the store would merge an arm without stores into the path.
+      auto whole_block = [&](auto ck_store, auto bottom, int b, const Ops& c, Ops& tgt) {
         s2 xs[8], ys[8], ap[8];
         taken(c);
         prep(c, xs, ys, ap);
-        issue(b - 3, tgt);
+        issue(b - 3, tgt, b >= 3);
 #pragma unroll
         for (int j = 7; j >= 0; j--) {
           beta_step<AR>(o, xs[j], ys[j]);
@@ -631,35 +654,33 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
               store_block_v<AR::kIs8>(CK, ((uint32_t)b & m_own()) * 64 + lane, ck);
             }
           }
-          if (AR::norm_in_block(j)) {
+          if (bottom.value && j == 0) {
+            AR::normalize_if(o, norm_mask(b != 0));
+          } else if (AR::norm_in_block(j)) {
             AR::normalize(o);
           }
         }
       };
-      constexpr std::integral_constant<bool, true>  kStore{};
-      constexpr std::integral_constant<bool, false> kNoStore{};
+      constexpr std::integral_constant<bool, true>  kStore{}, kBottom{};
+      constexpr std::integral_constant<bool, false> kNoStore{}, kInner{};
       // Two bodies, each emitted once, never two arms of one loop trip (at a merge the compiler counts the arm with the fewest loads in
-      // flight): the general loop runs the groups above the whole-block range in the first trip of the outer loop and the group below it
-      // (blocks 3 ... 0) in the second; the whole-block loop has groups only in the first.  Every way into either loop carries what its back
-      // edge carries: the requests of the next three blocks.
+      // flight): the general loop runs the groups that hold a block from the beta buffer or a ragged one (a sub-block has more than 40 steps, so
+      // nblk >= 6 and there is at least one), the whole-block loop every group below them, down to block 0.  The way into either loop carries
+      // what its back edge carries: the requests of the next three blocks.
       int b = ((int)nblk - 1) | 3;
 #pragma nounroll
-      for (int trip = 0; trip < 2; trip++) {
-        const int above = trip == 0 && nblk > 4 ? (int)nblk - 5 : -1; // (never below -1: the general loop ends with block 0, as the one loop it replaces did)
+      for (; b > top; b -= 4) {
+        block(b, nx3, cur);
+        block(b - 1, nx2, nx3);
+        block(b - 2, nxt, nx2);
+        block(b - 3, cur, nxt);
+      }
 #pragma nounroll
-        for (; b > above; b -= 4) {
-          block(b, nx3, cur);
-          block(b - 1, nx2, nx3);
-          block(b - 2, nxt, nx2);
-          block(b - 3, cur, nxt);
-        }
-#pragma nounroll
-        for (; b >= 7; b -= 4) {
-          whole_block(kNoStore, b, nx3, cur);
-          whole_block(kStore, b - 1, nx2, nx3);
-          whole_block(kNoStore, b - 2, nxt, nx2);
-          whole_block(kStore, b - 3, cur, nxt);
-        }
+      for (; b >= 3; b -= 4) {
+        whole_block(kNoStore, kInner, b, nx3, cur);
+        whole_block(kStore, kInner, b - 1, nx2, nx3);
+        whole_block(kNoStore, kInner, b - 2, nxt, nx2);
+        whole_block(kStore, kBottom, b - 3, cur, nxt);
       }
     } else {
       // (8-step check-points: the 8-bit and the early-stop kernels.  With four rotating sets the int16 early-stop kernels spill -- their forward
@@ -725,12 +746,15 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // ... and the last half iteration of a complete run files sign bits only: the next a-priori array would never be read
     const bool sign_rows = bit_rows && n + 1 == p.n_end;
 
-    // The forward main pass has two bodies.  The general one takes any block: ragged, the last one, one that is not there.  The whole-block one (16-step
-    // form only) takes a whole block that is neither the first nor the last of its sub-block and whose walks do not start from the sub-block's end: its
-    // length is 8, the block above it exists, no step is step 0 and no stored value is the one at the sub-block's end, so the schedule of the normalisation is
-    // the step's position in the block and a block's steps are straight-line code.
-    constexpr std::integral_constant<bool, true>  kWhole{};
-    constexpr std::integral_constant<bool, false> kGeneral{};
+    // The forward main pass has two bodies.  The general one takes any block: ragged, one that is not there.  The whole-block one (16-step form only) takes
+    // a whole block of a group of four whole blocks: its length is 8, so the schedule of the normalisation is the step's position in the block and a block's
+    // steps are straight-line code; the three normalisations that an end of the sub-block takes out of that schedule are masked (below, at the loops).
+    // (a whole block carries its place in its group of four: it says which of its normalisations can fall on an end of the sub-block and is masked)
+    constexpr FwdBody<false, -1> kGeneral{};
+    constexpr FwdBody<true, 0>   kWhole0{};
+    constexpr FwdBody<true, 1>   kWhole1{};
+    constexpr FwdBody<true, 2>   kWhole2{};
+    constexpr FwdBody<true, 3>   kWhole3{};
     // one block of the main pass, in two parts (between them the 16-step form requests its next check-point).
     // rederive: beta[8b+1 .. 8b+len] (the stored, pre-normalisation values) from the value at the block's upper boundary into
     // this lane's private LDS slots (registers are needed for the prefetched operands)
@@ -749,7 +773,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       for (int j = 6; j >= 0; j--) {
         if (whole.value || j <= len - 2) {
           uint32_t idx = b * 8 + j + 2; // index of the stored value we start from
-          if (whole.value ? AR::norm_in_block(j + 2) : (idx != long_sb && AR::norm_at(idx))) {
+          if constexpr (whole.pos == 3) {
+            if (j == 6) { // the group's last block may be the sub-block's: the value at its end is not normalised
+              ARW::normalize_if(st, norm_mask(idx != long_sb));
+            } else if (AR::norm_in_block(j + 2)) {
+              AR::normalize(st);
+            }
+          } else if (whole.value ? AR::norm_in_block(j + 2) : (idx != long_sb && AR::norm_at(idx))) {
             AR::normalize(st);
           }
           beta_step<AR>(st, xs[j + 1], ys[j + 1]);
@@ -771,7 +801,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
                               from_u(b1.x), from_u(b1.y), from_u(b1.z), from_u(b1.w)};
           s2       llr = alpha_step<AR, true>(o, B, xs[j], ys[j]);
           uint32_t k   = b * 8 + j;
-          if (whole.value ? AR::norm_in_block(j) : AR::norm_at(k)) {
+          if constexpr (whole.pos == 0) {
+            if (j == 0) { // the group's first block may be block 0: step 0 is not followed by a normalisation
+              ARW::normalize_if(o, norm_mask(k != 0));
+            } else if (AR::norm_in_block(j)) {
+              AR::normalize(o);
+            }
+          } else if (whole.value ? AR::norm_in_block(j) : AR::norm_at(k)) {
             AR::normalize(o);
           }
           s2 proc = llr;
@@ -943,7 +979,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
               for (int j = 7; j >= 0; j--) {
                 if (whole.value || j < len1) {
                   uint32_t idx = (b + 1) * 8 + j + 1; // index of the value we start from
-                  if (whole.value ? AR::norm_in_block(j + 1) : (idx != long_sb && AR::norm_at(idx))) {
+                  if constexpr (whole.pos == 2) {
+                    if (j == 7) { // the group's second pair may start from the check-point at the sub-block's end, which is not normalised
+                      AR::normalize_if(st, norm_mask(idx != long_sb));
+                    } else if (AR::norm_in_block(j + 1)) {
+                      AR::normalize(st);
+                    }
+                  } else if (whole.value ? AR::norm_in_block(j + 1) : (idx != long_sb && AR::norm_at(idx))) {
                     AR::normalize(st);
                   }
                   beta_step<AR>(st, x1[j], y1[j]);
@@ -964,14 +1006,21 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       constexpr std::integral_constant<bool, false> kOdd{};
       // (one way out, at the bottom: a `break` behind each block is routed through the loop's latch, and the waits at the loop's top are
       // then counted as if a block's own request could still be open there; a block skipped as a whole is an arm without requests)
-      // A group of four starting at b takes the whole-block body when 4 <= b and b + 5 <= nblk: blocks b ... b + 3 are whole (b + 3 <= nblk - 2), none is the
-      // last one, and the pairs' check-points are those of boundaries b + 2 and b + 4 <= nblk - 1, not the sub-block's end.  As in the backward pass the two bodies are
-      // two loops, each emitted once: the general loop runs blocks 0 ... 3 in the first trip of the outer loop and the groups behind the whole-block range in the
-      // second, the whole-block loop has groups only in the first; every way into either loop carries one request in flight, as its back edge does.
-      uint32_t b = 0;
+      // A group of four starting at b takes the whole-block body when its blocks b ... b + 3 are whole ones: b + 5 <= nblk where the last block may be
+      // ragged or the group behind it is not complete, b + 4 <= nblk where the sub-block is a multiple of 32 steps (wl).  Three normalisations of a group can
+      // then fall on an end of the sub-block, where the schedule leaves them out, and are masked instead of branched around (AR::normalize_if): the one behind
+      // step 0 in the first block, and in the second pair -- whose check-point is then the sub-block's end, slot nblk -- the first one of the even block's
+      // walk and of the odd block's re-derivation.  What runs off the end (block b + 3 ... b + 6, the next pair's check-point) is clamped in both bodies.
+      // As in the backward pass the two bodies are two loops, each emitted once.  The general loop runs blocks 0 ... 3 in the first trip of the outer loop
+      // only where the whole-block loop cannot take them (never with nblk >= 6) and the groups behind the whole-block range in the second; the whole-block
+      // loop has groups only in the first.  Every way into either loop carries one request in flight, as its back edge does.  (One loop behind the other,
+      // without the outer one, is the same schedule with 3 more registers and 45 more vector instructions per whole-block group: the compiler then forms the
+      // row addresses of the last half iteration's stores differently.)
+      uint32_t       b  = 0;
+      const uint32_t wl = (long_sb & 31u) ? 5u : 4u;
 #pragma nounroll
       for (int trip = 0; trip < 2; trip++) {
-        const uint32_t gend = trip == 0 ? 4u : nblk;
+        const uint32_t gend = trip == 0 ? (wl <= nblk ? 0u : 4u) : nblk;
 #pragma nounroll
         for (; b < gend; b += 4) {
           block(kGeneral, kEven, b, q0, q1, q3);
@@ -980,11 +1029,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           block(kGeneral, kOdd, b + 3, q3, q0, q2);
         }
 #pragma nounroll
-        for (; b + 5 <= nblk; b += 4) {
-          block(kWhole, kEven, b, q0, q1, q3);
-          block(kWhole, kOdd, b + 1, q1, q2, q0);
-          block(kWhole, kEven, b + 2, q2, q3, q1);
-          block(kWhole, kOdd, b + 3, q3, q0, q2);
+        for (; b + wl <= nblk; b += 4) {
+          block(kWhole0, kEven, b, q0, q1, q3);
+          block(kWhole1, kOdd, b + 1, q1, q2, q0);
+          block(kWhole2, kEven, b + 2, q2, q3, q1);
+          block(kWhole3, kOdd, b + 3, q3, q0, q2);
         }
       }
     }

@@ -466,7 +466,8 @@ typedef struct SRSRAN_API { /* srsran_chest_dl_res_t behind fill_res (entries it
   float rsrp_corr_pair[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]; /* q->rsrp_corr[rx][port] */
   srsran_hip_chest_dl_state_t state;                   /* hand it to the next subframe's call */
 } srsran_hip_chest_dl_res_t;
-/* the stage by itself -- also what a UE binding calls ahead of PCFICH / PDCCH / PHICH, which stay on the host and need the grids.  sf_symbols[rx]: the
+/* the stage by itself -- also what a UE binding calls ahead of PCFICH / PHICH, which stay on the host and need the grids, and of the PDCCH search
+ * (srsran_hip_pdcch_search_sf, phy_conv_abi.h, which takes the grids and these estimates).  sf_symbols[rx]: the
  * received grids, 2 cp_nsymb x 12 nof_prb points each, HOST memory, only read.  ce: NULL (the measurements only), or what a caller passes res->ce as
  * (cf_t* ce[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = [port][rx]); a NULL entry is not written.  The measurements do not depend on which entries are there. */
 SRSRAN_API int srsran_hip_chest_dl_estimate(const srsran_hip_chest_dl_t* cfg, const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],
@@ -477,7 +478,8 @@ SRSRAN_API int srsran_hip_chest_dl_estimate(const srsran_hip_chest_dl_t* cfg, co
  * on the device, or 0 when the grant asks for zero forcing (pdsch.c:819: est->decoder_zf on one port, g->decoder with MIMO; diversity combining takes none).
  * Inside the one receive frame the host stages the received grids only (whole: the estimator reads every CRS symbol), the estimator's kernel writes the ce
  * grids into device scratch, the de-mapping kernel reads them there, and the twin's front-end kernels run unchanged: one launch more than the _sf twin, still
- * one host wait.  The call re-estimates rather than taking a handle from the stage call: between the two the UE decodes the PDCCH on the host.
+ * one host wait.  The call re-estimates rather than taking a handle from the stage call: between the two the UE finds the CFI on the host and searches the PDCCH
+ * (srsran_hip_pdcch_search_sf, phy_conv_abi.h: a call of its own, since the grant is its result).
  * Refused before the device is looked for, with one line on stderr, SRSRAN_ERROR_INVALID_INPUTS, *res = {0, 0, NAN}, *est_out zeroed and nothing else written:
  * everything the _sf twin refuses, everything srsran_hip_chest_dl_estimate refuses, an estimator description whose cell, subframe or antenna count is not
  * the call's, a grant that does not span both whole slots (nof_symb_slot[s] != cp_nsymb: the estimator's grids), decoder_zf above 1.

@@ -14,13 +14,20 @@
  * chain-back that starts from state 0 at the last step (the six zeroed decision words past the end make the best state moot), without tail biting L + 6
  * steps and a chain-back from state 0.
  *
- * NOT taken: srsran_viterbi_init_sse / _avx2 / _neon (the 8-bit decoders), srsran_pdcch_extract_llr (REG de-mapping and the diversity front end), the
- * 0 / 1A format differentiation and the RNTI match (they need dci_cfg: the caller's), the NR polar PDCCH.
+ *   lib/src/phy/phch/regs.c:66-146, 249-373, 492-523, 590-781  the REG map of the control region (srsran_regs_init_opts and what it calls)
+ *   lib/src/phy/phch/pdcch.c:424-487                           srsran_pdcch_extract_llr: REG gather, equaliser, QPSK demodulator, descrambler
+ *   lib/src/phy/mimo/precoding.c:182-305, 428-503              the equaliser bodies the PDCCH runs (no CSI)
+ *
+ * NOT taken: srsran_viterbi_init_sse / _avx2 / _neon (the 8-bit decoders); PCFICH and PHICH (the CFI of a PDCCH search is the caller's, which is why there
+ * is no _est form of it yet -- the REG map restated for the search already knows their REGs); the transmit side (srsran_pdcch_encode,
+ * srsran_regs_pdcch_put); more than 2 receive antennas; the 0 / 1A format differentiation and the RNTI match (they need dci_cfg: the caller's); the NR
+ * polar PDCCH.
  */
 #ifndef SRSRAN_AMD_PHY_CONV_ABI_H
 #define SRSRAN_AMD_PHY_CONV_ABI_H
 
 #include "srsran_amd/phy_abi.h"
+#include "srsran_amd/phy_modem_abi.h" /* cf_t, SRSRAN_MAX_PORTS */
 
 #ifdef __cplusplus
 extern "C" {
@@ -100,6 +107,54 @@ SRSRAN_API int srsran_hip_pdcch_dci_decode_multi(const float* llr, uint32_t nof_
  * in front, the rest (and the rows of candidates that were not decoded) 0 */
 SRSRAN_API int srsran_hip_pdcch_dci_decode_multi_dbg(const float* llr, uint32_t nof_llr, uint32_t n, const srsran_hip_pdcch_cand_t* cand,
                                                      srsran_hip_pdcch_res_t* res, float* rm_f, uint16_t* symbols);
+
+/* ---- the PDCCH search of a subframe from the received grids: REG de-mapping, equaliser, demodulator, descrambler, the mean rule and the decodes on the
+ * device (pdcch_map.h, pdcch_kernels.hip, pdcch_host.cpp) */
+
+/* the control region of one subframe: what srsran_regs_init_opts, srsran_pdcch_set_cell and srsran_pdcch_extract_llr read of the cell and of
+ * srsran_dl_sf_cfg_t.  44 bytes, no padding.  A description outside these ranges is refused. */
+typedef struct SRSRAN_API {
+  uint32_t cell_nof_prb;       /* 6 .. 110 */
+  uint32_t cell_nof_ports;     /* 1, 2 or 4 */
+  uint32_t cell_id;            /* 0 .. 503 */
+  uint32_t cp_nsymb;           /* 7 (normal cyclic prefix) or 6 (extended) */
+  uint32_t phich_length;       /* 0 normal, 1 extended */
+  uint32_t phich_resources;    /* 0 .. 3: Ng = 1/6, 1/2, 1, 2 */
+  uint32_t phich_mi;           /* 0 .. 3; 0: the subframe has no PHICH */
+  uint32_t mbsfn_or_sf1_6_tdd; /* 0 or 1 (regs.c:331-341) */
+  uint32_t cfi;                /* 1 .. 3; the region spans cfi symbols, cfi + 1 when cell_nof_prb <= 10 */
+  uint32_t sf_idx;             /* 0 .. 9: the scrambling sequence's c_init = sf_idx 512 + cell_id */
+  uint32_t nof_rx;             /* 1 or 2 receive antennas */
+} srsran_hip_pdcch_sf_t;
+
+/* Host only (no device is looked for).  What srsran_regs_pdcch_nregs returns for the description -- a multiple of 9 -- or -1 for a NULL or out-of-range one. */
+SRSRAN_API int srsran_hip_regs_pdcch_nregs(const srsran_hip_pdcch_sf_t* sf);
+/* Host only.  re_idx: the 4 nregs grid indices k + l 12 cell_nof_prb of the region's REs, in the order srsran_regs_pdcch_get reads them.  Returns nregs
+ * or -1. */
+SRSRAN_API int srsran_hip_regs_pdcch_table(const srsran_hip_pdcch_sf_t* sf, uint32_t* re_idx);
+/* srsran_regs_pdcch_get on n_planes (1 .. 10) grids at once, HOST memory, one launch: d[p][i] = grids[p][re_idx[i]].  Each grid holds at least the
+ * region's symbols (rows of 12 cell_nof_prb points), each d 4 nregs points.  Returns 4 nregs, -1 for what is refused (one line on stderr) or failed. */
+SRSRAN_API int srsran_hip_regs_pdcch_get(const srsran_hip_pdcch_sf_t* sf, uint32_t n_planes, const cf_t* const* grids, cf_t* const* d);
+/* srsran_pdcch_extract_llr.  sf_symbols[rx]: the received grids, ce[port][rx]: the estimate grids (HOST memory; only the region's symbols are read),
+ * noise_estimate: channel->noise_estimate (halved here, as pdcch.c:471 does; one port only); llr: 72 NOF_CCE floats.  One fused kernel: the REs are read
+ * through the REG table, equalised (one port: sum y conj(h) / (sum |h|^2 + noise), noise added when above 0; two ports: the SFBC combiner with the
+ * hh == 0 -> 1e-4 rule; four ports: the reference's body WITHOUT CSI, precoding.c:465-498), layer de-mapped by where they are stored, demodulated
+ * (x -sqrt 2) and descrambled.  Returns 72 NOF_CCE, SRSRAN_ERROR_INVALID_INPUTS for what is refused, SRSRAN_ERROR on a device-side failure. */
+SRSRAN_API int srsran_hip_pdcch_extract_llr(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], float noise_estimate,
+                                            float* llr);
+/* The whole search of a subframe: srsran_hip_pdcch_extract_llr chained into the decodes of srsran_hip_pdcch_dci_decode_multi without a host wait between
+ * them; the mean rule runs on the device (a double sum in index order: mean and decoded come out as the host's).  One upload (the region's rows of the
+ * planes and the candidates; the REG table is resident), two launches, one download, one host wait.  n == 0 returns 0 and touches nothing.  Refused with
+ * SRSRAN_ERROR_INVALID_INPUTS before the device is looked for, one line on stderr, n results zeroed (when res and n allow): NULL pointers (a needed plane
+ * included), a description out of range, n > 256, L > 3, nof_bits 0 or above 128, ncce 72 + (72 << L) > 72 NOF_CCE of this cfi.  A device-side failure
+ * returns SRSRAN_ERROR (there is no CPU fallback). */
+SRSRAN_API int srsran_hip_pdcch_search_sf(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], float noise_estimate,
+                                          uint32_t n, const srsran_hip_pdcch_cand_t* cand, srsran_hip_pdcch_res_t* res);
+/* the same; each output may be NULL.  llr_out: the 72 NOF_CCE soft bits; d_out: the 36 NOF_CCE equalised symbols; sym_out[rx] / ce_out[port][rx] (the arrays
+ * or any entry may be NULL): the extracted planes, 36 NOF_CCE points each; rm_f / symbols: as srsran_hip_pdcch_dci_decode_multi_dbg */
+SRSRAN_API int srsran_hip_pdcch_search_sf_dbg(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
+                                              float noise_estimate, uint32_t n, const srsran_hip_pdcch_cand_t* cand, srsran_hip_pdcch_res_t* res, float* llr_out,
+                                              cf_t* d_out, cf_t* const* sym_out, cf_t* const (*ce_out)[SRSRAN_MAX_PORTS], float* rm_f, uint16_t* symbols);
 
 #ifdef __cplusplus
 }

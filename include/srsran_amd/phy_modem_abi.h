@@ -95,7 +95,7 @@ SRSRAN_API int srsran_hip_predecoding_single(const cf_t* d_y, const cf_t* d_h, c
  * _csi variant (srsran_predecoding_diversity_csi, the one srsran_pdsch_decode runs: a UE object always has q->csi) whether or not csi is given; csi[0]
  * (nof_symbols floats) is written when csi and csi[0] are non-NULL.  On 2 ports the reference's variants without csi are the same formula; on 4 ports its
  * generic body without csi reads OTHER channel samples (precoding.c:473-476: ports 0 / 2 at 4i and ports 1 / 3 at 4i + 2 for all four layers, against
- * :723-743) and is not reproduced.  2 ports: a pair whose channel gain is 0 divides by 1e-4 (:699-701).  Float arithmetic, every operation rounded once
+ * :723-743) and is not reproduced here (the PDCCH search runs it: srsran_hip_pdcch_extract_llr, phy_conv_abi.h).  2 ports: a pair whose channel gain is 0 divides by 1e-4 (:699-701).  Float arithmetic, every operation rounded once
  * in a fixed order: equals the reference to a few ulp of the sum of products.  nof_symbols must be even (2 ports) or a multiple of 4 (4 ports: the
  * reference leaves the last two symbols of any other grant unwritten, :715; here it is refused with -1).  Returns nof_symbols / nof_ports, or -1. */
 SRSRAN_API int srsran_predecoding_diversity_multi(cf_t* y[SRSRAN_MAX_PORTS], cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], cf_t* x[SRSRAN_MAX_LAYERS],

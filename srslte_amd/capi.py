@@ -300,6 +300,11 @@ class HipPdcchCand(C.Structure):  # srsran_hip_pdcch_cand_t
     _fields_ = [("ncce", C.c_uint32), ("L", C.c_uint32), ("nof_bits", C.c_uint32)]
 
 
+class HipPdcchSf(C.Structure):  # srsran_hip_pdcch_sf_t: the control region of one subframe (44 bytes)
+    _fields_ = [(f, C.c_uint32) for f in ("cell_nof_prb", "cell_nof_ports", "cell_id", "cp_nsymb", "phich_length", "phich_resources", "phich_mi",
+                                          "mbsfn_or_sf1_6_tdd", "cfi", "sf_idx", "nof_rx")]
+
+
 class HipPdcchRes(C.Structure):  # srsran_hip_pdcch_res_t
     _fields_ = [("payload", C.c_uint8 * HIP_DCI_ROW), ("crc_rem", C.c_uint16), ("decoded", C.c_uint16), ("mean", C.c_float)]
 
@@ -734,6 +739,14 @@ def lib():
             "srsran_hip_viterbi_decode_us_multi": (i32, [C.POINTER(Viterbi), u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]),
             "srsran_hip_pdcch_dci_decode_multi": (i32, [vp, u32, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes)]),
             "srsran_hip_pdcch_dci_decode_multi_dbg": (i32, [vp, u32, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), vp, vp]),
+            # the PDCCH search from the grids: sf_symbols is cf_t*[], ce / ce_out are cf_t*[][SRSRAN_MAX_PORTS] ([port][rx]), passed as arrays of pointers
+            "srsran_hip_regs_pdcch_nregs": (i32, [C.POINTER(HipPdcchSf)]),
+            "srsran_hip_regs_pdcch_table": (i32, [C.POINTER(HipPdcchSf), vp]),
+            "srsran_hip_regs_pdcch_get": (i32, [C.POINTER(HipPdcchSf), u32, vp, vp]),
+            "srsran_hip_pdcch_extract_llr": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, vp]),
+            "srsran_hip_pdcch_search_sf": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes)]),
+            "srsran_hip_pdcch_search_sf_dbg": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), vp, vp, vp,
+                                                     vp, vp, vp]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

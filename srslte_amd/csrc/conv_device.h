@@ -9,6 +9,8 @@ constexpr uint32_t kMaxFrame  = 2048; // SRSRAN_HIP_VITERBI_MAX_FRAMEBITS
 constexpr uint32_t kDciBits   = 144;  // SRSRAN_HIP_DCI_MAX_BITS + 16
 constexpr uint32_t kDciSyms   = 3 * kDciBits;
 constexpr uint32_t kDciOutRow = kDciBits + 4; // payload, crc_rem (uint16), two bytes of padding
+constexpr uint32_t kDciResRow = kDciBits + 8; // srsran_hip_pdcch_res_t: payload, crc_rem, decoded (uint16), mean (float)
+constexpr uint32_t kDciMaxE   = 576;          // soft bits of a candidate at aggregation level 3
 
 enum : uint32_t { IN_US = 0, IN_F32 = 1 };
 
@@ -40,6 +42,8 @@ inline size_t lds_bytes(uint32_t Lmax, bool tail_biting) // of a launch whose lo
 hipError_t launch_viterbi(const uint8_t* in, const VitJob* jobs, uint8_t* out, uint32_t n, uint32_t Lmax, bool tail_biting, hipStream_t st);
 // out: n rows of kDciOutRow bytes; dbg_rm / dbg_sym: nullptr or n rows of kDciSyms values
 hipError_t launch_pdcch_dci(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st);
+// the form with the mean rule on the device: a wave per candidate of the search, skipped or not; out: n rows of kDciResRow bytes (srsran_hip_pdcch_res_t)
+hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st);
 
 } // namespace conv
 } // namespace phyhip

@@ -144,19 +144,24 @@ __global__ __launch_bounds__(64) void viterbi_kernel(const uint8_t* __restrict__
 __constant__ uint8_t kPermCC[32]    = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
 __constant__ uint8_t kPermCCInv[32] = {16, 0, 24, 8, 20, 4, 28, 12, 18, 2, 26, 10, 22, 6, 30, 14, 17, 1, 25, 9, 21, 5, 29, 13, 19, 3, 27, 11, 23, 7, 31, 15};
 
-__global__ __launch_bounds__(64) void pdcch_dci_kernel(const float* __restrict__ llr, const DciJob* __restrict__ jobs, uint8_t* __restrict__ out,
-                                                       float* __restrict__ dbg_rm, uint16_t* __restrict__ dbg_sym)
+// what one candidate's decode keeps in LDS
+struct DciLds {
+  uint64_t words[2 * kDciBits];
+  float    rm[kDciSyms];
+  uint16_t sym[kDciSyms];
+  uint8_t  bits[kDciBits];
+};
+
+// One candidate on the calling wave (block of 64): e: its job.E soft bits; row: kDciBits payload bytes, crc_rem (2 bytes, low first), 2 zero bytes;
+// dbg_rm / dbg_sym: nullptr or the candidate's kDciSyms-value rows.
+__device__ __forceinline__ void dci_wave(const float* __restrict__ e, const DciJob& job, DciLds& s, uint8_t* __restrict__ row, float* __restrict__ dbg_rm,
+                                         uint16_t* __restrict__ dbg_sym)
 {
-  __shared__ uint64_t words[2 * kDciBits];
-  __shared__ float    rm[kDciSyms];
-  __shared__ uint16_t sym[kDciSyms];
-  __shared__ uint8_t  bits[kDciBits];
-  DciJob         job  = jobs[blockIdx.x];
-  job.first           = uniform(job.first);
-  job.E               = uniform(job.E);
-  job.nof_bits        = uniform(job.nof_bits);
-  const uint32_t lane = threadIdx.x, L = job.nof_bits + 16, n3 = 3 * L;
-  const float*   e    = llr + job.first;
+  uint64_t* const words = s.words;
+  float* const    rm    = s.rm;
+  uint16_t* const sym   = s.sym;
+  uint8_t* const  bits  = s.bits;
+  const uint32_t  lane = threadIdx.x, L = job.nof_bits + 16, n3 = 3 * L;
   // (a) srsran_rm_conv_rx: the lane that owns an output position walks the inputs that land on it in increasing k -- the sum order of the reference's one
   // pass over the input.  The position's first input is its rank among the non-dummy places of the circular buffer; the others follow every 3 L inputs.
   const uint32_t nrows = (L - 1) / 32 + 1, K_p = nrows * 32, ndummy = K_p - L; // ndummy < 32: the dummies are the first ndummy places of row 0
@@ -189,15 +194,14 @@ __global__ __launch_bounds__(64) void pdcch_dci_kernel(const float* __restrict__
       sym[o] = q;
     }
     if (dbg_rm) {
-      dbg_rm[(size_t)blockIdx.x * kDciSyms + o] = o < n3 ? rm[o] : 0.f;
+      dbg_rm[o] = o < n3 ? rm[o] : 0.f;
     }
     if (dbg_sym) {
-      dbg_sym[(size_t)blockIdx.x * kDciSyms + o] = q;
+      dbg_sym[o] = q;
     }
   }
   __syncthreads();
   // (c) the decoder over nof_bits + 16 bits with tail biting
-  uint8_t* row = out + (size_t)blockIdx.x * kDciOutRow;
   viterbi_wave(sym, L, true, words, row, bits);
   for (uint32_t i = L + lane; i < kDciBits; i += 64) {
     row[i] = 0;
@@ -217,6 +221,77 @@ __global__ __launch_bounds__(64) void pdcch_dci_kernel(const float* __restrict__
     row[kDciBits + 1]  = (uint8_t)(rem >> 8);
     row[kDciBits + 2]  = 0;
     row[kDciBits + 3]  = 0;
+  }
+}
+
+__device__ __forceinline__ DciJob uniform_job(const DciJob* jobs)
+{
+  DciJob job   = jobs[blockIdx.x];
+  job.first    = uniform(job.first);
+  job.E        = uniform(job.E);
+  job.nof_bits = uniform(job.nof_bits);
+  return job;
+}
+
+__global__ __launch_bounds__(64) void pdcch_dci_kernel(const float* __restrict__ llr, const DciJob* __restrict__ jobs, uint8_t* __restrict__ out,
+                                                       float* __restrict__ dbg_rm, uint16_t* __restrict__ dbg_sym)
+{
+  __shared__ DciLds s;
+  const DciJob      job = uniform_job(jobs);
+  dci_wave(llr + job.first, job, s, out + (size_t)blockIdx.x * kDciOutRow, dbg_rm ? dbg_rm + (size_t)blockIdx.x * kDciSyms : nullptr,
+           dbg_sym ? dbg_sym + (size_t)blockIdx.x * kDciSyms : nullptr);
+}
+
+// The form behind the device front end (pdcch_kernels.hip): the soft bits are where that kernel left them, EVERY candidate of the search has a wave, and the
+// rule of srsran_pdcch_decode_msg (pdcch.c:388-393) runs here: mean = (double sum of |soft bit| in index order) / E, decoded = mean > 0.3 -- bit for bit what
+// srsran_hip_pdcch_dci_decode_multi computes on the host (conv_host.cpp).  The 64 lanes widen the candidate's |soft bits| into LDS; lane 0 adds them in index
+// order (at most 576 dependent additions: the order is the result).  A candidate that is skipped leaves a zero row (and zero _dbg rows) with its mean.
+// out: one kDciResRow-byte row per candidate in the layout of srsran_hip_pdcch_res_t.
+__global__ __launch_bounds__(64) void pdcch_dci_sf_kernel(const float* __restrict__ llr, const DciJob* __restrict__ jobs, uint8_t* __restrict__ out,
+                                                          float* __restrict__ dbg_rm, uint16_t* __restrict__ dbg_sym)
+{
+  __shared__ DciLds s;
+  __shared__ double mag[kDciMaxE];
+  __shared__ double mean_s;
+  const DciJob      job  = uniform_job(jobs);
+  const uint32_t    lane = threadIdx.x;
+  const float*      e    = llr + job.first;
+  uint8_t*          row  = out + (size_t)blockIdx.x * kDciResRow;
+  for (uint32_t k = lane; k < job.E; k += 64) {
+    mag[k] = (double)fabsf(e[k]);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    double sum = 0;
+    for (uint32_t k = 0; k < job.E; k++) {
+      sum = __dadd_rn(sum, mag[k]);
+    }
+    mean_s = __ddiv_rn(sum, (double)job.E);
+  }
+  __syncthreads();
+  const double mean    = mean_s;
+  const bool   decoded = mean > 0.3;
+  float*       rm_row  = dbg_rm ? dbg_rm + (size_t)blockIdx.x * kDciSyms : nullptr;
+  uint16_t*    sym_row = dbg_sym ? dbg_sym + (size_t)blockIdx.x * kDciSyms : nullptr;
+  if (decoded) { // (wave-uniform)
+    dci_wave(e, job, s, row, rm_row, sym_row);
+  } else {
+    for (uint32_t i = lane; i < kDciBits + 4; i += 64) {
+      row[i] = 0;
+    }
+    for (uint32_t o = lane; o < kDciSyms; o += 64) {
+      if (rm_row) {
+        rm_row[o] = 0.f;
+      }
+      if (sym_row) {
+        sym_row[o] = 0;
+      }
+    }
+  }
+  if (lane == 0) { // behind dci_wave's own stores of lane 0 to bytes kDciBits .. kDciBits + 3
+    row[kDciBits + 2]                                   = decoded ? 1 : 0;
+    row[kDciBits + 3]                                   = 0;
+    *reinterpret_cast<float*>(row + kDciBits + 4)       = (float)mean;
   }
 }
 
@@ -241,6 +316,15 @@ hipError_t launch_pdcch_dci(const float* llr, const DciJob* jobs, uint8_t* out, 
     return hipSuccess;
   }
   hipLaunchKernelGGL(pdcch_dci_kernel, dim3(n), dim3(64), 0, st, llr, jobs, out, dbg_rm, dbg_sym);
+  return hipGetLastError();
+}
+
+hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st)
+{
+  if (n == 0) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(pdcch_dci_sf_kernel, dim3(n), dim3(64), 0, st, llr, jobs, out, dbg_rm, dbg_sym);
   return hipGetLastError();
 }
 

@@ -166,6 +166,49 @@ __device__ __forceinline__ void sfbc_finish(const Sfbc& a, float scaling, float 
   csi = PORTS == 2 ? make_float2(a.g0, a.g0) : make_float2(__fdiv_rn(d0, nof_rx), __fdiv_rn(d1, nof_rx));
 }
 
+// ---- four ports WITHOUT CSI: srsran_predecoding_diversity_gen_ (mimo/precoding.c:465-498), the body srsran_predecoding_diversity_multi runs when csi is
+// NULL -- which the PDSCH never does and the PDCCH always does (pdcch.c:473; pdcch_kernels.hip).  It is NOT the formula above: one quad of REs (r0 .. r3 on
+// sub-carriers 4i .. 4i + 3) reads ports 0 and 2 at 4i (h0, h2) and ports 1 and 3 at 4i + 2 (h1, h3) for all four layers, and each pair of layers shares
+// one gain:
+//   x0 += conj(h0) r0 + h2 conj(r1)   x1 += -h2 conj(r0) + conj(h0) r1   g02 += |h0|^2 + |h2|^2
+//   x2 += conj(h1) r2 + h3 conj(r3)   x3 += -h3 conj(r2) + conj(h1) r3   g13 += |h1|^2 + |h3|^2      per receive antenna,
+// then x / (g scaling) * M_SQRT2 (sfbc_quot).  No replacement value: a quad whose gain is 0 gives what the formula gives.  Operation order as written there,
+// every product, sum and quotient rounded by itself: the two complex products of a symbol are formed, added to each other, then to the accumulator; a gain's
+// four squares are summed left to right, then added.
+__device__ __forceinline__ float rn_sub(float a, float b);
+struct Sfbc4 {
+  float2 x[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+  float  g02 = 0.f, g13 = 0.f;
+};
+__device__ __forceinline__ void sfbc4_pair(float2& xa, float2& xb, float& g, float2 hp, float2 hq, float2 ra, float2 rb)
+{
+  const float ar = rn_add(rn_mul(hp.x, ra.x), rn_mul(hp.y, ra.y)); // conj(hp) ra
+  const float ai = rn_sub(rn_mul(hp.x, ra.y), rn_mul(hp.y, ra.x));
+  const float br = rn_add(rn_mul(hq.x, rb.x), rn_mul(hq.y, rb.y)); // hq conj(rb)
+  const float bi = rn_sub(rn_mul(hq.y, rb.x), rn_mul(hq.x, rb.y));
+  const float cr = rn_add(rn_mul(hp.x, rb.x), rn_mul(hp.y, rb.y)); // conj(hp) rb
+  const float ci = rn_sub(rn_mul(hp.x, rb.y), rn_mul(hp.y, rb.x));
+  const float dr = rn_add(rn_mul(hq.x, ra.x), rn_mul(hq.y, ra.y)); // hq conj(ra)
+  const float di = rn_sub(rn_mul(hq.y, ra.x), rn_mul(hq.x, ra.y));
+  xa             = make_float2(rn_add(xa.x, rn_add(ar, br)), rn_add(xa.y, rn_add(ai, bi)));
+  xb             = make_float2(rn_add(xb.x, rn_sub(cr, dr)), rn_add(xb.y, rn_sub(ci, di)));
+  g              = rn_add(g, rn_add(rn_add(rn_add(rn_mul(hp.x, hp.x), rn_mul(hp.y, hp.y)), rn_mul(hq.x, hq.x)), rn_mul(hq.y, hq.y)));
+}
+__device__ __forceinline__ void sfbc4_add(Sfbc4& a, float2 h0, float2 h1, float2 h2, float2 h3, float2 r0, float2 r1, float2 r2, float2 r3)
+{
+  sfbc4_pair(a.x[0], a.x[1], a.g02, h0, h2, r0, r1);
+  sfbc4_pair(a.x[2], a.x[3], a.g13, h1, h3, r2, r3);
+}
+__device__ __forceinline__ void sfbc4_finish(const Sfbc4& a, float scaling, float2* x)
+{
+  const float d02 = rn_mul(a.g02, scaling), d13 = rn_mul(a.g13, scaling);
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    const float d = l < 2 ? d02 : d13;
+    x[l]          = make_float2(sfbc_quot(a.x[l].x, d), sfbc_quot(a.x[l].y, d));
+  }
+}
+
 // ---- 2x2 spatial multiplexing and large-delay CDD on 2 ports, 2 receive antennas (mimo/precoding.c:841-1812 receive, :2044-2203 transmit; utils/mat.c:63-109):
 // the one arithmetic of the per-stage kernels and the fused kernels of spmux_kernels.hip.  Operation order: that of the reference's scalar loop bodies
 // (the `for (; i < nof_symbols; ...)` tails, the _csi variants), a complex product evaluated as C does ((ar br - ai bi) + j (ar bi + ai br)), every

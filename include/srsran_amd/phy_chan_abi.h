@@ -466,8 +466,9 @@ typedef struct SRSRAN_API { /* srsran_chest_dl_res_t behind fill_res (entries it
   float rsrp_corr_pair[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS]; /* q->rsrp_corr[rx][port] */
   srsran_hip_chest_dl_state_t state;                   /* hand it to the next subframe's call */
 } srsran_hip_chest_dl_res_t;
-/* the stage by itself -- also what a UE binding calls ahead of PCFICH / PHICH, which stay on the host and need the grids, and of the PDCCH search
- * (srsran_hip_pdcch_search_sf, phy_conv_abi.h, which takes the grids and these estimates).  sf_symbols[rx]: the
+/* the stage by itself.  A UE binding no longer needs it ahead of PCFICH / PHICH and the PDCCH search: they run on the device, and
+ * srsran_hip_pdcch_search_est (phy_conv_abi.h) chains this estimator, both channels and the search in one call from the received grids; the calls that take
+ * these estimates (srsran_hip_pcfich_decode, srsran_hip_phich_decode_multi, srsran_hip_pdcch_search_sf) remain for callers that hold them.  sf_symbols[rx]: the
  * received grids, 2 cp_nsymb x 12 nof_prb points each, HOST memory, only read.  ce: NULL (the measurements only), or what a caller passes res->ce as
  * (cf_t* ce[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = [port][rx]); a NULL entry is not written.  The measurements do not depend on which entries are there. */
 SRSRAN_API int srsran_hip_chest_dl_estimate(const srsran_hip_chest_dl_t* cfg, const srsran_hip_chest_dl_state_t* state_in, cf_t* const sf_symbols[],

@@ -18,15 +18,18 @@
  *   lib/src/phy/phch/pdcch.c:424-487                           srsran_pdcch_extract_llr: REG gather, equaliser, QPSK demodulator, descrambler
  *   lib/src/phy/mimo/precoding.c:182-305, 428-503              the equaliser bodies the PDCCH runs (no CSI)
  *
- * NOT taken: srsran_viterbi_init_sse / _avx2 / _neon (the 8-bit decoders); PCFICH and PHICH (the CFI of a PDCCH search is the caller's, which is why there
- * is no _est form of it yet -- the REG map restated for the search already knows their REGs); the transmit side (srsran_pdcch_encode,
- * srsran_regs_pdcch_put); more than 2 receive antennas; the 0 / 1A format differentiation and the RNTI match (they need dci_cfg: the caller's); the NR
- * polar PDCCH.
+ *   lib/src/phy/phch/pcfich.c:118-137, 156-222; phich.c:147-171, 181-312   srsran_pcfich_decode and srsran_phich_decode (ctrl_kernels.hip)
+ *   lib/src/phy/ue/ue_dl.c:315-343                             estimate_pdcch_pcfich: estimator, PCFICH, PDCCH front end -- srsran_hip_pdcch_search_est
+ *
+ * NOT taken: srsran_viterbi_init_sse / _avx2 / _neon (the 8-bit decoders); the transmit side (srsran_pcfich_encode, srsran_phich_encode, srsran_pdcch_encode,
+ * srsran_regs_*_put); srsran_phich_calc (the resource of a grant: the caller's); more than 2 receive antennas; the 0 / 1A format differentiation and the RNTI
+ * match (they need dci_cfg: the caller's); the NR polar PDCCH.
  */
 #ifndef SRSRAN_AMD_PHY_CONV_ABI_H
 #define SRSRAN_AMD_PHY_CONV_ABI_H
 
 #include "srsran_amd/phy_abi.h"
+#include "srsran_amd/phy_chan_abi.h"  /* srsran_hip_chest_dl_t and its state and result (srsran_hip_pdcch_search_est) */
 #include "srsran_amd/phy_modem_abi.h" /* cf_t, SRSRAN_MAX_PORTS */
 
 #ifdef __cplusplus
@@ -155,6 +158,94 @@ SRSRAN_API int srsran_hip_pdcch_search_sf(const srsran_hip_pdcch_sf_t* sf, cf_t*
 SRSRAN_API int srsran_hip_pdcch_search_sf_dbg(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS],
                                               float noise_estimate, uint32_t n, const srsran_hip_pdcch_cand_t* cand, srsran_hip_pdcch_res_t* res, float* llr_out,
                                               cf_t* d_out, cf_t* const* sym_out, cf_t* const (*ce_out)[SRSRAN_MAX_PORTS], float* rm_f, uint16_t* symbols);
+
+/* ---- PCFICH and PHICH on the device (pdcch_map.h, ctrl_kernels.hip, ctrl_host.cpp): the CFI of a subframe and its HARQ indications from the received
+ * grids and the estimates.  sf->cfi is not read by any of these calls, but the description goes through the same validation as everywhere: it must hold
+ * 1 .. 3. */
+
+/* Host only (no device is looked for).  re_idx: the 16 grid indices srsran_regs_pcfich_get reads (all on symbol 0), in its order: four REGs at
+ * k = (6 (cell_id % (2 nof_prb)) + 6 (i nof_prb / 2)) % (12 nof_prb), found by their first sub-carrier.  Returns 16, or -1 for what the PDCCH table refuses. */
+SRSRAN_API int srsran_hip_regs_pcfich_table(const srsran_hip_pdcch_sf_t* sf, uint32_t re_idx[16]);
+/* Host only.  srsran_regs_phich_ngroups: phich_mi ceilf(Ng (nof_prb / 8)), twice that with the extended cyclic prefix, 0 when phich_mi == 0; -1 as above. */
+SRSRAN_API int srsran_hip_regs_phich_ngroups(const srsran_hip_pdcch_sf_t* sf);
+/* Host only.  re_idx: the 12 grid indices k + l 12 nof_prb srsran_regs_phich_get reads for the group (mapping unit ngroup / 2 with the extended prefix), on
+ * symbols 0 .. 2.  Returns 12, or -1 (ngroup >= ngroups included). */
+SRSRAN_API int srsran_hip_regs_phich_table(const srsran_hip_pdcch_sf_t* sf, uint32_t ngroup, uint32_t re_idx[12]);
+
+/* srsran_pcfich_decode (pcfich.c:118-137, 156-222).  sf_symbols[rx], ce[port][rx]: HOST memory, only symbol 0 is read; noise_estimate:
+ * channel->noise_estimate, NOT halved (unlike the PDCCH), one port only, added to the gain when above 0 (the body the reference runs on 16 symbols,
+ * srsran_predecoding_single_gen, adds it as it is: the same for every estimate that is not negative).  One launch of one wave: the 16 REs through the table,
+ * the PDCCH's three equalisers (four ports WITHOUT CSI), layer de-mapping by where the result is stored, the QPSK float demodulator, the descrambler with
+ * c_init = (sf_idx + 1)(2 cell_id + 1) 512 + cell_id, and three correlations against 2 b - 1 of Table 5.3.4-1, each summed in index order from 0
+ * (srsran_vec_dot_prod_fff is a plain loop, and the reference's flags do not let the compiler reorder it).  The decision is the reference's: max_corr starts at
+ * 0 and the comparison is strict, so when no correlation is positive *cfi = 1 and *corr = 0.  corr may be NULL.  One upload, one launch, one download, one host
+ * wait.  Returns 1 as the reference does; SRSRAN_ERROR_INVALID_INPUTS with one line on stderr and *cfi, *corr zeroed, before the device is looked for, for NULL
+ * pointers (a needed plane included) and a description the map refuses; SRSRAN_ERROR on a device-side failure (there is no CPU fallback). */
+SRSRAN_API int srsran_hip_pcfich_decode(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], float noise_estimate,
+                                        uint32_t* cfi, float* corr);
+/* the same; each output may be NULL.  data_f: the 32 descrambled soft bits (q->data_f); d: the 16 equalised symbols (q->d); corr3: the three correlations */
+SRSRAN_API int srsran_hip_pcfich_decode_dbg(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], float noise_estimate,
+                                            uint32_t* cfi, float* corr, float data_f[32], cf_t d[16], float corr3[3]);
+
+#define SRSRAN_HIP_PHICH_MAX_RESOURCES 16
+
+typedef struct SRSRAN_API {
+  uint32_t ngroup; /* below srsran_hip_regs_phich_ngroups */
+  uint32_t nseq;   /* below 8 (normal cyclic prefix) or 4 (extended) */
+} srsran_hip_phich_resource_t;
+
+typedef struct SRSRAN_API {
+  uint32_t ack_value; /* srsran_phich_ack_decode: 1 when the mean of the three soft bits is above that of their negatives */
+  float    distance;  /* that mean: max_corr starts at -9999 and the comparison is strict */
+  float    bits[3];   /* q->data_rx: -(re + im) of z in float, times M_SQRT1_2 in double, rounded once */
+  cf_t     z[3];      /* q->z: the de-spread symbols */
+} srsran_hip_phich_res_t; /* 44 bytes */
+
+/* srsran_phich_decode (phich.c:147-171, 181-312) of n resources of one subframe in one launch, one wave per resource: the group's 12 REs per plane, the
+ * equalisers and the noise rule of srsran_hip_pcfich_decode, with the extended prefix d0[4 i + 2 (ngroup % 2) + {0, 1}], the descrambler of the PCFICH's c_init
+ * (12 chips), the de-spreading sum of conj(w[nseq][j]) d[NSF i + j] / NSF in j order from 0 (NSF 4, or 2 with the extended prefix), the BPSK float demodulator and
+ * the decision.  Only the symbols the PHICH reaches (at most 0 .. 2) are read.  n == 0 is a no-op (0).  One upload, one launch, one download, one host wait.
+ * Returns SRSRAN_SUCCESS; SRSRAN_ERROR_INVALID_INPUTS with one line on stderr and the n results zeroed (when res and n allow), before the device is looked
+ * for, for NULL pointers (a needed plane included), a description the map refuses, n > 16, ngroup >= ngroups, nseq >= 8 (4 with the extended prefix);
+ * SRSRAN_ERROR on a device-side failure. */
+SRSRAN_API int srsran_hip_phich_decode_multi(const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], float noise_estimate,
+                                             uint32_t n, const srsran_hip_phich_resource_t* r, srsran_hip_phich_res_t* res);
+
+/* ---- the control side of a subframe from the received grids alone: what estimate_pdcch_pcfich (ue_dl.c:315-343) chains -- srsran_chest_dl_estimate_cfg,
+ * srsran_pcfich_decode, srsran_pdcch_extract_llr -- with the candidate decodes and srsran_phich_decode behind it, in one device call */
+typedef struct SRSRAN_API {
+  uint32_t n_cand[3]; /* the lengths of the three candidate lists: n_cand[c - 1] candidates for CFI c, each 0 .. 256 */
+  uint32_t cfi3_to_2; /* 1: the TDD subframe 1 / 6 rule of ue_dl.c:331, a decoded CFI of 3 becomes 2 before the PDCCH; 0 or 1 */
+  uint32_t n_phich;   /* PHICH resources, 0 .. 16 */
+} srsran_hip_pdcch_est_t;
+
+/* sf: the description (cfi is not read, but must hold 1 .. 3); est, state_in: the estimator's, as srsran_hip_chest_dl_estimate takes them (phy_chan_abi.h);
+ * sf_symbols[rx]: the whole received grids, HOST memory; cand: the three lists one behind the other -- the list of CFI c holds the candidates valid for that
+ * CFI's NOF_CCE, since the caller cannot know the CFI yet; res: max(n_cand) rows, of which the first n_cand[cfi - 1] are filled and the rest stay zero; phich /
+ * phich_res: opt->n_phich resources and results (may be NULL when it is 0); *cfi: the decoded CFI after the cfi3_to_2 rule; *cfi_corr: its correlation (may be
+ * NULL); est_out: what srsran_hip_chest_dl_estimate returns.
+ * On the device, in stream order and without a host wait between them: chest_dl_kernel (the ce grids go to device scratch, the pairs' noise estimates to device
+ * memory), ctrl_kernel (PCFICH and PHICH with the noise estimate fill_res reports, averaged on the device; it leaves the CFI as one word of device memory),
+ * pdcch_front_kernel launched for the region of CFI 3 (it reads that word, takes the table and the size of that CFI's region -- all three tables are resident --
+ * and one port takes half the noise estimate) and pdcch_dci_sf_kernel launched for max(n_cand) waves (it takes that CFI's list; waves past its length leave).
+ * One upload (the whole grids -- the estimator reads every CRS symbol -- the pilot rows, the estimator's jobs, the three lists and the PHICH resources), four
+ * launches, one download (the estimator's records, the CFI and its correlation, the PHICH results, the result rows), one host wait.
+ * Refused with SRSRAN_ERROR_INVALID_INPUTS before the device is looked for, one line on stderr, the results, *cfi, *cfi_corr and *est_out zeroed (when the
+ * pointers and counts allow): everything srsran_hip_pdcch_search_sf, srsran_hip_chest_dl_estimate and srsran_hip_phich_decode_multi refuse, an estimator
+ * description whose cell, subframe or antenna count is not sf's, nof_rx above 2, n_cand[c] > 256, a candidate past the region of its list's CFI, cfi3_to_2
+ * above 1, a description on which any of the three CFIs has no table.  A device-side failure returns SRSRAN_ERROR (there is no CPU fallback). */
+SRSRAN_API int srsran_hip_pdcch_search_est(const srsran_hip_pdcch_sf_t* sf, const srsran_hip_chest_dl_t* est, const srsran_hip_chest_dl_state_t* state_in,
+                                           cf_t* const sf_symbols[], const srsran_hip_pdcch_est_t* opt, const srsran_hip_pdcch_cand_t* cand,
+                                           srsran_hip_pdcch_res_t* res, const srsran_hip_phich_resource_t* phich, srsran_hip_phich_res_t* phich_res, uint32_t* cfi,
+                                           float* cfi_corr, srsran_hip_chest_dl_res_t* est_out);
+/* the same; each output may be NULL.  llr_out: the 72 NOF_CCE soft bits of the decoded CFI (the caller sizes it for CFI 3; what lies behind is not written);
+ * pcfich_data_f: the PCFICH's 32 soft bits; ce_grid_out[port][rx] (the array or an entry may be NULL): the pair's whole ce grid; rm_f / symbols: max(n_cand)
+ * rows as srsran_hip_pdcch_search_sf_dbg has them, the rows past the chosen list's length zero */
+SRSRAN_API int srsran_hip_pdcch_search_est_dbg(const srsran_hip_pdcch_sf_t* sf, const srsran_hip_chest_dl_t* est, const srsran_hip_chest_dl_state_t* state_in,
+                                               cf_t* const sf_symbols[], const srsran_hip_pdcch_est_t* opt, const srsran_hip_pdcch_cand_t* cand,
+                                               srsran_hip_pdcch_res_t* res, const srsran_hip_phich_resource_t* phich, srsran_hip_phich_res_t* phich_res,
+                                               uint32_t* cfi, float* cfi_corr, srsran_hip_chest_dl_res_t* est_out, float* llr_out, float pcfich_data_f[32],
+                                               cf_t* const (*ce_grid_out)[SRSRAN_MAX_PORTS], float* rm_f, uint16_t* symbols);
 
 #ifdef __cplusplus
 }

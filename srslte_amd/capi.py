@@ -309,6 +309,18 @@ class HipPdcchRes(C.Structure):  # srsran_hip_pdcch_res_t
     _fields_ = [("payload", C.c_uint8 * HIP_DCI_ROW), ("crc_rem", C.c_uint16), ("decoded", C.c_uint16), ("mean", C.c_float)]
 
 
+class HipPhichResource(C.Structure):  # srsran_hip_phich_resource_t
+    _fields_ = [("ngroup", C.c_uint32), ("nseq", C.c_uint32)]
+
+
+class HipPhichRes(C.Structure):  # srsran_hip_phich_res_t (44 bytes); z: re, im
+    _fields_ = [("ack_value", C.c_uint32), ("distance", C.c_float), ("bits", C.c_float * 3), ("z", C.c_float * 2 * 3)]
+
+
+class HipPdcchEst(C.Structure):  # srsran_hip_pdcch_est_t
+    _fields_ = [("n_cand", C.c_uint32 * 3), ("cfi3_to_2", C.c_uint32), ("n_phich", C.c_uint32)]
+
+
 class HipCell(C.Structure):
     _fields_ = [("peak_pos", C.c_int32), ("peak_value", C.c_float), ("psr", C.c_float), ("sss_available", C.c_int32),
                 ("m0", C.c_uint32), ("m1", C.c_uint32), ("m0_value", C.c_float), ("m1_value", C.c_float), ("N_id_1", C.c_int32),
@@ -747,6 +759,19 @@ def lib():
             "srsran_hip_pdcch_search_sf": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes)]),
             "srsran_hip_pdcch_search_sf_dbg": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, u32, C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), vp, vp, vp,
                                                      vp, vp, vp]),
+            # PCFICH and PHICH: the same pointer arrays
+            "srsran_hip_regs_pcfich_table": (i32, [C.POINTER(HipPdcchSf), vp]),
+            "srsran_hip_regs_phich_ngroups": (i32, [C.POINTER(HipPdcchSf)]),
+            "srsran_hip_regs_phich_table": (i32, [C.POINTER(HipPdcchSf), u32, vp]),
+            "srsran_hip_pcfich_decode": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, C.POINTER(u32), C.POINTER(C.c_float)]),
+            "srsran_hip_pcfich_decode_dbg": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, C.POINTER(u32), C.POINTER(C.c_float), vp, vp, vp]),
+            "srsran_hip_phich_decode_multi": (i32, [C.POINTER(HipPdcchSf), vp, vp, C.c_float, u32, C.POINTER(HipPhichResource), C.POINTER(HipPhichRes)]),
+            "srsran_hip_pdcch_search_est": (i32, [C.POINTER(HipPdcchSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp, C.POINTER(HipPdcchEst),
+                                                  C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), C.POINTER(HipPhichResource), C.POINTER(HipPhichRes),
+                                                  C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pdcch_search_est_dbg": (i32, [C.POINTER(HipPdcchSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp, C.POINTER(HipPdcchEst),
+                                                      C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), C.POINTER(HipPhichResource), C.POINTER(HipPhichRes),
+                                                      C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(HipChestDlRes), vp, vp, vp, vp, vp]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

@@ -42,8 +42,15 @@ inline size_t lds_bytes(uint32_t Lmax, bool tail_biting) // of a launch whose lo
 hipError_t launch_viterbi(const uint8_t* in, const VitJob* jobs, uint8_t* out, uint32_t n, uint32_t Lmax, bool tail_biting, hipStream_t st);
 // out: n rows of kDciOutRow bytes; dbg_rm / dbg_sym: nullptr or n rows of kDciSyms values
 hipError_t launch_pdcch_dci(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st);
+// a search whose CFI a kernel ahead on the stream leaves in device memory (ctrl_kernels.hip): `jobs` holds the lists of CFI 1, 2 and 3 one behind the other,
+// the launch has max(n[]) waves, a wave reads *cfi (1 .. 3), takes job first[cfi - 1] + its number of that list and leaves when the list is shorter
+struct DciSel {
+  const uint32_t* cfi; // nullptr: one list, every wave has a job
+  uint32_t        first[3], n[3];
+};
 // the form with the mean rule on the device: a wave per candidate of the search, skipped or not; out: n rows of kDciResRow bytes (srsran_hip_pdcch_res_t)
-hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st);
+hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st,
+                               const DciSel* sel = nullptr);
 
 } // namespace conv
 } // namespace phyhip

@@ -246,13 +246,21 @@ __global__ __launch_bounds__(64) void pdcch_dci_kernel(const float* __restrict__
 // rule of srsran_pdcch_decode_msg (pdcch.c:388-393) runs here: mean = (double sum of |soft bit| in index order) / E, decoded = mean > 0.3 -- bit for bit what
 // srsran_hip_pdcch_dci_decode_multi computes on the host (conv_host.cpp).  The 64 lanes widen the candidate's |soft bits| into LDS; lane 0 adds them in index
 // order (at most 576 dependent additions: the order is the result).  A candidate that is skipped leaves a zero row (and zero _dbg rows) with its mean.
-// out: one kDciResRow-byte row per candidate in the layout of srsran_hip_pdcch_res_t.
+// out: one kDciResRow-byte row per candidate in the layout of srsran_hip_pdcch_res_t.  With sel.cfi the wave picks its list by the CFI in device memory
+// (conv_device.h: DciSel) and leaves, writing nothing, when that list is shorter than its number.
 __global__ __launch_bounds__(64) void pdcch_dci_sf_kernel(const float* __restrict__ llr, const DciJob* __restrict__ jobs, uint8_t* __restrict__ out,
-                                                          float* __restrict__ dbg_rm, uint16_t* __restrict__ dbg_sym)
+                                                          float* __restrict__ dbg_rm, uint16_t* __restrict__ dbg_sym, const DciSel sel)
 {
   __shared__ DciLds s;
   __shared__ double mag[kDciMaxE];
   __shared__ double mean_s;
+  if (sel.cfi) {
+    const uint32_t c = min(uniform(*sel.cfi) - 1u, 2u);
+    if (blockIdx.x >= sel.n[c]) {
+      return;
+    }
+    jobs += sel.first[c];
+  }
   const DciJob      job  = uniform_job(jobs);
   const uint32_t    lane = threadIdx.x;
   const float*      e    = llr + job.first;
@@ -319,12 +327,12 @@ hipError_t launch_pdcch_dci(const float* llr, const DciJob* jobs, uint8_t* out, 
   return hipGetLastError();
 }
 
-hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st)
+hipError_t launch_pdcch_dci_sf(const float* llr, const DciJob* jobs, uint8_t* out, float* dbg_rm, uint16_t* dbg_sym, uint32_t n, hipStream_t st, const DciSel* sel)
 {
   if (n == 0) {
     return hipSuccess;
   }
-  hipLaunchKernelGGL(pdcch_dci_sf_kernel, dim3(n), dim3(64), 0, st, llr, jobs, out, dbg_rm, dbg_sym);
+  hipLaunchKernelGGL(pdcch_dci_sf_kernel, dim3(n), dim3(64), 0, st, llr, jobs, out, dbg_rm, dbg_sym, sel ? *sel : DciSel{});
   return hipGetLastError();
 }
 

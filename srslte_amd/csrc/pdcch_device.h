@@ -1,6 +1,7 @@
 // pdcch_device.h -- what pdcch_host.cpp and pdcch_kernels.hip share: the parameter block of the PDCCH front end and the launches.
 #pragma once
 #include "hip_common.h"
+#include "modem_device.h"
 
 namespace phyhip {
 namespace pdcch {
@@ -24,6 +25,12 @@ struct FrontParams {
   float2*         dbg_d;      // nullptr, or nsym equalised symbols
   float2*         dbg_planes; // nullptr, or the extracted planes: plane p at dbg_planes + p * dbg_stride, nsym points each
   uint32_t        dbg_stride;
+  // what the search from the received grids alone sets (srsran_hip_pdcch_search_est); all null / zero: the behaviour above
+  const float2*   ce;        // nullptr: the estimate grids lie behind the received ones in `planes`; else [port][rx] at ce + (port * nof_rx + rx) * plane_stride
+  modem::NoiseAvg noise_dev; // v != nullptr: one port takes half the estimate a kernel ahead on the stream left, instead of `noise`
+  const uint32_t* cfi_dev;   // nullptr, or the CFI (1 .. 3) in device memory: the launch covers nsym (the largest region), the kernel takes
+  const uint32_t* tab3[3];   //   the table and the size of that CFI's region, and the lanes past it leave
+  uint32_t        nsym3[3];
 };
 hipError_t launch_front(const FrontParams& p, hipStream_t st);
 // srsran_regs_pdcch_get on n_planes staged planes: out[p * out_stride + i] = planes[p * plane_stride + tab[i]], i < nsym

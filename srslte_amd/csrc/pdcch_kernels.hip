@@ -3,15 +3,15 @@
 //
 // One lane per group of `ports` neighbouring REs of a REG (a REG has four, so a group never leaves it): one symbol on one port, an SFBC pair on two, a quad
 // on four.  The lane reads its REs of every plane straight from the staged grids through the REG table (pdcch_map.h) -- there is no extracted plane in
-// memory -- equalises them, and stores its 2 * ports soft bits where the layer de-mapping puts them: symbol j of group g is symbol g * ports + j of d.
-//   one port    x = sum_rx y conj(h) / (sum_rx |h|^2 [+ noise when noise > 0])      srsran_predecoding_single_multi, precoding.c:182-305
-//   two ports   modem_arith.h sfbc_add<2> / sfbc_finish<2>                           srsran_predecoding_diversity_gen_, :438-463 (hh == 0 -> 1e-4)
-//   four ports  modem_arith.h sfbc4_add / sfbc4_finish                               the body WITHOUT CSI, :465-498
+// memory -- equalises them (pdcch_arith.h: eq_group), and stores its 2 * ports soft bits where the layer de-mapping puts them: symbol j of group g is
+// symbol g * ports + j of d;
 // then soft bit = component * (float)-M_SQRT2 (srsran_demod_soft_demodulate, QPSK to float), its sign flipped where the chip of the sequence with
 // c_init = sf_idx * 512 + cell_id is 1 (srsran_scrambling_f_offset).  A wave covers 128 * ports consecutive soft bits, so its chips start at a multiple of
 // 128: make_chips (modem_arith.h) from the tables srsran_sequence_apply_f uses.  Every operation of the one-port and four-port arithmetic is rounded once in a
 // fixed order (rn_*); no atomics: the same input gives the same bits.  Indices are 32-bit; the table's entries were bounds-checked when it was built.
-#include "modem_arith.h"
+// In the search from the received grids alone the CFI, and so the table and the region's size, and the noise estimate are read from device memory, where the
+// kernels ahead on the stream left them (pdcch_device.h: FrontParams::cfi_dev, noise_dev).
+#include "pdcch_arith.h"
 #include "pdcch_device.h"
 
 namespace phyhip {
@@ -26,67 +26,37 @@ __global__ __launch_bounds__(64) void pdcch_front_kernel(const FrontParams p)
   constexpr uint32_t                               BITS = 2 * PORTS; // soft bits of a lane
   __shared__ __attribute__((aligned(16))) uint32_t cb[4 * PORTS + 4];
   const uint32_t lane = threadIdx.x, g = blockIdx.x * 64u + lane, bit0 = blockIdx.x * 64u * BITS;
+  const uint32_t* tab  = p.tab;
+  uint32_t        nsym = p.nsym;
+  if (p.cfi_dev) { // the region of the CFI the PCFICH kernel left (wave-uniform)
+    const uint32_t c = min(*p.cfi_dev - 1u, 2u);
+    tab  = p.tab3[c];
+    nsym = p.nsym3[c];
+    if (bit0 >= 2u * nsym) {
+      return;
+    }
+  }
   if (lane < 4 * PORTS + 4) {
     cb[lane] = 0; // chips_at reads one word past the last one
   }
-  make_chips(p.x1_bits, p.x2_cols, p.seed, bit0, min(64u * BITS, 2u * p.nsym - bit0), cb);
-  if (g * PORTS >= p.nsym) {
+  make_chips(p.x1_bits, p.x2_cols, p.seed, bit0, min(64u * BITS, 2u * nsym - bit0), cb);
+  if (g * PORTS >= nsym) {
     return;
   }
   uint32_t idx[PORTS];
-  if (PORTS == 4) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p.tab + g * 4u);
-    idx[0] = t.x, idx[PORTS > 1 ? 1 : 0] = t.y, idx[PORTS > 2 ? 2 : 0] = t.z, idx[PORTS > 3 ? 3 : 0] = t.w;
-  } else if (PORTS == 2) {
-    const uint2 t = *reinterpret_cast<const uint2*>(p.tab + g * 2u);
-    idx[0] = t.x, idx[PORTS > 1 ? 1 : 0] = t.y;
+  if constexpr (PORTS == 4) {
+    const uint4 t = *reinterpret_cast<const uint4*>(tab + g * 4u);
+    idx[0] = t.x, idx[1] = t.y, idx[2] = t.z, idx[3] = t.w;
+  } else if constexpr (PORTS == 2) {
+    const uint2 t = *reinterpret_cast<const uint2*>(tab + g * 2u);
+    idx[0] = t.x, idx[1] = t.y;
   } else {
-    idx[0] = p.tab[g];
+    idx[0] = tab[g];
   }
   const uint32_t stride = p.plane_stride, nof_rx = p.nof_rx;
   float2         x[PORTS];
-  if (PORTS == 1) {
-    float xr = 0.f, xi = 0.f, gain = 0.f;
-    for (uint32_t a = 0; a < nof_rx; a++) {
-      const float2 y = p.planes[a * stride + idx[0]], h = p.planes[(nof_rx + a) * stride + idx[0]];
-      const float  pr = rn_add(rn_mul(h.x, y.x), rn_mul(h.y, y.y)); // conj(h) y
-      const float  pi = rn_sub(rn_mul(h.x, y.y), rn_mul(h.y, y.x));
-      const float  sq = rn_add(rn_mul(h.x, h.x), rn_mul(h.y, h.y));
-      xr              = a == 0 ? pr : rn_add(xr, pr);
-      xi              = a == 0 ? pi : rn_add(xi, pi);
-      gain            = a == 0 ? sq : rn_add(gain, sq);
-    }
-    if (p.noise > 0.f) {
-      gain = rn_add(gain, p.noise);
-    }
-    x[0] = make_float2(rn_div(xr, gain), rn_div(xi, gain));
-  } else if (PORTS == 2) {
-    Sfbc acc;
-    for (uint32_t a = 0; a < nof_rx; a++) {
-      const float2* y  = p.planes + a * stride;
-      const float2* h0 = p.planes + (nof_rx + a) * stride;
-      const float2* h1 = p.planes + (2 * nof_rx + a) * stride;
-      const uint32_t k0 = idx[0], k1 = idx[PORTS > 1 ? 1 : 0];
-      sfbc_add<2>(acc, h0[k0], h1[k1], h1[k0], h0[k1], y[k0], y[k1]);
-    }
-    float2 csi;
-    sfbc_finish<2>(acc, 1.0f, (float)nof_rx, x[0], x[PORTS > 1 ? 1 : 0], csi);
-  } else {
-    Sfbc4 acc;
-    for (uint32_t a = 0; a < nof_rx; a++) {
-      const float2*  y  = p.planes + a * stride;
-      const uint32_t k0 = idx[0], k1 = idx[PORTS > 1 ? 1 : 0], k2 = idx[PORTS > 2 ? 2 : 0], k3 = idx[PORTS > 3 ? 3 : 0];
-      const float2   h0 = p.planes[(nof_rx + a) * stride + k0], h1 = p.planes[(2 * nof_rx + a) * stride + k2];
-      const float2   h2 = p.planes[(3 * nof_rx + a) * stride + k0], h3 = p.planes[(4 * nof_rx + a) * stride + k2];
-      sfbc4_add(acc, h0, h1, h2, h3, y[k0], y[k1], y[k2], y[k3]);
-    }
-    float2 x4[4];
-    sfbc4_finish(acc, 1.0f, x4);
-#pragma unroll
-    for (int j = 0; j < PORTS; j++) {
-      x[j] = x4[j];
-    }
-  }
+  const float noise = (PORTS == 1 && p.noise_dev.v) ? rn_mul(noise_avg(p.noise_dev), 0.5f) : p.noise; // pdcch.c:471
+  eq_group<PORTS>(p.planes, p.ce ? p.ce : p.planes + nof_rx * stride, stride, nof_rx, idx, noise, x);
   const uint32_t c = chips_at(cb, lane * BITS);
   float          v[BITS];
 #pragma unroll

@@ -1,6 +1,7 @@
 // pdcch_map.h -- which REs of a subframe grid the PDCCH's control region takes, in the order srsran_regs_pdcch_get reads them: srsran_regs_init_opts and
 // what it calls (phch/regs.c:692-781), restated as written and with its quirks.  ONE restatement, plain C++ (no device code): srsran_hip_regs_pdcch_nregs /
-// _table and the table the front-end kernel reads through (pdcch_kernels.hip) all come from build().
+// _table, the table the front-end kernel reads through (pdcch_kernels.hip) and the REs of the PCFICH and the PHICH groups (srsran_hip_regs_pcfich_table /
+// _phich_ngroups / _phich_table, ctrl_host.cpp) all come from build().
 //
 // The rules.  The region's symbols are l = 0 .. max_ctrl - 1, max_ctrl = 4 on a cell of at most 10 PRB and 3 otherwise.  Symbol l has n[l] REGs per PRB
 // (regs_num_x_symbol, :590): 2 on symbol 0, 2 on symbol 1 of a 4-port cell, 2 on symbol 3 with the extended cyclic prefix, else 3.
@@ -73,6 +74,12 @@ inline uint32_t nof_ctrl_symbols(const srsran_hip_pdcch_sf_t& sf) // the rows of
 struct Table {
   uint32_t              nregs = 0; // a multiple of 9
   std::vector<uint32_t> re_idx;    // 4 nregs grid indices, each below nof_ctrl_symbols 12 nof_prb (checked by build)
+  // the two small channels (they do not depend on the cfi): what srsran_regs_pcfich_get and srsran_regs_phich_get read, in their order
+  uint32_t              pcfich[16] = {}; // on symbol 0: each below 12 nof_prb
+  uint32_t              phich_units = 0; // mapping units (ngroups_phich before the doubling): phich_mi ceilf(Ng (nof_prb / 8)), 0 without PHICH
+  uint32_t              phich_groups = 0; // srsran_regs_phich_ngroups: the units, twice that with the extended prefix (group g reads unit g / 2)
+  uint32_t              phich_rows = 0;   // the grid rows the units reach: 1 .. 3, 0 without PHICH
+  std::vector<uint32_t> phich;            // 12 grid indices per unit, each below phich_rows 12 nof_prb
 };
 
 // the fields the table depends on (sf_idx and nof_rx do not enter)
@@ -155,7 +162,12 @@ inline bool build(const srsran_hip_pdcch_sf_t& sf, Table& out)
       return false;
     }
     f->assigned = true;
+    for (uint32_t t = 0; t < 4; t++) {
+      out.pcfich[4 * q + t] = f->k[t]; // symbol 0
+    }
   }
+  out.phich_units = out.phich_groups = out.phich_rows = 0;
+  out.phich.clear();
   // PHICH (:249)
   if (sf.phich_mi > 0) {
     const float    ng     = sf.phich_resources == 0 ? (float)1 / 6 : sf.phich_resources == 1 ? (float)1 / 2 : sf.phich_resources == 2 ? 1.f : 2.f;
@@ -176,8 +188,14 @@ inline bool build(const srsran_hip_pdcch_sf_t& sf, Table& out)
         }
         const uint32_t ni = ((id * c[li] / c[alt ? 1 : 0]) + mi + q * c[li] / 3) % c[li];
         per[li][ni]->assigned = true;
+        for (uint32_t t = 0; t < 4; t++) {
+          out.phich.push_back(per[li][ni]->k[t] + li * nof_prb * 12);
+        }
+        out.phich_rows = li + 1 > out.phich_rows ? li + 1 : out.phich_rows;
       }
     }
+    out.phich_units  = units;
+    out.phich_groups = sf.cp_nsymb == 6 ? 2 * units : units;
   }
   // PDCCH (:66-146)
   const uint32_t    nctrl = nof_ctrl_symbols(sf);
@@ -224,6 +242,10 @@ inline bool build(const srsran_hip_pdcch_sf_t& sf, Table& out)
   }
   return true;
 }
+
+// the table of a description the calls take -- in range, and one the reference's own initialisation succeeds on -- built once per thread (pdcch_host.cpp);
+// nullptr with *why set for any other
+const Table* table_of(const srsran_hip_pdcch_sf_t* sf, const char** why);
 
 } // namespace pdcch_map
 } // namespace phyhip

@@ -1,6 +1,7 @@
 """The model of the convolutional-code receive chain (tests/conv_model.py) against what the reference gave (tests/golden/conv_ref.npz, written by
 tools/gen_golden_conv.py from the reference's own viterbi37_avx2_16bit.c, viterbi.c, rm_conv.c and pdcch.c): exact on every case -- quantised symbols, decoded
-bits, best state, the 64 final metrics, de-matched floats, crc_rem.  And the model against itself: the intrinsic-by-intrinsic step is the plain step the kernel
+bits, best state, the 64 final metrics, de-matched floats, crc_rem.  The same on the length sweep (tests/golden/conv_sweep_ref.npz, the generator's --sweep: every
+tail-biting frame length 1 .. 144, the tailed lengths around the chain-back's 64-word blocks, 2048 bits, every DCI length 17 .. 144).  And the model against itself: the intrinsic-by-intrinsic step is the plain step the kernel
 runs (metrics and decision layout), the lane-owner form of the rate de-matcher gives the reference's sums, clean codewords come back.  No device."""
 import os
 
@@ -10,8 +11,9 @@ import pytest
 import conv_model as M
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_ref.npz")
+SWEEP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_sweep_ref.npz")  # tools/gen_golden_conv.py --sweep
 KIND_F, KIND_S, KIND_US = 0, 1, 2
-_rec = None
+_rec = _sweep = _sweep_model = None
 
 
 def record():
@@ -42,6 +44,96 @@ def p_cases():
         out.append(dict(name=str(name), E=E, nof_bits=nof_bits, rnti=rnti, llr=d["p_llr_%d" % i], rm=d["p_rm_%d" % i], sym=d["p_sym_%d" % i], bits=d["p_bits_%d" % i],
                         crc=int(d["p_crc_%d" % i]), best=int(d["p_best_%d" % i]), met=d["p_met_%d" % i], mean=float(d["p_mean_%d" % i])))
     return out
+
+
+def sweep_record():
+    global _sweep
+    if _sweep is None:
+        with np.load(SWEEP) as z:
+            _sweep = {k: z[k] for k in z.files}
+        _sweep["v_bits"], _sweep["p_bits"] = np.unpackbits(_sweep["v_bits"]), np.unpackbits(_sweep["p_bits"])
+    return _sweep
+
+
+def sweep_v_cases():
+    """the frames of the length sweep: dict(name, kind, tb, framebits, L, gain, vin, bits, best, met) -- no symbols: the model's are the reference's (asserted by
+    the generator)"""
+    d = sweep_record()
+    out = []
+    for i, name in enumerate(d["v_names"]):
+        kind, tb, framebits, L, o_in, o_bits = (int(v) for v in d["v_cfg"][i])
+        vin = d["v_in_f" if kind == KIND_F else "v_in_us"][o_in:o_in + 3 * (L + (0 if tb else 6))]
+        out.append(dict(name=str(name), kind=kind, tb=tb, framebits=framebits, L=L, gain=0.0, vin=vin, bits=d["v_bits"][o_bits:o_bits + L], best=int(d["v_best"][i]),
+                        met=d["v_met"][i]))
+    return out
+
+
+def sweep_p_cases():
+    """the PDCCH cases of the length sweep: dict(name, E, nof_bits, rnti, llr, bits, crc, best, met)"""
+    d = sweep_record()
+    out = []
+    for i, name in enumerate(d["p_names"]):
+        E, nof_bits, rnti, o_llr, o_bits = (int(v) for v in d["p_cfg"][i])
+        out.append(dict(name=str(name), E=E, nof_bits=nof_bits, rnti=rnti, llr=d["p_llr"][o_llr:o_llr + E], bits=d["p_bits"][o_bits:o_bits + nof_bits + 16],
+                        crc=int(d["p_crc"][i]), best=int(d["p_best"][i]), met=d["p_met"][i]))
+    return out
+
+
+def sweep_model():
+    """what the model gives on every case of the sweep, computed once (about ten seconds) and shared, the GPU tests included: (frames, PDCCH cases) in the order of
+    sweep_v_cases() / sweep_p_cases(); a frame's entry is M.decode's dict with its symbols added as "sym", a PDCCH case's is M.dci_decode's"""
+    global _sweep_model
+    if _sweep_model is None:
+        V, P = [], []
+        for c in sweep_v_cases():
+            sym = M.quant_f(c["vin"]) if c["kind"] == KIND_F else c["vin"]
+            V.append(dict(M.decode(sym, c["L"], bool(c["tb"])), sym=sym))
+        for c in sweep_p_cases():
+            P.append(M.dci_decode(c["llr"], c["nof_bits"]))
+        _sweep_model = (V, P)
+    return _sweep_model
+
+
+def nw_of(L, tb):
+    """decision words the kernel keeps (conv_device.h: nof_words)"""
+    return max(2 * L - 6, 0) if tb else L
+
+
+def test_sweep_record_holds_every_length():
+    V, P = sweep_v_cases(), sweep_p_cases()
+    tb = [c for c in V if c["tb"] and c["kind"] == KIND_F]
+    assert sorted(c["L"] for c in tb) == list(range(1, 145)) and all(c["framebits"] == c["L"] and c["vin"].dtype == np.float32 for c in tb)
+    assert {nw_of(c["L"], True) % 64 for c in tb} >= {0, 2, 62}  # the chain-back's last block exactly full, just begun, nearly full
+    assert any(nw_of(c["L"], True) < c["L"] for c in tb)  # fewer words than bits: L <= 5
+    tailed = [c for c in V if not c["tb"]]
+    assert {c["L"] for c in tailed} >= {63, 64, 65, 127, 128} and all(c["kind"] == KIND_US and c["vin"].size == 3 * (c["L"] + 6) for c in tailed)
+    assert any(c["L"] == 2048 and c["tb"] for c in V) and all(c["L"] <= c["framebits"] <= 2048 for c in V)
+    assert sorted(c["nof_bits"] + 16 for c in P) == list(range(17, 145))
+    assert len({(M.rm_geometry(3 * (c["nof_bits"] + 16))[2], c["E"]) for c in P}) == 128 == len(P)  # every ndummy with every E
+    assert all(c["llr"].size == c["E"] and M.pdcch_mean(c["llr"], 0, {72: 0, 144: 1, 288: 2, 576: 3}[c["E"]]) > 0.3 for c in P)
+    assert os.path.getsize(SWEEP) < 400 * 1024
+
+
+def test_sweep_frames_model_is_the_reference():
+    """every frame of the sweep: decoded bits, best state and the 64 final metrics exact; the best state moot on every tail-biting frame.  The record holds no
+    symbol rows (the generator asserted the quantiser against the reference's); the final metrics are sums over every symbol, so they hold the quantiser too"""
+    V = sweep_v_cases()
+    for c, m in zip(V, sweep_model()[0]):
+        assert m["sym"].dtype == np.uint16 and m["sym"].size == c["vin"].size, c["name"]
+        assert np.array_equal(m["bits"], c["bits"]) and m["best_state"] == c["best"] and np.array_equal(m["metrics"], c["met"]) and m["best_moot"], c["name"]
+        if c["kind"] == KIND_US and not c["tb"] and c["L"] >= 58:
+            assert m["wrapped"], c["name"]
+
+
+def test_sweep_pdcch_cases_model_is_the_reference():
+    """every DCI length of the sweep: bits, crc_rem, best state and final metrics exact, and the kernel's form of the de-matcher gives dci_decode's floats"""
+    P = sweep_p_cases()
+    for c, m in zip(P, sweep_model()[1]):
+        assert np.array_equal(m["bits"], c["bits"]) and m["crc_rem"] == c["crc"] and m["best_state"] == c["best"], c["name"]
+        assert np.array_equal(m["metrics"], c["met"]) and m["best_moot"], c["name"]
+        assert M.rm_rx_owner(c["llr"], 3 * (c["nof_bits"] + 16)).tobytes() == m["rm"].tobytes(), c["name"]
+        if c["name"].endswith("clean") and c["E"] >= 3 * (c["nof_bits"] + 16) // 2:
+            assert c["crc"] == c["rnti"], c["name"]
 
 
 def test_record_holds_the_cases_the_kernel_can_go_wrong_on():

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import conv_model as M
-from test_conv_golden import KIND_F, KIND_S, KIND_US, p_cases, v_cases
+from test_conv_golden import KIND_F, KIND_S, KIND_US, p_cases, sweep_model, sweep_p_cases, sweep_v_cases, v_cases
 
 pytestmark = pytest.mark.gpu
 LEVEL = {72: 0, 144: 1, 288: 2, 576: 3}
@@ -63,6 +63,76 @@ def test_us_multi_gives_the_recorded_bits(L, tb):
         assert np.array_equal(o[:c["L"]], c["bits"]) and np.all(o[c["L"]:] == 0xEE), c["name"]
 
 
+def us_multi(L, q, syms, lengths):
+    """srsran_hip_viterbi_decode_us_multi on the frames -> (rc, the output of each with 8 guard bytes of 0xEE behind it)"""
+    n = len(syms)
+    syms = [np.ascontiguousarray(s, np.uint16) for s in syms]
+    outs = [np.full(n_bits + 8, 0xEE, np.uint8) for n_bits in lengths]
+    rc = L.srsran_hip_viterbi_decode_us_multi(C.byref(q), n, (C.c_void_p * n)(*[s.ctypes.data for s in syms]), (C.c_void_p * n)(*[o.ctypes.data for o in outs]),
+                                              (C.c_uint32 * n)(*lengths))
+    return rc, outs
+
+
+def sweep_frames(tb):
+    """(case, its symbols) of the length sweep's frames with this termination, in the record's order; the symbols are M.quant_f of the recorded floats or the
+    recorded uint16, which the generator proved to be the reference's"""
+    V, model = sweep_v_cases(), sweep_model()[0]
+    return [(c, m["sym"]) for c, m in zip(V, model) if c["tb"] == tb]
+
+
+def test_sweep_tail_biting_lengths_through_decode_f(L):
+    """every frame length 1 .. 144 with tail biting by srsran_viterbi_decode_f on a 144-bit handle: the max search and the quantiser at every 3 L % 64, the
+    chain-back at every (2 L - 6) % 64 and with fewer words than bits (L <= 5)"""
+    q = handle(L, 144, 1)
+    frames = [(c, s) for c, s in sweep_frames(1) if c["kind"] == KIND_F]
+    assert [c["L"] for c, _ in frames] == list(range(1, 145))
+    bad = []
+    for c, _ in frames:
+        vin, data = np.ascontiguousarray(c["vin"]), np.full(c["L"] + 8, 0xEE, np.uint8)
+        assert L.srsran_viterbi_decode_f(C.byref(q), vin.ctypes.data, data.ctypes.data, c["L"]) == 144, c["name"]
+        if not (np.array_equal(data[:c["L"]], c["bits"]) and np.all(data[c["L"]:] == 0xEE)):
+            bad.append(c["L"])
+    L.srsran_viterbi_free(C.byref(q))
+    assert not bad, "lengths that failed: %s" % bad
+
+
+@pytest.mark.parametrize("framebits", [144, 2048])
+def test_sweep_tail_biting_lengths_side_by_side(L, framebits):
+    """the 144 frames in ONE launch on the model's symbols; on the 2048-bit handle the 2048-bit frame goes first, so every short frame is decoded in an LDS
+    layout sized by the longest frame the library accepts"""
+    frames = [(c, s) for c, s in sweep_frames(1) if c["L"] <= 144]
+    assert len(frames) == 144
+    if framebits == 2048:
+        frames = [(c, s) for c, s in sweep_frames(1) if c["L"] == 2048] + frames
+        assert len(frames) == 145 and frames[0][0]["L"] == 2048
+    q = handle(L, framebits, 1)
+    rc, outs = us_multi(L, q, [s for _, s in frames], [c["L"] for c, _ in frames])
+    assert rc == framebits
+    bad = [c["L"] for (c, _), o in zip(frames, outs) if not (np.array_equal(o[:c["L"]], c["bits"]) and np.all(o[c["L"]:] == 0xEE))]
+    assert not bad, "lengths that failed: %s" % bad
+
+
+def test_sweep_tailed_lengths(L):
+    """the tailed lengths around the chain-back's blocks (63, 64, 65, 127, 128, ...) in one launch and each by itself through decode_us; the 2047-bit frame
+    through decode_us on the 2048-bit handle"""
+    frames = sweep_frames(0)
+    short = [(c, s) for c, s in frames if c["L"] <= 144]
+    assert {c["L"] for c, _ in short} >= {1, 5, 6, 7, 63, 64, 65, 127, 128, 129} and [c["L"] for c, _ in frames if c["L"] > 144] == [2047]
+    q = handle(L, 144, 0)
+    rc, outs = us_multi(L, q, [s for _, s in short], [c["L"] for c, _ in short])
+    assert rc == 144
+    bad = [c["L"] for (c, _), o in zip(short, outs) if not (np.array_equal(o[:c["L"]], c["bits"]) and np.all(o[c["L"]:] == 0xEE))]
+    assert not bad, "lengths that failed in the multi launch: %s" % bad
+    big = handle(L, 2048, 0)
+    for c, s in frames:
+        sym, data = np.ascontiguousarray(s), np.full(c["L"] + 8, 0xEE, np.uint8)
+        h = big if c["L"] > 144 else q
+        assert L.srsran_viterbi_decode_us(C.byref(h), sym.ctypes.data, data.ctypes.data, c["L"]) == h.framebits, c["name"]
+        if not (np.array_equal(data[:c["L"]], c["bits"]) and np.all(data[c["L"]:] == 0xEE)):
+            bad.append(c["L"])
+    assert not bad, "lengths that failed through decode_us: %s" % bad
+
+
 def run_pdcch(L, llr, cands, dbg=True):
     """-> (rc, results, rm rows, symbol rows)"""
     from srslte_amd import capi
@@ -110,6 +180,29 @@ def test_pdcch_cases_give_the_record(L):
         assert np.float32(c["mean"]) == np.float32(res[i].mean), c["name"]
         check_result(res[i], rm[i], sym[i], dict(rm=c["rm"], sym=c["sym"], bits=c["bits"], crc=c["crc"]) if c["mean"] > 0.3 else None, c["nof_bits"], c["name"])
     assert sum(1 for c in P if c["mean"] <= 0.3) >= 2
+    rc2, res2, _, _ = run_pdcch(L, llr, cands, dbg=False)
+    assert rc2 == 0 and bytes(res2) == bytes(res)
+
+
+def test_sweep_dci_lengths_in_one_call(L):
+    """every DCI length 17 .. 144 -- every ndummy of the rate de-matcher with every E once -- back to back on CCE boundaries (480 CCE, 128 candidates) in ONE
+    call: decoded, payload and crc_rem against the record, the mean against the model's, the de-matched floats and the symbols bit for bit the model's (which
+    the generator held to the reference's), zeros behind 3 L; the plain call gives the same result bytes"""
+    P, model = sweep_p_cases(), sweep_model()[1]
+    first = np.concatenate([[0], np.cumsum([c["E"] // 72 for c in P])])
+    assert len(P) == 128 and first[-1] == 480
+    llr = np.concatenate([c["llr"] for c in P])
+    cands = [(int(first[i]), LEVEL[c["E"]], c["nof_bits"]) for i, c in enumerate(P)]
+    rc, res, rm, sym = run_pdcch(L, llr, cands)
+    assert rc == 0
+    bad = []
+    for i, (c, m) in enumerate(zip(P, model)):
+        try:
+            assert np.float32(M.pdcch_mean(llr, cands[i][0], cands[i][1])) == np.float32(res[i].mean), c["name"]
+            check_result(res[i], rm[i], sym[i], dict(rm=m["rm"], sym=m["sym"], bits=c["bits"], crc=c["crc"]), c["nof_bits"], c["name"])
+        except AssertionError as e:
+            bad.append((c["nof_bits"] + 16, str(e)[:120]))
+    assert not bad, "lengths that failed: %s" % bad
     rc2, res2, _, _ = run_pdcch(L, llr, cands, dbg=False)
     assert rc2 == 0 and bytes(res2) == bytes(res)
 

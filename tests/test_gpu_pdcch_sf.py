@@ -127,6 +127,38 @@ def test_search_equals_the_candidate_call_on_its_own_soft_bits(L, c):
             assert np.all(o["rm"][i * 432:(i + 1) * 432] == 0) and np.all(o["sym"][i * 432:(i + 1) * 432] == 0)
 
 
+def test_search_sweeps_every_dci_size_on_one_region(L):
+    """the test above with a candidate list that sweeps the size: nof_bits 1 .. 128 at CCE 0 of one recorded region of at least 8 CCE, the level rotating
+    0 .. 3 -- every length of the rate de-matcher and the chain-back through the kernel that applies the mean rule on the device.  Result, rm and symbol rows bit
+    for bit what srsran_hip_pdcch_dci_decode_multi_dbg gives on the call's own llr_out; decoded, crc_rem, payload, rm and symbols what the model gives on it"""
+    import conv_model as CM
+    import pdcch_map_model as PM
+
+    def busy(c):  # at least 8 CCE, and CCE 0 carries energy at every level (judged on the recorded soft bits, which the device's equal to 1e-6)
+        return c["table"].size // 36 >= 8 and all(CM.pdcch_mean(c["llr"], 0, lv) > 0.5 for lv in range(4))
+
+    c = next(c for c in CASES if busy(c))
+    cands = [(0, (nof_bits - 1) % 4, nof_bits) for nof_bits in range(1, 129)]
+    r = Region(dict(c, cand=np.array(cands, np.uint32)))
+    res, o = r.search_dbg(L)
+    ref = (r.capi.HipPdcchRes * r.n)()
+    rm, sym = np.full(r.n * 432, 77.0, np.float32), np.full(r.n * 432, 77, np.uint16)
+    llr = np.ascontiguousarray(o["llr"])
+    assert L.srsran_hip_pdcch_dci_decode_multi_dbg(llr.ctypes.data, llr.size, r.n, r.cand, ref, rm.ctypes.data, sym.ctypes.data) == 0
+    bad = [cands[i][2] for i in range(r.n) if bytes(res[i]) != bytes(ref[i])]
+    assert not bad, "nof_bits whose result rows differ: %s" % bad
+    assert same_bits(o["rm"], rm) and same_bits(o["sym"], sym)
+    assert bytes(r.search(L)) == bytes(res)
+    want = PM.search(llr, cands)
+    for i, (w, (_, lv, nof_bits)) in enumerate(zip(want, cands)):
+        n3 = 3 * (nof_bits + 16)
+        payload = np.frombuffer(bytes(res[i].payload), np.uint8)
+        assert w["decoded"] and res[i].decoded == 1 and res[i].crc_rem == w["crc_rem"] and np.float32(res[i].mean) == np.float32(w["mean"]), (c["name"], nof_bits)
+        assert np.array_equal(payload[:nof_bits + 16], w["bits"]) and not payload[nof_bits + 16:].any(), (c["name"], nof_bits)
+        assert same_bits(o["rm"][i * 432:i * 432 + n3], w["rm"]) and not o["rm"][i * 432 + n3:(i + 1) * 432].any(), (c["name"], nof_bits)
+        assert np.array_equal(o["sym"][i * 432:i * 432 + n3], w["sym"]) and not o["sym"][i * 432 + n3:(i + 1) * 432].any(), (c["name"], nof_bits)
+
+
 def test_four_threads_with_different_regions_give_what_each_gives_alone(L):
     picks = [CASES[0], CASES[3], CASES[4], CASES[7]]
     alone = [(bytes(Region(c).search(L)), Region(c).extract(L).tobytes()) for c in picks]

@@ -93,7 +93,12 @@ label, dev = sharding.init_collectives(rank, world, torch.device("cpu"), prefer=
 cfg = sharding.broadcast_config({"k_cb": 6144} if rank == 0 else None, dev)
 seen = sharding.ranks_seen(rank, None, dev)
 t = sharding.max_over_ranks(float(rank + 1), dev)
-print(json.dumps({"rank": rank, "label": label, "cfg": cfg, "seen": seen, "t": t, "backend": dist.get_backend()}), flush=True)
+line = json.dumps({"rank": rank, "label": label, "cfg": cfg, "seen": seen, "t": t, "backend": dist.get_backend()}) + "\n"
+# the ranks may share one pipe (torch.distributed.run): the line and its newline go out in ONE write, which a pipe keeps whole below PIPE_BUF -- print()
+# on an unbuffered stdout writes the newline by itself, and another rank's line can land in front of it
+assert len(line) < 4096
+sys.stdout.flush()
+os.write(1, line.encode())
 dist.destroy_process_group()
 """
 

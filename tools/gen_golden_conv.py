@@ -4,6 +4,7 @@ viterbi37_avx2_16bit.c) and srsran_pdcch_dci_decode (pdcch.c:335-368: srsran_rm_
 tests/golden/conv_ref.npz.
 
     python tools/gen_golden_conv.py          (needs the reference tree)
+    python tools/gen_golden_conv.py --sweep  (the length sweep, tests/golden/conv_sweep_ref.npz: main_sweep(); conv_ref.npz is left alone)
 
 tools/conv_ref_wrap.c includes the reference's viterbi37_avx2_16bit.c where it lies (struct v37 is read) and is compiled with the REF_FLAGS of oracle/Makefile,
 together with viterbi.c, rm_conv.c, pdcch.c and the reference files they bind into, into a temporary directory (nothing compiled is kept); loaded lazily.
@@ -32,6 +33,7 @@ import conv_model as M  # noqa: E402
 from gen_golden_csi import ref_flags  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "conv_ref.npz")
+OUT_SWEEP = os.path.join(ROOT, "tests", "golden", "conv_sweep_ref.npz")
 REF_FILES = ["fec/convolutional/viterbi.c", "fec/convolutional/viterbi37_port.c", "fec/convolutional/viterbi37_sse.c", "fec/convolutional/viterbi37_avx2.c",
              "fec/convolutional/parity.c", "fec/turbo/rm_conv.c", "phch/pdcch.c", "fec/crc.c", "utils/bit.c", "utils/vector.c", "utils/vector_simd.c",
              "utils/debug.c", "utils/phy_logger.c"]
@@ -196,5 +198,108 @@ def main():
     print(OUT, os.path.getsize(OUT), "bytes,", len(V), "handle cases,", len(P), "PDCCH cases")
 
 
+# ---------------------------------------------------------------------------------------------------------------- the length sweep
+SWEEP_TAILED = [1, 2, 5, 6, 7, 58, 62, 63, 64, 65, 66, 127, 128, 129]
+SWEEP_E = (72, 144, 288, 576)
+
+
+def sweep_E(L):
+    """every one of the 128 pairs (ndummy, E) once over L = 17 .. 144"""
+    return SWEEP_E[((L - 17) // 32 + L % 32) % 4]
+
+
+def sweep_v_cases(rng):
+    cases = []
+    snrs = SNRS + ["none"]
+
+    def label(snr):
+        return "clean" if snr is None else snr if isinstance(snr, str) else "snr_%g" % snr
+
+    for L in range(1, 145):  # tail biting, float soft bits, default gain: every length
+        snr = snrs[(L - 1) % len(snrs)] if L >= 7 else "none"  # M.encode needs six bits in front of the first with tail biting
+        coded = np.zeros(3 * L) if isinstance(snr, str) else M.encode(rng.integers(0, 2, L), True)
+        cases.append(dict(name="f_%d_%s" % (L, label(snr)), kind=KIND_F, tb=1, framebits=L, L=L, vin=soft(rng, coded, snr), gain=0.0))
+    for L in SWEEP_TAILED:  # tailed, uint16 straight in, uniform over the whole range: the metrics wrap
+        cases.append(dict(name="us_%d_tailed" % L, kind=KIND_US, tb=0, framebits=L, L=L, vin=rng.integers(0, 65536, 3 * (L + 6)).astype(np.uint16), gain=0.0))
+    for L, tb in ((2048, 1), (2047, 0)):  # the frames that size the LDS at its limit: symbols of a noisy codeword
+        sym = M.quant_f(soft(rng, M.encode(rng.integers(0, 2, L), bool(tb)), 0.0))
+        cases.append(dict(name="us_%d_%s" % (L, "snr_0" if tb else "tailed_on_2048"), kind=KIND_US, tb=tb, framebits=2048, L=L, vin=sym, gain=0.0))
+    return cases
+
+
+def sweep_p_cases(rng):
+    cases = []
+    snrs = SNRS + ["none"]
+    for L in range(17, 145):
+        nof_bits, E, snr = L - 16, sweep_E(L), snrs[(L - 17) % len(snrs)]
+        rnti = int(rng.integers(1, 0xFFF0))
+        tx = M.dci_encode(rng.integers(0, 2, nof_bits), rnti, E)
+        cases.append(dict(name="L%d_E%d_%s" % (L, E, "clean" if snr is None else snr), E=E, nof_bits=nof_bits, llr=soft(rng, tx, snr, amp=2.0), rnti=rnti))
+    return cases
+
+
+def pack_table(rows):
+    """arrays of one type one behind the other -> (the whole, the offset of each)"""
+    off = np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.uint32)
+    return np.concatenate(rows), off[:-1]
+
+
+def main_sweep():
+    """tests/golden/conv_sweep_ref.npz: every frame length 1 .. 144 with tail biting, the tailed lengths around the chain-back's 64-word blocks, the two frames at
+    the LDS limit, and every DCI length 17 .. 144 (every ndummy with every E once).  Inputs and what the reference gave (bits packed, crc_rem, best state, final
+    metrics), a few concatenated arrays and an offset table; the model is asserted against the reference on every case, exactly as in main()."""
+    rng = np.random.default_rng(2412)
+    V, P = sweep_v_cases(rng), sweep_p_cases(rng)
+    assert len({(rm_geometry_ndummy(c["nof_bits"] + 16), c["E"]) for c in P}) == 128
+    v_bits, v_best, v_met, p_bits, p_crc, p_best, p_met = [], [], [], [], [], [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        lib = load_wrapper(tmp)
+        for c in V:
+            bits, sym, best, met = ref_viterbi(lib, c)
+            assert np.array_equal(model_sym(c), sym), c["name"]
+            m = M.decode(sym, c["L"], bool(c["tb"]))
+            assert np.array_equal(m["bits"], bits) and m["best_state"] == best and np.array_equal(m["metrics"], met) and m["best_moot"], c["name"]
+            if c["kind"] == KIND_US and c["L"] >= 58:
+                assert m["wrapped"], c["name"]
+            print("V %-22s best %2d  wrapped %d  ones %d / %d" % (c["name"], best, m["wrapped"], int(bits.sum()), bits.size))
+            v_bits.append(bits), v_best.append(best), v_met.append(met)
+        for c in P:
+            rm, sym, bits, crc, best, met = ref_dci(lib, c)
+            m = M.dci_decode(c["llr"], c["nof_bits"])
+            assert rm.tobytes() == m["rm"].tobytes() and rm.tobytes() == M.rm_rx_owner(c["llr"], rm.size).tobytes(), c["name"]
+            assert np.array_equal(sym, m["sym"]) and np.array_equal(bits, m["bits"]) and crc == m["crc_rem"] and best == m["best_state"], c["name"]
+            assert np.array_equal(met, m["metrics"]) and m["best_moot"], c["name"]
+            mean = M.pdcch_mean(c["llr"], 0, SWEEP_E.index(c["E"]))
+            assert mean > 0.3, (c["name"], mean)
+            print("P %-22s crc_rem %04x (rnti %04x)  mean %.4f  wrapped %d" % (c["name"], crc, c["rnti"], mean, m["wrapped"]))
+            p_bits.append(bits), p_crc.append(crc), p_best.append(best), p_met.append(met)
+    d = {"v_names": np.array([c["name"] for c in V]), "p_names": np.array([c["name"] for c in P])}
+    in_f, off_f = pack_table([c["vin"] for c in V if c["kind"] == KIND_F])
+    in_us, off_us = pack_table([c["vin"] for c in V if c["kind"] == KIND_US])
+    off_in = {KIND_F: iter(off_f), KIND_US: iter(off_us)}
+    allbits, off_bits = pack_table(v_bits)
+    d["v_in_f"], d["v_in_us"], d["v_bits"] = in_f.astype(np.float32), in_us.astype(np.uint16), np.packbits(allbits)
+    # per frame: kind, tail biting, framebits, L, where its input starts in v_in_f / v_in_us, where its bits start in the unpacked v_bits
+    d["v_cfg"] = np.array([[c["kind"], c["tb"], c["framebits"], c["L"], next(off_in[c["kind"]]), off_bits[i]] for i, c in enumerate(V)], np.uint32)
+    d["v_best"], d["v_met"] = np.array(v_best, np.uint8), np.array(v_met, np.uint16)
+    llr, off_llr = pack_table([c["llr"] for c in P])
+    allbits, off_bits = pack_table(p_bits)
+    d["p_llr"], d["p_bits"] = llr.astype(np.float32), np.packbits(allbits)
+    # per candidate: E, nof_bits, rnti, where its soft bits start in p_llr, where its nof_bits + 16 bits start in the unpacked p_bits
+    d["p_cfg"] = np.array([[c["E"], c["nof_bits"], c["rnti"], off_llr[i], off_bits[i]] for i, c in enumerate(P)], np.uint32)
+    d["p_crc"], d["p_best"], d["p_met"] = np.array(p_crc, np.uint16), np.array(p_best, np.uint8), np.array(p_met, np.uint16)
+    np.savez_compressed(OUT_SWEEP, **d)
+    size = os.path.getsize(OUT_SWEEP)
+    print(OUT_SWEEP, size, "bytes,", len(V), "frames,", len(P), "PDCCH cases")
+    assert size < 400 * 1024, size
+
+
+def rm_geometry_ndummy(L):
+    return M.rm_geometry(3 * L)[2]
+
+
 if __name__ == "__main__":
-    main()
+    if "--sweep" in sys.argv[1:]:
+        main_sweep()
+    else:
+        main()

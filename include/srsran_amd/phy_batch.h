@@ -113,6 +113,10 @@ SRSRAN_API int  srsran_hip_ldpc_batch_run_crc_map(srsran_hip_ldpc_batch_t* h, co
                                                   uint32_t msg_stride, const uint32_t* d_cw_map, uint32_t n_cw, uint32_t cdwd_rm_length,
                                                   uint32_t crc_polynom, uint32_t crc_order, int32_t* d_nof_iterations, void* stream);
 SRSRAN_API void srsran_hip_ldpc_batch_free(srsran_hip_ldpc_batch_t* h);
+/* debug/parity aid: which kernel form the object's last launch was routed to (host-side record, no device work).  out = { packed kernel
+ * (two lifted positions per lane) 0/1, check-to-variable messages in LDS 0/1, CRC early stop 0/1, code words per workgroup, workgroups
+ * launched, code words }; all zero before the first launch.  Never needed by an application. */
+SRSRAN_API int  srsran_hip_ldpc_batch_last_launch(srsran_hip_ldpc_batch_t* h, int32_t out[6]);
 /* d_llrs   : n_cw x (N-2Z) int8 (only the first cdwd_rm_length... all N-2Z are read, as the reference does),
  *            `llr_stride` bytes apart;  d_message: n_cw x K bytes, one bit per byte, `msg_stride` apart.
  * d_iter_msgs (optional, may be NULL): n_cw x max_nof_iter x K/8 packed hard decisions after every

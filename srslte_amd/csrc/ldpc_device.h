@@ -56,10 +56,10 @@ struct Params {
 
 #define LDPC_MAX_SLOTS 4096 // resident workgroup slots (256 CUs x up to 4); each owns one c2v slab per code word it holds
 int        grid_slots(const Params& p);
-hipError_t launch(const Params& p, hipStream_t stream);
+hipError_t launch(const Params& p, hipStream_t stream, int* grid = nullptr); // grid: receives the number of workgroups launched
 size_t     lds_bytes(const Params& p);
 bool       packed_applies(const Params& p); // int8, layered, even lifting size, no per-iteration / soft-bit side outputs
-hipError_t launch_packed(const Params& p, hipStream_t stream);
+hipError_t launch_packed(const Params& p, hipStream_t stream, int* grid = nullptr);
 bool       packed_c2v_lds_fits(const Params& p); // one code word per workgroup with its messages in LDS fits a CU's LDS
 
 } // namespace ldpc

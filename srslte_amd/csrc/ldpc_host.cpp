@@ -137,6 +137,9 @@ struct srsran_hip_ldpc_batch {
   std::vector<uint16_t> row_start;
   int* d_row_start = nullptr;
   int* d_edges     = nullptr;
+  // what the last ldpc_batch_run decided (srsran_hip_ldpc_batch_last_launch): packed kernel, messages in LDS, CRC early stop, code words
+  // per workgroup, workgroups launched, code words
+  int32_t last_launch[6] = {0, 0, 0, 0, 0, 0};
 };
 
 extern "C" int srsran_hip_ldpc_batch_create(srsran_hip_ldpc_batch_t** hh, srsran_basegraph_t bg, uint16_t ls,
@@ -433,7 +436,21 @@ static int ldpc_batch_run(srsran_hip_ldpc_batch_t* h, const void* d_llrs, uint32
       p.c2v_lds   = 1;
     }
   }
-  PHY_HIP_CHECK(ldpc::launch(p, (hipStream_t)stream), SRSRAN_ERROR);
+  int grid = 0;
+  PHY_HIP_CHECK(ldpc::launch(p, (hipStream_t)stream, &grid), SRSRAN_ERROR);
+  const int32_t ll[6] = {p.packed, p.c2v_lds, p.crc_order ? 1 : 0, p.cpb, grid, p.n_cw};
+  std::copy(ll, ll + 6, h->last_launch);
+  return SRSRAN_SUCCESS;
+}
+
+// debug/parity entry point: which kernel form the last run of this object was routed to -- packed (0/1), messages in LDS (0/1), CRC early
+// stop (0/1), code words per workgroup, workgroups launched, code words.  All zero before the first launch; host-side only.
+extern "C" int srsran_hip_ldpc_batch_last_launch(srsran_hip_ldpc_batch_t* h, int32_t out[6])
+{
+  if (!h || !out) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  std::copy(h->last_launch, h->last_launch + 6, out);
   return SRSRAN_SUCCESS;
 }
 

@@ -485,7 +485,7 @@ size_t lds_bytes(const Params& p)
 }
 
 template <class POL, bool FLOOD, bool ES>
-static hipError_t launch_pol(const Params& p, hipStream_t stream)
+static hipError_t launch_pol(const Params& p, hipStream_t stream, int* grid_out)
 {
   const size_t lds = lds_bytes(p);
   static bool  attr_set = false;
@@ -500,25 +500,28 @@ static hipError_t launch_pol(const Params& p, hipStream_t stream)
   int threads = p.cpb * p.Z;
   threads     = ((threads + 63) / 64) * 64;
   dim3 grid(grid_slots(p));
+  if (grid_out) {
+    *grid_out = (int)grid.x;
+  }
   hipLaunchKernelGGL((ldpc_layered_kernel<POL, FLOOD, ES>), grid, dim3(threads), lds, stream, p);
   return hipGetLastError();
 }
 
-hipError_t launch(const Params& p, hipStream_t stream)
+hipError_t launch(const Params& p, hipStream_t stream, int* grid)
 {
   if (p.packed) {
-    return launch_packed(p, stream);
+    return launch_packed(p, stream, grid);
   }
   switch (p.dtype) {
     case DT_I8:
       if (p.crc_order) {
-        return p.flood ? launch_pol<Pol8, true, true>(p, stream) : launch_pol<Pol8, false, true>(p, stream);
+        return p.flood ? launch_pol<Pol8, true, true>(p, stream, grid) : launch_pol<Pol8, false, true>(p, stream, grid);
       }
-      return p.flood ? launch_pol<Pol8, true, false>(p, stream) : launch_pol<Pol8, false, false>(p, stream);
+      return p.flood ? launch_pol<Pol8, true, false>(p, stream, grid) : launch_pol<Pol8, false, false>(p, stream, grid);
     case DT_I16:
-      return (p.flood || p.crc_order) ? hipErrorInvalidValue : launch_pol<Pol16, false, false>(p, stream);
+      return (p.flood || p.crc_order) ? hipErrorInvalidValue : launch_pol<Pol16, false, false>(p, stream, grid);
     case DT_F32:
-      return (p.flood || p.crc_order) ? hipErrorInvalidValue : launch_pol<PolF, false, false>(p, stream);
+      return (p.flood || p.crc_order) ? hipErrorInvalidValue : launch_pol<PolF, false, false>(p, stream, grid);
     default:
       return hipErrorInvalidValue;
   }

@@ -387,7 +387,7 @@ int grid_slots_packed(const Params& p)
 }
 
 template <bool ES, bool CL>
-static hipError_t launch_packed_es(const Params& p, hipStream_t stream)
+static hipError_t launch_packed_es(const Params& p, hipStream_t stream, int* grid_out)
 {
   static bool attr_set[kMaxDevices] = {};
   const int   dev = current_device();
@@ -400,7 +400,11 @@ static hipError_t launch_packed_es(const Params& p, hipStream_t stream)
   }
   int threads = p.cpb * (p.Z / 2);
   threads     = ((threads + 63) / 64) * 64;
-  hipLaunchKernelGGL((ldpc_packed_kernel<ES, CL>), dim3(grid_slots_packed(p)), dim3(threads), lds_bytes_packed(p), stream, p);
+  const int grid = grid_slots_packed(p);
+  if (grid_out) {
+    *grid_out = grid;
+  }
+  hipLaunchKernelGGL((ldpc_packed_kernel<ES, CL>), dim3(grid), dim3(threads), lds_bytes_packed(p), stream, p);
   return hipGetLastError();
 }
 
@@ -413,15 +417,15 @@ bool packed_c2v_lds_fits(const Params& p)
   return lds_bytes_packed(q) <= 156 * 1024;
 }
 
-hipError_t launch_packed(const Params& p, hipStream_t stream)
+hipError_t launch_packed(const Params& p, hipStream_t stream, int* grid)
 {
   if (lds_bytes_packed(p) > 156 * 1024 || p.cpb * (p.Z / 2) > 768 || (p.c2v_lds && p.cpb != 1)) {
     return hipErrorInvalidValue;
   }
   if (p.c2v_lds) {
-    return p.crc_order ? launch_packed_es<true, true>(p, stream) : launch_packed_es<false, true>(p, stream);
+    return p.crc_order ? launch_packed_es<true, true>(p, stream, grid) : launch_packed_es<false, true>(p, stream, grid);
   }
-  return p.crc_order ? launch_packed_es<true, false>(p, stream) : launch_packed_es<false, false>(p, stream);
+  return p.crc_order ? launch_packed_es<true, false>(p, stream, grid) : launch_packed_es<false, false>(p, stream, grid);
 }
 
 } // namespace ldpc

@@ -158,8 +158,11 @@ def test_full_size_roundtrip_property(hiplib):
     n_cw = 2048
     msgs, llrs = O.ldpc_llrs(0, 384, 4, 30.0, seed=2)
     big = np.tile(llrs, (n_cw // 4, 1))
-    out = S.LdpcBatch(0, 384, 0.8, 20, n_cw).decode(big)
+    dec = S.LdpcBatch(0, 384, 0.8, 20, n_cw)
+    out = dec.decode(big)
     assert np.array_equal(out, np.tile(msgs, (n_cw // 4, 1)))
+    form = (C.c_int32 * 6)()  # packed, messages in LDS, early stop, words per workgroup, workgroups, words (srsran_hip_ldpc_batch_last_launch)
+    assert S.lib().srsran_hip_ldpc_batch_last_launch(dec._h, C.byref(form)) == 0 and list(form)[:3] == [1, 0, 0] and form[4] * form[3] < form[5] == n_cw
 
 
 def _fs_llrs(bg, Z, n_cw, snr, seed, kind):

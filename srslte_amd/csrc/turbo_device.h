@@ -41,6 +41,9 @@ struct WinParams {
   const uint32_t* crc_mult; // nb multipliers x^(W (nb-1-d)) mod g
   int*            noi;      // out: half iterations run per code block
   uint8_t*        crc_ok;   // out: 1 = CRC matched
+  // fixed-iteration int16 window kernels: the backward main pass requests the blocks below this one with the default cache policy, the forward
+  // main pass finds a part of them in the L2 (turbo_kernels.hip, the whole-block loop of the backward pass); at most the sub-block's block count, 0 = none
+  uint32_t        reuse_blocks;
 };
 
 struct GenParams {
@@ -70,6 +73,13 @@ struct GenParams {
 hipError_t launch_gen_lat(const GenParams& p, hipStream_t stream);
 size_t     gen_lat_lds_bytes(uint32_t K);
 constexpr uint32_t kGenLatMaxBlocks = 8192; // (K = 400: 8192 blocks 0.33 against 0.51 ms per half iteration, 32768 blocks 1.36 against 0.69: tools/measure/gen_time.py)
+
+// WinParams::reuse_blocks of the product (SRSRAN_HIP_TDEC_REUSE_BLOCKS overrides it).  In blocks, whatever K is: a wave moves the same bytes per block
+// at every K, and it is the bytes between a block's two reads that decide whether the second one is served from the L2.  Measured at K = 6144, 131,040
+// blocks (profiles/turbo_reuse_policy.json; median step of the headline benchmark, parent 18.79 ms): 0: 18.84, 4: 18.75, 8: 18.66, 12: 18.53, 16: 18.46,
+// 24: 18.41, 32: 18.46, 48: 18.55; on a second box (parent 18.94 +- 0.03): 16: 18.60, 20: 18.56, 24: 18.57, 28: 18.53, 32: 18.56.  20 is the smallest
+// split within the parent's own run-to-run spread of the best one.
+constexpr uint32_t kReuseBlocks = 20;
 
 // dwords of workspace per code block for the window decoder with nb sub-blocks
 static inline uint32_t win_ws_dwords(uint32_t K, int nb)

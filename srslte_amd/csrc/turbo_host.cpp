@@ -390,6 +390,11 @@ static turbo::WinParams win_params(const srsran_hip_tdec_batch* h, const Workspa
   p.n_cb      = (int)n_cb;
   p.sb_layout = sb_layout;
   p.in_is8    = in_is8 ? 1 : 0;
+  if (h->nb) {
+    const int      k    = knob(KNOB_TDEC_REUSE_BLOCKS);
+    const uint32_t nblk = (h->K / (uint32_t)h->nb + 7) / 8;
+    p.reuse_blocks      = std::min(k >= 0 ? (uint32_t)k : turbo::kReuseBlocks, nblk);
+  }
   return p;
 }
 static turbo::GenParams gen_params(const srsran_hip_tdec_batch* h, const Workspace& ws, const void* d_input, bool in_is8, uint8_t* d_output, uint32_t n_cb,

@@ -440,8 +440,12 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // of decoder 1 and the exchanged rows of decoder 2 are the same bytes of their arrays (a block of a blocked array and the 8 rows of a block
     // of a row array are one contiguous run of the wave's slab, 16 bytes per lane and half), only the array differs; and a request that is not
     // needed (no block b, no a-priori array in this half iteration) goes, from every lane, to the first 16 bytes of the array.
+    // nt: the cache policy of the request (16-step form).  kStream, the kernel's NT, for every request that is the bytes' last use before they are
+    // rewritten -- all but those of the backward main pass's lowest blocks, which the forward main pass reads again soon enough (kReuse: there).
+    constexpr std::integral_constant<bool, NT>    kStream{};
+    constexpr std::integral_constant<bool, false> kReuse{};
     const uint32_t* X = dec1 ? S : A2;
-    auto issue = [&](uint32_t b, Ops& q, bool ok = true) {
+    auto issue = [&](auto nt, uint32_t b, Ops& q, bool ok = true) {
       if constexpr (CKS == 16) {
         static_assert(!ES, "the early-stop masks differ between blocked and row arrays");
         const bool oka = ok && has_app;
@@ -450,9 +454,9 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         // (opaque: the addresses of the requests whose block index is the same in every half iteration -- the first ones of each pass -- are
         // otherwise all formed once in front of the half-iteration loop and held across it, in registers the forward main pass does not have)
         asm volatile("" : "+v"(ln), "+v"(la));
-        issue_rows_raw<AR::kIs8, NT>(X, bb, ln, q.x);
-        issue_rows_raw<AR::kIs8, NT>(Y, bb, ln, q.y);
-        issue_rows_raw<AR::kIs8, NT>(A1, ba, la, q.a);
+        issue_rows_raw<AR::kIs8, nt.value>(X, bb, ln, q.x);
+        issue_rows_raw<AR::kIs8, nt.value>(Y, bb, ln, q.y);
+        issue_rows_raw<AR::kIs8, nt.value>(A1, ba, la, q.a);
       } else {
         if (dec1) {
           load_block_raw<AR::kIs8, NT>(S, (b & m_own()) * 64 + lane, q.x);
@@ -514,9 +518,9 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     {
       const uint32_t w0 = long_sb - TD_WIN_OVERLAP;
       const uint32_t bl = nblk - 1;
-      issue(w0 >> 3, cur);
+      issue(kStream, w0 >> 3, cur);
       for (uint32_t b = w0 >> 3; b <= bl; b++) {
-        issue(b < bl ? b + 1 : TD_WIN_OVERLAP / 8 - 1, nxt); // after the warm-up the backward warm-up starts at the end of the head window
+        issue(kStream, b < bl ? b + 1 : TD_WIN_OVERLAP / 8 - 1, nxt); // after the warm-up the backward warm-up starts at the end of the head window
         s2 xs[8], ys[8], ap[8];
         prep(cur, xs, ys, ap);
         if (b + 4 > bl) {
@@ -555,7 +559,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // pass 0: 40 steps on the head of every sub-block, all states unknown
     for (int b = TD_WIN_OVERLAP / 8 - 1; b >= 0; b--) {
       if (b > 0) {
-        issue(b - 1, nxt); // (pass 1 starts with the four blocks the forward warm-up left in the beta buffer)
+        issue(kStream, b - 1, nxt); // (pass 1 starts with the four blocks the forward warm-up left in the beta buffer)
       }
       s2 xs[8], ys[8], ap[8];
       prep(cur, xs, ys, ap);
@@ -607,7 +611,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           taken(c);
           prep(c, xs, ys, ap);
         }
-        issue(b - 3, tgt, b >= 3 && b - 3 <= top);
+        issue(kStream, b - 3, tgt, b >= 3 && b - 3 <= top);
         if (b < (int)nblk) {
 #pragma unroll
           for (int j = 7; j >= 0; j--) {
@@ -636,11 +640,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       // that is not needed (issue); step 0 is not followed by a normalisation, so the fourth block's last one is masked (`bottom`); and the
       // check-point the fourth block files is, for block 0, slot 0 of CK, which exists and which no pass reads (the forward passes start at slot
       // 2 or, with 8-step check-points, at slot 1) -- a branch around the store would merge an arm without stores into the path.
-      auto whole_block = [&](auto ck_store, auto bottom, int b, const Ops& c, Ops& tgt) {
+      auto whole_block = [&](auto nt, auto ck_store, auto bottom, int b, const Ops& c, Ops& tgt) {
         s2 xs[8], ys[8], ap[8];
         taken(c);
         prep(c, xs, ys, ap);
-        issue(b - 3, tgt, b >= 3);
+        issue(nt, b - 3, tgt, b >= 3);
 #pragma unroll
         for (int j = 7; j >= 0; j--) {
           beta_step<AR>(o, xs[j], ys[j]);
@@ -675,12 +679,26 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         block(b - 2, nxt, nx2);
         block(b - 3, cur, nxt);
       }
+      // The whole-block loop is itself two copies of one body, one behind the other, that differ in the policy of their requests.  The forward main
+      // pass reads block b again once the wave has gone down to block 0 and come back up: the lower the block, the fewer bytes the chip moves
+      // between its two reads, and below p.reuse_blocks a good part of the lines is still in the L2 when it is wanted again -- if the first read left it there.
+      // So the groups that request only blocks >= reuse_blocks keep the non-temporal policy, the groups below them (a group whose top block is b
+      // requests blocks b - 3 ... b - 6) request with the default one.  The bound is the same in every lane and a run-time value (WinParams);
+      // the way from the first copy into the second carries the three requests its back edge carries.  reuse_blocks = 0: no trip of the second copy.
+      const int b_reuse = p.reuse_blocks ? (int)p.reuse_blocks + 6 : 3;
+#pragma nounroll
+      for (; b >= b_reuse; b -= 4) {
+        whole_block(kStream, kNoStore, kInner, b, nx3, cur);
+        whole_block(kStream, kStore, kInner, b - 1, nx2, nx3);
+        whole_block(kStream, kNoStore, kInner, b - 2, nxt, nx2);
+        whole_block(kStream, kStore, kBottom, b - 3, cur, nxt);
+      }
 #pragma nounroll
       for (; b >= 3; b -= 4) {
-        whole_block(kNoStore, kInner, b, nx3, cur);
-        whole_block(kStore, kInner, b - 1, nx2, nx3);
-        whole_block(kNoStore, kInner, b - 2, nxt, nx2);
-        whole_block(kStore, kBottom, b - 3, cur, nxt);
+        whole_block(kReuse, kNoStore, kInner, b, nx3, cur);
+        whole_block(kReuse, kStore, kInner, b - 1, nx2, nx3);
+        whole_block(kReuse, kNoStore, kInner, b - 2, nxt, nx2);
+        whole_block(kReuse, kStore, kBottom, b - 3, cur, nxt);
       }
     } else {
       // (8-step check-points: the 8-bit and the early-stop kernels.  With four rotating sets the int16 early-stop kernels spill -- their forward
@@ -688,7 +706,7 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       for (int b = (int)nblk - 1; b >= 0; b--) {
         const bool ahead = b + 3 <= (int)nblk; // block b - 2 is one of those
         if (b > 1 && ahead) {
-          issue(b - 2, nx2);
+          issue(kStream, b - 2, nx2);
         }
         s2 xs[8], ys[8], ap[8];
         if (b + 4 >= (int)nblk) {
@@ -883,13 +901,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       load_block_raw<AR::kIs8, NT>(CK, (1u & m_own()) * 64 + lane, ck);
       load_lut(lut, pl, tr);
       if (nblk > 1) {
-        issue(1, nxt);
+        issue(kStream, 1, nxt);
       }
       for (uint32_t b = 0; b < nblk; b++) {
         const int len = (long_sb - b * 8) < 8 ? (int)(long_sb - b * 8) : 8;
         s2        xs[8], ys[8], ap[8];
         if (b + 2 < nblk) {
-          issue(b + 2, nx2);
+          issue(kStream, b + 2, nx2);
         }
         if (b + 1 < nblk) {
           load_block_raw<AR::kIs8, NT>(CK, ((b + 2) & m_own()) * 64 + lane, ckn);
@@ -928,13 +946,13 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       Ops&     q3 = nx3;
       uint32_t ck[8], tr[8];
       load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & m_own()) * 64 + lane, ck);
-      issue(1, q1, nblk > 1);
+      issue(kStream, 1, q1, nblk > 1);
       // The loop is entered with exactly what its back edge brings: one request in flight, everything before it taken.  The waits at the top of
       // the loop are counted for the worse of the two ways in; with all of these requests still open on this one, the count that suits it
       // would, on the back edge, reach into the last block's request.  (Once per half iteration: block 1's operands are waited for here.)
       asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
       taken(q1);
-      issue(2, q2, nblk > 2);
+      issue(kStream, 2, q2, nblk > 2);
       // b may lie behind the last block (the loop below goes over four blocks whatever the count): such a block has no steps, len = 0.  It makes
       // its requests and goes the same way as every other: an arm of its own, or one around the others' work, is a way on which the compiler
       // sees the table entries and the check-point still open, and its wait for them, placed behind the row stores, reaches into the request.
@@ -952,14 +970,14 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
         taken(c);
         if constexpr (even.value) {
           taken(held); // (also where there is no block b + 1: the set was requested all the same)
-          issue(b + 3, tgt, b + 3 < nblk);
+          issue(kStream, b + 3, tgt, b + 3 < nblk);
         } else {
           // the check-point's last use is the copy at the start of the re-derivation: the next pair's is requested there, ahead of the operands
           prep(c, xs, ys, ap);
           rederive_start(len, ckv, st);
           const uint32_t bn = b + 3 < nblk ? b + 3 : nblk;
           load_block_raw<AR::kIs8, NT>(CK, (bn & m_own()) * 64 + lane, ck);
-          issue(b + 3, tgt, b + 3 < nblk);
+          issue(kStream, b + 3, tgt, b + 3 < nblk);
         }
         {
           if constexpr (even.value) {

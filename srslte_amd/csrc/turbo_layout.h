@@ -16,6 +16,9 @@ namespace turbo {
 // too, 11.58 ms with the check-points as well; non-temporal STORES cost (12.2 ms).  The 8-bit decoders (14.7 -> 15.8 ms) and the
 // early-stop mode (-2.5 % on the transport-block benches) lose with it -- their smaller, partly re-touched working sets do hit in L2 --
 // so NT = fixed iterations and int16 only.
+// One stream of that decoder is read again soon enough: the lowest blocks of the backward main pass, which the forward main pass takes up once the wave has
+// turned round.  Those requests use the default policy (WinParams::reuse_blocks; turbo_kernels.hip, the whole-block loop of the backward pass), and the
+// second read is in part served by the L2 (2.2 % fewer bytes leave it): 18.79 -> 18.41 ms per step of the headline benchmark.  The exchanged rows alone stored non-temporally: 18.79 -> 19.37 ms.
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ uint4 ws_load16(const void* p)

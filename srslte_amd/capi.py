@@ -373,6 +373,28 @@ class LdpcDecoder(C.Structure):
                 ("free", C.c_void_p), ("decode_f", C.c_void_p), ("decode_s", C.c_void_p), ("decode_c", C.c_void_p)]
 
 
+class HipPrachCfg(C.Structure):  # srsran_hip_prach_cfg_t (phy_prach_abi.h)
+    _fields_ = [("nof_prb", C.c_uint32), ("config_idx", C.c_uint32), ("root_seq_idx", C.c_uint32), ("zero_corr_zone", C.c_uint32),
+                ("num_ra_preambles", C.c_uint32), ("hs_flag", C.c_uint32), ("freq_domain_offset_calc", C.c_uint32), ("detect_factor", C.c_float)]
+
+
+class HipPrachInfo(C.Structure):  # srsran_hip_prach_info_t
+    _fields_ = [(n, C.c_uint32) for n in ("N_zc", "N_cs", "N_ifft_ul", "N_ifft_prach", "N_seq", "N_cp", "N_roots", "n_wins", "num_ra_preambles")] + \
+        [("root_seqs_idx", C.c_uint32 * 64), ("root_u", C.c_uint32 * 64)]
+
+
+class HipPrachOcc(C.Structure):  # srsran_hip_prach_occ_t
+    _fields_ = [("freq_offset", C.c_uint32), ("sig_len", C.c_uint32), ("signal", C.c_void_p)]
+
+
+class HipPrachRes(C.Structure):  # srsran_hip_prach_res_t
+    _fields_ = [("n_indices", C.c_uint32), ("indices", C.c_uint32 * 128), ("t_offsets", C.c_float * 128), ("peak_to_avg", C.c_float * 128)]
+
+
+class HipPrachDbg(C.Structure):  # srsran_hip_prach_dbg_t
+    _fields_ = [(n, C.c_void_p) for n in ("prach_bins", "corr", "corr_ave", "cross_sum", "peak_values", "peak_offsets")]
+
+
 _lib = None
 
 
@@ -773,6 +795,16 @@ def lib():
             "srsran_hip_pdcch_search_est_dbg": (i32, [C.POINTER(HipPdcchSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp, C.POINTER(HipPdcchEst),
                                                       C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), C.POINTER(HipPhichResource), C.POINTER(HipPhichRes),
                                                       C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(HipChestDlRes), vp, vp, vp, vp, vp]),
+            # random-access detection (phy_prach_abi.h)
+            "srsran_hip_prach_set_root_order": (i32, [vp]),
+            "srsran_hip_prach_plan": (i32, [C.POINTER(HipPrachCfg), C.POINTER(HipPrachInfo)]),
+            "srsran_hip_prach_create": (i32, [C.POINTER(vp), C.POINTER(HipPrachCfg)]),
+            "srsran_hip_prach_destroy": (None, [vp]),
+            "srsran_hip_prach_info": (i32, [vp, C.POINTER(HipPrachInfo)]),
+            "srsran_hip_prach_root_spectrum": (i32, [vp, u32, vp]),
+            "srsran_hip_prach_detect_offset": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, C.POINTER(u32)]),
+            "srsran_hip_prach_detect_offset_dbg": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(HipPrachDbg)]),
+            "srsran_hip_prach_detect_multi": (i32, [vp, u32, C.POINTER(HipPrachOcc), C.POINTER(HipPrachRes)]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

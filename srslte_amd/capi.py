@@ -395,6 +395,36 @@ class HipPrachDbg(C.Structure):  # srsran_hip_prach_dbg_t
     _fields_ = [(n, C.c_void_p) for n in ("prach_bins", "corr", "corr_ave", "cross_sum", "peak_values", "peak_offsets")]
 
 
+class HipPucchCell(C.Structure):  # srsran_hip_pucch_cell_t (phy_pucch_abi.h)
+    _fields_ = [("nof_prb", C.c_uint32), ("cp", C.c_uint32), ("id", C.c_uint32)]
+
+
+class HipPucchSf(C.Structure):  # srsran_hip_pucch_sf_t
+    _fields_ = [("tti", C.c_uint32), ("shortened", C.c_uint32)]
+
+
+class HipPucchJob(C.Structure):  # srsran_hip_pucch_job_t
+    _fields_ = [(n, C.c_uint32) for n in ("format", "n_pucch", "N_cs", "delta_pucch_shift", "n_rb_2", "group_hopping_en", "rnti", "nof_uci_bits", "meas_ta_en",
+                                          "filter_len")] + \
+        [("filter", C.c_float * 3)] + \
+        [(n, C.c_float) for n in ("threshold_format1", "threshold_data_valid_format1a", "threshold_data_valid_format2", "threshold_dmrs_detection")]
+
+
+class HipPucchPlan(C.Structure):  # srsran_hip_pucch_plan_t
+    _fields_ = [("n_rs", C.c_uint32), ("n_prb", C.c_uint32 * 2), ("u", C.c_uint32 * 2), ("N_sf", C.c_uint32 * 2)] + \
+        [(n, C.c_uint32 * 5 * 2) for n in ("sym", "n_cs", "n_oc", "n_prime_ns")] + [(n, C.c_uint32 * 3 * 2) for n in ("dmrs_sym", "dmrs_n_cs", "dmrs_n_oc")]
+
+
+class HipPucchRes(C.Structure):  # srsran_hip_pucch_res_t
+    _fields_ = [("detected", C.c_uint32), ("correlation", C.c_float), ("dmrs_correlation", C.c_float), ("pucch_bits", C.c_uint8 * 13), ("drs_bits", C.c_uint8 * 2),
+                ("ack_valid", C.c_uint8)] + \
+        [(n, C.c_float) for n in ("noise_estimate", "noise_estimate_dbm", "snr", "snr_db", "rsrp", "rsrp_dBfs", "epre", "epre_dBfs", "ta_us")]
+
+
+class HipPucchDbg(C.Structure):  # srsran_hip_pucch_dbg_t
+    _fields_ = [(n, C.c_void_p) for n in ("z", "llr", "ce", "pilot_estimates")]
+
+
 _lib = None
 
 
@@ -805,6 +835,14 @@ def lib():
             "srsran_hip_prach_detect_offset": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, C.POINTER(u32)]),
             "srsran_hip_prach_detect_offset_dbg": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(HipPrachDbg)]),
             "srsran_hip_prach_detect_multi": (i32, [vp, u32, C.POINTER(HipPrachOcc), C.POINTER(HipPrachRes)]),
+            # PUCCH receive (phy_pucch_abi.h)
+            "srsran_hip_pucch_set_tables": (i32, [vp, vp]),
+            "srsran_hip_pucch_plan": (i32, [C.POINTER(HipPucchCell), C.POINTER(HipPucchSf), C.POINTER(HipPucchJob), C.POINTER(HipPucchPlan)]),
+            "srsran_hip_pucch_decode_multi": (i32, [C.POINTER(HipPucchCell), C.POINTER(HipPucchSf), u32, C.POINTER(HipPucchJob), vp, C.POINTER(HipPucchRes)]),
+            "srsran_hip_pucch_decode": (i32, [C.POINTER(HipPucchCell), C.POINTER(HipPucchSf), C.POINTER(HipPucchJob), vp, C.POINTER(HipPucchRes)]),
+            "srsran_hip_pucch_decode_dbg": (i32, [C.POINTER(HipPucchCell), C.POINTER(HipPucchSf), C.POINTER(HipPucchJob), vp, C.POINTER(HipPucchRes),
+                                                  C.POINTER(HipPucchDbg)]),
+            "srsran_hip_chest_ul_estimate_pucch": (i32, [C.POINTER(HipPucchCell), C.POINTER(HipPucchSf), C.POINTER(HipPucchJob), vp, vp, C.POINTER(HipPucchRes)]),
             "srsran_hip_cellsearch_create": (i32, [C.POINTER(vp), u32, u32, i32, i32, u32]),
             "srsran_hip_cellsearch_free": (None, [vp]),
             "srsran_hip_cellsearch_run": (i32, [vp, vp, u32, i32, vp, vp]),

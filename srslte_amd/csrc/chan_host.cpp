@@ -20,7 +20,7 @@ ChanStage* phyhip::chan::stage_for(const char* who)
 {
   static thread_local StageRef<ChanStage> r;
   if (!device_available()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
+    call::no_device(who);
     return nullptr;
   }
   bind_thread();
@@ -623,8 +623,7 @@ extern "C" int srsran_hip_chest_ul_estimate_pusch_multi(uint32_t n, const srsran
   const auto*            rec = reinterpret_cast<const chest_ul::Record*>(s->pin + o_rec);
   const chest_ul::Params cp  = {reinterpret_cast<const float2*>(s->pin.get()), reinterpret_cast<float2*>(s->pin + o_out), jobs,
                                 reinterpret_cast<chest_ul::Record*>(s->pin + o_rec), nullptr, n, (uint32_t)(4 * points), (uint32_t)(2 * points)};
-  const bool launched = chest_ul::launch(cp, st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+  if (call::settle(chest_ul::launch(cp, st), st) != hipSuccess) {
     set_error("%s: channel estimator launch failed", who);
     return SRSRAN_ERROR;
   }
@@ -772,8 +771,7 @@ extern "C" int srsran_hip_pdsch_get(const srsran_hip_pdsch_sf_t* sf, uint32_t n_
   pdsch_map::fill_table(*sf, w, reinterpret_cast<pdsch_map::Seg*>(s->pin + o_tab));
   const pdsch_map::DemapParams dp = {reinterpret_cast<const float2*>(s->pin.get()), reinterpret_cast<float2*>(s->pin + o_out), reinterpret_cast<const pdsch_map::Seg*>(s->pin + o_tab),
                                      w.n_seg, n_planes, (uint32_t)(sb / sizeof(cf_t)), w.staged_points(), (uint32_t)(nb / sizeof(cf_t)), w.nof_re};
-  const bool launched = pdsch_map::launch_demap(dp, st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+  if (call::settle(pdsch_map::launch_demap(dp, st), st) != hipSuccess) {
     return -1;
   }
   for (uint32_t i = 0; i < n_planes; i++) {

@@ -3,11 +3,11 @@
 // codewords (pdsch_decode_grant: staging, transport-block stage, CSI weighting, the _dbg outputs and their bookkeeping; a scheme adds its kernels), PDSCH
 // transmit of a TTI's codewords -- and the frame of a per-stage call on host planes.
 #pragma once
+#include "call_frame.h"
 #include "hip_common.h"
 #include "joblist.h"
 #include "pdsch_map.h"
 #include "sch_stage.h"
-#include "stage.h"
 #include "srsran_amd/phy_chan_abi.h"
 
 #include <map>
@@ -185,8 +185,7 @@ bool run_on_planes(const char* who, PlaneGroup* grp, uint32_t n_grp, Launch laun
     return false;
   }
   place_planes(s->pin, grp, n_grp);
-  const bool launched = launch(st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+  if (call::settle(launch(st), st) != hipSuccess) {
     return false;
   }
   for (uint32_t g = 0; g < n_grp; g++) {

@@ -82,8 +82,7 @@ extern "C" int srsran_hip_chest_dl_estimate(const srsran_hip_chest_dl_t* cfg, co
   const auto*            rec = reinterpret_cast<const chest_dl::Record*>(s->pin + o_rec);
   const chest_dl::Params cp  = {reinterpret_cast<const float2*>(s->pin.get()), reinterpret_cast<float2*>(s->pin + o_out), jobs,
                                 reinterpret_cast<chest_dl::Record*>(s->pin + o_rec), nullptr, n, l.in_points, n_out * l.grid_points};
-  const bool launched = chest_dl::launch(cp, st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !launched) {
+  if (call::settle(chest_dl::launch(cp, st), st) != hipSuccess) {
     set_error("%s: channel estimator launch failed", who);
     return SRSRAN_ERROR;
   }

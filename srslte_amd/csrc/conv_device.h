@@ -1,6 +1,7 @@
 // conv_device.h -- what conv_host.cpp and conv_kernels.hip share: the jobs of the Viterbi and PDCCH kernels and their launches.
 #pragma once
 #include "hip_common.h"
+#include "srsran_amd/phy_conv_abi.h"
 
 namespace phyhip {
 namespace conv {
@@ -27,6 +28,24 @@ struct DciJob { // one candidate, one wave
   uint32_t E;        // soft bits: 72 << L
   uint32_t nof_bits; // 1 .. 128
 };
+// host side: nullptr, or why a candidate is refused in a region of nof_llr soft bits (`past`: the caller's sentence for a location outside it)
+inline const char* dci_cand_invalid(const srsran_hip_pdcch_cand_t& c, uint64_t nof_llr, const char* past = "a location past the end of the control region")
+{
+  if (c.L > 3) {
+    return "aggregation level above 3";
+  }
+  if ((uint64_t)c.ncce * 72 + (72u << c.L) > nof_llr) {
+    return past;
+  }
+  if (c.nof_bits == 0 || c.nof_bits > SRSRAN_HIP_DCI_MAX_BITS) {
+    return "nof_bits outside 1 .. 128";
+  }
+  return nullptr;
+}
+inline DciJob dci_job(const srsran_hip_pdcch_cand_t& c) // of a candidate that has passed
+{
+  return DciJob{c.ncce * 72, 72u << c.L, c.nof_bits};
+}
 
 // decision words a frame keeps in LDS: with tail biting those of steps L + 6 .. 3 L - 1, without those of steps 6 .. L + 5
 inline uint32_t nof_words(uint32_t L, bool tail_biting)

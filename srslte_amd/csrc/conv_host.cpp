@@ -1,10 +1,10 @@
 // conv_host.cpp -- the LTE convolutional code's receive side (include/srsran_amd/phy_conv_abi.h): the reference's srsran_viterbi_* handle API on the
 // device decoder, n frames in one launch (srsran_hip_viterbi_decode_us_multi) and the PDCCH blind search's decodes in one call
-// (srsran_hip_pdcch_dci_decode_multi).  The kernels are in conv_kernels.hip.  Every call is one upload, one launch, one download and one host wait on the
-// calling thread's staging context (stage.h), which srsran_hip_warmup() prepares (warmup_host.cpp).  One layout serves the pinned image and the device
+// (srsran_hip_pdcch_dci_decode_multi).  The kernels are in conv_kernels.hip.  Every call is one round trip (call_frame.h) with one launch on the calling
+// thread's staging context, which srsran_hip_warmup() prepares (warmup_host.cpp).  One layout serves the pinned image and the device
 // buffer: [jobs | inputs || outputs]; what is in front of || goes up, what is behind comes down.
+#include "call_frame.h"
 #include "conv_device.h"
-#include "stage.h"
 #include "srsran_amd/phy_conv_abi.h"
 
 #include <cmath>
@@ -17,13 +17,7 @@ static_assert(conv::kMaxFrame == SRSRAN_HIP_VITERBI_MAX_FRAMEBITS && conv::kDciB
 
 namespace {
 
-struct ConvStage {
-  StageStream st;
-  HostImage   pin;
-  DeviceBuf   dev;
-  bool        ready() { return st.open(); }
-  bool        grow(size_t need) { return pin.grow(need, need / 2) && dev.grow(need, need / 2); }
-};
+struct ConvStage : call::Stage {};
 
 ConvStage& conv_stage() // of the calling thread, on the device it is bound to
 {
@@ -47,8 +41,7 @@ int run_frames(const char* who, const srsran_viterbi_t* q, uint32_t kind, const 
   const size_t   es   = kind == conv::IN_F32 ? sizeof(float) : sizeof(uint16_t);
   ConvStage&     s    = conv_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   size_t   off  = al256((size_t)n * sizeof(conv::VitJob));
   uint32_t Lmax = 0;
@@ -71,15 +64,10 @@ int run_frames(const char* who, const srsran_viterbi_t* q, uint32_t kind, const 
   for (uint32_t i = 0; i < n; i++) {
     memcpy(s.pin + jobs[i].o_in, f[i].in, (size_t)3 * (f[i].L + (tail ? 0 : 6)) * es);
   }
-  PHY_HIP_CHECK(hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-  const hipError_t e = conv::launch_viterbi(s.dev, reinterpret_cast<const conv::VitJob*>(s.dev.get()), s.dev, n, Lmax, tail, s.st);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s.st);
-    fprintf(stderr, "[srsran_phy_hip] %s: launch: %s\n", who, hipGetErrorString(e));
+  const auto enqueue = [&](hipStream_t st) { return conv::launch_viterbi(s.dev, reinterpret_cast<const conv::VitJob*>(s.dev.get()), s.dev, n, Lmax, tail, st); };
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, off - up, enqueue)) {
     return SRSRAN_ERROR;
   }
-  PHY_HIP_CHECK(hipMemcpyAsync(s.pin + up, s.dev + up, off - up, hipMemcpyDeviceToHost, s.st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
   for (uint32_t i = 0; i < n; i++) {
     memcpy(f[i].out, s.pin + jobs[i].o_out, f[i].L);
   }
@@ -234,18 +222,11 @@ static int pdcch_multi(const char* who, const float* llr, uint32_t nof_llr, uint
   if (!why) {
     memset(res, 0, (size_t)n * sizeof(*res));
     for (uint32_t i = 0; i < n && !why; i++) {
-      if (cand[i].L > 3) {
-        why = "aggregation level above 3";
-      } else if ((uint64_t)cand[i].ncce * 72 + (72u << cand[i].L) > nof_llr) {
-        why = "a location past the end of the control region";
-      } else if (cand[i].nof_bits == 0 || cand[i].nof_bits > SRSRAN_HIP_DCI_MAX_BITS) {
-        why = "nof_bits outside 1 .. 128";
-      }
+      why = conv::dci_cand_invalid(cand[i], nof_llr);
     }
   }
   if (why) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-    return SRSRAN_ERROR_INVALID_INPUTS;
+    return call::refused(who, why);
   }
   if (rm_f) {
     memset(rm_f, 0, (size_t)n * conv::kDciSyms * sizeof(float));
@@ -259,15 +240,15 @@ static int pdcch_multi(const char* who, const float* llr, uint32_t nof_llr, uint
   jobs.reserve(n);
   slot.reserve(n);
   for (uint32_t i = 0; i < n; i++) {
-    const uint32_t e_bits = 72u << cand[i].L, first = cand[i].ncce * 72;
-    double         mean   = 0;
-    for (uint32_t k = 0; k < e_bits; k++) {
-      mean += fabsf(llr[first + k]);
+    const conv::DciJob job  = conv::dci_job(cand[i]);
+    double             mean = 0;
+    for (uint32_t k = 0; k < job.E; k++) {
+      mean += fabsf(llr[job.first + k]);
     }
-    mean /= e_bits;
+    mean /= job.E;
     res[i].mean = (float)mean;
     if (mean > 0.3) {
-      jobs.push_back(conv::DciJob{first, e_bits, cand[i].nof_bits});
+      jobs.push_back(job);
       slot.push_back(i);
     }
   }
@@ -277,9 +258,8 @@ static int pdcch_multi(const char* who, const float* llr, uint32_t nof_llr, uint
   }
   ConvStage& s = conv_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
     memset(res, 0, (size_t)n * sizeof(*res));
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   const bool   dbg   = rm_f || symbols;
   const size_t o_llr = al256((size_t)m * sizeof(conv::DciJob)), up = al256(o_llr + (size_t)nof_llr * sizeof(float));
@@ -292,19 +272,11 @@ static int pdcch_multi(const char* who, const float* llr, uint32_t nof_llr, uint
   }
   memcpy(s.pin, jobs.data(), (size_t)m * sizeof(conv::DciJob));
   memcpy(s.pin + o_llr, llr, (size_t)nof_llr * sizeof(float));
-  hipError_t e = hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = conv::launch_pdcch_dci(reinterpret_cast<const float*>(s.dev + o_llr), reinterpret_cast<const conv::DciJob*>(s.dev.get()), s.dev + up,
-                               dbg ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr, dbg ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, m, s.st);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, end - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+  const auto enqueue = [&](hipStream_t st) {
+    return conv::launch_pdcch_dci(reinterpret_cast<const float*>(s.dev + o_llr), reinterpret_cast<const conv::DciJob*>(s.dev.get()), s.dev + up,
+                                  dbg ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr, dbg ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, m, st);
+  };
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, end - up, enqueue)) {
     memset(res, 0, (size_t)n * sizeof(*res));
     return SRSRAN_ERROR;
   }

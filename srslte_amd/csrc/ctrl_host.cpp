@@ -1,14 +1,12 @@
 // ctrl_host.cpp -- the PCFICH and the PHICH of a subframe (include/srsran_amd/phy_conv_abi.h: srsran_hip_regs_pcfich_table / _phich_ngroups / _phich_table,
 // srsran_hip_pcfich_decode{,_dbg}, srsran_hip_phich_decode_multi).  The REs are pdcch_map.h's; the receivers are ctrl_kernels.hip's one kernel.  A call is one
-// upload, one launch, one download and one host wait on the calling thread's staging context (stage.h).  One layout serves the pinned image and the device
+// round trip (call_frame.h) with one launch on the calling thread's staging context.  One layout serves the pinned image and the device
 // buffer:
 //   [the PHICH jobs | the rows of every plane the channel reaches || the PCFICH's row | the PHICH rows]
 // what is in front of || goes up, what is behind comes down.  The PCFICH stages row 0 alone, the PHICH the rows its mapping units reach (at most 3).
+#include "call_frame.h"
 #include "ctrl_device.h"
-#include "stage.h"
 #include "srsran_amd/phy_conv_abi.h"
-
-#include <string>
 
 using namespace phyhip;
 
@@ -19,24 +17,12 @@ static_assert(sizeof(srsran_hip_phich_resource_t) == 8, "phy_conv_abi.h layout")
 
 namespace {
 
-struct CtrlStage {
-  StageStream st;
-  HostImage   pin;
-  DeviceBuf   dev;
-  bool        ready() { return st.open(); }
-  bool        grow(size_t need) { return pin.grow(need, need / 2) && dev.grow(need, need / 2); }
-};
+struct CtrlStage : call::Stage {};
 
 CtrlStage& ctrl_stage() // of the calling thread, on the device it is bound to
 {
   static thread_local StageRef<CtrlStage> r;
   return r.get();
-}
-
-int refuse(const char* who, const char* why)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-  return SRSRAN_ERROR_INVALID_INPUTS;
 }
 
 // one call: the PCFICH (row != nullptr), or n PHICH resources
@@ -49,45 +35,32 @@ int run(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols
   if (!why && (!sf_symbols || !ce || (!row && (!r || !res)))) {
     why = "NULL argument";
   }
-  for (uint32_t a = 0; !why && a < sf->nof_rx; a++) {
-    why = !sf_symbols[a] ? "a received grid is NULL" : nullptr;
-    for (uint32_t p = 0; !why && p < sf->cell_nof_ports; p++) {
-      why = !ce[p][a] ? "an estimate grid is NULL" : nullptr;
-    }
+  if (!why) {
+    why = pdcch_map::planes_invalid(*sf, sf_symbols, ce);
   }
   if (!why) {
     why = ctrl::phich_invalid(*t, *sf, n, r);
   }
   if (why) {
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   CtrlStage&    s = ctrl_stage();
   modem::Params mp;
-  const auto    fail = [&](const char* what) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, what);
-    return SRSRAN_ERROR;
-  };
   if (!s.ready()) {
-    const std::string text = std::string(get_error()) + " (there is no CPU fallback)";
-    return fail(text.c_str());
+    return call::no_device(who);
   }
   if (!modem::params_for(mp, modem::LLR_F32)) {
-    return fail("the sequence tables could not be placed on the device");
+    return call::failed(who, "the sequence tables could not be placed on the device");
   }
   const uint32_t rows = row ? 1u : t->phich_rows, n_planes = sf->nof_rx * (1 + sf->cell_nof_ports);
   const size_t   pb = (size_t)rows * 12 * sf->cell_nof_prb * sizeof(cf_t), pstride = al256(pb);
   const size_t   o_planes = al256((size_t)n * sizeof(ctrl::PhichJob)), up = o_planes + n_planes * pstride;
   const size_t   o_phich = al256(up + (row ? sizeof(ctrl::PcfichRow) : 0)), end = o_phich + (size_t)n * sizeof(ctrl::PhichRow);
   if (!s.grow(end)) {
-    return fail("the staging allocation failed");
+    return call::failed(who, "the staging allocation failed");
   }
   ctrl::phich_jobs(reinterpret_cast<ctrl::PhichJob*>(s.pin.get()), *t, *sf, n, r);
-  for (uint32_t a = 0; a < sf->nof_rx; a++) {
-    memcpy(s.pin + o_planes + a * pstride, sf_symbols[a], pb);
-    for (uint32_t p = 0; p < sf->cell_nof_ports; p++) {
-      memcpy(s.pin + o_planes + (sf->nof_rx + p * sf->nof_rx + a) * pstride, ce[p][a], pb);
-    }
-  }
+  pdcch_map::stage_planes(s.pin + o_planes, *sf, sf_symbols, ce, pb, pstride);
   ctrl::Params cp = {};
   cp.rx           = reinterpret_cast<const float2*>(s.dev + o_planes);
   cp.stride       = (uint32_t)(pstride / sizeof(cf_t));
@@ -106,18 +79,8 @@ int run(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols
   cp.jobs       = reinterpret_cast<const ctrl::PhichJob*>(s.dev.get());
   cp.n_phich    = n;
   cp.phich_out  = reinterpret_cast<ctrl::PhichRow*>(s.dev + o_phich);
-  hipError_t e  = hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = ctrl::launch(cp, s.st);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, end - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return fail(get_error());
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, end - up, [&](hipStream_t st) { return ctrl::launch(cp, st); })) {
+    return SRSRAN_ERROR;
   }
   if (row) {
     memcpy(row, s.pin + up, sizeof(*row));
@@ -138,7 +101,7 @@ int pcfich(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symb
     *corr = 0.f;
   }
   if (!cfi) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   ctrl::PcfichRow row;
   const int       rc = run(who, sf, sf_symbols, ce, noise_estimate, &row, 0, nullptr, nullptr);

@@ -3,7 +3,9 @@
 // that run both in front of the codeword's front end are in nr_chan_host.cpp; the rules are in nr_map.h, the kernels in nr_chest_kernels.hip.
 // The staging context is the transport-block one (sch_nr_internal.h).  One layout serves the pinned image and the device buffer:
 //   [grid | table | granted PRBs | estimator job | de-mapper job | record | output]
-// the regions in front of the record are uploaded in one copy; the record and the output are written to the pinned image by the kernels themselves.
+// the regions in front of the record go up in the one copy of a round trip (call_frame.h) that brings nothing down: the record and the output are written to
+// the pinned image by the kernels themselves.
+#include "call_frame.h"
 #include "hip_common.h"
 #include "nr_chest_device.h"
 #include "sch_nr_internal.h"
@@ -21,19 +23,16 @@ int nr_grid_stage(const char* who, int what, const srsran_hip_nr_grid_t* grid, c
     memset(res, 0, sizeof(*res));
   }
   if (!grid || !sf_symbols || (what == 0 && !out) || (what == 1 && !res)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: NULL argument\n", who);
-    return SRSRAN_ERROR_INVALID_INPUTS;
+    return call::refused(who, "NULL argument");
   }
   if (const char* why = nr_map::invalid(*grid)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-    return SRSRAN_ERROR_INVALID_INPUTS;
+    return call::refused(who, why);
   }
   const uint32_t nof_re = nr_map::nof_re(*grid), n_seg = nr_map::nof_seg(*grid), n_prbs = nr_map::granted_prbs(*grid);
   const uint32_t grid_points = nr_map::NSYMB * 12 * grid->nof_prb;
   NrTbStage&     s           = tb_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   const size_t o_grid = 0, o_tab = al256((size_t)grid_points * sizeof(cf_t)), o_prbs = al256(o_tab + (size_t)n_seg * sizeof(nr_map::Seg));
   const size_t o_ej = al256(o_prbs + (size_t)n_prbs * sizeof(uint16_t)), o_dj = al256(o_ej + sizeof(nr_chest::EstJob));
@@ -41,8 +40,7 @@ int nr_grid_stage(const char* who, int what, const srsran_hip_nr_grid_t* grid, c
   const size_t end = al256(o_out + (size_t)nof_re * sizeof(cf_t));
   modem::Params mp;
   if (!s.grow(end) || !modem::params_for(mp, modem::LLR_I8)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::failed(who, get_error());
   }
   memcpy(s.pin + o_grid, sf_symbols, (size_t)grid_points * sizeof(cf_t));
   nr_map::Seg*        tab  = reinterpret_cast<nr_map::Seg*>(s.pin + o_tab);
@@ -53,31 +51,28 @@ int nr_grid_stage(const char* who, int what, const srsran_hip_nr_grid_t* grid, c
   float2*             dout = reinterpret_cast<float2*>(s.pin + o_out);
   const float2*       dgrid = reinterpret_cast<const float2*>(s.dev + o_grid);
   nr_map::fill_table(*grid, tab);
-  // one upload of the grid, the table and the jobs; the output and the record are written to the pinned image
-  const size_t up = o_rec;
-  hipError_t   e;
   const nr_map::Seg* d_tab = reinterpret_cast<const nr_map::Seg*>(s.dev + o_tab);
   if (what == 0) {
     *dj = nr_chest::DemapJob{0, n_seg, 0, nof_re};
-    PHY_HIP_CHECK(hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-    nr_chest::DemapParams dp{dgrid, grid_points, reinterpret_cast<const nr_chest::DemapJob*>(s.dev + o_dj), 1, n_seg, d_tab, n_seg, dout, nof_re};
-    e = nr_chest::launch_demap(dp, s.st);
   } else {
     nr_chest::fill_job(*grid, ej, prbs);
     ej->o_prb = 0, ej->o_tab = 0, ej->n_seg = out ? n_seg : 0, ej->o_ce = 0, ej->nof_re = out ? nof_re : 0;
-    PHY_HIP_CHECK(hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+  }
+  const auto enqueue = [&](hipStream_t st) {
+    if (what == 0) {
+      nr_chest::DemapParams dp{dgrid, grid_points, reinterpret_cast<const nr_chest::DemapJob*>(s.dev + o_dj), 1, n_seg, d_tab, n_seg, dout, nof_re};
+      return nr_chest::launch_demap(dp, st);
+    }
     const nr_chest::EstJob* d_ej   = reinterpret_cast<const nr_chest::EstJob*>(s.dev + o_ej);
     const uint16_t*         d_prbs = reinterpret_cast<const uint16_t*>(s.dev + o_prbs);
     nr_chest::EstParams ep{dgrid, grid_points, d_ej, d_prbs, n_prbs, d_tab, n_seg, out ? dout : nullptr, out ? nof_re : 0, rec, nullptr, 1, out ? n_seg : 0, mp.x1_bits,
                            mp.x2_cols};
-    e = nr_chest::launch_est(ep, s.st);
-  }
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s.st);
-    fprintf(stderr, "[srsran_phy_hip] %s: launch: %s\n", who, hipGetErrorString(e));
+    return nr_chest::launch_est(ep, st);
+  };
+  // the grid, the table and the jobs go up; nothing comes down: the output and the record are written to the pinned image
+  if (!call::round_trip(who, s.st, s.pin, s.dev, o_rec, o_rec, 0, enqueue)) {
     return SRSRAN_ERROR;
   }
-  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
   if (out) {
     memcpy(out, s.pin + o_out, (size_t)nof_re * sizeof(cf_t));
   }

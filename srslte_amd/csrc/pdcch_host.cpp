@@ -1,27 +1,26 @@
 // pdcch_host.cpp -- the PDCCH search of a subframe from the received grids (include/srsran_amd/phy_conv_abi.h: srsran_hip_regs_pdcch_*,
 // srsran_hip_pdcch_extract_llr, srsran_hip_pdcch_search_sf{,_dbg}).  The REG map is pdcch_map.h's; the front end is pdcch_kernels.hip; the decodes, with the mean
-// rule on the device, are conv_kernels.hip's pdcch_dci_sf_kernel.  A search is one upload, two launches, one download and one host wait on the calling
-// thread's staging context (stage.h).  One layout serves the pinned image and the device buffer:
+// rule on the device, are conv_kernels.hip's pdcch_dci_sf_kernel.  A search is one round trip (call_frame.h) with two launches on the calling thread's
+// staging context.  One layout serves the pinned image and the device buffer:
 //   [candidates | the region's rows of every plane || results | soft bits | _dbg: de-matched floats | symbols | equalised symbols | extracted planes]
 // what is in front of || goes up; of what is behind, a search brings down the results, srsran_hip_pdcch_extract_llr the soft bits, _dbg everything.
 // The search from the received grids alone (srsran_hip_pdcch_search_est{,_dbg}: run_est) puts the estimator and the PCFICH / PHICH kernel in front on the same
-// stream: one upload, four launches, one download, one host wait; its layout stands at the function.
+// stream: one round trip with four launches; its layout stands at the function.
 // A description's table is built once per thread and uploaded once per staging context; both caches are small and start over when they are full.  That is
 // safe because nothing of the thread's is in flight between two calls and because a call never holds an entry across an eviction: a call that takes one table
 // looks up once, and run_est, which holds the tables of CFI 1, 2 and 3 at once, makes room for all that are missing BEFORE its first lookup (reserve_all_cfi),
 // so none of its three lookups can empty the cache under the pointers it already has.
+#include "call_frame.h"
 #include "chest_dl_device.h"
 #include "conv_device.h"
 #include "ctrl_device.h"
 #include "modem_device.h"
 #include "pdcch_device.h"
 #include "pdcch_map.h"
-#include "stage.h"
 #include "srsran_amd/phy_conv_abi.h"
 
 #include <algorithm>
 #include <memory>
-#include <string>
 
 using namespace phyhip;
 
@@ -89,13 +88,8 @@ struct DeviceTable {
   StageBuf<StageMem::Device> d;
 };
 
-struct PdcchStage {
-  StageStream                               st;
-  HostImage                                 pin;
-  DeviceBuf                                 dev;
+struct PdcchStage : call::Stage {
   std::vector<std::unique_ptr<DeviceTable>> tables;
-  bool                                      ready() { return st.open(); }
-  bool                                      grow(size_t need) { return pin.grow(need, need / 2) && dev.grow(need, need / 2); }
   // the description's table in device memory: uploaded at its first use, resident from then on
   const uint32_t* table(const srsran_hip_pdcch_sf_t& sf, const pdcch_map::Table& t)
   {
@@ -121,12 +115,6 @@ PdcchStage& pdcch_stage() // of the calling thread, on the device it is bound to
 {
   static thread_local StageRef<PdcchStage> r;
   return r.get();
-}
-
-int refuse(const char* who, const char* why)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-  return SRSRAN_ERROR_INVALID_INPUTS;
 }
 
 struct Dbg {
@@ -160,41 +148,30 @@ int run(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols
   if (!why && n > SRSRAN_HIP_PDCCH_MAX_CANDIDATES) {
     why = "more than 256 candidates";
   }
-  for (uint32_t a = 0; !why && a < sf->nof_rx; a++) {
-    why = !sf_symbols[a] ? "a received grid is NULL" : nullptr;
-    for (uint32_t p = 0; !why && p < sf->cell_nof_ports; p++) {
-      why = !ce[p][a] ? "an estimate grid is NULL" : nullptr;
-    }
+  if (!why) {
+    why = pdcch_map::planes_invalid(*sf, sf_symbols, ce);
   }
   const uint32_t nsym = t ? 4 * t->nregs : 0, nof_llr = 2 * nsym;
   for (uint32_t i = 0; i < n && !why; i++) {
-    if (cand[i].L > 3) {
-      why = "aggregation level above 3";
-    } else if ((uint64_t)cand[i].ncce * 72 + (72u << cand[i].L) > nof_llr) {
-      why = "a location past the end of the control region";
-    } else if (cand[i].nof_bits == 0 || cand[i].nof_bits > SRSRAN_HIP_DCI_MAX_BITS) {
-      why = "nof_bits outside 1 .. 128";
-    }
+    why = conv::dci_cand_invalid(cand[i], nof_llr);
   }
   if (why) {
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   PdcchStage&   s = pdcch_stage();
   modem::Params mp;
-  const auto    fail = [&](const char* what) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, what);
+  const auto    zeroed = [&](int rc) { // a failed search leaves no result row behind
     if (search) {
       memset(res, 0, (size_t)n * sizeof(*res));
     }
-    return SRSRAN_ERROR;
+    return rc;
   };
   if (!s.ready()) {
-    const std::string text = std::string(get_error()) + " (there is no CPU fallback)";
-    return fail(text.c_str());
+    return zeroed(call::no_device(who));
   }
   const uint32_t* d_tab = s.table(*sf, *t);
   if (!d_tab || !modem::params_for(mp, modem::LLR_F32)) {
-    return fail("the REG table or the sequence tables could not be placed on the device");
+    return zeroed(call::failed(who, "the REG table or the sequence tables could not be placed on the device"));
   }
   const uint32_t n_planes = sf->nof_rx * (1 + sf->cell_nof_ports);
   const size_t   pb = plane_bytes(*sf), pstride = al256(pb), xstride = al256((size_t)nsym * sizeof(cf_t));
@@ -207,18 +184,13 @@ int run(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols
   const size_t   end   = want_x ? o_x + n_planes * xstride : o_x;
   const size_t   down  = dbg ? end : search ? o_llr : o_rm; // a search brings down the results alone
   if (!s.grow(end)) {
-    return fail("the staging allocation failed");
+    return zeroed(call::failed(who, "the staging allocation failed"));
   }
   conv::DciJob* jobs = reinterpret_cast<conv::DciJob*>(s.pin.get());
   for (uint32_t i = 0; i < n; i++) {
-    jobs[i] = conv::DciJob{cand[i].ncce * 72, 72u << cand[i].L, cand[i].nof_bits};
+    jobs[i] = conv::dci_job(cand[i]);
   }
-  for (uint32_t a = 0; a < sf->nof_rx; a++) {
-    memcpy(s.pin + o_planes + a * pstride, sf_symbols[a], pb);
-    for (uint32_t p = 0; p < sf->cell_nof_ports; p++) {
-      memcpy(s.pin + o_planes + (sf->nof_rx + p * sf->nof_rx + a) * pstride, ce[p][a], pb);
-    }
-  }
+  pdcch_map::stage_planes(s.pin + o_planes, *sf, sf_symbols, ce, pb, pstride);
   pdcch::FrontParams fp = {}; // (what only the search from the received grids alone sets stays null)
   fp.planes       = reinterpret_cast<const float2*>(s.dev + o_planes);
   fp.plane_stride = (uint32_t)(pstride / sizeof(cf_t));
@@ -235,22 +207,16 @@ int run(const char* who, const srsran_hip_pdcch_sf_t* sf, cf_t* const sf_symbols
   fp.dbg_d        = want_d ? reinterpret_cast<float2*>(s.dev + o_d) : nullptr;
   fp.dbg_planes   = want_x ? reinterpret_cast<float2*>(s.dev + o_x) : nullptr;
   fp.dbg_stride   = (uint32_t)(xstride / sizeof(cf_t));
-  hipError_t e    = hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = pdcch::launch_front(fp, s.st);
-  }
-  if (e == hipSuccess) {
-    e = conv::launch_pdcch_dci_sf(fp.llr, reinterpret_cast<const conv::DciJob*>(s.dev.get()), s.dev + up, want_rm ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr,
-                                  want_sym ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, n, s.st);
-  }
-  if (e == hipSuccess && down > up) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, down - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return fail(get_error());
+  const auto enqueue = [&](hipStream_t st) {
+    hipError_t e = pdcch::launch_front(fp, st);
+    if (e == hipSuccess) {
+      e = conv::launch_pdcch_dci_sf(fp.llr, reinterpret_cast<const conv::DciJob*>(s.dev.get()), s.dev + up, want_rm ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr,
+                                    want_sym ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, n, st);
+    }
+    return e;
+  };
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, down - up, enqueue)) {
+    return zeroed(SRSRAN_ERROR);
   }
   if (search) {
     memcpy(res, s.pin + up, (size_t)n * sizeof(*res));
@@ -357,30 +323,21 @@ int run_est(const char* who, const srsran_hip_pdcch_sf_t* sf, const srsran_hip_c
   for (uint32_t c = 0; !why && c < 3; c++) {
     first[c] = n_jobs;
     for (uint32_t i = 0; i < opt->n_cand[c] && !why; i++) {
-      const srsran_hip_pdcch_cand_t& k = cand[n_jobs + i];
-      if (k.L > 3) {
-        why = "aggregation level above 3";
-      } else if ((uint64_t)k.ncce * 72 + (72u << k.L) > 8ull * t[c]->nregs) {
-        why = "a location past the end of the control region of its list's CFI";
-      } else if (k.nof_bits == 0 || k.nof_bits > SRSRAN_HIP_DCI_MAX_BITS) {
-        why = "nof_bits outside 1 .. 128";
-      }
+      why = conv::dci_cand_invalid(cand[n_jobs + i], 8ull * t[c]->nregs, "a location past the end of the control region of its list's CFI");
     }
     n_jobs += opt->n_cand[c];
   }
   if (why) {
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   PdcchStage&   s = pdcch_stage();
   modem::Params mp;
-  const auto    fail = [&](const char* what) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, what);
+  const auto    zeroed = [&](int rc) {
     zero();
-    return SRSRAN_ERROR;
+    return rc;
   };
   if (!s.ready()) {
-    const std::string text = std::string(get_error()) + " (there is no CPU fallback)";
-    return fail(text.c_str());
+    return zeroed(call::no_device(who));
   }
   const uint32_t* d_tab[3];
   reserve_all_cfi(s.tables, *sf);
@@ -390,7 +347,7 @@ int run_est(const char* who, const srsran_hip_pdcch_sf_t* sf, const srsran_hip_c
     d_tab[c]                  = s.table(one, *t[c]);
   }
   if (!d_tab[0] || !d_tab[1] || !d_tab[2] || !modem::params_for(mp, modem::LLR_F32)) {
-    return fail("the REG tables or the sequence tables could not be placed on the device");
+    return zeroed(call::failed(who, "the REG tables or the sequence tables could not be placed on the device"));
   }
   const chest_dl::Layout l       = chest_dl::layout_of(*est);
   const uint32_t         n_pairs = est->nof_rx * est->nof_ports, nsym3 = 4 * t[2]->nregs;
@@ -410,7 +367,7 @@ int run_est(const char* who, const srsran_hip_pdcch_sf_t* sf, const srsran_hip_c
   const size_t o_dg = o_dn + 256, end = o_dg + n_pairs * gb;
   const size_t down = want_g ? end : (want_rm || want_sym) ? o_dn : want_llr ? o_rm : o_llr;
   if (!s.grow(end)) {
-    return fail("the staging allocation failed");
+    return zeroed(call::failed(who, "the staging allocation failed"));
   }
   chest_dl::stage_input(reinterpret_cast<cf_t*>(s.pin.get()), *est, l, sf_symbols);
   auto* ejobs = reinterpret_cast<chest_dl::Job*>(s.pin + o_ej);
@@ -421,7 +378,7 @@ int run_est(const char* who, const srsran_hip_pdcch_sf_t* sf, const srsran_hip_c
   }
   conv::DciJob* jobs = reinterpret_cast<conv::DciJob*>(s.pin + o_jobs);
   for (uint32_t i = 0; i < n_jobs; i++) {
-    jobs[i] = conv::DciJob{cand[i].ncce * 72, 72u << cand[i].L, cand[i].nof_bits};
+    jobs[i] = conv::dci_job(cand[i]);
   }
   ctrl::phich_jobs(reinterpret_cast<ctrl::PhichJob*>(s.pin + o_pj), *t[0], *sf, n_ph, phich);
   const modem::NoiseAvg  noise = {reinterpret_cast<const float*>(s.dev + o_dn), est->nof_rx, est->nof_ports};
@@ -468,33 +425,27 @@ int run_est(const char* who, const srsran_hip_pdcch_sf_t* sf, const srsran_hip_c
     fp.tab3[c]  = d_tab[c];
     fp.nsym3[c] = 4 * t[c]->nregs;
   }
-  hipError_t e = hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = chest_dl::launch(ep, s.st);
-  }
-  if (e == hipSuccess) {
-    e = ctrl::launch(cp, s.st);
-  }
-  if (e == hipSuccess) {
-    e = pdcch::launch_front(fp, s.st);
-  }
-  if (e == hipSuccess) {
-    e = conv::launch_pdcch_dci_sf(fp.llr, reinterpret_cast<const conv::DciJob*>(s.dev + o_jobs), s.dev + o_res, want_rm ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr,
-                                  want_sym ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, max_n, s.st, &sel);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, down - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return fail(get_error());
+  const auto enqueue = [&](hipStream_t st) {
+    hipError_t e = chest_dl::launch(ep, st);
+    if (e == hipSuccess) {
+      e = ctrl::launch(cp, st);
+    }
+    if (e == hipSuccess) {
+      e = pdcch::launch_front(fp, st);
+    }
+    if (e == hipSuccess) {
+      e = conv::launch_pdcch_dci_sf(fp.llr, reinterpret_cast<const conv::DciJob*>(s.dev + o_jobs), s.dev + o_res, want_rm ? reinterpret_cast<float*>(s.dev + o_rm) : nullptr,
+                                    want_sym ? reinterpret_cast<uint16_t*>(s.dev + o_sym) : nullptr, max_n, st, &sel);
+    }
+    return e;
+  };
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, down - up, enqueue)) {
+    return zeroed(SRSRAN_ERROR);
   }
   const ctrl::PcfichRow* row = reinterpret_cast<const ctrl::PcfichRow*>(s.pin + o_pc);
   const uint32_t         c   = *reinterpret_cast<const uint32_t*>(s.pin + o_cfi) - 1;
   if (c > 2) {
-    return fail("the CFI word left by the device is not 1 .. 3");
+    return zeroed(call::failed(who, "the CFI word left by the device is not 1 .. 3"));
   }
   const uint32_t n = opt->n_cand[c];
   *cfi             = c + 1;
@@ -580,37 +531,29 @@ extern "C" int srsran_hip_regs_pdcch_get(const srsran_hip_pdcch_sf_t* sf, uint32
     why = (!grids[p] || !d[p]) ? "a plane is NULL" : nullptr;
   }
   if (why) {
-    refuse(who, why);
+    call::refused(who, why);
     return -1;
   }
   PdcchStage& s = pdcch_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
+    call::no_device(who);
     return -1;
   }
   const uint32_t  nsym  = 4 * t->nregs;
   const size_t    pb = plane_bytes(*sf), pstride = al256(pb), xstride = al256((size_t)nsym * sizeof(cf_t)), up = n_planes * pstride, end = up + n_planes * xstride;
   const uint32_t* d_tab = s.table(*sf, *t);
   if (!d_tab || !s.grow(end)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: the REG table or the staging images could not be allocated\n", who);
+    call::failed(who, "the REG table or the staging images could not be allocated");
     return -1;
   }
   for (uint32_t p = 0; p < n_planes; p++) {
     memcpy(s.pin + p * pstride, grids[p], pb);
   }
-  hipError_t e = hipMemcpyAsync(s.dev, s.pin, up, hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = pdcch::launch_gather(reinterpret_cast<const float2*>(s.dev.get()), (uint32_t)(pstride / sizeof(cf_t)), d_tab, nsym, n_planes,
-                             reinterpret_cast<float2*>(s.dev + up), (uint32_t)(xstride / sizeof(cf_t)), s.st);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, end - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+  const auto enqueue = [&](hipStream_t st) {
+    return pdcch::launch_gather(reinterpret_cast<const float2*>(s.dev.get()), (uint32_t)(pstride / sizeof(cf_t)), d_tab, nsym, n_planes,
+                                reinterpret_cast<float2*>(s.dev + up), (uint32_t)(xstride / sizeof(cf_t)), st);
+  };
+  if (!call::round_trip(who, s.st, s.pin, s.dev, up, up, end - up, enqueue)) {
     return -1;
   }
   for (uint32_t p = 0; p < n_planes; p++) {
@@ -623,7 +566,7 @@ extern "C" int srsran_hip_pdcch_extract_llr(const srsran_hip_pdcch_sf_t* sf, cf_
                                             float* llr)
 {
   if (!llr) {
-    return refuse("srsran_hip_pdcch_extract_llr", "NULL argument");
+    return call::refused("srsran_hip_pdcch_extract_llr", "NULL argument");
   }
   return run("srsran_hip_pdcch_extract_llr", sf, sf_symbols, ce, noise_estimate, 0, nullptr, nullptr, llr, nullptr);
 }

@@ -22,6 +22,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace phyhip {
@@ -246,6 +247,32 @@ inline bool build(const srsran_hip_pdcch_sf_t& sf, Table& out)
 // the table of a description the calls take -- in range, and one the reference's own initialisation succeeds on -- built once per thread (pdcch_host.cpp);
 // nullptr with *why set for any other
 const Table* table_of(const srsran_hip_pdcch_sf_t* sf, const char** why);
+
+// the grids a call on sf's planes takes -- a received grid per antenna, an estimate grid per (port, antenna): nullptr, or which one is missing
+inline const char* planes_invalid(const srsran_hip_pdcch_sf_t& sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS])
+{
+  for (uint32_t a = 0; a < sf.nof_rx; a++) {
+    if (!sf_symbols[a]) {
+      return "a received grid is NULL";
+    }
+    for (uint32_t p = 0; p < sf.cell_nof_ports; p++) {
+      if (!ce[p][a]) {
+        return "an estimate grid is NULL";
+      }
+    }
+  }
+  return nullptr;
+}
+// the first pb bytes of each of them into planes of stride pstride from `at`, in the order the kernels index: [rx | port-major estimates]
+inline void stage_planes(uint8_t* at, const srsran_hip_pdcch_sf_t& sf, cf_t* const sf_symbols[], cf_t* const (*ce)[SRSRAN_MAX_PORTS], size_t pb, size_t pstride)
+{
+  for (uint32_t a = 0; a < sf.nof_rx; a++) {
+    memcpy(at + a * pstride, sf_symbols[a], pb);
+    for (uint32_t p = 0; p < sf.cell_nof_ports; p++) {
+      memcpy(at + (sf.nof_rx + p * sf.nof_rx + a) * pstride, ce[p][a], pb);
+    }
+  }
+}
 
 } // namespace pdcch_map
 } // namespace phyhip

@@ -1,17 +1,16 @@
 // prach_host.cpp -- random-access detection in one device call (include/srsran_amd/phy_prach_abi.h): the plan of a cell (srsran_prach_set_cell_ and
-// srsran_prach_gen_seqs, prach.c:359-460, 528-654, restated as written), the handle with the root spectra, and the detection calls.  A call is one upload,
-// the two launches of prach_kernels.hip, one download and one host wait on the calling thread's staging context (stage.h); the decisions of
+// srsran_prach_gen_seqs, prach.c:359-460, 528-654, restated as written), the handle with the root spectra, and the detection calls.  A call is one round trip
+// (call_frame.h) with the two launches of prach_kernels.hip on the calling thread's staging context; the decisions of
 // srsran_prach_process (:830-859) are taken here from the records that came down.  One layout serves the pinned image and the device buffer:
 //   [the first N_ifft_prach samples of every occasion || the roots' records | prach_bins | corr] and, on the device alone, the first stage's streams
 // what is in front of || goes up, what is behind comes down (the last two only for the _dbg call).
+#include "call_frame.h"
 #include "prach_device.h"
-#include "stage.h"
 #include "tables/lte_prach_tables.h"
 #include "srsran_amd/phy_prach_abi.h"
 
 #include <cmath>
 #include <complex>
-#include <string>
 
 using namespace phyhip;
 
@@ -36,12 +35,7 @@ namespace {
 constexpr uint32_t kDetectFactor = 18; // PRACH_DETECT_FACTOR
 constexpr uint32_t kDeltaF = 15000, kDeltaFRa = 1250, kPhi = 7, kRbSc = 12;
 
-struct PrachStage {
-  StageStream st;
-  HostImage   pin;
-  DeviceBuf   dev;
-  bool        ready() { return st.open(); }
-};
+struct PrachStage : call::Stage {};
 
 PrachStage& prach_stage() // of the calling thread, on the device it is bound to
 {
@@ -53,18 +47,6 @@ PrachStage& prach_stage() // of the calling thread, on the device it is bound to
 std::mutex g_order_mu;
 uint32_t   g_order[838];
 bool       g_have_order = false;
-
-int refuse(const char* who, const char* why)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-  return SRSRAN_ERROR_INVALID_INPUTS;
-}
-
-int fail(const char* who, const char* what)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, what);
-  return SRSRAN_ERROR;
-}
 
 // srsran_prach_set_cell_ and srsran_prach_gen_seqs; nullptr, or why the configuration is refused
 const char* plan(const srsran_hip_prach_cfg_t& c, srsran_hip_prach_info_t& p)
@@ -230,7 +212,7 @@ int run(const char* who, srsran_hip_prach* h, uint32_t n, const srsran_hip_prach
   TraceRange  trace_(who);
   const char* why = nullptr;
   if (!h) {
-    return refuse(who, "NULL handle");
+    return call::refused(who, "NULL handle");
   }
   const srsran_hip_prach_info_t& p = h->info;
   for (uint32_t o = 0; !why && o < n; o++) {
@@ -243,20 +225,19 @@ int run(const char* who, srsran_hip_prach* h, uint32_t n, const srsran_hip_prach
     }
   }
   if (why) {
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   PHY_DEV_GUARD(h->tag, who, SRSRAN_ERROR);
   PrachStage& s = prach_stage();
   if (!s.ready()) {
-    const std::string text = std::string(get_error()) + " (there is no CPU fallback)";
-    return fail(who, text.c_str());
+    return call::no_device(who);
   }
   const uint32_t N = p.N_ifft_prach, D = N / prach::kFirst, R = p.num_ra_preambles, rec_words = prach::kRecHead + 2 * p.n_wins;
   const size_t   up = al256((size_t)n * N * sizeof(cf_t)), o_bins = al256(up + (size_t)n * R * rec_words * 4);
   const size_t   o_corr = al256(o_bins + (dbg ? (size_t)n * prach::kNzc * sizeof(cf_t) : 0));
   const size_t   down = al256(o_corr + (dbg ? (size_t)n * R * prach::kNzc * 4 : 0)), end = down + (size_t)n * D * prach::kNzc * sizeof(double2);
-  if (!s.pin.grow(down, down / 2) || !s.dev.grow(end, end / 2)) {
-    return fail(who, "the staging allocation failed");
+  if (!s.grow(down, end)) {
+    return call::failed(who, "the staging allocation failed");
   }
   prach::Params k = {};
   for (uint32_t o = 0; o < n; o++) {
@@ -283,18 +264,8 @@ int run(const char* who, srsran_hip_prach* h, uint32_t n, const srsran_hip_prach
   k.N_cs      = (int)p.N_cs;
   k.rec_words = (int)rec_words;
   k.norm      = 1.0 / sqrt((double)N);
-  hipError_t e = hipMemcpyAsync(s.dev, s.pin, (size_t)n * N * sizeof(cf_t), hipMemcpyHostToDevice, s.st);
-  if (e == hipSuccess) {
-    e = prach::launch(k, s.st);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s.pin + up, s.dev + up, down - up, hipMemcpyDeviceToHost, s.st);
-  }
-  const hipError_t w = hipStreamSynchronize(s.st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return fail(who, get_error());
+  if (!call::round_trip(who, s.st, s.pin, s.dev, (size_t)n * N * sizeof(cf_t), up, down - up, [&](hipStream_t st) { return prach::launch(k, st); })) {
+    return SRSRAN_ERROR;
   }
   const uint32_t* rec = reinterpret_cast<const uint32_t*>(s.pin + up);
   for (uint32_t o = 0; o < n; o++) {
@@ -333,10 +304,10 @@ int detect(const char* who, srsran_hip_prach_t* h, uint32_t freq_offset, const c
     *n_indices = 0;
   }
   if (!h || !signal || !indices || !n_indices) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   if (max_det == 0) {
-    return refuse(who, "max_det is 0");
+    return call::refused(who, "max_det is 0");
   }
   const srsran_hip_prach_occ_t occ = {freq_offset, sig_len, signal};
   const Out                    out = {indices, t_offsets, peak_to_avg, max_det, n_indices};
@@ -355,7 +326,7 @@ extern "C" int srsran_hip_prach_set_root_order(const uint32_t* order)
   bool seen[839] = {};
   for (int i = 0; i < 838; i++) {
     if (order[i] < 1 || order[i] > 838 || seen[order[i]]) {
-      return refuse("srsran_hip_prach_set_root_order", "not a permutation of 1 .. 838");
+      return call::refused("srsran_hip_prach_set_root_order", "not a permutation of 1 .. 838");
     }
     seen[order[i]] = true;
   }
@@ -370,12 +341,12 @@ extern "C" int srsran_hip_prach_plan(const srsran_hip_prach_cfg_t* cfg, srsran_h
     memset(info, 0, sizeof(*info));
   }
   if (!cfg || !info) {
-    return refuse("srsran_hip_prach_plan", "NULL argument");
+    return call::refused("srsran_hip_prach_plan", "NULL argument");
   }
   const char* why = plan(*cfg, *info);
   if (why) {
     memset(info, 0, sizeof(*info));
-    return refuse("srsran_hip_prach_plan", why);
+    return call::refused("srsran_hip_prach_plan", why);
   }
   return SRSRAN_SUCCESS;
 }
@@ -387,17 +358,16 @@ extern "C" int srsran_hip_prach_create(srsran_hip_prach_t** hp, const srsran_hip
     *hp = nullptr;
   }
   if (!hp || !cfg) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   srsran_hip_prach_info_t info;
   const char*             why = plan(*cfg, info);
   if (why) {
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   PrachStage& s = prach_stage();
   if (!s.ready()) {
-    const std::string text = std::string(get_error()) + " (there is no CPU fallback)";
-    return fail(who, text.c_str());
+    return call::no_device(who);
   }
   srsran_hip_prach* h = new srsran_hip_prach;
   h->cfg              = *cfg;
@@ -427,17 +397,16 @@ extern "C" int srsran_hip_prach_create(srsran_hip_prach_t** hp, const srsran_hip
   put(o_seq, seq);
   int rc = SRSRAN_SUCCESS;
   if (!h->tab.grow(end)) {
-    rc = fail(who, "the device allocation failed");
+    rc = call::failed(who, "the device allocation failed");
   } else {
     hipError_t e = upload(h->tab, img.data(), end);
     if (e == hipSuccess) { // get_precoded_dft, :346-357: forward, norm, no mirror
-      e = prach::launch_root_spectra(reinterpret_cast<const float2*>(h->tab + o_seq), reinterpret_cast<float2*>(h->tab + h->o_spec), (int)R, s.st);
-      const hipError_t w = hipStreamSynchronize(s.st);
-      e                  = e != hipSuccess ? e : w;
+      e = call::settle(prach::launch_root_spectra(reinterpret_cast<const float2*>(h->tab + o_seq), reinterpret_cast<float2*>(h->tab + h->o_spec), (int)R, s.st), s.st);
     }
     if (e != hipSuccess) {
       set_error("%s: %s", who, hipGetErrorString(e));
-      rc = fail(who, get_error());
+      fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+      rc = SRSRAN_ERROR;
     }
   }
   if (rc != SRSRAN_SUCCESS) {
@@ -456,7 +425,7 @@ extern "C" void srsran_hip_prach_destroy(srsran_hip_prach_t* h)
 extern "C" int srsran_hip_prach_info(const srsran_hip_prach_t* h, srsran_hip_prach_info_t* info)
 {
   if (!h || !info) {
-    return refuse("srsran_hip_prach_info", "NULL argument");
+    return call::refused("srsran_hip_prach_info", "NULL argument");
   }
   *info = h->info;
   return SRSRAN_SUCCESS;
@@ -466,10 +435,10 @@ extern "C" int srsran_hip_prach_root_spectrum(srsran_hip_prach_t* h, uint32_t i,
 {
   const char* who = "srsran_hip_prach_root_spectrum";
   if (!h || !out) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   if (i >= h->info.num_ra_preambles) {
-    return refuse(who, "root index beyond the roots searched");
+    return call::refused(who, "root index beyond the roots searched");
   }
   PHY_DEV_GUARD(h->tag, who, SRSRAN_ERROR);
   bind_thread();
@@ -492,7 +461,7 @@ extern "C" int srsran_hip_prach_detect_offset_dbg(srsran_hip_prach_t* h, uint32_
     if (n_indices) {
       *n_indices = 0;
     }
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   return detect(who, h, freq_offset, signal, sig_len, indices, t_offsets, peak_to_avg, max_det, n_indices, dbg);
 }
@@ -504,13 +473,13 @@ extern "C" int srsran_hip_prach_detect_multi(srsran_hip_prach_t* h, uint32_t n, 
     return SRSRAN_SUCCESS;
   }
   if (n > SRSRAN_HIP_PRACH_MAX_OCC) {
-    return refuse(who, "more than 8 occasions");
+    return call::refused(who, "more than 8 occasions");
   }
   if (res) {
     memset(res, 0, (size_t)n * sizeof(*res));
   }
   if (!h || !occ || !res) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   Out out[SRSRAN_HIP_PRACH_MAX_OCC];
   for (uint32_t o = 0; o < n; o++) {

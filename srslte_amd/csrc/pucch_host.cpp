@@ -1,5 +1,5 @@
 // pucch_host.cpp -- PUCCH receive in one device call (include/srsran_amd/phy_pucch_abi.h): the caller's tables, the plan (pucch_map.h), and the calls.  A call
-// is one upload, the launch of pucch_kernels.hip, one download and one host wait on the calling thread's staging context (chan_internal.h); what the
+// is one round trip (call_frame.h) with the launch of pucch_kernels.hip on the calling thread's grant staging context (chan_internal.h); what the
 // reference decides in float on the host (the measurements' dB and rounding rules, the thresholds) is taken from the records that came down
 // (pucch_map.h finish).  One layout serves the pinned image and the device buffer:
 //   [the jobs | the column blocks || the records | the intermediates]
@@ -30,18 +30,6 @@ int8_t     g_phi[30][12];
 uint32_t   g_basis[pucch::kWordBits];
 bool       g_have_tables = false;
 
-int refuse(const char* who, const char* why)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, why);
-  return SRSRAN_ERROR_INVALID_INPUTS;
-}
-
-int fail(const char* who, const char* what)
-{
-  fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, what);
-  return SRSRAN_ERROR;
-}
-
 bool tables(int8_t phi[30][12], uint32_t* basis)
 {
   std::lock_guard<std::mutex> lk(g_tab_mu);
@@ -60,7 +48,7 @@ int run(const char* who, const srsran_hip_pucch_cell_t* cell, const srsran_hip_p
   int8_t     phi[30][12];
   pucch::Params k = {};
   if (!tables(phi, k.basis)) {
-    return refuse(who, "the tables have not been set (srsran_hip_pucch_set_tables)");
+    return call::refused(who, "the tables have not been set (srsran_hip_pucch_set_tables)");
   }
   std::vector<srsran_hip_pucch_plan_t> plans(n);
   pucch::CellSeq                       seq;
@@ -72,13 +60,13 @@ int run(const char* who, const srsran_hip_pucch_cell_t* cell, const srsran_hip_p
     }
     if (why) {
       const std::string text = "job " + std::to_string(i) + ": " + why;
-      return refuse(who, text.c_str());
+      return call::refused(who, text.c_str());
     }
   }
   chan::ChanStage* s  = chan::stage_for(who);
   hipStream_t      st = s ? sch::stage_stream() : nullptr;
   if (!st) {
-    return s ? fail(who, "no stream on the calling thread's staging context") : SRSRAN_ERROR;
+    return s ? call::failed(who, "no stream on the calling thread's staging context") : SRSRAN_ERROR;
   }
   // the column blocks the jobs touch: (slot, PRB) -> block
   const uint32_t        nsymb = cell->cp ? 6 : 7, block_pts = nsymb * pucch::kNre;
@@ -97,7 +85,7 @@ int run(const char* who, const srsran_hip_pucch_cell_t* cell, const srsran_hip_p
   const size_t o_cols = al256((size_t)n * sizeof(pucch::Job)), o_rec = al256(o_cols + blocks.size() * block_pts * sizeof(cf_t));
   const size_t o_dbg = al256(o_rec + (size_t)n * sizeof(pucch::Record)), end = o_dbg + (want_dbg ? (size_t)n * sizeof(pucch::Dbg) : 0);
   if (!s->grow(end, end)) {
-    return fail(who, "the staging allocation failed");
+    return call::failed(who, "the staging allocation failed");
   }
   auto* dj = reinterpret_cast<pucch::Job*>(s->pin.get());
   for (uint32_t i = 0; i < n; i++) {
@@ -120,24 +108,14 @@ int run(const char* who, const srsran_hip_pucch_cell_t* cell, const srsran_hip_p
   k.n_jobs = n;
   k.n_cols = (uint32_t)blocks.size();
   k.qpsk_s = (float)(-100 * M_SQRT2);
-  hipError_t e = hipMemcpyAsync(s->dev, s->pin, o_rec, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    e = pucch::launch(k, st);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(s->pin + o_rec, s->dev + o_rec, end - o_rec, hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t w = hipStreamSynchronize(st);
-  e                  = e != hipSuccess ? e : w;
-  if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    return fail(who, get_error());
+  if (!call::round_trip(who, st, s->pin, s->dev, o_rec, o_rec, end - o_rec, [&](hipStream_t q) { return pucch::launch(k, q); })) {
+    return SRSRAN_ERROR;
   }
   const auto* rec = reinterpret_cast<const pucch::Record*>(s->pin + o_rec);
   const auto* d   = reinterpret_cast<const pucch::Dbg*>(s->pin + o_dbg);
   for (uint32_t i = 0; i < n; i++) {
     if (rec[i].bad) {
-      return fail(who, "the kernel refused a job record");
+      return call::failed(who, "the kernel refused a job record");
     }
     pucch::finish(jobs[i], plans[i].n_rs, rec[i], ce_grid == nullptr, res[i]);
   }
@@ -171,7 +149,7 @@ int one(const char* who, const srsran_hip_pucch_cell_t* cell, const srsran_hip_p
     memset(res, 0, sizeof(*res));
   }
   if (!cell || !sf || !job || !sf_symbols || !res) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   return run(who, cell, sf, 1, job, sf_symbols, res, dbg, ce_grid);
 }
@@ -195,7 +173,7 @@ extern "C" int srsran_hip_pucch_set_tables(const cf_t base[30][12], const uint8_
       const float               q = std::arg(v) * 4.0f / (float)M_PI;
       const int                 f = (int)lroundf(q);
       if (!(fabsf(std::abs(v) - 1.0f) < 1e-5f) || !(fabsf(q - (float)f) < 1e-4f) || (f != -3 && f != -1 && f != 1 && f != 3)) {
-        return refuse(who, "a base sequence value is not unit-modulus with phi in {-3, -1, 1, 3}");
+        return call::refused(who, "a base sequence value is not unit-modulus with phi in {-3, -1, 1, 3}");
       }
       phi[u][k] = (int8_t)f;
     }
@@ -203,7 +181,7 @@ extern "C" int srsran_hip_pucch_set_tables(const cf_t base[30][12], const uint8_
   for (uint32_t n = 0; n < pucch::kWordBits; n++) {
     for (uint32_t i = 0; i < pucch::kBits2; i++) {
       if (basis[n][i] > 1) {
-        return refuse(who, "a basis entry is neither 0 nor 1");
+        return call::refused(who, "a basis entry is neither 0 nor 1");
       }
       masks[n] |= (uint32_t)basis[n][i] << i;
     }
@@ -222,19 +200,19 @@ extern "C" int srsran_hip_pucch_plan(const srsran_hip_pucch_cell_t* cell, const 
     memset(plan, 0, sizeof(*plan));
   }
   if (!cell || !sf || !job || !plan) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   int8_t   phi[30][12];
   uint32_t basis[pucch::kWordBits];
   if (!tables(phi, basis)) {
-    return refuse(who, "the tables have not been set (srsran_hip_pucch_set_tables)");
+    return call::refused(who, "the tables have not been set (srsran_hip_pucch_set_tables)");
   }
   pucch::CellSeq seq;
   pucch::cell_seq(*cell, seq);
   const char* why = pucch::plan(*cell, seq, *sf, *job, *plan);
   if (why) {
     memset(plan, 0, sizeof(*plan));
-    return refuse(who, why);
+    return call::refused(who, why);
   }
   return SRSRAN_SUCCESS;
 }
@@ -247,13 +225,13 @@ extern "C" int srsran_hip_pucch_decode_multi(const srsran_hip_pucch_cell_t* cell
     return SRSRAN_SUCCESS;
   }
   if (n > SRSRAN_HIP_PUCCH_MAX_JOBS) {
-    return refuse(who, "more than 256 jobs");
+    return call::refused(who, "more than 256 jobs");
   }
   if (res) {
     memset(res, 0, (size_t)n * sizeof(*res));
   }
   if (!cell || !sf || !jobs || !sf_symbols || !res) {
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   const int rc = run(who, cell, sf, n, jobs, sf_symbols, res, nullptr, nullptr);
   if (rc != SRSRAN_SUCCESS) {
@@ -276,7 +254,7 @@ extern "C" int srsran_hip_pucch_decode_dbg(const srsran_hip_pucch_cell_t* cell, 
     if (res) {
       memset(res, 0, sizeof(*res));
     }
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   return one(who, cell, sf, job, sf_symbols, res, dbg, nullptr);
 }
@@ -289,7 +267,7 @@ extern "C" int srsran_hip_chest_ul_estimate_pucch(const srsran_hip_pucch_cell_t*
     if (res) {
       memset(res, 0, sizeof(*res));
     }
-    return refuse(who, "NULL argument");
+    return call::refused(who, "NULL argument");
   }
   return one(who, cell, sf, job, sf_symbols, res, nullptr, ce);
 }

@@ -94,6 +94,20 @@ def begin_of(p, nof_prb, freq_offset):
     return 7 + 12 * k_0 + 6
 
 
+def preamble(p, nof_prb, freq_offset, u, shift, delay=0):
+    """the N_ifft_prach samples of one preamble behind the cyclic prefix, as srsran_prach_gen makes them (:656-690): root u cyclically shifted by `shift`
+    (C_v), the forward 839-point DFT with norm, placed at begin_of() in the mirrored spectrum, the backward mirror transform with norm; then a cyclic
+    delay of whole samples"""
+    n = p["N_ifft_prach"]
+    j = (np.arange(N_ZC, dtype=np.int64) + shift) % N_ZC
+    seq = np.exp(-2j * np.pi * ((u * j * (j + 1)) % (2 * N_ZC)) / (2 * N_ZC))
+    spec = np.zeros(n, np.complex128)
+    b = begin_of(p, nof_prb, freq_offset)
+    spec[b:b + N_ZC] = np.fft.fft(seq) / np.sqrt(N_ZC)
+    x = np.fft.ifft(np.roll(spec, -(n // 2))) * np.sqrt(n)  # copy_pre of a backward mirror plan: in[k] = spec[(k + n / 2) mod n]
+    return np.roll(x, delay)
+
+
 def bins(p, nof_prb, freq_offset, signal):
     n = p["N_ifft_prach"]
     x = np.fft.fft(np.asarray(signal[:n], np.complex128)) / np.sqrt(n)
@@ -146,3 +160,27 @@ def detect(cfg, freq_offset, signal, detect_factor=18.0, n_ifft_ul=None):
     b = bins(p, cfg["nof_prb"], freq_offset, signal)
     roots = [correlate(p, b, root_spectrum(u)) for u in p["root_u"][:p["num_ra_preambles"]]]
     return p, b, roots, decide(p, cfg, roots, detect_factor)
+
+
+def margins(case, rec, aux, tol):
+    """the assertions tools/gen_golden_prach.py makes on the reference alone, so that a tolerance hides no wrong decision (tests/test_prach_sizes.py makes them
+    on this model for the sizes the record does not hold).  case: name, cfg; rec: ind, sent, ave, pv, po, cross; aux: f, p, corr_all, n_wins, N_cs"""
+    name, f, p = case["name"], aux["f"], aux["p"]
+    assert sorted(int(v) for v in rec["ind"]) == sorted(int(v) for v in rec["sent"]), (name, rec["ind"], rec["sent"])
+    win = aux["N_cs"] or 839
+    for i in range(rec["ave"].size):
+        corr, top = aux["corr_all"][i], float(aux["corr_all"][i].max())
+        thr = float(f * rec["ave"][i])
+        for j in range(aux["n_wins"]):
+            m = 100.0 * max(tol["pv"], tol["ave"]) * top
+            assert abs(float(rec["pv"][i, j]) - thr) > m + 100.0 * tol["ave"] * thr, (name, i, j)
+            if rec["pv"][i, j] > thr:
+                start = (839 - j * aux["N_cs"]) % 839
+                w = np.sort(corr[start:start + win])
+                assert w[-1] - w[-2] > 100.0 * tol["corr"] * top, (name, i, j)
+        if case["cfg"][6] and i * aux["n_wins"] in set(int(v) // aux["n_wins"] * aux["n_wins"] for v in rec["ind"]):
+            x = phase_samples(p, complex(rec["cross"][i]))
+            assert abs(x - np.floor(x) - 0.5) > 0.05, (name, i, x)
+    if "offsets" in case:  # the peak on the first and on the last sample of a window
+        got = [int(rec["po"][int(k) // aux["n_wins"], int(k) % aux["n_wins"]]) for k in rec["ind"]]
+        assert got == case["offsets"] and case["offsets"][-1] == aux["N_cs"] - 1, (name, got)

@@ -1,7 +1,7 @@
 """CPU-only checks of the PUCCH entry points (include/srsran_amd/phy_pucch_abi.h), in the manner of test_prach_abi.py: the library exports them and the ctypes
 mirror binds them, the structs have the declared sizes in the header and in the mirror, a plain C caller compiles under -Wall -Werror,
-srsran_hip_pucch_set_tables refuses what it should, takes what it is handed and NULL removes it, srsran_hip_pucch_plan (pure host code) equals the record of
-the reference and tests/pucch_model.py over the sweep of the reference's pucch_test.c (:214-217: formats x delta 1 .. 3 x N_cs step delta x n_pucch 1, 51, 101)
+srsran_hip_pucch_set_tables refuses what it should, takes what it is handed and NULL removes it, srsran_hip_pucch_plan (pure host code) equals both records of
+the reference (pucch_ref.npz, pucch_sweep_ref.npz) and tests/pucch_model.py over the sweep of the reference's pucch_test.c (:214-217: formats x delta 1 .. 3 x N_cs step delta x n_pucch 1, 51, 101)
 on both prefixes, every refusal that needs no device comes with one line on stderr and zeroed results, and a valid call without a device fails loudly.  No
 kernel is launched."""
 import ctypes as C
@@ -145,6 +145,24 @@ def test_plan_equals_the_record_of_the_reference(L, capfd):
             w[37:47] = 0  # n' of formats 2x is not exposed by the reference
         assert np.array_equal(w, M.record()["plan"][c]), c
     assert capfd.readouterr().err == ""
+
+
+def test_plan_equals_the_reference_over_the_sweep(L, capfd):
+    """tests/golden/pucch_sweep_ref.npz holds the reference's OWN plan of every job: six cell sizes, both prefixes, 30 and more cell ids, every subframe"""
+    import pucch_sweep as S
+    from srslte_amd import capi
+
+    seen = 0
+    for g in range(S.n_groups()):
+        cell, sf, jobs, _, rows = S.group(g)
+        for j, i in zip(jobs, rows):
+            rc, w = plan_of(L, capi, cell, sf, j)
+            assert rc == 0, (g, j)
+            if j["format"] >= M.F2:
+                w[37:47] = 0  # n' of formats 2x is not exposed by the reference
+            assert np.array_equal(w, S.record()["plan"][i]), (g, j)
+            seen += 1
+    assert seen == S.record()["job"].shape[0] >= 150 and capfd.readouterr().err == ""
 
 
 def test_plan_equals_the_model_over_the_reference_tests_sweep(L, capfd):

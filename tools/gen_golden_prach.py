@@ -2,7 +2,8 @@
 """Record what the reference's PRACH detector (lib/src/phy/phch/prach.c: srsran_prach_set_cfg, srsran_prach_gen, srsran_prach_detect_offset and
 srsran_prach_process) gives on seeded occasions: tests/golden/prach_ref.npz.
 
-    python tools/gen_golden_prach.py        (needs the reference tree, oracle/liboracle.so and oracle/_ref/libsrsran_ref.so: `make -C oracle`)
+    python tools/gen_golden_prach.py                  (needs the reference tree, oracle/liboracle.so and oracle/_ref/libsrsran_ref.so: `make -C oracle`)
+    python tools/gen_golden_prach.py --check-sizes    (the same needs; the model against the reference at the stream counts the record does not hold; writes nothing)
 
 tools/prach_ref_wrap.c includes the reference's prach.c where it lies and is compiled with the REF_FLAGS of oracle/Makefile into a temporary directory (nothing
 compiled is kept).  The reference's transform backend is not available: the wrapper supplies the srsran_dft_* functions prach.c calls and routes a run to
@@ -33,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import oracle_api as O  # noqa: E402
 import prach_model as M  # noqa: E402
+from prach_model import margins  # noqa: E402
 from gen_golden_csi import ref_flags  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "prach_ref.npz")
@@ -141,27 +143,58 @@ def run_case(W, ref, case, rng):
     return rec, worst, dict(f=f, corr_all=corr_all, order=order, p=p, n_wins=n_wins, N_cs=N_cs)
 
 
-def margins(case, rec, aux, tol):
-    """the reference-only assertions"""
-    name, f, p = case["name"], aux["f"], aux["p"]
-    assert sorted(int(v) for v in rec["ind"]) == sorted(int(v) for v in rec["sent"]), (name, rec["ind"], rec["sent"])
-    win = aux["N_cs"] or 839
-    for i in range(rec["ave"].size):
-        corr, top = aux["corr_all"][i], float(aux["corr_all"][i].max())
-        thr = float(f * rec["ave"][i])
-        for j in range(aux["n_wins"]):
-            m = 100.0 * max(tol["pv"], tol["ave"]) * top
-            assert abs(float(rec["pv"][i, j]) - thr) > m + 100.0 * tol["ave"] * thr, (name, i, j)
-            if rec["pv"][i, j] > thr:
-                start = (839 - j * aux["N_cs"]) % 839
-                w = np.sort(corr[start:start + win])
-                assert w[-1] - w[-2] > 100.0 * tol["corr"] * top, (name, i, j)
-        if case["cfg"][6] and i * aux["n_wins"] in set(int(v) // aux["n_wins"] * aux["n_wins"] for v in rec["ind"]):
-            x = M.phase_samples(p, complex(rec["cross"][i]))
-            assert abs(x - np.floor(x) - 0.5) > 0.05, (name, i, x)
-    if "offsets" in case:  # the peak on the first and on the last sample of a window
-        got = [int(rec["po"][int(k) // aux["n_wins"], int(k) % aux["n_wins"]]) for k in rec["ind"]]
-        assert got == case["offsets"] and case["offsets"][-1] == aux["N_cs"] - 1, (name, got)
+def check_sizes():
+    """--check-sizes: the reference on the occasions of tests/prach_sizes.py (D = 4, 6, 8, 8, 12, 12: stream counts the record does not hold), the model
+    against it: equal detections, t_offsets and peak offsets, every deviation within the tolerance prach_ref.npz stores.  Prints, writes nothing."""
+    import prach_sizes as Z
+
+    tol = {q: float(np.load(OUT)["tol_" + q]) for q in QUANT}
+    print("stored tolerances", {q: "%.3g" % tol[q] for q in QUANT})
+    with tempfile.TemporaryDirectory() as tmp:
+        W = load_wrap(tmp)
+        ref = C.CDLL(O.REF_LIB)
+        W.prach_ref_open.argtypes = [C.c_void_p, C.c_float]
+        W.prach_ref_detect.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint32)]
+        W.prach_ref_root.argtypes = [C.c_uint32] + [C.c_void_p] * 5
+        over = []
+        for size in Z.SIZES:
+            cfg = Z.cfg_of(size)
+            ref.srsran_use_standard_symbol_size(C.c_bool(size[1]))
+            d = np.array([cfg[k] for k in M.CFG_FIELDS], np.uint32)
+            assert W.prach_ref_open(P(d), C.c_float(0.0)) == 0, size
+            info = np.zeros(9 + 64, np.uint32)
+            W.prach_ref_info(P(info))
+            N_ul, R, n_wins = int(info[2]), int(info[8]), int(info[7])
+            assert N_ul == M.symbol_sz(*size)
+            rsi = [int(v) for v in info[9:9 + int(info[6])]]
+            for o, (fo, sig, sent) in enumerate(Z.occasions(size)):
+                sig = np.array(sig)
+                ind, toff, p2a, n = np.zeros(64 * 65, np.uint32), np.zeros(64 * 65, np.float32), np.zeros(64 * 65, np.float32), C.c_uint32(0)
+                assert W.prach_ref_detect(fo, P(sig), sig.size, P(ind), P(toff), P(p2a), C.byref(n)) == 0
+                ind, toff, p2a = ind[:n.value], toff[:n.value], p2a[:n.value]
+                bins = np.zeros(839, np.complex64)
+                W.prach_ref_bins(P(bins))
+                ave, cross = np.zeros(R, np.float32), np.zeros(R, np.complex64)
+                pv, po, corr = np.zeros((R, n_wins), np.float32), np.zeros((R, n_wins), np.uint32), np.zeros((R, 839), np.float32)
+                for i in range(R):
+                    W.prach_ref_root(i, P(corr[i]), P(ave[i:]), P(cross[i:]), P(pv[i]), P(po[i]))
+                spec = np.zeros((R, 839), np.complex64)
+                for i in range(R):
+                    W.prach_ref_spectrum(rsi[i], P(spec[i]))
+                p, mb, mroots, (mind, mtoff, mp2a) = M.detect(cfg, fo, sig, 18.0, n_ifft_ul=N_ul)
+                assert [p[k] for k in ("N_zc", "N_cs", "N_ifft_ul", "N_ifft_prach", "N_seq", "N_cp", "N_roots", "n_wins", "num_ra_preambles")] == [int(v) for v in info[:9]]
+                assert np.array_equal(mind, ind) and [int(v) for v in ind] == sent and np.array_equal(mtoff, toff), (size, o, mind, ind, mtoff, toff)
+                assert np.array_equal(np.array([r[4] for r in mroots]), po), (size, o)
+                w = dict(spec=max(dev(M.root_spectrum(p["root_u"][i]), spec[i]) for i in range(R)), bins=dev(mb, bins), corr=max(dev(mroots[i][0], corr[i]) for i in range(R)),
+                         ave=max(abs(mroots[i][1] - ave[i]) / ave[i] for i in range(R)), cross=max(abs(mroots[i][2] - cross[i]) / ave[i] for i in range(R)),
+                         pv=max(float(np.max(np.abs(mroots[i][3] - pv[i])) / corr[i].max()) for i in range(R)), p2a=float(np.max(np.abs(mp2a - p2a) / p2a)))
+                over += [(Z.name(size), o, q) for q in QUANT if w[q] > tol[q]]
+                print("%-22s fo %2d %s detections %s  deviation %s" % (Z.name(size), fo, "wraps" if Z.wraps(p, size[0], fo) else "     ", ind,
+                                                                      {q: "%.2g" % w[q] for q in QUANT}), flush=True)
+        ref.srsran_use_standard_symbol_size(C.c_bool(False))
+        W.prach_ref_close()
+    assert not over, ("deviations above the stored tolerance", over)
+    print("every deviation lies within the stored tolerances")
 
 
 def main():
@@ -193,4 +226,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    check_sizes() if "--check-sizes" in sys.argv[1:] else main()

@@ -114,7 +114,7 @@ __device__ __forceinline__ void kept_ops(const uint4 (&Bl)[8][2][64], uint32_t s
   ys[4] = from_u(y1.x), ys[5] = from_u(y1.y), ys[6] = from_u(y1.z), ys[7] = from_u(y1.w);
 }
 
-// What the whole-block bodies of the main passes (tdec_win_unit, 16-step form) hand Ar16::normalize_if where a group lies at an end of the sub-block: 0 or
+// What the whole-block bodies of the forward main pass (tdec_win_unit, 16-step form) hand Ar16::normalize_if where a group lies at an end of the sub-block: 0 or
 // ~0, the same in every lane, and opaque like sub_x there (a mask known to be 0 or ~0 is turned back into two arms).
 __device__ __forceinline__ uint32_t norm_mask(bool on)
 {
@@ -504,6 +504,11 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
     // compute.  Four sets whose roles rotate (the loops are unrolled by hand over four blocks): a set-to-set copy would wait for the set
     // that was just requested.
     Ops cur, nxt, nx2, nx3;
+    // The turn from the backward to the forward main pass (16-step form, sub-blocks of 8 blocks or more: the backward pass's bottom group is a
+    // whole-block one).  The backward pass ends on block 0 and the forward pass starts there, so what it starts from never leaves the registers:
+    // the raw operands of blocks 0, 1 and 2 stay in their sets and the check-point at boundary 2 in ck2.  The same in every lane.
+    const bool turned = CKS == 16 && nblk >= 8;
+    uint32_t   ck2[8];
 
     // ================= forward warm-up (turbodecoder_win.h:684-750): the last 40 steps of every sub-block, all states unknown.
     // It needs nothing the backward recursion produces and runs FIRST: the backward main pass starts with the very blocks it
@@ -633,18 +638,14 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
           }
         }
       };
-      // The whole-block body: a block of a group of four whose top block b (b = 3 mod 4) has 3 <= b <= nblk - 5.  Every block of such a group
-      // is a whole one fetched from HBM (b <= top), so the schedule of the normalisation is the step's position in the block; the check-point
-      // is stored by the even blocks, second and fourth of the group.  The bottom group (blocks 3 ... 0) differs from the others in three
-      // things, none of them an arm: the requests of blocks 2 ... 0 run off the array's start and go to its first 16 bytes, like every request
-      // that is not needed (issue); step 0 is not followed by a normalisation, so the fourth block's last one is masked (`bottom`); and the
-      // check-point the fourth block files is, for block 0, slot 0 of CK, which exists and which no pass reads (the forward passes start at slot
-      // 2 or, with 8-step check-points, at slot 1) -- a branch around the store would merge an arm without stores into the path.
-      auto whole_block = [&](auto nt, auto ck_store, auto bottom, int b, const Ops& c, Ops& tgt) {
+      // The whole-block body: a block of a group of four whose top block b (b = 3 mod 4) has 7 <= b <= nblk - 5.  Every block of such a group
+      // is a whole one fetched from HBM (b <= top) and so is the block it requests (b - 3 >= 1), so the schedule of the normalisation is the
+      // step's position in the block; the check-point is stored by the even blocks, second and fourth of the group.
+      auto whole_block = [&](auto nt, auto ck_store, int b, const Ops& c, Ops& tgt) {
         s2 xs[8], ys[8], ap[8];
         taken(c);
         prep(c, xs, ys, ap);
-        issue(nt, b - 3, tgt, b >= 3);
+        issue(nt, b - 3, tgt);
 #pragma unroll
         for (int j = 7; j >= 0; j--) {
           beta_step<AR>(o, xs[j], ys[j]);
@@ -658,19 +659,45 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
               store_block_v<AR::kIs8>(CK, ((uint32_t)b & m_own()) * 64 + lane, ck);
             }
           }
-          if (bottom.value && j == 0) {
-            AR::normalize_if(o, norm_mask(b != 0));
+          if (AR::norm_in_block(j)) {
+            AR::normalize(o);
+          }
+        }
+      };
+      // The bottom group (blocks 3 ... 0) where it is a whole-block one: straight-line code behind the loops, because it is where the pass turns.  Block b
+      // lives in set b mod 4, so the raw operands of blocks 0, 1 and 2 are, or will be, in `cur`, `nxt` and `nx2` -- the sets the forward main pass calls
+      // q0, q1 and q2 and starts from.  Block 3 makes the group's only request (block 0, the bytes' last use before they are rewritten); nothing is
+      // requested for blocks that are not there, so `nxt` and `nx2` keep what arrived.  Block 2 leaves its check-point, the one the forward pass starts
+      // from, in ck2 instead of slot 2 of CK.  Blocks 1 and 0 have no steps at all: all the backward pass ever made of them was the check-point at
+      // boundary 0, which no pass reads (the forward pass derives the values inside its first pair from boundary 2), and their operands are
+      // taken by the forward pass's first pair.
+      auto turn_block = [&](auto first, const Ops& c) {
+        s2 xs[8], ys[8], ap[8];
+        taken(c);
+        prep(c, xs, ys, ap);
+        if constexpr (first.value) {
+          issue(kStream, 0, cur);
+        }
+#pragma unroll
+        for (int j = 7; j >= 0; j--) {
+          beta_step<AR>(o, xs[j], ys[j]);
+          if (!first.value && j == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+              ck2[i] = to_u(o[i]);
+            }
           } else if (AR::norm_in_block(j)) {
             AR::normalize(o);
           }
         }
       };
-      constexpr std::integral_constant<bool, true>  kStore{}, kBottom{};
-      constexpr std::integral_constant<bool, false> kNoStore{}, kInner{};
+      constexpr std::integral_constant<bool, true>  kStore{};
+      constexpr std::integral_constant<bool, false> kNoStore{};
       // Two bodies, each emitted once, never two arms of one loop trip (at a merge the compiler counts the arm with the fewest loads in
       // flight): the general loop runs the groups that hold a block from the beta buffer or a ragged one (a sub-block has more than 40 steps, so
-      // nblk >= 6 and there is at least one), the whole-block loop every group below them, down to block 0.  The way into either loop carries
-      // what its back edge carries: the requests of the next three blocks.
+      // nblk >= 6 and there is at least one), the whole-block loop every group below them down to blocks 7 ... 4, the straight-line bottom group
+      // blocks 3 ... 0 (nblk >= 8; a shorter sub-block's bottom group holds a block from the beta buffer and is the general loop's last trip).  The
+      // way into either loop and into the bottom group carries what a back edge carries: the requests of the next three blocks.
       int b = ((int)nblk - 1) | 3;
 #pragma nounroll
       for (; b > top; b -= 4) {
@@ -685,20 +712,24 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       // So the groups that request only blocks >= reuse_blocks keep the non-temporal policy, the groups below them (a group whose top block is b
       // requests blocks b - 3 ... b - 6) request with the default one.  The bound is the same in every lane and a run-time value (WinParams);
       // the way from the first copy into the second carries the three requests its back edge carries.  reuse_blocks = 0: no trip of the second copy.
-      const int b_reuse = p.reuse_blocks ? (int)p.reuse_blocks + 6 : 3;
+      const int b_reuse = p.reuse_blocks ? (int)p.reuse_blocks + 6 : 7;
 #pragma nounroll
       for (; b >= b_reuse; b -= 4) {
-        whole_block(kStream, kNoStore, kInner, b, nx3, cur);
-        whole_block(kStream, kStore, kInner, b - 1, nx2, nx3);
-        whole_block(kStream, kNoStore, kInner, b - 2, nxt, nx2);
-        whole_block(kStream, kStore, kBottom, b - 3, cur, nxt);
+        whole_block(kStream, kNoStore, b, nx3, cur);
+        whole_block(kStream, kStore, b - 1, nx2, nx3);
+        whole_block(kStream, kNoStore, b - 2, nxt, nx2);
+        whole_block(kStream, kStore, b - 3, cur, nxt);
       }
 #pragma nounroll
-      for (; b >= 3; b -= 4) {
-        whole_block(kReuse, kNoStore, kInner, b, nx3, cur);
-        whole_block(kReuse, kStore, kInner, b - 1, nx2, nx3);
-        whole_block(kReuse, kNoStore, kInner, b - 2, nxt, nx2);
-        whole_block(kReuse, kStore, kBottom, b - 3, cur, nxt);
+      for (; b >= 7; b -= 4) {
+        whole_block(kReuse, kNoStore, b, nx3, cur);
+        whole_block(kReuse, kStore, b - 1, nx2, nx3);
+        whole_block(kReuse, kNoStore, b - 2, nxt, nx2);
+        whole_block(kReuse, kStore, b - 3, cur, nxt);
+      }
+      if (turned) { // (b = 3 here; where the general loop ran the bottom group, b = -1)
+        turn_block(std::true_type{}, nx3);
+        turn_block(std::false_type{}, nx2);
       }
     } else {
       // (8-step check-points: the 8-bit and the early-stop kernels.  With four rotating sets the int16 early-stop kernels spill -- their forward
@@ -944,15 +975,28 @@ __device__ __forceinline__ void tdec_win_unit(const WinParams& p, const uint32_t
       Ops&     q1 = nxt;
       Ops&     q2 = nx2;
       Ops&     q3 = nx3;
-      uint32_t ck[8], tr[8];
-      load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & m_own()) * 64 + lane, ck);
-      issue(kStream, 1, q1, nblk > 1);
-      // The loop is entered with exactly what its back edge brings: one request in flight, everything before it taken.  The waits at the top of
-      // the loop are counted for the worse of the two ways in; with all of these requests still open on this one, the count that suits it
-      // would, on the back edge, reach into the last block's request.  (Once per half iteration: block 1's operands are waited for here.)
-      asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
-      taken(q1);
-      issue(kStream, 2, q2, nblk > 2);
+      uint32_t(&ck)[8] = ck2;
+      uint32_t tr[8];
+      // Behind the backward pass's straight-line bottom group (`turned`) everything the first pair needs is here: blocks 0 ... 2 in q0 ... q2, the
+      // check-point of boundary 2 in ck.  Nothing is requested, and the first thing that touches memory is block 0's own table load.  Elsewhere
+      // only block 0 is here.  (An arm with requests next to a way without: the waits inside the loop are counted for the arm and are what they
+      // were; the way without has nothing in flight.  The two ways leave the sets in different registers, and the copies that settle it behind the
+      // merge wait for block 2 on the arm's way as well: once per half iteration of a sub-block of 7 blocks or fewer)
+      if (!turned) {
+        load_block_raw<AR::kIs8, NT>(CK, ((nblk < 2 ? nblk : 2u) & m_own()) * 64 + lane, ck);
+        issue(kStream, 1, q1, nblk > 1);
+        // The loop is entered with no more than its back edge brings: one request in flight, everything before it taken.  The waits at the top of
+        // the loop are counted for the worst of the ways in; with all of these requests still open on this one, the count that suits it
+        // would, on the back edge, reach into the last block's request.  (Once per half iteration: block 1's operands are waited for here.)
+        asm volatile("" ::"v"(ck[0]), "v"(ck[1]), "v"(ck[2]), "v"(ck[3]), "v"(ck[4]), "v"(ck[5]), "v"(ck[6]), "v"(ck[7]));
+        taken(q1);
+        issue(kStream, 2, q2, nblk > 2);
+      } else {
+        // (block 0 was requested two blocks of steps ago, by block 3: waited for here, not at the loop's top, where the count would hold on the back edge too)
+        taken(q1);
+        taken(q2);
+        taken(q0);
+      }
       // b may lie behind the last block (the loop below goes over four blocks whatever the count): such a block has no steps, len = 0.  It makes
       // its requests and goes the same way as every other: an arm of its own, or one around the others' work, is a way on which the compiler
       // sees the table entries and the check-point still open, and its wait for them, placed behind the row stores, reaches into the request.

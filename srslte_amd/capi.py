@@ -373,6 +373,23 @@ class LdpcDecoder(C.Structure):
                 ("free", C.c_void_p), ("decode_f", C.c_void_p), ("decode_s", C.c_void_p), ("decode_c", C.c_void_p)]
 
 
+class HipPbchCell(C.Structure):  # srsran_hip_pbch_cell_t (phy_pbch_abi.h)
+    _fields_ = [(n, C.c_uint32) for n in ("nof_prb", "nof_ports", "id", "cp_nsymb")]
+
+
+class HipPbchState(C.Structure):  # srsran_hip_pbch_state_t
+    _fields_ = [("frame_idx", C.c_uint32), ("llr", C.c_float * (4 * 480))]
+
+
+class HipPbchRes(C.Structure):  # srsran_hip_pbch_res_t
+    _fields_ = [("ret", C.c_int32), ("nof_tx_ports", C.c_uint32), ("sfn_offset", C.c_int32), ("src", C.c_uint32), ("dst", C.c_uint32), ("nb", C.c_uint32),
+                ("payload", C.c_uint8 * 24)]
+
+
+class HipPbchRow(C.Structure):  # srsran_hip_pbch_row_t
+    _fields_ = [("bits", C.c_uint8 * 40), ("crc_rem", C.c_uint16), ("ones", C.c_uint16), ("zero", C.c_uint32)]
+
+
 class HipPrachCfg(C.Structure):  # srsran_hip_prach_cfg_t (phy_prach_abi.h)
     _fields_ = [("nof_prb", C.c_uint32), ("config_idx", C.c_uint32), ("root_seq_idx", C.c_uint32), ("zero_corr_zone", C.c_uint32),
                 ("num_ra_preambles", C.c_uint32), ("hs_flag", C.c_uint32), ("freq_domain_offset_calc", C.c_uint32), ("detect_factor", C.c_float)]
@@ -825,6 +842,20 @@ def lib():
             "srsran_hip_pdcch_search_est_dbg": (i32, [C.POINTER(HipPdcchSf), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), vp, C.POINTER(HipPdcchEst),
                                                       C.POINTER(HipPdcchCand), C.POINTER(HipPdcchRes), C.POINTER(HipPhichResource), C.POINTER(HipPhichRes),
                                                       C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(HipChestDlRes), vp, vp, vp, vp, vp]),
+            # PBCH / MIB decoding (phy_pbch_abi.h): ce is cf_t*[SRSRAN_MAX_PORTS]; _multi takes arrays of pointers and of cf_t*[SRSRAN_MAX_PORTS]
+            "srsran_hip_pbch_nof_re": (i32, [C.POINTER(HipPbchCell)]),
+            "srsran_hip_pbch_table": (i32, [C.POINTER(HipPbchCell), vp]),
+            "srsran_hip_pbch_mib_unpack": (None, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+            "srsran_hip_pbch_try_frames": (i32, [C.POINTER(HipPbchCell), vp, u32, C.POINTER(HipPbchRow)]),
+            "srsran_hip_pbch_try_frames_dbg": (i32, [C.POINTER(HipPbchCell), vp, u32, C.POINTER(HipPbchRow), vp, vp]),
+            "srsran_hip_pbch_decode": (i32, [C.POINTER(HipPbchCell), C.POINTER(HipPbchState), vp, vp, C.c_float, C.POINTER(HipPbchRes)]),
+            "srsran_hip_pbch_decode_dbg": (i32, [C.POINTER(HipPbchCell), C.POINTER(HipPbchState), vp, vp, C.c_float, C.POINTER(HipPbchRes), vp, vp,
+                                                 C.POINTER(HipPbchRow), C.POINTER(u32)]),
+            "srsran_hip_pbch_decode_est": (i32, [C.POINTER(HipPbchCell), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), C.POINTER(HipPbchState), vp,
+                                                 C.POINTER(HipPbchRes), C.POINTER(HipChestDlRes)]),
+            "srsran_hip_pbch_decode_est_dbg": (i32, [C.POINTER(HipPbchCell), C.POINTER(HipChestDl), C.POINTER(HipChestDlState), C.POINTER(HipPbchState), vp,
+                                                     C.POINTER(HipPbchRes), C.POINTER(HipChestDlRes), vp, vp, C.POINTER(HipPbchRow), C.POINTER(u32)]),
+            "srsran_hip_pbch_decode_multi": (i32, [u32, C.POINTER(HipPbchCell), C.POINTER(C.POINTER(HipPbchState)), vp, vp, vp, C.POINTER(HipPbchRes)]),
             # random-access detection (phy_prach_abi.h)
             "srsran_hip_prach_set_root_order": (i32, [vp]),
             "srsran_hip_prach_plan": (i32, [C.POINTER(HipPrachCfg), C.POINTER(HipPrachInfo)]),

@@ -1,5 +1,5 @@
 // pdcch_arith.h -- the equaliser of the downlink control channels on one group of `PORTS` neighbouring REs of a REG, as pdcch.c:466-475, pcfich.c:197-205 and
-// phich.c:248-256 run it: one symbol on one port, an SFBC pair on two, a quad on four.  Shared by pdcch_kernels.hip and ctrl_kernels.hip.  Device code only.
+// phich.c:248-256 run it: one symbol on one port, an SFBC pair on two, a quad on four.  Shared by pdcch_kernels.hip, ctrl_kernels.hip and pbch_kernels.hip (pbch.c:506-512: the same calls).  Device code only.
 //   one port    x = sum_rx y conj(h) / (sum_rx |h|^2 [+ noise when noise > 0])      srsran_predecoding_single_multi, precoding.c:182-305
 //   two ports   modem_arith.h sfbc_add<2> / sfbc_finish<2>                           srsran_predecoding_diversity_gen_, :438-463 (hh == 0 -> 1e-4)
 //   four ports  modem_arith.h sfbc4_add / sfbc4_finish                               the body WITHOUT CSI, :465-498

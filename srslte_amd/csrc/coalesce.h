@@ -20,6 +20,7 @@
 // whether it was merged or not.  SRSRAN_HIP_COALESCE=0 turns merging off (every handle then uses its private stream).
 #pragma once
 #include "hip_common.h"
+#include "stage.h"
 
 #include <condition_variable>
 #include <deque>
@@ -55,9 +56,8 @@ public:
     n_lanes = n_lanes < 1 ? 1 : (n_lanes > kMaxLanes ? kMaxLanes : n_lanes);
     for (int l = 0; l < n_lanes && ok_; l++) {
       Lane& ln = lanes_[l];
-      ok_      = hipStreamCreateWithFlags(&ln.st, hipStreamNonBlocking) == hipSuccess && hipMalloc(&ln.d_in, in_stride_ * max_batch) == hipSuccess &&
-            hipMalloc(&ln.d_out, out_stride_ * max_batch) == hipSuccess && hipHostMalloc(&ln.h_in, in_stride_ * max_batch) == hipSuccess &&
-            hipHostMalloc(&ln.h_out, out_stride_ * max_batch) == hipSuccess;
+      ok_      = ln.st.open() && ln.d_in.grow(in_stride_ * max_batch) && ln.d_out.grow(out_stride_ * max_batch) && ln.h_in.grow(in_stride_ * max_batch) &&
+            ln.h_out.grow(out_stride_ * max_batch);
       if (ok_) {
         ln.eng = make(l);
         ok_    = (bool)ln.eng.run;
@@ -65,7 +65,7 @@ public:
       free_.push_back(l);
     }
   }
-  ~Coalescer()
+  ~Coalescer() // a lane's work is waited for and its engine released before its buffers and stream go (with lanes_)
   {
     for (Lane& ln : lanes_) {
       if (ln.st) {
@@ -73,13 +73,6 @@ public:
       }
       if (ln.eng.destroy) {
         ln.eng.destroy();
-      }
-      (void)hipFree(ln.d_in);
-      (void)hipFree(ln.d_out);
-      (void)hipHostFree(ln.h_in);
-      (void)hipHostFree(ln.h_out);
-      if (ln.st) {
-        (void)hipStreamDestroy(ln.st);
       }
     }
   }
@@ -149,15 +142,16 @@ private:
     bool        taken;
   };
   struct Lane {
-    hipStream_t st = nullptr;
-    void *      d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+    StageStream                st;
+    DeviceBuf                  d_in, d_out;
+    StageBuf<StageMem::Pinned> h_in, h_out;
     Engine      eng;
   };
   int process(Lane& ln, const std::vector<Req*>& batch, uint64_t tag)
   {
     const uint32_t n = (uint32_t)batch.size();
     for (uint32_t i = 0; i < n; i++) {
-      memcpy(static_cast<uint8_t*>(ln.h_in) + i * in_stride_, batch[i]->in, in_bytes_);
+      memcpy(ln.h_in + i * in_stride_, batch[i]->in, in_bytes_);
     }
     int rc = SRSRAN_SUCCESS;
     if (hipMemcpyAsync(ln.d_in, ln.h_in, in_stride_ * (n - 1) + in_bytes_, hipMemcpyHostToDevice, ln.st) != hipSuccess) {
@@ -180,7 +174,7 @@ private:
       return rc;
     }
     for (uint32_t i = 0; i < n; i++) {
-      memcpy(batch[i]->out, static_cast<uint8_t*>(ln.h_out) + i * out_stride_, out_bytes_);
+      memcpy(batch[i]->out, ln.h_out + i * out_stride_, out_bytes_);
     }
     return SRSRAN_SUCCESS;
   }

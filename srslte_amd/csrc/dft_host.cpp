@@ -4,6 +4,7 @@
 // There is no planner and no wisdom file: a "plan" is a radix list + an exact twiddle table in HBM.
 #include "dft_device.h"
 #include "hip_common.h"
+#include "stage.h"
 
 #include <cmath>
 #include <complex>
@@ -20,19 +21,15 @@ struct DftCtx {
   int         N = 0;
   int         npass = 0;
   int         radix[16] = {};
-  float2*     d_tw = nullptr;
-  float2*     d_in = nullptr;
-  float2*     d_out = nullptr;
-  cf_t*       h_in = nullptr;  // pinned staging
-  cf_t*       h_out = nullptr; // pinned staging
-  size_t      cap_in = 0, cap_out = 0;
-  hipStream_t stream = nullptr;
+  using Tw = StageBuf<StageMem::Device, float2>;
+  Tw          d_tw;
+  StagePair<float2, StageMem::HostImage, cf_t> in, out; // device arrays and their pinned staging, exactly as large as the largest call so far
+  StageStream stream;
   // N > 4096: four-step decomposition N = N1 * N2, both <= 4096 (N1 transforms of length N2 after N2 of length N1)
   int     N1 = 0, N2 = 0;
   int     npass1 = 0, npass2 = 0, radix1[16] = {}, radix2[16] = {};
-  float2* d_tw1 = nullptr;
-  float2* d_tw2 = nullptr;
-  float2* d_tmp[2] = {nullptr, nullptr};
+  Tw      d_tw1, d_tw2;
+  Tw      d_tmp[2];
   // guru geometry
   cf_t* g_in = nullptr;
   cf_t* g_out = nullptr;
@@ -57,17 +54,15 @@ void factorize(int N, int* radix, int* npass)
   *npass = (n == 1) ? np : 0; // anything else: direct evaluation
 }
 
-int upload_twiddles(float2** d, int N)
+int upload_twiddles(DftCtx::Tw& d, int N) // a fresh table of exactly N entries
 {
   std::vector<std::complex<float>> tw(N);
   for (int i = 0; i < N; i++) {
     double a = -2.0 * M_PI * (double)i / (double)N;
     tw[i]    = std::complex<float>((float)cos(a), (float)sin(a));
   }
-  (void)hipFree(*d);
-  *d = nullptr;
-  PHY_HIP_CHECK(hipMalloc(d, N * sizeof(float2)), SRSRAN_ERROR);
-  PHY_HIP_CHECK(upload(*d, tw.data(), N * sizeof(float2)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(d.alloc(N)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(upload(d, tw.data(), N * sizeof(float2)), SRSRAN_ERROR);
   return SRSRAN_SUCCESS;
 }
 
@@ -112,13 +107,11 @@ int ctx_set_large(DftCtx* c, int N)
   c->N2 = N / best;
   factorize(c->N1, c->radix1, &c->npass1);
   factorize(c->N2, c->radix2, &c->npass2);
-  if (upload_twiddles(&c->d_tw1, c->N1) || upload_twiddles(&c->d_tw2, c->N2)) {
+  if (upload_twiddles(c->d_tw1, c->N1) || upload_twiddles(c->d_tw2, c->N2)) {
     return SRSRAN_ERROR;
   }
   for (auto& t : c->d_tmp) {
-    (void)hipFree(t);
-    t = nullptr;
-    PHY_HIP_CHECK(hipMalloc(&t, (size_t)N * sizeof(float2)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(t.alloc(N)), SRSRAN_ERROR);
   }
   return SRSRAN_SUCCESS;
 }
@@ -133,40 +126,26 @@ int ctx_set_size(DftCtx* c, int N)
   if (c->N == N) {
     return SRSRAN_SUCCESS;
   }
+  const int planned = c->N;
   c->N1 = c->N2 = 0;
+  int rc;
   if (N > DFT_MAX_POINTS) {
-    return ctx_set_large(c, N);
+    rc = ctx_set_large(c, N);
+  } else {
+    c->N = N;
+    factorize(N, c->radix, &c->npass);
+    rc = upload_twiddles(c->d_tw, N);
   }
-  c->N = N;
-  factorize(N, c->radix, &c->npass);
-  std::vector<std::complex<float>> tw(N);
-  for (int i = 0; i < N; i++) {
-    double a = -2.0 * M_PI * (double)i / (double)N;
-    tw[i]    = std::complex<float>((float)cos(a), (float)sin(a));
+  if (rc && c->N != planned) {
+    c->N = c->N1 = c->N2 = 0; // an allocation or upload failed after the old tables went: no length is planned, the same request is tried again
   }
-  (void)hipFree(c->d_tw);
-  c->d_tw = nullptr;
-  PHY_HIP_CHECK(hipMalloc(&c->d_tw, N * sizeof(float2)), SRSRAN_ERROR);
-  PHY_HIP_CHECK(upload(c->d_tw, tw.data(), N * sizeof(float2)), SRSRAN_ERROR);
-  return SRSRAN_SUCCESS;
+  return rc;
 }
 
 int ctx_reserve(DftCtx* c, size_t n_in, size_t n_out)
 {
-  if (n_in > c->cap_in) {
-    (void)hipFree(c->d_in);
-    (void)hipHostFree(c->h_in);
-    PHY_HIP_CHECK(hipMalloc(&c->d_in, n_in * sizeof(float2)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(host_image_alloc(&c->h_in, n_in * sizeof(cf_t)), SRSRAN_ERROR);
-    c->cap_in = n_in;
-  }
-  if (n_out > c->cap_out) {
-    (void)hipFree(c->d_out);
-    (void)hipHostFree(c->h_out);
-    PHY_HIP_CHECK(hipMalloc(&c->d_out, n_out * sizeof(float2)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(host_image_alloc(&c->h_out, n_out * sizeof(cf_t)), SRSRAN_ERROR);
-    c->cap_out = n_out;
-  }
+  PHY_HIP_CHECK(grown(c->in.grow(n_in)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(c->out.grow(n_out)), SRSRAN_ERROR);
   return SRSRAN_SUCCESS;
 }
 
@@ -176,7 +155,7 @@ DftCtx* ctx_new(int N)
     return nullptr;
   }
   auto* c = new DftCtx;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || ctx_set_size(c, N)) {
+  if (!c->stream.open() || ctx_set_size(c, N)) {
     delete c;
     return nullptr;
   }
@@ -185,21 +164,6 @@ DftCtx* ctx_new(int N)
 
 void ctx_free(DftCtx* c)
 {
-  if (!c) {
-    return;
-  }
-  (void)hipFree(c->d_tw);
-  (void)hipFree(c->d_tw1);
-  (void)hipFree(c->d_tw2);
-  (void)hipFree(c->d_tmp[0]);
-  (void)hipFree(c->d_tmp[1]);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_out);
-  (void)hipHostFree(c->h_in);
-  (void)hipHostFree(c->h_out);
-  if (c->stream) {
-    (void)hipStreamDestroy(c->stream);
-  }
   delete c;
 }
 
@@ -353,16 +317,16 @@ extern "C" void srsran_dft_run_r(srsran_dft_plan_t* plan, const float* in, float
     return;
   }
   const size_t bytes = (size_t)plan->size * sizeof(float);
-  memcpy(c->h_in, in, bytes);
+  memcpy(c->in.h, in, bytes);
   // (one transform per call: the kernel loads its input once and stores its output once, so it works on the pinned host images themselves --
   // no copy operation on either side, 6-9 us each whatever the size: tools/probe/roundtrip_probe.hip)
   dft::Params p;
-  fill_params(&p, c, c->h_in, c->h_out, !plan->forward, false, false, false, plan->db);
+  fill_params(&p, c, c->in.h, c->out.h, !plan->forward, false, false, false, plan->db);
   p.real_mode = plan->forward ? 1 : 2;
   p.norm      = plan->norm ? 1.0f / (float)plan->size : 0.0f; // dft_fftw.c:374-377: 1/N, not 1/sqrt(N)
   PHY_HIP_CHECK_VOID(dft::launch(p, c->stream));
   PHY_HIP_CHECK_VOID(hipStreamSynchronize(c->stream));
-  memcpy(out, c->h_out, bytes);
+  memcpy(out, c->out.h, bytes);
 }
 
 extern "C" int srsran_dft_replan_c(srsran_dft_plan_t* plan, const int new_dft_points)
@@ -470,28 +434,28 @@ static void run_contiguous(srsran_dft_plan_t* plan, const cf_t* in, cf_t* out, b
     return;
   }
   const size_t bytes = (size_t)plan->size * sizeof(cf_t);
-  memcpy(c->h_in, in, bytes);
+  memcpy(c->in.h, in, bytes);
   // copy_post leaves the last `dc` output samples untouched: seed the staging buffer with the caller's data
-  memcpy(c->h_out, out, bytes);
+  memcpy(c->out.h, out, bytes);
   if (c->N1) {
     // four-step path: several passes over the data, which therefore lives on the device
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_in, c->h_in, bytes, hipMemcpyHostToDevice, c->stream));
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_out, c->h_out, bytes, hipMemcpyHostToDevice, c->stream));
-    if (run_large(c, c->d_in, c->d_out, !plan->forward, options && plan->mirror, options && plan->dc, options && plan->norm,
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->in.d, c->in.h, bytes, hipMemcpyHostToDevice, c->stream));
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->out.d, c->out.h, bytes, hipMemcpyHostToDevice, c->stream));
+    if (run_large(c, c->in.d, c->out.d, !plan->forward, options && plan->mirror, options && plan->dc, options && plan->norm,
                   options && plan->db, c->stream)) {
       fprintf(stderr, "[srsran_phy_hip] srsran_dft_run: %s\n", get_error());
       return;
     }
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->h_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->out.h, c->out.d, bytes, hipMemcpyDeviceToHost, c->stream));
   } else {
     // one kernel, input loaded once, output stored once: on the pinned host images themselves (see srsran_dft_run_r)
     dft::Params p;
-    fill_params(&p, c, c->h_in, c->h_out, !plan->forward, options && plan->mirror, options && plan->dc, options && plan->norm,
+    fill_params(&p, c, c->in.h, c->out.h, !plan->forward, options && plan->mirror, options && plan->dc, options && plan->norm,
                 options && plan->db);
     PHY_HIP_CHECK_VOID(dft::launch(p, c->stream));
   }
   PHY_HIP_CHECK_VOID(hipStreamSynchronize(c->stream));
-  memcpy(out, c->h_out, bytes);
+  memcpy(out, c->out.h, bytes);
 }
 
 extern "C" void srsran_dft_run_c(srsran_dft_plan_t* plan, const cf_t* in, cf_t* out)
@@ -533,14 +497,14 @@ extern "C" void srsran_dft_run_guru_c(srsran_dft_plan_t* plan)
     if (ctx_reserve(c, plan->size, plan->size)) {
       return;
     }
-    memcpy(c->h_in, c->g_in, bytes);
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_in, c->h_in, bytes, hipMemcpyHostToDevice, c->stream));
-    if (run_large(c, c->d_in, c->d_out, !plan->forward, false, false, false, false, c->stream)) {
+    memcpy(c->in.h, c->g_in, bytes);
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->in.d, c->in.h, bytes, hipMemcpyHostToDevice, c->stream));
+    if (run_large(c, c->in.d, c->out.d, !plan->forward, false, false, false, false, c->stream)) {
       return;
     }
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->h_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->out.h, c->out.d, bytes, hipMemcpyDeviceToHost, c->stream));
     PHY_HIP_CHECK_VOID(hipStreamSynchronize(c->stream));
-    memcpy(c->g_out, c->h_out, bytes);
+    memcpy(c->g_out, c->out.h, bytes);
     return;
   }
   const int    N       = plan->size;
@@ -549,25 +513,25 @@ extern "C" void srsran_dft_run_guru_c(srsran_dft_plan_t* plan)
   if (ctx_reserve(c, span_in, span_out)) {
     return;
   }
-  memcpy(c->h_in, c->g_in, span_in * sizeof(cf_t));
-  PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_in, c->h_in, span_in * sizeof(cf_t), hipMemcpyHostToDevice, c->stream));
+  memcpy(c->in.h, c->g_in, span_in * sizeof(cf_t));
+  PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->in.d, c->in.h, span_in * sizeof(cf_t), hipMemcpyHostToDevice, c->stream));
   dft::Params p;
-  fill_params(&p, c, c->d_in, c->d_out, !plan->forward, false, false, false, false);
+  fill_params(&p, c, c->in.d, c->out.d, !plan->forward, false, false, false, false);
   p.idist    = c->idist;
   p.odist    = c->odist;
   p.istride  = c->istride;
   p.ostride  = c->ostride;
   p.how_many = c->how_many;
   PHY_HIP_CHECK_VOID(dft::launch(p, c->stream));
-  PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->h_out, c->d_out, span_out * sizeof(cf_t), hipMemcpyDeviceToHost, c->stream));
+  PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->out.h, c->out.d, span_out * sizeof(cf_t), hipMemcpyDeviceToHost, c->stream));
   PHY_HIP_CHECK_VOID(hipStreamSynchronize(c->stream));
   // write only the samples the transform produces (gaps between transforms belong to the caller)
   for (int b = 0; b < c->how_many; b++) {
     if (c->ostride == 1) {
-      memcpy(c->g_out + (size_t)b * c->odist, c->h_out + (size_t)b * c->odist, (size_t)N * sizeof(cf_t));
+      memcpy(c->g_out + (size_t)b * c->odist, c->out.h + (size_t)b * c->odist, (size_t)N * sizeof(cf_t));
     } else {
       for (int k = 0; k < N; k++) {
-        c->g_out[(size_t)b * c->odist + (size_t)k * c->ostride] = c->h_out[(size_t)b * c->odist + (size_t)k * c->ostride];
+        c->g_out[(size_t)b * c->odist + (size_t)k * c->ostride] = c->out.h[(size_t)b * c->odist + (size_t)k * c->ostride];
       }
     }
   }
@@ -717,12 +681,12 @@ extern "C" int srsran_dft_precoding(srsran_dft_precoding_t* q, cf_t* input, cf_t
     return SRSRAN_ERROR;
   }
   // all symbols in one launch (the reference loops srsran_dft_run_c per symbol, :122-124)
-  memcpy(c->h_in, input, n * sizeof(cf_t));
+  memcpy(c->in.h, input, n * sizeof(cf_t));
   dft::Params p; // (the kernel works on the pinned host images themselves, see srsran_dft_run_r)
-  fill_params(&p, c, c->h_in, c->h_out, !plan->forward, plan->mirror, plan->dc, plan->norm, plan->db);
+  fill_params(&p, c, c->in.h, c->out.h, !plan->forward, plan->mirror, plan->dc, plan->norm, plan->db);
   p.how_many = (int)nof_symbols;
   PHY_HIP_CHECK(dft::launch(p, c->stream), SRSRAN_ERROR);
   PHY_HIP_CHECK(hipStreamSynchronize(c->stream), SRSRAN_ERROR);
-  memcpy(output, c->h_out, n * sizeof(cf_t));
+  memcpy(output, c->out.h, n * sizeof(cf_t));
   return SRSRAN_SUCCESS;
 }

@@ -126,17 +126,16 @@ struct srsran_hip_ldpc_batch {
   bool     flood    = false;       // flooded schedule (ldpc_dec_c_flood.c), int8 only
   int      cpb      = 1;           // code words per workgroup (choose_cpb)
   int      slots    = 1;           // c2v slabs allocated = most workgroups a launch may use
-  int*     d_col_start = nullptr;
-  int*     d_col_edges = nullptr;
+  using Ints = StageBuf<StageMem::Device, int>;
+  Ints     d_col_start, d_col_edges;
   // x^((Z-1-c) bgK) mod g per generator used with this object (CRC early stop): one device table each, filled on first use and kept --
   // a batch that alternates CRC24A / CRC24B / CRC16 code words (sch_nr.c:606-619) never re-uploads or synchronises
-  std::map<uint64_t, uint32_t*> crc_mult;
-  void*    d_c2v    = nullptr;     // check-to-variable messages: slots x cpb slabs of E x Z messages
-  unsigned int* d_work = nullptr;  // packed kernel: the counter its workgroups take their code words from
+  std::map<uint64_t, StageBuf<StageMem::Device, uint32_t>> crc_mult;
+  DeviceBuf d_c2v;                 // check-to-variable messages: slots x cpb slabs of E x Z messages
+  StageBuf<StageMem::Device, unsigned int> d_work; // packed kernel: the counter its workgroups take their code words from
   uint32_t max_cw   = 0;
   std::vector<uint16_t> row_start;
-  int* d_row_start = nullptr;
-  int* d_edges     = nullptr;
+  Ints d_row_start, d_edges;
   // what the last ldpc_batch_run decided (srsran_hip_ldpc_batch_last_launch): packed kernel, messages in LDS, CRC early stop, code words
   // per workgroup, workgroups launched, code words
   int32_t last_launch[6] = {0, 0, 0, 0, 0, 0};
@@ -195,7 +194,7 @@ extern "C" int srsran_hip_ldpc_batch_create_typed(srsran_hip_ldpc_batch_t** hh, 
   if (!device_available()) {
     return SRSRAN_ERROR;
   }
-  auto* h     = new srsran_hip_ldpc_batch;
+  std::unique_ptr<srsran_hip_ldpc_batch> h(new srsran_hip_ldpc_batch);
   h->bg       = bg;
   h->Z        = ls;
   h->N        = d.N;
@@ -226,8 +225,8 @@ extern "C" int srsran_hip_ldpc_batch_create_typed(srsran_hip_ldpc_batch_t** hh, 
   for (int e = 0; e < d.E; e++) {
     ed[e] = (int)col[e] * (int)ls | ((int)shift[e] << 16);
   }
-  PHY_HIP_CHECK(hipMalloc(&h->d_row_start, (d.M + 1) * sizeof(int)), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipMalloc(&h->d_edges, d.E * sizeof(int)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->d_row_start.grow(d.M + 1)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->d_edges.grow(d.E)), SRSRAN_ERROR);
   PHY_HIP_CHECK(upload(h->d_row_start, rs.data(), (d.M + 1) * sizeof(int)), SRSRAN_ERROR);
   PHY_HIP_CHECK(upload(h->d_edges, ed.data(), d.E * sizeof(int)), SRSRAN_ERROR);
   if (flood) {
@@ -242,8 +241,8 @@ extern "C" int srsran_hip_ldpc_batch_create_typed(srsran_hip_ldpc_batch_t** hh, 
       }
     }
     cs[d.N] = (int)ce.size();
-    PHY_HIP_CHECK(hipMalloc(&h->d_col_start, cs.size() * sizeof(int)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipMalloc(&h->d_col_edges, ce.size() * sizeof(int)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_col_start.grow(cs.size())), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_col_edges.grow(ce.size())), SRSRAN_ERROR);
     PHY_HIP_CHECK(upload(h->d_col_start, cs.data(), cs.size() * sizeof(int)), SRSRAN_ERROR);
     PHY_HIP_CHECK(upload(h->d_col_edges, ce.data(), ce.size() * sizeof(int)), SRSRAN_ERROR);
   }
@@ -255,27 +254,15 @@ extern "C" int srsran_hip_ldpc_batch_create_typed(srsran_hip_ldpc_batch_t** hh, 
     slots = slots < 2048 ? slots : 2048; // resident workgroups (256 CUs x at most 5 ... 8) with room to spare; words are handed out by a counter
     h->cpb             = (int)cpb;
     h->slots           = (int)slots;
-    PHY_HIP_CHECK(hipMalloc(&h->d_c2v, slots * cpb * d.E * ls * es), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipMalloc(&h->d_work, sizeof(unsigned int)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_c2v.grow(slots * cpb * d.E * ls * es)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_work.grow(1)), SRSRAN_ERROR);
   }
-  *hh = h;
+  *hh = h.release();
   return SRSRAN_SUCCESS;
 }
 
 extern "C" void srsran_hip_ldpc_batch_free(srsran_hip_ldpc_batch_t* h)
 {
-  if (!h) {
-    return;
-  }
-  hipFree(h->d_row_start);
-  hipFree(h->d_edges);
-  hipFree(h->d_col_start);
-  hipFree(h->d_col_edges);
-  for (auto& kv : h->crc_mult) {
-    hipFree(kv.second);
-  }
-  hipFree(h->d_c2v);
-  hipFree(h->d_work);
   delete h;
 }
 
@@ -372,7 +359,7 @@ static int ldpc_batch_run(srsran_hip_ldpc_batch_t* h, const void* d_llrs, uint32
       set_error("ldpc batch: CRC early stop needs the int8 decoder, a generator of order 8..24 and an iteration array");
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
-    uint32_t*& d_mult = h->crc_mult[((uint64_t)crc_order << 32) | crc_poly];
+    auto& d_mult = h->crc_mult[((uint64_t)crc_order << 32) | crc_poly];
     if (!d_mult) {
       // x^n mod g by repeated multiplication with x; lane c needs n = (Z - 1 - c) * bgK
       const uint32_t mask = (1u << crc_order) - 1u, g = crc_poly & mask;
@@ -384,7 +371,7 @@ static int ldpc_batch_run(srsran_hip_ldpc_batch_t* h, const void* d_llrs, uint32
           r = ((r << 1) & mask) ^ (((r >> (crc_order - 1)) & 1u) ? g : 0u);
         }
       }
-      PHY_HIP_CHECK(hipMalloc(&d_mult, Z * sizeof(uint32_t)), SRSRAN_ERROR);
+      PHY_HIP_CHECK(grown(d_mult.grow(Z)), SRSRAN_ERROR);
       // once per (object, generator); upload() returns when the device has the table (hip_common.h)
       PHY_HIP_CHECK(upload(d_mult, m.data(), Z * sizeof(uint32_t)), SRSRAN_ERROR);
     }
@@ -487,15 +474,13 @@ namespace {
 struct LdpcCtx {
   DeviceTag tag;
   srsran_hip_ldpc_batch_t* b      = nullptr;
-  hipStream_t              stream = nullptr;
+  StageStream              stream;
   size_t                   esz    = 1;       // bytes per LLR (1 / 2 / 4)
   uint32_t                 n_iter = 0;       // iterations the device runs: max_nof_iter, twice that for the flooded schedule
-  int8_t*                  d_llr  = nullptr;
-  uint8_t*                 d_msg  = nullptr;
-  uint8_t*                 d_iter = nullptr;
-  int8_t*                  h_llr  = nullptr; // pinned
-  uint8_t*                 h_msg  = nullptr; // pinned
-  uint8_t*                 h_iter = nullptr; // pinned
+  StageBuf<StageMem::Device, int8_t> d_llr;
+  DeviceBuf                          d_msg, d_iter;
+  StageBuf<StageMem::Pinned, int8_t> h_llr;
+  StageBuf<StageMem::Pinned>         h_msg, h_iter;
   int                      dec_type = 0;     // srsran_ldpc_decoder_type_t given at init
   std::vector<uint8_t>     rec;              // one output record of the shared submission queue (message + iteration count)
 };
@@ -523,15 +508,6 @@ void ldpc_ctx_free(void* o)
   LdpcCtx* c = reinterpret_cast<LdpcCtx*>(q->ptr);
   if (c) {
     srsran_hip_ldpc_batch_free(c->b);
-    hipFree(c->d_llr);
-    hipFree(c->d_msg);
-    hipFree(c->d_iter);
-    hipHostFree(c->h_llr);
-    hipHostFree(c->h_msg);
-    hipHostFree(c->h_iter);
-    if (c->stream) {
-      hipStreamDestroy(c->stream);
-    }
     delete c;
   }
   if (q->pcm) {
@@ -644,8 +620,8 @@ int ldpc_decode_any(void* o, const void* llrs, uint8_t* message, uint32_t cdwd_r
   if (crc) {
     // CRC early stop on the device (ldpc_decoder.c:87-99): the kernel leaves the iteration loop at the first match and
     // reports the iteration count (0: no match within the budget, the reference's return value as well)
-    int* d_nit = reinterpret_cast<int*>(c->d_iter);
-    if (srsran_hip_ldpc_batch_run_crc(c->b, reinterpret_cast<const int8_t*>(c->d_llr), n_llr, c->d_msg, liftK, 1, cdwd_rm_length,
+    int* d_nit = reinterpret_cast<int*>(c->d_iter.get());
+    if (srsran_hip_ldpc_batch_run_crc(c->b, reinterpret_cast<const int8_t*>(c->d_llr.get()), n_llr, c->d_msg, liftK, 1, cdwd_rm_length,
                                       (uint32_t)crc->polynom, (uint32_t)crc->order, d_nit, c->stream)) {
       fprintf(stderr, "[srsran_phy_hip] srsran_ldpc_decoder: %s\n", get_error());
       return -1;
@@ -653,7 +629,7 @@ int ldpc_decode_any(void* o, const void* llrs, uint8_t* message, uint32_t cdwd_r
     PHY_HIP_CHECK(hipMemcpyAsync(c->h_msg, c->d_msg, liftK, hipMemcpyDeviceToHost, c->stream), -1);
     PHY_HIP_CHECK(hipMemcpyAsync(c->h_iter, d_nit, sizeof(int), hipMemcpyDeviceToHost, c->stream), -1);
     PHY_HIP_CHECK(hipStreamSynchronize(c->stream), -1);
-    const int nit = *reinterpret_cast<const int*>(c->h_iter);
+    const int nit = *reinterpret_cast<const int*>(c->h_iter.get());
     // the reference extracts the message at every iteration it checks: after a failed run `message` holds the last one
     memcpy(message, c->h_msg, liftK);
     return nit;
@@ -747,11 +723,8 @@ extern "C" int srsran_ldpc_decoder_init(srsran_ldpc_decoder_t* q, const srsran_l
   }
   const uint32_t n_llr = q->liftN - 2 * q->ls, msg_bytes = (q->liftK + 7) / 8;
   bool ok = srsran_hip_ldpc_batch_create_typed(&c->b, q->bg, q->ls, q->scaling_fctr, q->max_nof_iter, 1, args->type) == SRSRAN_SUCCESS &&
-            hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&c->d_llr, n_llr * esz) == hipSuccess && hipMalloc(&c->d_msg, q->liftK) == hipSuccess &&
-            hipMalloc(&c->d_iter, (size_t)msg_bytes * c->n_iter) == hipSuccess &&
-            hipHostMalloc(&c->h_llr, n_llr * esz) == hipSuccess && hipHostMalloc(&c->h_msg, q->liftK) == hipSuccess &&
-            hipHostMalloc(&c->h_iter, (size_t)msg_bytes * c->n_iter) == hipSuccess;
+            c->stream.open() && c->d_llr.grow(n_llr * esz) && c->d_msg.grow(q->liftK) && c->d_iter.grow((size_t)msg_bytes * c->n_iter) &&
+            c->h_llr.grow(n_llr * esz) && c->h_msg.grow(q->liftK) && c->h_iter.grow((size_t)msg_bytes * c->n_iter);
   if (!ok) {
     fprintf(stderr, "[srsran_phy_hip] srsran_ldpc_decoder_init: %s\n", get_error());
     srsran_ldpc_decoder_free(q);

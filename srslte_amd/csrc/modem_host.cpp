@@ -315,15 +315,10 @@ extern "C" uint32_t srsran_hip_sequence_pusch_seed(uint16_t rnti, uint32_t nslot
 
 // ---- batched, device resident --------------------------------------------------------------------------------------------------
 struct srsran_hip_demod {
-  DeviceTag tag;
-  modem::Job* d_jobs  = nullptr;
-  modem::Job* h_jobs  = nullptr; // pinned
-  size_t      cap     = 0;
-  uint32_t*   d_map   = nullptr; // job of every tile
-  uint32_t*   h_map   = nullptr; // pinned
-  size_t      map_cap = 0;
-  hipEvent_t  done    = nullptr; // the previous call's kernel has consumed d_jobs / h_jobs
-  bool        pending = false;
+  DeviceTag             tag;
+  StagePair<modem::Job> jobs;
+  StagePair<uint32_t>   map;  // job of every tile
+  StageEvent            done; // the previous call's kernel has consumed the jobs and the map
 };
 
 extern "C" int srsran_hip_demod_create(srsran_hip_demod_t** hh)
@@ -336,7 +331,7 @@ extern "C" int srsran_hip_demod_create(srsran_hip_demod_t** hh)
     return SRSRAN_ERROR;
   }
   srsran_hip_demod* h = new srsran_hip_demod;
-  if (hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
+  if (!h->done.ok()) {
     delete h;
     return SRSRAN_ERROR;
   }
@@ -349,14 +344,7 @@ extern "C" void srsran_hip_demod_free(srsran_hip_demod_t* h)
   if (!h) {
     return;
   }
-  if (h->pending) {
-    (void)hipEventSynchronize(h->done);
-  }
-  (void)hipFree(h->d_jobs);
-  (void)hipHostFree(h->h_jobs);
-  (void)hipFree(h->d_map);
-  (void)hipHostFree(h->h_map);
-  (void)hipEventDestroy(h->done);
+  (void)h->done.wait();
   delete h;
 }
 
@@ -382,21 +370,8 @@ extern "C" int srsran_hip_demod_run(srsran_hip_demod_t* h, const void* d_in, voi
     }
   }
   hipStream_t st = (hipStream_t)stream;
-  if (h->pending) {
-    PHY_HIP_CHECK(hipEventSynchronize(h->done), SRSRAN_ERROR);
-    h->pending = false;
-  }
-  if (n_jobs > h->cap) {
-    (void)hipFree(h->d_jobs);
-    (void)hipHostFree(h->h_jobs);
-    h->d_jobs = nullptr;
-    h->h_jobs = nullptr;
-    h->cap    = 0;
-    const size_t cap = (size_t)n_jobs + n_jobs / 2 + 16;
-    PHY_HIP_CHECK(hipMalloc(&h->d_jobs, cap * sizeof(modem::Job)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipHostMalloc(&h->h_jobs, cap * sizeof(modem::Job)), SRSRAN_ERROR);
-    h->cap = cap;
-  }
+  PHY_HIP_CHECK(h->done.wait(), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->jobs.grow(n_jobs, n_jobs / 2 + 16)), SRSRAN_ERROR);
   modem::Params p;
   if (!fill_params(p, llr_type)) {
     return SRSRAN_ERROR;
@@ -405,36 +380,25 @@ extern "C" int srsran_hip_demod_run(srsran_hip_demod_t* h, const void* d_in, voi
   for (uint32_t i = 0; i < n_jobs; i++) {
     const srsran_hip_demod_job_t& j = jobs[i];
     const uint32_t                nt = modem::tiles_of(j.mod, j.nof_symbols);
-    h->h_jobs[i] = modem::Job{j.mod, j.nof_symbols, j.symbol_offset, j.llr_offset, j.seed, j.descramble & 3u, tiles, nt};
+    h->jobs.h[i] = modem::Job{j.mod, j.nof_symbols, j.symbol_offset, j.llr_offset, j.seed, j.descramble & 3u, tiles, nt};
     tiles += nt;
   }
-  if (tiles > h->map_cap) {
-    (void)hipFree(h->d_map);
-    (void)hipHostFree(h->h_map);
-    h->d_map   = nullptr;
-    h->h_map   = nullptr;
-    h->map_cap = 0;
-    const size_t cap = (size_t)tiles + tiles / 2 + 256;
-    PHY_HIP_CHECK(hipMalloc(&h->d_map, cap * sizeof(uint32_t)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipHostMalloc(&h->h_map, cap * sizeof(uint32_t)), SRSRAN_ERROR);
-    h->map_cap = cap;
-  }
+  PHY_HIP_CHECK(grown(h->map.grow(tiles, tiles / 2 + 256)), SRSRAN_ERROR);
   for (uint32_t i = 0, t = 0; i < n_jobs; i++) {
-    for (uint32_t k = 0; k < h->h_jobs[i].ntiles; k++) {
-      h->h_map[t++] = i;
+    for (uint32_t k = 0; k < h->jobs.h[i].ntiles; k++) {
+      h->map.h[t++] = i;
     }
   }
-  PHY_HIP_CHECK(hipMemcpyAsync(h->d_map, h->h_map, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
-  p.tile_job = h->d_map;
+  PHY_HIP_CHECK(hipMemcpyAsync(h->map.d, h->map.h, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+  p.tile_job = h->map.d;
   p.in      = d_in;
   p.out     = d_llr;
-  p.jobs    = h->d_jobs;
+  p.jobs    = h->jobs.d;
   p.n_jobs  = n_jobs;
   p.n_tiles = tiles;
-  PHY_HIP_CHECK(hipMemcpyAsync(h->d_jobs, h->h_jobs, n_jobs * sizeof(modem::Job), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(hipMemcpyAsync(h->jobs.d, h->jobs.h, n_jobs * sizeof(modem::Job), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
   PHY_HIP_CHECK(modem::launch(p, st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipEventRecord(h->done, st), SRSRAN_ERROR);
-  h->pending = true;
+  PHY_HIP_CHECK(h->done.record(st), SRSRAN_ERROR);
   return SRSRAN_SUCCESS;
 }
 

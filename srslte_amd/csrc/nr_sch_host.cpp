@@ -1,6 +1,7 @@
 // nr_sch_host.cpp -- C ABI of NR LDPC rate matching and the LDPC encoder (include/srsran_amd/phy_nr_sch_abi.h).
 #include "hip_common.h"
 #include "nr_sch_device.h"
+#include "stage.h"
 #include "srsran_amd/phy_nr_sch_abi.h"
 #include "tables/nr_ldpc_bg_table.h"
 
@@ -58,8 +59,8 @@ bool rm_cfg(uint32_t E, int bg, uint32_t ls, uint32_t rv, int mod, uint32_t Nref
 // ---- device copy of one (base graph, lifting size) + the encoder's solving order ----------------------------------------------
 struct Graph {
   int              bgN = 0, bgM = 0, bgK = 0, Z = 0;
-  int*             d_row_start = nullptr;
-  int*             d_edges     = nullptr;
+  StageBuf<StageMem::Device, int> d_row_start;
+  StageBuf<StageMem::Device, int> d_edges;
   int              a           = 0;
   nrsch::EncStep   step[3];
 };
@@ -143,7 +144,7 @@ bool build_graph(int bg, int Z, Graph* g)
   if (n_steps != 3) {
     return false;
   }
-  if (hipMalloc(&g->d_row_start, rs.size() * sizeof(int)) != hipSuccess || hipMalloc(&g->d_edges, ed.size() * sizeof(int)) != hipSuccess ||
+  if (!g->d_row_start.grow(rs.size()) || !g->d_edges.grow(ed.size()) ||
       upload(g->d_row_start, rs.data(), rs.size() * sizeof(int)) != hipSuccess ||
       upload(g->d_edges, ed.data(), ed.size() * sizeof(int)) != hipSuccess) {
     set_error("nr_sch: cannot put the base graph on the device");
@@ -170,11 +171,8 @@ uint32_t enc_layers(const Graph& g, uint32_t cdwd_rm_length)
 struct srsran_hip_nr_sch {
   DeviceTag tag;
   std::map<uint32_t, Graph> graphs; // bg << 16 | Z
-  nrsch::CbJob*             d_jobs  = nullptr;
-  nrsch::CbJob*             h_jobs  = nullptr; // pinned
-  size_t                    cap     = 0;
-  hipEvent_t                done    = nullptr;
-  bool                      pending = false;
+  StagePair<nrsch::CbJob>   jobs;
+  StageEvent                done; // the previous call's kernel has consumed the jobs
 
   const Graph* graph(int bg, int Z)
   {
@@ -185,7 +183,7 @@ struct srsran_hip_nr_sch {
       if (!build_graph(bg, Z, &g)) {
         return nullptr;
       }
-      it = graphs.emplace(key, g).first;
+      it = graphs.emplace(key, std::move(g)).first;
     }
     return &it->second;
   }
@@ -193,31 +191,17 @@ struct srsran_hip_nr_sch {
   // job list -> device (the previous call's kernel must have consumed the buffer first)
   int stage(const srsran_hip_ldpc_cb_t* cbs, uint32_t n, const Graph* enc, hipStream_t st, const uint8_t* new_data = nullptr)
   {
-    if (pending) {
-      PHY_HIP_CHECK(hipEventSynchronize(done), SRSRAN_ERROR);
-      pending = false;
-    }
-    if (n > cap) {
-      (void)hipFree(d_jobs);
-      (void)hipHostFree(h_jobs);
-      d_jobs = nullptr;
-      h_jobs = nullptr;
-      cap    = 0;
-      const size_t c = (size_t)n + n / 2 + 16;
-      PHY_HIP_CHECK(hipMalloc(&d_jobs, c * sizeof(nrsch::CbJob)), SRSRAN_ERROR);
-      PHY_HIP_CHECK(hipHostMalloc(&h_jobs, c * sizeof(nrsch::CbJob)), SRSRAN_ERROR);
-      cap = c;
-    }
+    PHY_HIP_CHECK(done.wait(), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(jobs.grow(n, n / 2 + 16)), SRSRAN_ERROR);
     for (uint32_t i = 0; i < n; i++) {
-      h_jobs[i] = nrsch::CbJob{cbs[i].in_offset, cbs[i].out_offset, cbs[i].E, enc ? enc_layers(*enc, cbs[i].E) : ((new_data && new_data[i]) ? 1u : 0u)};
+      jobs.h[i] = nrsch::CbJob{cbs[i].in_offset, cbs[i].out_offset, cbs[i].E, enc ? enc_layers(*enc, cbs[i].E) : ((new_data && new_data[i]) ? 1u : 0u)};
     }
-    PHY_HIP_CHECK(hipMemcpyAsync(d_jobs, h_jobs, n * sizeof(nrsch::CbJob), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+    PHY_HIP_CHECK(hipMemcpyAsync(jobs.d, jobs.h, n * sizeof(nrsch::CbJob), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
     return SRSRAN_SUCCESS;
   }
   int finish(hipStream_t st)
   {
-    PHY_HIP_CHECK(hipEventRecord(done, st), SRSRAN_ERROR);
-    pending = true;
+    PHY_HIP_CHECK(done.record(st), SRSRAN_ERROR);
     return SRSRAN_SUCCESS;
   }
 };
@@ -232,7 +216,7 @@ extern "C" int srsran_hip_nr_sch_create(srsran_hip_nr_sch_t** hh)
     return SRSRAN_ERROR;
   }
   srsran_hip_nr_sch* h = new srsran_hip_nr_sch;
-  if (hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
+  if (!h->done.ok()) {
     delete h;
     return SRSRAN_ERROR;
   }
@@ -245,16 +229,7 @@ extern "C" void srsran_hip_nr_sch_free(srsran_hip_nr_sch_t* h)
   if (!h) {
     return;
   }
-  if (h->pending) {
-    (void)hipEventSynchronize(h->done);
-  }
-  for (auto& kv : h->graphs) {
-    (void)hipFree(kv.second.d_row_start);
-    (void)hipFree(kv.second.d_edges);
-  }
-  (void)hipFree(h->d_jobs);
-  (void)hipHostFree(h->h_jobs);
-  (void)hipEventDestroy(h->done);
+  (void)h->done.wait();
   delete h;
 }
 
@@ -303,7 +278,7 @@ static int rm_batch(srsran_hip_nr_sch_t* h, bool tx, int llr_type, const void* d
   nrsch::RmParams p{};
   p.in     = d_in;
   p.out    = d_out;
-  p.jobs   = h->d_jobs;
+  p.jobs   = h->jobs.d;
   p.n_cb   = n_cb;
   p.Ncb    = c.Ncb;
   p.k0     = c.k0;
@@ -361,7 +336,7 @@ extern "C" int srsran_hip_ldpc_encode_batch(srsran_hip_nr_sch_t* h, const uint8_
   nrsch::EncParams p{};
   p.in        = d_messages;
   p.out       = d_codewords;
-  p.jobs      = h->d_jobs;
+  p.jobs      = h->jobs.d;
   p.n_cb      = n_cb;
   p.row_start = g->d_row_start;
   p.edges     = g->d_edges;
@@ -383,16 +358,14 @@ namespace {
 struct HostCtx { // behind srsran_ldpc_rm_t.ptr / srsran_ldpc_encoder_t.ptr
   DeviceTag tag;
   srsran_hip_nr_sch_t* h     = nullptr;
-  hipStream_t          st    = nullptr;
-  void*                d_in  = nullptr;
-  void*                d_out = nullptr;
-  size_t               cap_in = 0, cap_out = 0;
+  StageStream          st;
+  DeviceBuf            d_in, d_out;
 };
 
 HostCtx* ctx_new()
 {
   HostCtx* c = new HostCtx;
-  if (srsran_hip_nr_sch_create(&c->h) != SRSRAN_SUCCESS || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
+  if (srsran_hip_nr_sch_create(&c->h) != SRSRAN_SUCCESS || !c->st.open()) {
     srsran_hip_nr_sch_free(c->h);
     delete c;
     return nullptr;
@@ -406,25 +379,7 @@ void ctx_free(HostCtx* c)
     return;
   }
   srsran_hip_nr_sch_free(c->h);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_out);
-  (void)hipStreamDestroy(c->st);
   delete c;
-}
-
-bool ctx_grow(void** p, size_t* cap, size_t need)
-{
-  if (need <= *cap) {
-    return true;
-  }
-  (void)hipFree(*p);
-  *p   = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, need + 256) != hipSuccess) {
-    return false;
-  }
-  *cap = need + 256;
-  return true;
 }
 
 int rm_init(srsran_ldpc_rm_t* q)
@@ -460,7 +415,7 @@ int rm_host(srsran_ldpc_rm_t* q, bool tx, int llr_type, size_t es, const void* i
   HostCtx*     x        = (HostCtx*)q->ptr;
   PHY_DEV_GUARD(x->tag, "srsran_ldpc_rm", -1);
   const size_t in_bytes = tx ? c.N : E * es, out_bytes = tx ? E : c.N * es;
-  if (!ctx_grow(&x->d_in, &x->cap_in, in_bytes) || !ctx_grow(&x->d_out, &x->cap_out, out_bytes)) {
+  if (!x->d_in.grow(in_bytes, 256) || !x->d_out.grow(out_bytes, 256)) {
     return -1;
   }
   srsran_hip_ldpc_cb_t cb = {0, 0, E};
@@ -553,7 +508,7 @@ static int enc_encode(void* o, const uint8_t* input, uint8_t* output, uint32_t i
   }
   const size_t in_bytes = (size_t)q->liftK;
   const size_t written  = (size_t)(enc_layers(*g, cdwd_rm_length) + q->bgK - 2) * q->ls; // everything beyond stays as it was
-  if (!ctx_grow(&x->d_in, &x->cap_in, in_bytes) || !ctx_grow(&x->d_out, &x->cap_out, (size_t)(q->liftN - 2 * q->ls))) {
+  if (!x->d_in.grow(in_bytes, 256) || !x->d_out.grow((size_t)(q->liftN - 2 * q->ls), 256)) {
     return -1;
   }
   srsran_hip_ldpc_cb_t cb = {0, 0, cdwd_rm_length};

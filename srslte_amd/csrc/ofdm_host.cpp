@@ -4,9 +4,11 @@
 // lib/src/phy/common/phy_common.c:322-385 / lib/include/srsran/phy/common/phy_common.h:110-140.
 #include "hip_common.h"
 #include "ofdm_device.h"
+#include "stage.h"
 
 #include <cmath>
 #include <complex>
+#include <memory>
 #include <vector>
 
 using namespace phyhip;
@@ -184,9 +186,7 @@ struct srsran_hip_ofdm_batch {
   Geometry g;
   int      region  = 2; // non-MBSFN region length of an MBSFN subframe (default of ofdm.c:198)
   bool     tx      = false;
-  float2*  d_tw    = nullptr;
-  float2*  d_shift = nullptr;
-  float2*  d_ramp  = nullptr;
+  StageBuf<StageMem::Device, float2> d_tw, d_shift, d_ramp;
 };
 
 static int batch_build(srsran_hip_ofdm_batch_t** hh, const Geometry& g, bool tx, const cf_t* shift_tab, const cf_t* ramp_tab)
@@ -211,22 +211,22 @@ static int batch_build(srsran_hip_ofdm_batch_t** hh, const Geometry& g, bool tx,
     set_error("OFDM: rx window offset of %d samples exceeds the cyclic prefix (%d)", g.win_n, g.cp1);
     return SRSRAN_ERROR;
   }
-  auto* h = new srsran_hip_ofdm_batch;
+  std::unique_ptr<srsran_hip_ofdm_batch> h(new srsran_hip_ofdm_batch);
   h->g    = g;
   h->tx   = tx;
   std::vector<std::complex<float>> tw;
   make_twiddles(g.N, tw);
-  PHY_HIP_CHECK(hipMalloc(&h->d_tw, g.N * sizeof(float2)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->d_tw.grow(g.N)), SRSRAN_ERROR);
   PHY_HIP_CHECK(upload(h->d_tw, tw.data(), g.N * sizeof(float2)), SRSRAN_ERROR);
   if (g.shift_on) {
-    PHY_HIP_CHECK(hipMalloc(&h->d_shift, g.sf_sz * sizeof(float2)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_shift.grow(g.sf_sz)), SRSRAN_ERROR);
     PHY_HIP_CHECK(upload(h->d_shift, shift_tab, g.sf_sz * sizeof(float2)), SRSRAN_ERROR);
   }
   if (!tx && g.win_n) {
-    PHY_HIP_CHECK(hipMalloc(&h->d_ramp, g.N * sizeof(float2)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_ramp.grow(g.N)), SRSRAN_ERROR);
     PHY_HIP_CHECK(upload(h->d_ramp, ramp_tab, g.N * sizeof(float2)), SRSRAN_ERROR);
   }
-  *hh = h;
+  *hh = h.release();
   return SRSRAN_SUCCESS;
 }
 
@@ -294,12 +294,6 @@ extern "C" int srsran_hip_ofdm_batch_create(srsran_hip_ofdm_batch_t** hh, const 
 
 extern "C" void srsran_hip_ofdm_batch_free(srsran_hip_ofdm_batch_t* h)
 {
-  if (!h) {
-    return;
-  }
-  (void)hipFree(h->d_tw);
-  (void)hipFree(h->d_shift);
-  (void)hipFree(h->d_ramp);
   delete h;
 }
 
@@ -384,12 +378,10 @@ namespace {
 struct OfdmCtx {
   DeviceTag                tag;
   srsran_hip_ofdm_batch_t* b      = nullptr;
-  hipStream_t              stream = nullptr;
-  float2*                  d_time = nullptr; // sf_sz
-  float2*                  d_re   = nullptr; // nof_re * nsym
-  cf_t*                    h_time = nullptr; // pinned
-  cf_t*                    h_re   = nullptr; // pinned
-  size_t                   cap_time = 0, cap_re = 0;
+  StageStream              stream;
+  using Pair = StagePair<float2, StageMem::HostImage, cf_t>; // a device array and its pinned image, exactly as large as the largest geometry so far
+  Pair                     time; // sf_sz
+  Pair                     re;   // nof_re * nsym
   srsran_dft_dir_t         dir = SRSRAN_DFT_FORWARD;
 };
 
@@ -410,13 +402,6 @@ void ctx_free(OfdmCtx* c)
     return;
   }
   srsran_hip_ofdm_batch_free(c->b);
-  (void)hipFree(c->d_time);
-  (void)hipFree(c->d_re);
-  (void)hipHostFree(c->h_time);
-  (void)hipHostFree(c->h_re);
-  if (c->stream) {
-    (void)hipStreamDestroy(c->stream);
-  }
   delete c;
 }
 
@@ -470,7 +455,7 @@ int ofdm_init_(srsran_ofdm_t* q, srsran_ofdm_cfg_t* cfg, srsran_dft_dir_t dir)
     }
     c      = new OfdmCtx;
     c->dir = dir;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (!c->stream.open()) {
       delete c;
       return SRSRAN_ERROR;
     }
@@ -567,20 +552,8 @@ int ctx_sync(srsran_ofdm_t* q)
   }
   c->b->region = q->non_mbsfn_region;
   const size_t nt = (size_t)g.sf_sz, nr = (size_t)g.nof_re * 2 * g.nsym_slot;
-  if (nt > c->cap_time) {
-    (void)hipFree(c->d_time);
-    (void)hipHostFree(c->h_time);
-    PHY_HIP_CHECK(hipMalloc(&c->d_time, nt * sizeof(float2)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(host_image_alloc(&c->h_time, nt * sizeof(cf_t)), SRSRAN_ERROR);
-    c->cap_time = nt;
-  }
-  if (nr > c->cap_re) {
-    (void)hipFree(c->d_re);
-    (void)hipHostFree(c->h_re);
-    PHY_HIP_CHECK(hipMalloc(&c->d_re, nr * sizeof(float2)), SRSRAN_ERROR);
-    PHY_HIP_CHECK(host_image_alloc(&c->h_re, nr * sizeof(cf_t)), SRSRAN_ERROR);
-    c->cap_re = nr;
-  }
+  PHY_HIP_CHECK(grown(c->time.grow(nt)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(c->re.grow(nr)), SRSRAN_ERROR);
   return SRSRAN_SUCCESS;
 }
 
@@ -600,27 +573,27 @@ void rx_run(srsran_ofdm_t* q, cf_t* input, cf_t* output, bool with_ramp)
   OfdmCtx*       c  = ctx_of(q);
   const size_t   nt = q->sf_sz, nr = (size_t)q->nof_re * 2 * q->nof_symbols;
   const bool     sh = std::isnormal(q->cfg.freq_shift_f);
-  memcpy(c->h_time, input, nt * sizeof(cf_t));
+  memcpy(c->time.h, input, nt * sizeof(cf_t));
   // One subframe per call: the demodulator reads every sample once and writes every resource element once, so it works on the PINNED HOST
   // images themselves (mapped into the device's address space) -- no copy operation on either side of the kernel: a copy operation costs
   // 6-9 us whatever its size, the 380 KB of a 20 MHz subframe cross the bus in about as much (tools/probe/roundtrip_probe.hip).
-  float2* t_in = reinterpret_cast<float2*>(c->h_time);
+  float2* t_in = reinterpret_cast<float2*>(c->time.h.get());
   if (sh) {
     // ofdm.c:455-457 multiplies the caller's input buffer in place; reproduce the side effect (product kept on the device for the transform)
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->d_time, c->h_time, nt * sizeof(cf_t), hipMemcpyHostToDevice, c->stream));
-    PHY_HIP_CHECK_VOID(ofdm::launch_prod_ccc(c->d_time, c->b->d_shift, c->d_time, (int)nt, c->stream));
-    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->h_time, c->d_time, nt * sizeof(cf_t), hipMemcpyDeviceToHost, c->stream));
-    t_in = c->d_time;
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->time.d, c->time.h, nt * sizeof(cf_t), hipMemcpyHostToDevice, c->stream));
+    PHY_HIP_CHECK_VOID(ofdm::launch_prod_ccc(c->time.d, c->b->d_shift, c->time.d, (int)nt, c->stream));
+    PHY_HIP_CHECK_VOID(hipMemcpyAsync(c->time.h, c->time.d, nt * sizeof(cf_t), hipMemcpyDeviceToHost, c->stream));
+    t_in = c->time.d;
   }
-  if (batch_run(c->b, t_in, reinterpret_cast<float2*>(c->h_re), 1, false, false, c->stream, with_ramp)) {
+  if (batch_run(c->b, t_in, reinterpret_cast<float2*>(c->re.h.get()), 1, false, false, c->stream, with_ramp)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_ofdm_rx_sf: %s\n", get_error());
     return;
   }
   PHY_HIP_CHECK_VOID(hipStreamSynchronize(c->stream));
   if (sh) {
-    memcpy(input, c->h_time, nt * sizeof(cf_t));
+    memcpy(input, c->time.h, nt * sizeof(cf_t));
   }
-  memcpy(output, c->h_re, nr * sizeof(cf_t));
+  memcpy(output, c->re.h, nr * sizeof(cf_t));
 }
 
 } // namespace
@@ -773,9 +746,9 @@ extern "C" void srsran_ofdm_tx_sf(srsran_ofdm_t* q)
   }
   OfdmCtx*     c  = ctx_of(q);
   const size_t nt = q->sf_sz, nr = (size_t)q->nof_re * 2 * q->nof_symbols;
-  memcpy(c->h_re, q->cfg.in_buffer, nr * sizeof(cf_t));
+  memcpy(c->re.h, q->cfg.in_buffer, nr * sizeof(cf_t));
   // (as rx_run: the modulator reads and writes the pinned host images directly)
-  if (batch_run(c->b, reinterpret_cast<float2*>(c->h_re), reinterpret_cast<float2*>(c->h_time), 1, true, true, c->stream)) {
+  if (batch_run(c->b, reinterpret_cast<float2*>(c->re.h.get()), reinterpret_cast<float2*>(c->time.h.get()), 1, true, true, c->stream)) {
     fprintf(stderr, "[srsran_phy_hip] srsran_ofdm_tx_sf: %s\n", get_error());
     return;
   }
@@ -784,9 +757,9 @@ extern "C" void srsran_ofdm_tx_sf(srsran_ofdm_t* q)
     // the samples between the non-MBSFN and the MBSFN region are not written (ofdm.c:551-553)
     int pos[6], cp[6], gs = 0, gl = 0;
     mbsfn_layout((int)q->cfg.symbol_sz, (int)q->sf_sz, q->non_mbsfn_region, true, pos, cp, &gs, &gl);
-    memcpy(q->cfg.out_buffer, c->h_time, (size_t)gs * sizeof(cf_t));
-    memcpy(q->cfg.out_buffer + gs + gl, c->h_time + gs + gl, (nt - gs - gl) * sizeof(cf_t));
+    memcpy(q->cfg.out_buffer, c->time.h, (size_t)gs * sizeof(cf_t));
+    memcpy(q->cfg.out_buffer + gs + gl, c->time.h + gs + gl, (nt - gs - gl) * sizeof(cf_t));
   } else {
-    memcpy(q->cfg.out_buffer, c->h_time, nt * sizeof(cf_t));
+    memcpy(q->cfg.out_buffer, c->time.h, nt * sizeof(cf_t));
   }
 }

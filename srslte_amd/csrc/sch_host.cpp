@@ -68,14 +68,10 @@ struct srsran_hip_sch {
   // one turbo batch object per (K, arithmetic is 16 bit), grown on demand
   std::map<uint32_t, std::pair<srsran_hip_tdec_batch_t*, uint32_t>> dec; // K | 8-bit flag << 31 -> (object, capacity)
   turbo::WsArena arena;       // the one workspace all its decoders run in (turbo_device.h)
-  void*  d_scratch = nullptr; // job / descriptor / result arrays
-  void*  h_scratch = nullptr; // ... and their pinned host image: descriptors go up and verdicts come down with one asynchronous copy each
-  size_t scratch_cap = 0;
+  // job / descriptor / result arrays and their pinned host image: descriptors go up and verdicts come down with one asynchronous copy each
+  StagePair<uint8_t, StageMem::HostImage> scratch;
   // transport-block CRC: one row of 256 lane multipliers per block size seen so far (rm::tb_crc_multipliers), resident on the device
-  std::map<uint32_t, uint32_t> crc_row; // tbs -> row
-  uint32_t*                    d_crc_mult = nullptr;
-  uint32_t*                    h_crc_mult = nullptr; // pinned mirror: a new row goes up asynchronously on the call's stream, in front of the CRC kernel
-  uint32_t                     crc_rows_cap = 0;
+  RowTable crc_mult{256, 16, "sch decode"};
 };
 
 extern "C" int srsran_hip_sch_create(srsran_hip_sch_t** hh)
@@ -99,10 +95,6 @@ extern "C" void srsran_hip_sch_free(srsran_hip_sch_t* h)
   for (auto& kv : h->dec) {
     srsran_hip_tdec_batch_free(kv.second.first);
   }
-  (void)hipFree(h->d_scratch);
-  (void)hipHostFree(h->h_scratch);
-  (void)hipFree(h->d_crc_mult);
-  (void)hipHostFree(h->h_crc_mult);
   delete h;
 }
 
@@ -256,21 +248,13 @@ static int sch_decode(srsran_hip_sch_t* h, const void* d_e_bits, const srsran_hi
   const size_t o_jobs = 0, o_desc = al(o_jobs + n * sizeof(rm::RxJob)), o_tbj = al(o_desc + n * sizeof(turbo::CbDesc));
   const size_t o_noi = al(o_tbj + n_tb * sizeof(rm::TbCrcJob)), o_ok = al(o_noi + n * sizeof(int)), o_tbr = al(o_ok + n);
   const size_t bytes = al(o_tbr + n_tb * sizeof(rm::TbCrcResult));
-  if (bytes > h->scratch_cap) {
-    (void)hipFree(h->d_scratch);
-    (void)hipHostFree(h->h_scratch);
-    h->d_scratch = h->h_scratch = nullptr;
-    h->scratch_cap               = 0;
-    PHY_HIP_CHECK(hipMalloc(&h->d_scratch, bytes), SRSRAN_ERROR);
-    PHY_HIP_CHECK(host_image_alloc(&h->h_scratch, bytes), SRSRAN_ERROR);
-    h->scratch_cap = bytes;
-  }
-  uint8_t* hb   = static_cast<uint8_t*>(h->h_scratch);
+  PHY_HIP_CHECK(grown(h->scratch.grow(bytes)), SRSRAN_ERROR);
+  uint8_t* hb   = h->scratch.h;
   // A subframe's worth of code blocks or less: the kernels read the jobs / descriptors from, and write the verdicts into, the PINNED HOST image
   // themselves (it is mapped into the device's address space) -- four stream operations fewer per call (upload, clearing, two downloads;
   // 6-9 us each whatever the size, tools/probe/roundtrip_probe.hip), and what crosses the bus is a few hundred bytes.  Large batches keep the copies.
   const bool direct = n + n_tb <= 1024;
-  uint8_t*   base   = direct ? hb : static_cast<uint8_t*>(h->d_scratch);
+  uint8_t*   base   = direct ? hb : h->scratch.d.get();
   auto*    d_jobs = reinterpret_cast<rm::RxJob*>(base + o_jobs);
   auto*    d_desc = reinterpret_cast<turbo::CbDesc*>(base + o_desc);
   auto*    d_tbj  = reinterpret_cast<rm::TbCrcJob*>(base + o_tbj);
@@ -285,43 +269,7 @@ static int sch_decode(srsran_hip_sch_t* h, const void* d_e_bits, const srsran_hi
   const rm::TbCrcResult* tbr = reinterpret_cast<const rm::TbCrcResult*>(hb + o_tbr);
 
   // row of the CRC multiplier table for a block size: computed and uploaded the first time the size is seen by this object
-  auto crc_row_of = [&](uint32_t tbs_bits) -> uint32_t {
-    auto it = h->crc_row.find(tbs_bits);
-    if (it != h->crc_row.end()) {
-      return it->second;
-    }
-    const uint32_t row = (uint32_t)h->crc_row.size();
-    if (row >= h->crc_rows_cap) {
-      const uint32_t cap = h->crc_rows_cap ? 2 * h->crc_rows_cap : 16;
-      uint32_t *     nd = nullptr, *nh = nullptr;
-      if (hipMalloc(&nd, (size_t)cap * 256 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&nh, (size_t)cap * 256 * sizeof(uint32_t)) != hipSuccess ||
-          hipDeviceSynchronize() != hipSuccess || // nothing may still read the old table / copy from the old mirror when they are freed below
-          (h->d_crc_mult && (hipMemcpy(nd, h->d_crc_mult, (size_t)row * 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-                             hipDeviceSynchronize() != hipSuccess))) {
-        (void)hipFree(nd);
-        (void)hipHostFree(nh);
-        set_error("sch decode: device allocation of the CRC multiplier table failed");
-        return 0xffffffffu;
-      }
-      if (h->h_crc_mult) {
-        memcpy(nh, h->h_crc_mult, (size_t)row * 256 * sizeof(uint32_t));
-      }
-      (void)hipFree(h->d_crc_mult);
-      (void)hipHostFree(h->h_crc_mult);
-      h->d_crc_mult   = nd;
-      h->h_crc_mult   = nh;
-      h->crc_rows_cap = cap;
-    }
-    uint32_t* m = h->h_crc_mult + (size_t)row * 256;
-    rm::tb_crc_multipliers(tbs_bits, CRC24A, m);
-    // (stream order puts the row in front of the CRC kernel of this call; the pinned source stays where it is)
-    if (hipMemcpyAsync(h->d_crc_mult + (size_t)row * 256, m, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
-      set_error("sch decode: upload of the CRC multiplier table failed");
-      return 0xffffffffu;
-    }
-    h->crc_row[tbs_bits] = row;
-    return row;
-  };
+  auto crc_row_of = [&](uint32_t tbs_bits) { return h->crc_mult.row(tbs_bits, st, [&](uint32_t* m) { rm::tb_crc_multipliers(tbs_bits, CRC24A, m); }); };
   // pass 2: jobs and descriptors in launch order; per transport block the CRC job with the two runs of verdicts that are its code blocks
   size_t n_crc = 0;
   for (uint32_t t = 0; t < n_tb; t++) {
@@ -398,7 +346,7 @@ static int sch_decode(srsran_hip_sch_t* h, const void* d_e_bits, const srsran_hi
   }
   // transport-block CRC (sch.c:473-477,540-560) of the blocks whose code blocks are all good, straight behind the decoders
   if (n_crc) {
-    PHY_HIP_CHECK(rm::launch_tb_crc(d_data, d_tbj, (int)n_crc, CRC24A, d_ok, h->d_crc_mult, d_tbr, st, host_data), SRSRAN_ERROR);
+    PHY_HIP_CHECK(rm::launch_tb_crc(d_data, d_tbj, (int)n_crc, CRC24A, d_ok, h->crc_mult.device(), d_tbr, st, host_data), SRSRAN_ERROR);
   }
   if (!direct && (n || n_crc)) {
     PHY_HIP_CHECK(hipMemcpyAsync(hb + o_noi, base + o_noi, o_tbr + n_crc * sizeof(rm::TbCrcResult) - o_noi, hipMemcpyDeviceToHost, st), SRSRAN_ERROR);

@@ -131,23 +131,6 @@ struct Job {
   uint32_t Z, rv, mod, Nref, F, poly, order;
 };
 
-template <class T>
-bool ensure(T** d, T** h, size_t* cap, size_t n)
-{
-  if (n <= *cap) {
-    return true;
-  }
-  (void)hipFree(*d);
-  (void)hipHostFree(*h);
-  *d = nullptr, *h = nullptr, *cap = 0;
-  const size_t c = n + n / 2 + 16;
-  if (hipMalloc(d, c * sizeof(T)) != hipSuccess || host_image_alloc(h, c * sizeof(T)) != hipSuccess) {
-    return false;
-  }
-  *cap = c;
-  return true;
-}
-
 } // namespace
 
 // cbsegm.h:59-67 / cbsegm.c:277-285: NR segmentation for the two base graphs (srsran_sch_nr_fill_tb_info and the reference's own NR
@@ -167,31 +150,22 @@ struct srsran_hip_sch_nr {
   uint32_t max_iter = 10, max_cb = 0;
   srsran_hip_nr_sch_t*                         rm = nullptr;
   std::map<uint32_t, srsran_hip_ldpc_batch_t*> dec; // bg << 16 | Z
-  uint8_t*  d_msg   = nullptr; // max_cb x MSG_STRIDE, one bit per byte
-  uint8_t*  d_flags = nullptr; // max_cb
-  uint8_t*  h_flags = nullptr; // pinned
-  int *     d_iter = nullptr, *h_iter = nullptr;
-  size_t    iter_cap = 0;
-  uint32_t *d_map = nullptr, *h_map = nullptr;
-  size_t    map_cap = 0;
-  nrsch::CbFin *d_cbf = nullptr, *h_cbf = nullptr;
-  size_t        cbf_cap = 0;
-  nrsch::TbFin *d_tbf = nullptr, *h_tbf = nullptr;
-  size_t        tbf_cap = 0;
-  nrsch::TbFinRes *d_res = nullptr, *h_res = nullptr;
-  size_t           res_cap = 0;
-  // transport-block CRC: one row of 256 lane multipliers per (chunk size, CRC order) seen so far (nrsch::tb_finish_multipliers)
-  std::map<uint32_t, uint32_t> crc_row; // chunk | order << 24 -> row
-  uint32_t*                    d_crc_mult = nullptr;
-  uint32_t                     crc_rows_cap = 0;
+  template <class T>
+  using Pair = StagePair<T, StageMem::HostImage>;
+  DeviceBuf     d_msg; // max_cb x MSG_STRIDE, one bit per byte
+  Pair<uint8_t> flags; // max_cb
+  Pair<int>             iter;
+  Pair<uint32_t>        map;
+  Pair<nrsch::CbFin>    cbf;
+  Pair<nrsch::TbFin>    tbf;
+  Pair<nrsch::TbFinRes> res;
+  // transport-block CRC: one row of 256 lane multipliers per (chunk size, CRC order) seen so far (nrsch::tb_finish_multipliers); key: chunk | order << 24
+  RowTable crc_mult{256, 16, "sch_nr decode", false};
   // transmit side
-  uint8_t*      d_cw = nullptr; // max_cb x CW_STRIDE code words (one bit per byte, filler marks kept)
-  nrsch::TbEnc *d_tbe = nullptr, *h_tbe = nullptr;
-  size_t        tbe_cap = 0;
-  nrsch::CbEnc *d_cbe = nullptr, *h_cbe = nullptr;
-  size_t        cbe_cap = 0;
-  uint32_t*     d_tbcrc = nullptr;
-  size_t        tbcrc_cap = 0;
+  DeviceBuf          d_cw; // max_cb x CW_STRIDE code words (one bit per byte, filler marks kept)
+  Pair<nrsch::TbEnc> tbe;
+  Pair<nrsch::CbEnc> cbe;
+  StageBuf<StageMem::Device, uint32_t> d_tbcrc;
 };
 static const uint32_t MSG_STRIDE = 8448;
 static const uint32_t CW_STRIDE  = 66 * 384;
@@ -209,8 +183,7 @@ extern "C" int srsran_hip_sch_nr_create(srsran_hip_sch_nr_t** hh, float scaling_
   h->scaling  = std::isnormal(scaling_fctr) ? scaling_fctr : 0.8f; // sch_nr.c:275
   h->max_iter = max_nof_iter ? max_nof_iter : 10;                  // ldpc_decoder.c:42,579
   h->max_cb   = max_cb;
-  if (srsran_hip_nr_sch_create(&h->rm) != SRSRAN_SUCCESS || hipMalloc(&h->d_msg, (size_t)max_cb * MSG_STRIDE) != hipSuccess ||
-      hipMalloc(&h->d_flags, max_cb) != hipSuccess || host_image_alloc(&h->h_flags, max_cb) != hipSuccess) {
+  if (srsran_hip_nr_sch_create(&h->rm) != SRSRAN_SUCCESS || !h->d_msg.grow((size_t)max_cb * MSG_STRIDE) || !h->flags.grow(max_cb)) {
     srsran_hip_sch_nr_free(h);
     return SRSRAN_ERROR;
   }
@@ -227,53 +200,14 @@ extern "C" void srsran_hip_sch_nr_free(srsran_hip_sch_nr_t* h)
   for (auto& kv : h->dec) {
     srsran_hip_ldpc_batch_free(kv.second);
   }
-  (void)hipFree(h->d_msg);
-  (void)hipFree(h->d_flags);
-  (void)hipHostFree(h->h_flags);
-  (void)hipFree(h->d_iter), (void)hipHostFree(h->h_iter);
-  (void)hipFree(h->d_map), (void)hipHostFree(h->h_map);
-  (void)hipFree(h->d_cbf), (void)hipHostFree(h->h_cbf);
-  (void)hipFree(h->d_tbf), (void)hipHostFree(h->h_tbf);
-  (void)hipFree(h->d_res), (void)hipHostFree(h->h_res);
-  (void)hipFree(h->d_crc_mult);
-  (void)hipFree(h->d_cw);
-  (void)hipFree(h->d_tbe), (void)hipHostFree(h->h_tbe);
-  (void)hipFree(h->d_cbe), (void)hipHostFree(h->h_cbe);
-  (void)hipFree(h->d_tbcrc);
   delete h;
 }
 
 // row of the CRC multiplier table for a transport block: computed and uploaded the first time its (chunk size, CRC order) is seen
 static uint32_t crc_row_of(srsran_hip_sch_nr_t* h, uint32_t tbs_bits, uint32_t order)
 {
-  const uint32_t chunk = nrsch::tb_finish_chunk(tbs_bits), key = chunk | (order << 24);
-  auto           it    = h->crc_row.find(key);
-  if (it != h->crc_row.end()) {
-    return it->second;
-  }
-  const uint32_t row = (uint32_t)h->crc_row.size();
-  if (row >= h->crc_rows_cap) {
-    const uint32_t cap = h->crc_rows_cap ? 2 * h->crc_rows_cap : 16;
-    uint32_t*      nd  = nullptr;
-    if (hipMalloc(&nd, (size_t)cap * 256 * sizeof(uint32_t)) != hipSuccess ||
-        (h->d_crc_mult && (hipMemcpy(nd, h->d_crc_mult, (size_t)row * 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-                             hipDeviceSynchronize() != hipSuccess))) { // nothing may still read the old table when it is freed below
-      (void)hipFree(nd);
-      set_error("sch_nr decode: device allocation of the CRC multiplier table failed");
-      return 0xffffffffu;
-    }
-    (void)hipFree(h->d_crc_mult);
-    h->d_crc_mult   = nd;
-    h->crc_rows_cap = cap;
-  }
-  uint32_t m[256];
-  nrsch::tb_finish_multipliers(chunk, order, m);
-  if (upload(h->d_crc_mult + (size_t)row * 256, m, sizeof(m)) != hipSuccess) {
-    set_error("sch_nr decode: upload of the CRC multiplier table failed");
-    return 0xffffffffu;
-  }
-  h->crc_row[key] = row;
-  return row;
+  const uint32_t chunk = nrsch::tb_finish_chunk(tbs_bits);
+  return h->crc_mult.row(chunk | (order << 24), nullptr, [&](uint32_t* m) { nrsch::tb_finish_multipliers(chunk, order, m); });
 }
 
 int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, const srsran_hip_nr_tb_t* tbs, uint32_t n_tb, int8_t* d_softbuffer,
@@ -342,15 +276,15 @@ int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, 
     cb_hi = std::max(cb_hi, tbs[t].first_cb + cfg[t].C);
   }
   for (uint32_t i = cb_lo; i < cb_hi; i++) {
-    h->h_flags[i] = cb_crc[i] ? 1 : 0;
+    h->flags.h[i] = cb_crc[i] ? 1 : 0;
   }
   // A slot's worth of code blocks or less: the kernels read the job lists from, and write flags / iteration counts / results into, the PINNED HOST
   // images themselves (mapped into the device's address space): seven stream operations fewer per call, 6-9 us each whatever the size
   // (tools/probe/roundtrip_probe.hip).  Large batches keep the copies.
   const bool direct = n_jobs + n_tb <= 1024;
-  uint8_t*   x_flags = direct ? h->h_flags : h->d_flags;
+  uint8_t*   x_flags = direct ? h->flags.h.get() : h->flags.d.get();
   if (!direct) {
-    PHY_HIP_CHECK(hipMemcpyAsync(h->d_flags + cb_lo, h->h_flags + cb_lo, cb_hi - cb_lo, hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+    PHY_HIP_CHECK(hipMemcpyAsync(h->flags.d + cb_lo, h->flags.h + cb_lo, cb_hi - cb_lo, hipMemcpyHostToDevice, st), SRSRAN_ERROR);
   }
 
   if (n_jobs) {
@@ -393,21 +327,20 @@ int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, 
     if (!std::is_sorted(order.begin(), order.end(), by_dec)) {
       std::stable_sort(order.begin(), order.end(), by_dec);
     }
-    if (!ensure(&h->d_iter, &h->h_iter, &h->iter_cap, n_jobs) || !ensure(&h->d_map, &h->h_map, &h->map_cap, n_jobs) ||
-        !ensure(&h->d_cbf, &h->h_cbf, &h->cbf_cap, n_jobs)) {
+    if (!h->iter.grow(n_jobs, n_jobs / 2 + 16) || !h->map.grow(n_jobs, n_jobs / 2 + 16) || !h->cbf.grow(n_jobs, n_jobs / 2 + 16)) {
       return SRSRAN_ERROR;
     }
     for (uint32_t i = 0; i < n_jobs; i++) {
       const Job& j = jobs[order[i]];
-      h->h_map[i]  = j.cb;
-      h->h_cbf[i]  = nrsch::CbFin{j.cb, j.cb, j.cb_len};
+      h->map.h[i]  = j.cb;
+      h->cbf.h[i]  = nrsch::CbFin{j.cb, j.cb, j.cb_len};
     }
-    uint32_t*     x_map  = direct ? h->h_map : h->d_map;
-    nrsch::CbFin* x_cbf  = direct ? h->h_cbf : h->d_cbf;
-    int*          x_iter = direct ? h->h_iter : h->d_iter;
+    uint32_t*     x_map  = direct ? h->map.h.get() : h->map.d.get();
+    nrsch::CbFin* x_cbf  = direct ? h->cbf.h.get() : h->cbf.d.get();
+    int*          x_iter = direct ? h->iter.h.get() : h->iter.d.get();
     if (!direct) {
-      PHY_HIP_CHECK(hipMemcpyAsync(h->d_map, h->h_map, n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
-      PHY_HIP_CHECK(hipMemcpyAsync(h->d_cbf, h->h_cbf, n_jobs * sizeof(nrsch::CbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->map.d, h->map.h, n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->cbf.d, h->cbf.h, n_jobs * sizeof(nrsch::CbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
     }
     for (uint32_t i = 0; i < n_jobs;) {
       uint32_t e = i;
@@ -432,27 +365,27 @@ int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, 
     }
     PHY_HIP_CHECK(nrsch::launch_cb_finish(h->d_msg, MSG_STRIDE, x_cbf, x_iter, n_jobs, x_flags, d_cb_data, data_stride, st), SRSRAN_ERROR);
     if (!direct) {
-      PHY_HIP_CHECK(hipMemcpyAsync(h->h_iter, h->d_iter, n_jobs * sizeof(int), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->iter.h, h->iter.d, n_jobs * sizeof(int), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
     }
     // ---- back to transport blocks
-    if (!ensure(&h->d_tbf, &h->h_tbf, &h->tbf_cap, n_tb) || !ensure(&h->d_res, &h->h_res, &h->res_cap, n_tb)) {
+    if (!h->tbf.grow(n_tb, n_tb / 2 + 16) || !h->res.grow(n_tb, n_tb / 2 + 16)) {
       return SRSRAN_ERROR;
     }
     for (uint32_t t = 0; t < n_tb; t++) {
-      h->h_tbf[t] = nrsch::TbFin{tbs[t].first_cb, cfg[t].C, cfg[t].Kp, cfg[t].L_cb, cfg[t].L_tb, cfg[t].A, tbs[t].payload_offset,
+      h->tbf.h[t] = nrsch::TbFin{tbs[t].first_cb, cfg[t].C, cfg[t].Kp, cfg[t].L_cb, cfg[t].L_tb, cfg[t].A, tbs[t].payload_offset,
                                  crc_row_of(h, cfg[t].A, cfg[t].L_tb)};
-      if (h->h_tbf[t].mult == 0xffffffffu) {
+      if (h->tbf.h[t].mult == 0xffffffffu) {
         return SRSRAN_ERROR;
       }
     }
     if (!direct) {
-      PHY_HIP_CHECK(hipMemcpyAsync(h->d_tbf, h->h_tbf, n_tb * sizeof(nrsch::TbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->tbf.d, h->tbf.h, n_tb * sizeof(nrsch::TbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
     }
-    PHY_HIP_CHECK(nrsch::launch_tb_finish(d_cb_data, data_stride, x_flags, direct ? h->h_tbf : h->d_tbf, n_tb, d_payload, h->d_crc_mult,
-                                          direct ? h->h_res : h->d_res, st), SRSRAN_ERROR);
+    PHY_HIP_CHECK(nrsch::launch_tb_finish(d_cb_data, data_stride, x_flags, direct ? h->tbf.h.get() : h->tbf.d.get(), n_tb, d_payload, h->crc_mult.device(),
+                                          direct ? h->res.h.get() : h->res.d.get(), st), SRSRAN_ERROR);
     if (!direct) {
-      PHY_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, n_tb * sizeof(nrsch::TbFinRes), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
-      PHY_HIP_CHECK(hipMemcpyAsync(h->h_flags + cb_lo, h->d_flags + cb_lo, cb_hi - cb_lo, hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->res.h, h->res.d, n_tb * sizeof(nrsch::TbFinRes), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
+      PHY_HIP_CHECK(hipMemcpyAsync(h->flags.h + cb_lo, h->flags.d + cb_lo, cb_hi - cb_lo, hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
     }
     for (int i = 0; i < n_tail; i++) {
     if (tail[i].bytes) {
@@ -463,37 +396,37 @@ int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, 
     std::vector<uint32_t> it_sum(n_tb, 0);
     for (uint32_t i = 0; i < n_jobs; i++) {
       const Job& j = jobs[order[i]];
-      it_sum[j.tb] += h->h_iter[i] == 0 ? h->max_iter : (uint32_t)h->h_iter[i]; // :629-631
+      it_sum[j.tb] += h->iter.h[i] == 0 ? h->max_iter : (uint32_t)h->iter.h[i]; // :629-631
     }
     for (uint32_t t = 0; t < n_tb; t++) {
       for (uint32_t r = 0; r < cfg[t].C; r++) {
-        cb_crc[tbs[t].first_cb + r] = h->h_flags[tbs[t].first_cb + r];
+        cb_crc[tbs[t].first_cb + r] = h->flags.h[tbs[t].first_cb + r];
       }
-      res[t].all_decoded = h->h_res[t].all_decoded;
-      res[t].crc_ok      = h->h_res[t].crc_ok;
+      res[t].all_decoded = h->res.h[t].all_decoded;
+      res[t].crc_ok      = h->res.h[t].crc_ok;
       res[t].avg_iter    = (float)it_sum[t] / (float)cfg[t].C; // :657-661
       res[t].nof_cb      = cfg[t].C;
     }
     return SRSRAN_SUCCESS;
   }
   // nothing left to decode (every code block already had its CRC): assembly and transport CRC only
-  if (!ensure(&h->d_tbf, &h->h_tbf, &h->tbf_cap, n_tb) || !ensure(&h->d_res, &h->h_res, &h->res_cap, n_tb)) {
+  if (!h->tbf.grow(n_tb, n_tb / 2 + 16) || !h->res.grow(n_tb, n_tb / 2 + 16)) {
     return SRSRAN_ERROR;
   }
   for (uint32_t t = 0; t < n_tb; t++) {
-    h->h_tbf[t] = nrsch::TbFin{tbs[t].first_cb, cfg[t].C, cfg[t].Kp, cfg[t].L_cb, cfg[t].L_tb, cfg[t].A, tbs[t].payload_offset,
+    h->tbf.h[t] = nrsch::TbFin{tbs[t].first_cb, cfg[t].C, cfg[t].Kp, cfg[t].L_cb, cfg[t].L_tb, cfg[t].A, tbs[t].payload_offset,
                                crc_row_of(h, cfg[t].A, cfg[t].L_tb)};
-    if (h->h_tbf[t].mult == 0xffffffffu) {
+    if (h->tbf.h[t].mult == 0xffffffffu) {
       return SRSRAN_ERROR;
     }
   }
   if (!direct) {
-    PHY_HIP_CHECK(hipMemcpyAsync(h->d_tbf, h->h_tbf, n_tb * sizeof(nrsch::TbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+    PHY_HIP_CHECK(hipMemcpyAsync(h->tbf.d, h->tbf.h, n_tb * sizeof(nrsch::TbFin), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
   }
-  PHY_HIP_CHECK(nrsch::launch_tb_finish(d_cb_data, data_stride, x_flags, direct ? h->h_tbf : h->d_tbf, n_tb, d_payload, h->d_crc_mult,
-                                        direct ? h->h_res : h->d_res, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(nrsch::launch_tb_finish(d_cb_data, data_stride, x_flags, direct ? h->tbf.h.get() : h->tbf.d.get(), n_tb, d_payload, h->crc_mult.device(),
+                                        direct ? h->res.h.get() : h->res.d.get(), st), SRSRAN_ERROR);
   if (!direct) {
-    PHY_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, n_tb * sizeof(nrsch::TbFinRes), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
+    PHY_HIP_CHECK(hipMemcpyAsync(h->res.h, h->res.d, n_tb * sizeof(nrsch::TbFinRes), hipMemcpyDeviceToHost, st), SRSRAN_ERROR);
   }
   for (int i = 0; i < n_tail; i++) {
     if (tail[i].bytes) {
@@ -502,8 +435,8 @@ int phyhip::nrtb::sch_nr_decode(srsran_hip_sch_nr_t* h, const int8_t* d_e_bits, 
   }
   PHY_HIP_CHECK(hipStreamSynchronize(st), SRSRAN_ERROR);
   for (uint32_t t = 0; t < n_tb; t++) {
-    res[t].all_decoded = h->h_res[t].all_decoded;
-    res[t].crc_ok      = h->h_res[t].crc_ok;
+    res[t].all_decoded = h->res.h[t].all_decoded;
+    res[t].crc_ok      = h->res.h[t].crc_ok;
     res[t].avg_iter    = 0.0f;
     res[t].nof_cb      = cfg[t].C;
   }
@@ -694,7 +627,7 @@ extern "C" int srsran_hip_sch_nr_encode(srsran_hip_sch_nr_t* h, const uint8_t* d
   };
   std::vector<TbCfg> cfg(n_tb);
   std::vector<EJob>  jobs;
-  if (!ensure(&h->d_tbe, &h->h_tbe, &h->tbe_cap, n_tb)) {
+  if (!h->tbe.grow(n_tb, n_tb / 2 + 16)) {
     return SRSRAN_ERROR;
   }
   uint32_t n_cb = 0;
@@ -709,28 +642,20 @@ extern "C" int srsran_hip_sch_nr_encode(srsran_hip_sch_nr_t* h, const uint8_t* d
     set_error("sch_nr: %u code blocks in one call, the object was created for %u", n_cb, h->max_cb);
     return SRSRAN_ERROR;
   }
-  if (!ensure(&h->d_cbe, &h->h_cbe, &h->cbe_cap, n_cb)) {
+  if (!h->cbe.grow(n_cb, n_cb / 2 + 16)) {
     return SRSRAN_ERROR;
   }
-  if (!h->d_cw) {
-    PHY_HIP_CHECK(hipMalloc(&h->d_cw, (size_t)h->max_cb * CW_STRIDE), SRSRAN_ERROR);
-  }
-  if (n_tb > h->tbcrc_cap) {
-    (void)hipFree(h->d_tbcrc);
-    h->d_tbcrc   = nullptr;
-    h->tbcrc_cap = 0;
-    PHY_HIP_CHECK(hipMalloc(&h->d_tbcrc, ((size_t)n_tb + 16) * sizeof(uint32_t)), SRSRAN_ERROR);
-    h->tbcrc_cap = (size_t)n_tb + 16;
-  }
+  PHY_HIP_CHECK(grown(h->d_cw.grow((size_t)h->max_cb * CW_STRIDE)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->d_tbcrc.grow(n_tb, 16)), SRSRAN_ERROR);
   uint32_t row = 0;
   for (uint32_t t = 0; t < n_tb; t++) {
     const TbCfg& c = cfg[t];
-    h->h_tbe[t]    = nrsch::TbEnc{tbs[t].payload_offset, c.A, c.L_tb};
+    h->tbe.h[t]    = nrsch::TbEnc{tbs[t].payload_offset, c.A, c.L_tb};
     uint32_t bit = 0, out = tbs[t].e_offset;
     for (uint32_t r = 0; r < c.C; r++) {
       const bool     last   = r == c.C - 1;
       const uint32_t cb_len = c.Kp - c.L_cb - (last ? c.L_tb : 0);
-      h->h_cbe[row]         = nrsch::CbEnc{t, bit, cb_len, c.Kp, c.Kr, c.L_cb, last ? 1u : 0u, row};
+      h->cbe.h[row]         = nrsch::CbEnc{t, bit, cb_len, c.Kp, c.Kr, c.L_cb, last ? 1u : 0u, row};
       bit += (cb_len / 8) * 8; // input_ptr += cb_len / 8 (:448)
       const uint32_t E = get_E(c, r);
       jobs.push_back(EJob{c.bg, c.Z, tbs[t].rv & 3u, tbs[t].mod, c.Nref, E, out, row});
@@ -738,10 +663,10 @@ extern "C" int srsran_hip_sch_nr_encode(srsran_hip_sch_nr_t* h, const uint8_t* d
       row++;
     }
   }
-  PHY_HIP_CHECK(hipMemcpyAsync(h->d_tbe, h->h_tbe, n_tb * sizeof(nrsch::TbEnc), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipMemcpyAsync(h->d_cbe, h->h_cbe, n_cb * sizeof(nrsch::CbEnc), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(nrsch::launch_tb_crc_enc(d_payload, h->d_tbe, n_tb, h->d_tbcrc, st), SRSRAN_ERROR);
-  PHY_HIP_CHECK(nrsch::launch_cb_build(d_payload, h->d_cbe, n_cb, h->d_tbe, h->d_tbcrc, h->d_msg, MSG_STRIDE, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(hipMemcpyAsync(h->tbe.d, h->tbe.h, n_tb * sizeof(nrsch::TbEnc), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(hipMemcpyAsync(h->cbe.d, h->cbe.h, n_cb * sizeof(nrsch::CbEnc), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(nrsch::launch_tb_crc_enc(d_payload, h->tbe.d, n_tb, h->d_tbcrc, st), SRSRAN_ERROR);
+  PHY_HIP_CHECK(nrsch::launch_cb_build(d_payload, h->cbe.d, n_cb, h->tbe.d, h->d_tbcrc, h->d_msg, MSG_STRIDE, st), SRSRAN_ERROR);
   // LDPC encoder per (graph, Z), rate matcher per (graph, Z, rv, modulation, Nref)
   std::vector<uint32_t> order(n_cb);
   for (uint32_t i = 0; i < n_cb; i++) {

@@ -4,6 +4,10 @@
 #pragma once
 #include "hip_common.h"
 
+#include <cstring>
+#include <map>
+#include <utility>
+
 namespace phyhip {
 
 inline size_t al256(size_t v) // the next multiple of 256: the alignment of every region of a staging image
@@ -76,48 +80,174 @@ private:
   bool        tried_ = false;
 };
 
-// A buffer of T that only grows, in device memory or as a pinned host image the kernels work on themselves (host_image_alloc).  grow(need) leaves a
-// buffer that holds `need` elements alone; a smaller one is FREED and need + headroom elements are allocated -- the contents are not kept, and a failed
-// allocation leaves nullptr and capacity 0.  How much headroom a request gets is the site's policy (pinned memory is dear to re-allocate, and the
-// first-call latencies on record were measured with these policies).  Converts to the pointer it holds.
-enum class StageMem { Device, HostImage };
+// A buffer of T that only grows: in device memory, as a pinned host image the kernels work on themselves (host_image_alloc), or in plain pinned memory
+// (hipHostMalloc with default flags: the source and target of asynchronous copies).  grow(need) leaves a buffer that holds `need` elements alone; a
+// smaller one is FREED and need + headroom elements are allocated -- the contents are not kept, and a failed allocation leaves nullptr and capacity 0.
+// How much headroom a request gets is the site's policy (pinned memory is dear to re-allocate, and the first-call latencies on record were measured with
+// these policies).  Converts to the pointer it holds.  Movable, so that its owners can live in containers and a grown table can take an old one's place.
+enum class StageMem { Device, HostImage, Pinned };
 template <StageMem M, class T = uint8_t>
 class StageBuf {
 public:
   StageBuf()                           = default;
   StageBuf(const StageBuf&)            = delete;
   StageBuf& operator=(const StageBuf&) = delete;
-  ~StageBuf() { release(); }
-  bool grow(size_t need, size_t headroom = 0)
+  StageBuf(StageBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+  StageBuf& operator=(StageBuf&& o) noexcept
   {
-    if (need <= cap_) {
-      return true;
+    if (this != &o) {
+      release();
+      p_ = o.p_, cap_ = o.cap_;
+      o.p_ = nullptr, o.cap_ = 0;
     }
+    return *this;
+  }
+  ~StageBuf() { release(); }
+  bool grow(size_t need, size_t headroom = 0) { return need <= cap_ || alloc(need + headroom); }
+  bool alloc(size_t n) // a fresh buffer of exactly n elements, whatever was held
+  {
     release();
-    const size_t     n = need + headroom;
-    const hipError_t e = M == StageMem::Device ? hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T)) : host_image_alloc(&p_, n * sizeof(T));
+    void*            p = nullptr;
+    const hipError_t e = M == StageMem::Device ? hipMalloc(&p, n * sizeof(T)) : M == StageMem::HostImage ? host_image_alloc(&p, n * sizeof(T)) : hipHostMalloc(&p, n * sizeof(T));
     if (e != hipSuccess) {
-      p_ = nullptr;
       return false;
     }
+    p_   = static_cast<T*>(p);
     cap_ = n;
     return true;
   }
-  T* get() const { return p_; }
+  T*     get() const { return p_; }
+  size_t cap() const { return cap_; } // elements
   operator T*() const { return p_; }
+  T* operator->() const { return p_; }
 
 private:
   void release()
   {
-    (void)(M == StageMem::Device ? hipFree(p_) : hipHostFree(p_));
+    if (p_) {
+      (void)(M == StageMem::Device ? hipFree(p_) : hipHostFree(p_));
+    }
     p_   = nullptr;
     cap_ = 0;
   }
   T*     p_   = nullptr;
-  size_t cap_ = 0; // elements
+  size_t cap_ = 0;
 };
 using DeviceBuf = StageBuf<StageMem::Device>;
 using HostImage = StageBuf<StageMem::HostImage>;
+
+// A device array and its host twin of the same layout (H: plain pinned memory for copies, or a host image the kernels read themselves), growing together by
+// the site's headroom rule: the device side first, as every site allocated them.  After a failed grow() the side that failed is empty and the next call
+// tries again.
+template <class T = uint8_t, StageMem H = StageMem::Pinned, class TH = T> // (TH: the host's name for an element, where it has one of its own)
+struct StagePair {
+  static_assert(sizeof(T) == sizeof(TH), "one layout on both sides");
+  StageBuf<StageMem::Device, T> d;
+  StageBuf<H, TH>               h;
+  bool grow(size_t need, size_t headroom = 0) { return d.grow(need, headroom) && h.grow(need, headroom); }
+};
+
+// a grow() result as what PHY_HIP_CHECK takes
+inline hipError_t grown(bool ok)
+{
+  return ok ? hipSuccess : hipErrorOutOfMemory;
+}
+
+// "The previous call's kernel has consumed this buffer": an event recorded behind the launch and waited for before the host rewrites what the launch reads
+// (and before its owner releases it).  Created with its owner; ok() tells whether that worked.
+class StageEvent {
+public:
+  StageEvent()
+  {
+    if (hipEventCreateWithFlags(&ev_, hipEventDisableTiming) != hipSuccess) {
+      ev_ = nullptr;
+    }
+  }
+  StageEvent(const StageEvent&)            = delete;
+  StageEvent& operator=(const StageEvent&) = delete;
+  ~StageEvent()
+  {
+    if (ev_) {
+      (void)hipEventDestroy(ev_);
+    }
+  }
+  bool       ok() const { return ev_ != nullptr; }
+  hipError_t wait() // for the recorded work, if any
+  {
+    if (!pending_) {
+      return hipSuccess;
+    }
+    const hipError_t e = hipEventSynchronize(ev_);
+    pending_           = e != hipSuccess;
+    return e;
+  }
+  hipError_t record(hipStream_t st)
+  {
+    const hipError_t e = hipEventRecord(ev_, st);
+    pending_           = pending_ || e == hipSuccess;
+    return e;
+  }
+
+private:
+  hipEvent_t ev_      = nullptr;
+  bool       pending_ = false;
+};
+
+// A table of rows of `width` words on the device, one per key seen so far (CRC lane multipliers per message size).  With a pinned mirror, a new row is
+// computed into the mirror by fill(row) and goes up by an asynchronous copy on the call's stream, in front of the kernel that reads it; without one it is
+// computed on the stack and goes up with upload(), complete on return.  The table doubles when it is full and carries the old rows over; nothing may still
+// read the old table or copy from the old mirror when they are released, hence the device-wide waits.  row() returns a row INDEX (the table may move while
+// a call's jobs are still being written), or kNoRow with the error text set: "<who>: device allocation ..." or "<who>: upload ...".
+class RowTable {
+public:
+  static constexpr uint32_t kNoRow = 0xffffffffu, kMaxWidth = 256; // (rows of 64 and of 256 lane multipliers exist)
+  RowTable(uint32_t width, uint32_t first_cap, const char* who, bool mirror = true) : width_(width), first_cap_(first_cap), who_(who), mirror_(mirror) {}
+  const uint32_t* device() const { return d_; }
+  template <class Fill>
+  uint32_t row(uint32_t key, hipStream_t st, Fill&& fill)
+  {
+    auto it = row_.find(key);
+    if (it != row_.end()) {
+      return it->second;
+    }
+    const uint32_t r = (uint32_t)row_.size();
+    if (r >= rows_cap_) {
+      const uint32_t                       cap = rows_cap_ ? 2 * rows_cap_ : first_cap_;
+      StageBuf<StageMem::Device, uint32_t> nd;
+      StageBuf<StageMem::Pinned, uint32_t> nh;
+      if (!nd.grow((size_t)cap * width_) || (mirror_ && (!nh.grow((size_t)cap * width_) || hipDeviceSynchronize() != hipSuccess)) ||
+          (d_ && (hipMemcpy(nd, d_, (size_t)r * width_ * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess))) {
+        set_error("%s: device allocation of the CRC multiplier table failed", who_);
+        return kNoRow;
+      }
+      if (h_) {
+        memcpy(nh, h_, (size_t)r * width_ * sizeof(uint32_t));
+      }
+      d_        = std::move(nd);
+      h_        = std::move(nh);
+      rows_cap_ = cap;
+    }
+    uint32_t  tmp[kMaxWidth];
+    uint32_t* m = mirror_ ? h_ + (size_t)r * width_ : tmp;
+    fill(m);
+    uint32_t* dst = d_ + (size_t)r * width_;
+    if ((mirror_ ? hipMemcpyAsync(dst, m, width_ * sizeof(uint32_t), hipMemcpyHostToDevice, st) : upload(dst, m, width_ * sizeof(uint32_t))) != hipSuccess) {
+      set_error("%s: upload of the CRC multiplier table failed", who_);
+      return kNoRow;
+    }
+    row_.emplace(key, r);
+    return r;
+  }
+
+private:
+  std::map<uint32_t, uint32_t>         row_;
+  StageBuf<StageMem::Device, uint32_t> d_;
+  StageBuf<StageMem::Pinned, uint32_t> h_;
+  uint32_t                             rows_cap_ = 0;
+  const uint32_t                       width_, first_cap_;
+  const char* const                    who_;
+  const bool                           mirror_;
+};
 
 namespace rm {
 bool build_all_tables(); // every rate-matching table in one allocation and one upload (rm_host.cpp): what srsran_hip_warmup (warmup_host.cpp) starts with

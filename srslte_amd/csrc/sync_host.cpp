@@ -4,6 +4,7 @@
 // Mirrors (interface + behaviour) lib/src/phy/sync/pss.c, sss.c, find_sss.c, gen_sss.c and the default
 // path of srsran_sync_find (sync.c:629-843) of the reference.
 #include "hip_common.h"
+#include "stage.h"
 #include "srsran_amd/phy_sync_abi.h"
 #include "sync_device.h"
 #include "sync_glue.h"
@@ -138,32 +139,23 @@ struct PssEngine {
   uint32_t frame_size = 0, fft_size = 0, max_caps = 0;
   int      n_blocks = 0, hop = 0, n_out = 0, block_n = 4096;
   size_t   corr_stride = 0;
-  float2*  d_tw = nullptr;
-  float2*  d_filt = nullptr;
-  float2*  d_rep  = nullptr; // direct mode (frame_size < fft_size): the three time replicas
-  bool     direct = false;
-  float*   d_corr = nullptr;
-  float*   d_part_val = nullptr;
-  int*     d_part_idx = nullptr;
-  float2*  d_spec = nullptr; // block spectra between the hypotheses of a launch (32 KB per block and capture)
-  sync::PssResult* d_res = nullptr;
+  template <class T>
+  using Dev = StageBuf<StageMem::Device, T>;
+  Dev<float2> d_tw;
+  Dev<float2> d_filt;
+  Dev<float2> d_rep; // direct mode (frame_size < fft_size): the three time replicas
+  bool        direct = false;
+  Dev<float>  d_corr;
+  Dev<float>  d_part_val;
+  Dev<int>    d_part_idx;
+  Dev<float2> d_spec; // block spectra between the hypotheses of a launch (32 KB per block and capture)
+  Dev<sync::PssResult> d_res;
   cf_t     freq[3][SRSRAN_PSS_LEN];
   std::vector<cf_t> time[3];
 };
 
 void pss_engine_free(PssEngine* e)
 {
-  if (!e) {
-    return;
-  }
-  (void)hipFree(e->d_tw);
-  (void)hipFree(e->d_filt);
-  (void)hipFree(e->d_rep);
-  (void)hipFree(e->d_corr);
-  (void)hipFree(e->d_part_val);
-  (void)hipFree(e->d_part_idx);
-  (void)hipFree(e->d_spec);
-  (void)hipFree(e->d_res);
   delete e;
 }
 
@@ -239,18 +231,14 @@ PssEngine* pss_engine_new(uint32_t frame_size, uint32_t fft_size, int cfo_i, uin
       filt[(size_t)h * BN + k] = std::complex<float>((float)v.real(), (float)v.imag());
     }
   }
-  bool ok = hipMalloc(&e->d_tw, tw.size() * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&e->d_filt, 3 * (size_t)BN * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&e->d_corr, (size_t)max_caps * 3 * e->corr_stride * sizeof(float)) == hipSuccess &&
-            hipMalloc(&e->d_part_val, (size_t)max_caps * 3 * e->n_blocks * sizeof(float)) == hipSuccess &&
-            hipMalloc(&e->d_part_idx, (size_t)max_caps * 3 * e->n_blocks * sizeof(int)) == hipSuccess &&
-            hipMalloc(&e->d_spec, (size_t)max_caps * e->n_blocks * e->block_n * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&e->d_res, (size_t)max_caps * 3 * sizeof(sync::PssResult)) == hipSuccess &&
+  bool ok = e->d_tw.grow(tw.size()) && e->d_filt.grow(3 * (size_t)BN) && e->d_corr.grow((size_t)max_caps * 3 * e->corr_stride) &&
+            e->d_part_val.grow((size_t)max_caps * 3 * e->n_blocks) && e->d_part_idx.grow((size_t)max_caps * 3 * e->n_blocks) &&
+            e->d_spec.grow((size_t)max_caps * e->n_blocks * e->block_n) && e->d_res.grow((size_t)max_caps * 3) &&
             upload(e->d_tw, tw.data(), tw.size() * sizeof(float2)) == hipSuccess &&
             upload(e->d_filt, filt.data(), 3 * (size_t)BN * sizeof(float2)) == hipSuccess &&
             hipMemset(e->d_corr, 0, (size_t)max_caps * 3 * e->corr_stride * sizeof(float)) == hipSuccess;
   if (ok && e->direct) {
-    ok = hipMalloc(&e->d_rep, 3 * (size_t)fft_size * sizeof(float2)) == hipSuccess;
+    ok = e->d_rep.grow(3 * (size_t)fft_size);
     for (uint32_t h = 0; h < 3 && ok; h++) {
       ok = upload(e->d_rep + (size_t)h * fft_size, e->time[h].data(), fft_size * sizeof(float2)) == hipSuccess;
     }
@@ -300,17 +288,12 @@ int pss_engine_run(PssEngine* e, const void* d_in, uint32_t n_cap, int mask, int
 
 struct SssEngine {
   uint32_t fft_size = 0;
-  float2*  d_tw = nullptr;
-  float*   d_seq = nullptr; // s_tilde, c_tilde, z_tilde (3 x 31)
+  StageBuf<StageMem::Device, float2> d_tw;
+  StageBuf<StageMem::Device, float>  d_seq; // s_tilde, c_tilde, z_tilde (3 x 31)
 };
 
 void sss_engine_free(SssEngine* e)
 {
-  if (!e) {
-    return;
-  }
-  (void)hipFree(e->d_tw);
-  (void)hipFree(e->d_seq);
   delete e;
 }
 
@@ -338,7 +321,7 @@ SssEngine* sss_engine_new(uint32_t fft_size)
     seq[31 + i] = (float)ct[i];
     seq[62 + i] = (float)zt[i];
   }
-  bool ok = hipMalloc(&e->d_tw, fft_size * sizeof(float2)) == hipSuccess && hipMalloc(&e->d_seq, sizeof(seq)) == hipSuccess &&
+  bool ok = e->d_tw.grow(fft_size) && e->d_seq.grow(93) &&
             upload(e->d_tw, tw.data(), fft_size * sizeof(float2)) == hipSuccess &&
             upload(e->d_seq, seq, sizeof(seq)) == hipSuccess;
   if (!ok) {
@@ -378,14 +361,13 @@ namespace {
 struct PssCtx {
   DeviceTag tag;
   PssEngine*  e = nullptr;
-  hipStream_t stream = nullptr;
-  float2*     d_in = nullptr;
-  float2*     d_dec = nullptr; // decimated + filtered input (decimate > 1)
-  cf_t*       h_in = nullptr;
-  float*      h_avg = nullptr;
-  sync::PssResult* h_res = nullptr;
+  StageStream stream;
+  StageBuf<StageMem::Device, float2> d_in;  // full-rate input: frame (+ fft in the sliding dot-product mode)
+  StageBuf<StageMem::Device, float2> d_dec; // decimated + filtered input (decimate > 1)
+  StageBuf<StageMem::Pinned, cf_t>   h_in;
+  StageBuf<StageMem::Pinned, float>  h_avg;
+  StageBuf<StageMem::Pinned, sync::PssResult> h_res;
   int         cfo_i = 0;
-  size_t      in_cap = 0;
   bool        plans = false;   // dftp_input / idftp_input created (srsran_pss_filter and friends)
 };
 PssCtx* pctx(srsran_pss_t* q)
@@ -398,14 +380,6 @@ void pctx_free(PssCtx* c)
     return;
   }
   pss_engine_free(c->e);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_dec);
-  (void)hipHostFree(c->h_in);
-  (void)hipHostFree(c->h_avg);
-  (void)hipHostFree(c->h_res);
-  if (c->stream) {
-    (void)hipStreamDestroy(c->stream);
-  }
   delete c;
 }
 int pss_setup(srsran_pss_t* q, uint32_t frame_size, uint32_t fft_size, int offset)
@@ -473,16 +447,10 @@ extern "C" int srsran_pss_init_fft_offset_decim(srsran_pss_t* q, uint32_t max_fr
       memcpy(q->filter.taps, kDecimTaps[decimate - 2], 4 * sizeof(float));
     }
   }
-  // full-rate input: frame (+ fft in the sliding dot-product mode)
-  c->in_cap = (size_t)max_frame_size + max_fft_size;
+  const size_t in_cap = (size_t)max_frame_size + max_fft_size;
   bool ok = q->conv_output_avg && q->conv_output_abs && q->pss_signal_time[0] && q->pss_signal_time[1] && q->pss_signal_time[2] &&
             (decimate == 1 || q->filter.taps) &&
-            hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&c->d_in, c->in_cap * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&c->d_dec, c->in_cap * sizeof(float2)) == hipSuccess &&
-            hipHostMalloc(&c->h_in, c->in_cap * sizeof(cf_t)) == hipSuccess &&
-            hipHostMalloc(&c->h_avg, buffer_size * sizeof(float)) == hipSuccess &&
-            hipHostMalloc(&c->h_res, 3 * sizeof(sync::PssResult)) == hipSuccess;
+            c->stream.open() && c->d_in.grow(in_cap) && c->d_dec.grow(in_cap) && c->h_in.grow(in_cap) && c->h_avg.grow(buffer_size) && c->h_res.grow(3);
   if (!ok || pss_setup(q, q->frame_size, q->fft_size, offset)) {
     srsran_pss_free(q);
     return SRSRAN_ERROR;
@@ -591,7 +559,7 @@ extern "C" int srsran_pss_find_pss(srsran_pss_t* q, const cf_t* input, float* co
   // samples the reference reads: frame_size * decimate (pss.c:462), or frame_size + fft_size - 1 in the
   // sliding dot-product mode (pss.c:477-479)
   const size_t n_in = direct ? (size_t)q->frame_size + q->fft_size - 1 : (size_t)q->frame_size * q->decimate;
-  if (n_in > c->in_cap) {
+  if (n_in > c->d_in.cap()) {
     return SRSRAN_ERROR;
   }
   memcpy(c->h_in, input, n_in * sizeof(cf_t));
@@ -727,13 +695,12 @@ namespace {
 struct SssCtx {
   DeviceTag tag;
   SssEngine*  e = nullptr;
-  hipStream_t stream = nullptr;
-  float2*     d_in = nullptr;
-  float2*     d_ce = nullptr;
-  int*        d_pos = nullptr;
-  sync::SssResult* d_res = nullptr;
-  cf_t*       h_in = nullptr;
-  sync::SssResult* h_res = nullptr;
+  StageStream stream;
+  StageBuf<StageMem::Device, float2> d_in, d_ce;
+  StageBuf<StageMem::Device, int>    d_pos;
+  StageBuf<StageMem::Device, sync::SssResult> d_res;
+  StageBuf<StageMem::Pinned, cf_t>            h_in;
+  StageBuf<StageMem::Pinned, sync::SssResult> h_res;
 };
 SssCtx* sctx(srsran_sss_t* q)
 {
@@ -777,15 +744,6 @@ extern "C" void srsran_sss_free(srsran_sss_t* q)
   SssCtx* c = sctx(q);
   if (c) {
     sss_engine_free(c->e);
-    (void)hipFree(c->d_in);
-    (void)hipFree(c->d_ce);
-    (void)hipFree(c->d_pos);
-    (void)hipFree(c->d_res);
-    (void)hipHostFree(c->h_in);
-    (void)hipHostFree(c->h_res);
-    if (c->stream) {
-      (void)hipStreamDestroy(c->stream);
-    }
     delete c;
   }
   memset(q, 0, sizeof(srsran_sss_t));
@@ -801,12 +759,8 @@ extern "C" int srsran_sss_init(srsran_sss_t* q, uint32_t fft_size)
   q->dftp_input.p = c;
   c->e            = sss_engine_new(fft_size);
   int zero        = 0;
-  bool ok = c->e && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&c->d_in, (size_t)fft_size * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&c->d_ce, 3 * 62 * sizeof(float2)) == hipSuccess && hipMalloc(&c->d_pos, 3 * sizeof(int)) == hipSuccess &&
-            hipMalloc(&c->d_res, 3 * sizeof(sync::SssResult)) == hipSuccess &&
-            hipHostMalloc(&c->h_in, ((size_t)fft_size + 62) * sizeof(cf_t)) == hipSuccess &&
-            hipHostMalloc(&c->h_res, 3 * sizeof(sync::SssResult)) == hipSuccess &&
+  bool ok = c->e && c->stream.open() && c->d_in.grow(fft_size) && c->d_ce.grow(3 * 62) && c->d_pos.grow(3) && c->d_res.grow(3) &&
+            c->h_in.grow((size_t)fft_size + 62) && c->h_res.grow(3) &&
             hipMemset(c->d_pos, 0, 3 * sizeof(int)) == hipSuccess;
   (void)zero;
   if (!ok) {
@@ -922,7 +876,7 @@ static int sss_run(srsran_sss_t* q, const cf_t* input, int M, cf_t* ce, uint32_t
     PHY_HIP_CHECK(hipMemcpyAsync(c->d_ce + (size_t)q->N_id_2 * 62, c->h_in + N, 62 * sizeof(cf_t), hipMemcpyHostToDevice, c->stream), SRSRAN_ERROR);
   }
   sync::SssParams p;
-  sss_params(&p, c->e, c->d_in, N, 1, N, SRSRAN_CP_NORM, M, 1 << q->N_id_2, -1.0f, c->d_pos, ce ? c->d_ce : nullptr);
+  sss_params(&p, c->e, c->d_in, N, 1, N, SRSRAN_CP_NORM, M, 1 << q->N_id_2, -1.0f, c->d_pos, ce ? c->d_ce.get() : nullptr);
   PHY_HIP_CHECK(sync::launch_sss(p, nullptr, c->d_res, c->stream), SRSRAN_ERROR);
   PHY_HIP_CHECK(hipMemcpyAsync(c->h_res, c->d_res, 3 * sizeof(sync::SssResult), hipMemcpyDeviceToHost, c->stream), SRSRAN_ERROR);
   PHY_HIP_CHECK(hipStreamSynchronize(c->stream), SRSRAN_ERROR);
@@ -966,7 +920,7 @@ struct srsran_hip_cellsearch {
   DeviceTag tag;
   PssEngine*  pss = nullptr;
   SssEngine*  sss = nullptr;
-  sync::SssResult* d_sss = nullptr;
+  StageBuf<StageMem::Device, sync::SssResult> d_sss;
   srsran_cp_t cp = SRSRAN_CP_NORM;
   int         M = 1;
   uint32_t    max_caps = 0;
@@ -982,7 +936,7 @@ extern "C" int srsran_hip_cellsearch_create(srsran_hip_cellsearch_t** hh, uint32
   auto* h = new srsran_hip_cellsearch;
   h->pss  = pss_engine_new(frame_size, fft_size, 0, max_captures);
   h->sss  = h->pss ? sss_engine_new(fft_size) : nullptr;
-  if (!h->pss || !h->sss || hipMalloc(&h->d_sss, (size_t)max_captures * 3 * sizeof(sync::SssResult)) != hipSuccess) {
+  if (!h->pss || !h->sss || !h->d_sss.grow((size_t)max_captures * 3)) {
     srsran_hip_cellsearch_free(h);
     return SRSRAN_ERROR;
   }
@@ -1000,7 +954,6 @@ extern "C" void srsran_hip_cellsearch_free(srsran_hip_cellsearch_t* h)
   }
   pss_engine_free(h->pss);
   sss_engine_free(h->sss);
-  (void)hipFree(h->d_sss);
   delete h;
 }
 

@@ -34,10 +34,10 @@ bool qpp_params(uint32_t K, uint32_t* f1, uint32_t* f2)
 }
 
 struct Ctx { // behind srsran_tcod_t.temp
-  DeviceTag tag;
-  hipStream_t st    = nullptr;
-  uint8_t*    d_in  = nullptr;
-  uint8_t*    d_out = nullptr;
+  DeviceTag   tag;
+  StageStream st;
+  DeviceBuf   d_in;
+  DeviceBuf   d_out;
 };
 
 } // namespace
@@ -76,10 +76,7 @@ extern "C" int srsran_tcod_init(srsran_tcod_t* h, uint32_t max_long_cb)
     return -1;
   }
   Ctx* c = new Ctx;
-  if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_in, 6144 + 64) != hipSuccess ||
-      hipMalloc(&c->d_out, 3 * 6144 + 64) != hipSuccess) {
-    (void)hipFree(c->d_in);
-    (void)hipFree(c->d_out);
+  if (!c->st.open() || !c->d_in.grow(6144 + 64) || !c->d_out.grow(3 * 6144 + 64)) {
     delete c;
     return -1;
   }
@@ -94,11 +91,7 @@ extern "C" void srsran_tcod_free(srsran_tcod_t* h)
   }
   h->max_long_cb = 0;
   if (h->temp) {
-    Ctx* c = reinterpret_cast<Ctx*>(h->temp);
-    (void)hipFree(c->d_in);
-    (void)hipFree(c->d_out);
-    (void)hipStreamDestroy(c->st);
-    delete c;
+    delete reinterpret_cast<Ctx*>(h->temp);
     h->temp = nullptr;
   }
 }
@@ -271,22 +264,13 @@ extern "C" int srsran_rm_turbo_tx_lut(uint8_t* w_buff, uint8_t* systematic, uint
 
 // ------------------------------------------------------------------------------------------------ transport blocks, transmit side
 struct srsran_hip_sch_enc {
-  DeviceTag tag;
-  void*  d_scratch = nullptr;
-  void*  h_scratch = nullptr; // pinned
-  size_t cap       = 0;
-  hipEvent_t done  = nullptr;
-  bool   pending   = false;
+  DeviceTag   tag;
+  StagePair<> scratch;
+  StageEvent  done; // the previous call's kernels have consumed the scratch
   // lane multipliers of the two CRCs, one row of 64 per message length seen so far (key: length | generator << 31), resident on the device
-  std::map<uint32_t, uint32_t> mult_row;
-  uint32_t*                    d_mult = nullptr;
-  uint32_t*                    h_mult = nullptr; // pinned mirror: a new row goes up by an asynchronous copy on the call's stream, in front of the kernel
-  uint32_t                     mult_rows_cap = 0;
+  RowTable mult{64, 32, "sch encode"};
   // the latency kernel's rows of 256 lane multipliers (tcod_device.h: crc_lane_multipliers256), same scheme
-  std::map<uint32_t, uint32_t> mult256_row;
-  uint32_t*                    d_mult256 = nullptr;
-  uint32_t*                    h_mult256 = nullptr;
-  uint32_t                     mult256_rows_cap = 0;
+  RowTable mult256{256, 16, "sch encode"};
 };
 
 namespace {
@@ -337,79 +321,12 @@ void phyhip::tcod::crc_lane_multipliers256(uint32_t n_units, uint32_t bits_per_u
 // the first time the length is seen by this object
 static uint32_t enc_mult_row(srsran_hip_sch_enc_t* h, uint32_t n_units, bool cb, hipStream_t st)
 {
-  const uint32_t key = n_units | (cb ? 0x80000000u : 0u);
-  auto           it  = h->mult_row.find(key);
-  if (it == h->mult_row.end()) {
-    const uint32_t row = (uint32_t)h->mult_row.size();
-    if (row >= h->mult_rows_cap) {
-      const uint32_t cap = h->mult_rows_cap ? 2 * h->mult_rows_cap : 32;
-      uint32_t *     nd = nullptr, *nh = nullptr;
-      if (hipMalloc(&nd, (size_t)cap * 64 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&nh, (size_t)cap * 64 * sizeof(uint32_t)) != hipSuccess ||
-          hipDeviceSynchronize() != hipSuccess || // nothing may still read the old table / copy from the old mirror when they are freed below
-          (h->d_mult && (hipMemcpy(nd, h->d_mult, (size_t)row * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-                         hipDeviceSynchronize() != hipSuccess))) {
-        (void)hipFree(nd);
-        (void)hipHostFree(nh);
-        set_error("sch encode: device allocation of the CRC multiplier table failed");
-        return 0xffffffffu;
-      }
-      if (h->h_mult) {
-        memcpy(nh, h->h_mult, (size_t)row * 64 * sizeof(uint32_t));
-      }
-      (void)hipFree(h->d_mult);
-      (void)hipHostFree(h->h_mult);
-      h->d_mult        = nd;
-      h->h_mult        = nh;
-      h->mult_rows_cap = cap;
-    }
-    uint32_t* m = h->h_mult + (size_t)row * 64;
-    tcod::crc_lane_multipliers(n_units, cb ? 1u : 8u, cb ? 0x800063u : 0x864CFBu, m);
-    // (stream order puts the row in front of the kernel that reads it; the pinned source stays where it is)
-    if (hipMemcpyAsync(h->d_mult + (size_t)row * 64, m, 64 * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
-      set_error("sch encode: upload of the CRC multiplier table failed");
-      return 0xffffffffu;
-    }
-    it = h->mult_row.emplace(key, row).first;
-  }
-  return it->second; // (a row INDEX: the table may move while a call's jobs are still being written)
+  return h->mult.row(n_units | (cb ? 0x80000000u : 0u), st, [&](uint32_t* m) { tcod::crc_lane_multipliers(n_units, cb ? 1u : 8u, cb ? 0x800063u : 0x864CFBu, m); });
 }
 
 static uint32_t enc_mult256_row(srsran_hip_sch_enc_t* h, uint32_t n_units, bool cb, hipStream_t st)
 {
-  const uint32_t key = n_units | (cb ? 0x80000000u : 0u);
-  auto           it  = h->mult256_row.find(key);
-  if (it == h->mult256_row.end()) {
-    const uint32_t row = (uint32_t)h->mult256_row.size();
-    if (row >= h->mult256_rows_cap) {
-      const uint32_t cap = h->mult256_rows_cap ? 2 * h->mult256_rows_cap : 16;
-      uint32_t *     nd = nullptr, *nh = nullptr;
-      if (hipMalloc(&nd, (size_t)cap * 256 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&nh, (size_t)cap * 256 * sizeof(uint32_t)) != hipSuccess ||
-          hipDeviceSynchronize() != hipSuccess ||
-          (h->d_mult256 && (hipMemcpy(nd, h->d_mult256, (size_t)row * 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))) {
-        (void)hipFree(nd);
-        (void)hipHostFree(nh);
-        set_error("sch encode: device allocation of the CRC multiplier table failed");
-        return 0xffffffffu;
-      }
-      if (h->h_mult256) {
-        memcpy(nh, h->h_mult256, (size_t)row * 256 * sizeof(uint32_t));
-      }
-      (void)hipFree(h->d_mult256);
-      (void)hipHostFree(h->h_mult256);
-      h->d_mult256        = nd;
-      h->h_mult256        = nh;
-      h->mult256_rows_cap = cap;
-    }
-    uint32_t* m = h->h_mult256 + (size_t)row * 256;
-    tcod::crc_lane_multipliers256(n_units, cb ? 1u : 8u, cb ? 0x800063u : 0x864CFBu, m);
-    if (hipMemcpyAsync(h->d_mult256 + (size_t)row * 256, m, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
-      set_error("sch encode: upload of the CRC multiplier table failed");
-      return 0xffffffffu;
-    }
-    it = h->mult256_row.emplace(key, row).first;
-  }
-  return it->second;
+  return h->mult256.row(n_units | (cb ? 0x80000000u : 0u), st, [&](uint32_t* m) { tcod::crc_lane_multipliers256(n_units, cb ? 1u : 8u, cb ? 0x800063u : 0x864CFBu, m); });
 }
 
 extern "C" int srsran_hip_sch_enc_create(srsran_hip_sch_enc_t** hh)
@@ -422,7 +339,7 @@ extern "C" int srsran_hip_sch_enc_create(srsran_hip_sch_enc_t** hh)
     return SRSRAN_ERROR;
   }
   srsran_hip_sch_enc* h = new srsran_hip_sch_enc;
-  if (hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
+  if (!h->done.ok()) {
     delete h;
     return SRSRAN_ERROR;
   }
@@ -435,16 +352,7 @@ extern "C" void srsran_hip_sch_enc_free(srsran_hip_sch_enc_t* h)
   if (!h) {
     return;
   }
-  if (h->pending) {
-    (void)hipEventSynchronize(h->done);
-  }
-  (void)hipFree(h->d_scratch);
-  (void)hipHostFree(h->h_scratch);
-  (void)hipFree(h->d_mult);
-  (void)hipHostFree(h->h_mult);
-  (void)hipFree(h->d_mult256);
-  (void)hipHostFree(h->h_mult256);
-  (void)hipEventDestroy(h->done);
+  (void)h->done.wait();
   delete h;
 }
 
@@ -481,20 +389,9 @@ extern "C" int srsran_hip_sch_encode(srsran_hip_sch_enc_t* h, const uint8_t* d_d
     n_cb += seg[t].C;
   }
   const size_t bytes = n_cb * sizeof(tcod::TbCbJob) + n_tb * (sizeof(tcod::TbCrcJob) + 4) + 64;
-  if (h->pending) {
-    PHY_HIP_CHECK(hipEventSynchronize(h->done), SRSRAN_ERROR);
-    h->pending = false;
-  }
-  if (bytes > h->cap) {
-    (void)hipFree(h->d_scratch);
-    (void)hipHostFree(h->h_scratch);
-    h->d_scratch = h->h_scratch = nullptr;
-    h->cap                      = 0;
-    PHY_HIP_CHECK(hipMalloc(&h->d_scratch, bytes * 2), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipHostMalloc(&h->h_scratch, bytes * 2), SRSRAN_ERROR);
-    h->cap = bytes * 2;
-  }
-  uint8_t* hb   = static_cast<uint8_t*>(h->h_scratch);
+  PHY_HIP_CHECK(h->done.wait(), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(h->scratch.grow(bytes, bytes)), SRSRAN_ERROR);
+  uint8_t* hb   = h->scratch.h;
   auto*    cbs  = reinterpret_cast<tcod::TbCbJob*>(hb);
   auto*    crcs = reinterpret_cast<tcod::TbCrcJob*>(hb + n_cb * sizeof(tcod::TbCbJob));
   struct KInfo { // what every code block of one size and rv shares; the last look-up is kept (a batch is mostly one block size)
@@ -566,7 +463,7 @@ extern "C" int srsran_hip_sch_encode(srsran_hip_sch_enc_t* h, const uint8_t* d_d
       cbs[at++] = j;
     }
   }
-  uint8_t* db = static_cast<uint8_t*>(h->d_scratch);
+  uint8_t* db = h->scratch.d;
   PHY_HIP_CHECK(hipMemcpyAsync(db, hb, n_cb * sizeof(tcod::TbCbJob) + n_tb * sizeof(tcod::TbCrcJob), hipMemcpyHostToDevice, st), SRSRAN_ERROR);
   tcod::TbParams p{};
   p.data   = d_data;
@@ -576,8 +473,8 @@ extern "C" int srsran_hip_sch_encode(srsran_hip_sch_enc_t* h, const uint8_t* d_d
   p.tb_crc = reinterpret_cast<uint32_t*>(db + n_cb * sizeof(tcod::TbCbJob) + n_tb * sizeof(tcod::TbCrcJob));
   p.n_cb   = (uint32_t)n_cb;
   p.n_tb   = n_tb;
-  p.crc_mult = h->d_mult;
-  p.crc_mult256 = h->d_mult256;
+  p.crc_mult = h->mult.device();
+  p.crc_mult256 = h->mult256.device();
   // the code blocks OR their partial bytes into the output: clear every transport block's range first (adjacent ranges merged)
   std::vector<std::pair<uint32_t, uint32_t>> rng;
   for (uint32_t t = 0; t < n_tb; t++) {
@@ -597,8 +494,7 @@ extern "C" int srsran_hip_sch_encode(srsran_hip_sch_enc_t* h, const uint8_t* d_d
     PHY_HIP_CHECK(tcod::launch_tb_crc24a(p, st), SRSRAN_ERROR);
     PHY_HIP_CHECK(tcod::launch_tb_encode(p, st), SRSRAN_ERROR);
   }
-  PHY_HIP_CHECK(hipEventRecord(h->done, st), SRSRAN_ERROR);
-  h->pending = true;
+  PHY_HIP_CHECK(h->done.record(st), SRSRAN_ERROR);
   return SRSRAN_SUCCESS;
 }
 

@@ -11,6 +11,7 @@
 #include "turbo_layout.h"
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -148,19 +149,18 @@ struct srsran_hip_tdec_batch {
   int      nb      = 0; // 32, 16, 8 (window decoders) or 0 (scalar decoder)
   bool     arith8  = false; // 8-bit window decoder arithmetic (sse8: 16 sub-blocks, avx8: 32)
   // window decoder
-  uint32_t* d_ws     = nullptr;
+  StageBuf<StageMem::Device, uint32_t> d_ws;
   uint32_t  ws_stride = 0;
   uint32_t* d_deint  = nullptr;
   uint32_t* d_inter  = nullptr;
   // scalar decoder
-  short*    d_ws_gen    = nullptr;
+  StageBuf<StageMem::Device, short> d_ws_gen;
   uint16_t* d_inter16   = nullptr;
   uint16_t* d_deinter16 = nullptr;
   // optional parity aid
-  short* d_dec_llr = nullptr;
-  // latency kernel (small batches): its own workspace, allocated on first use for lat_cap code blocks
-  uint32_t* d_ws_lat      = nullptr;
-  uint32_t  lat_cap       = 0;
+  StageBuf<StageMem::Device, short> d_dec_llr;
+  // latency kernel (small batches): its own workspace, allocated on first use (workspace())
+  StageBuf<StageMem::Device, uint32_t> d_ws_lat;
   bool      state_in_lat  = false; // the decoder state of the last launch lives in the latency kernel's workspace
   bool      state_in_gen_lat = false; // scalar decoder: ... in the latency kernel's per-block layout of d_ws_gen
   bool      state_final   = false; // the last launch completed a run (WinParams::final_run): it left no state a later launch could resume
@@ -356,14 +356,10 @@ static Workspace workspace(srsran_hip_tdec_batch* h, Route r, uint32_t n_cb, hip
   } else {
     ws.stride = turbo::lat_ws_dwords(h->K, h->nb);
     bytes     = ws.stride * ((n_cb + 1u) & ~1u) * sizeof(uint32_t);
-    if (!h->arena && n_cb > h->lat_cap) {
+    if (!h->arena && ws.stride * n_cb > h->d_ws_lat.cap()) {
       // the object's own is allocated on first use, for a subframe's worth of blocks at least
-      (void)hipFree(h->d_ws_lat);
-      h->d_ws_lat = nullptr;
-      h->lat_cap  = 0;
       const uint32_t cap = ((n_cb > turbo::kLatMaxBlocks ? n_cb : (h->max_cb < turbo::kLatMaxBlocks ? h->max_cb : turbo::kLatMaxBlocks)) + 1u) & ~1u;
-      PHY_HIP_CHECK(hipMalloc(&h->d_ws_lat, ws.stride * cap * sizeof(uint32_t)), Workspace());
-      h->lat_cap = cap;
+      PHY_HIP_CHECK(grown(h->d_ws_lat.alloc(ws.stride * cap)), Workspace());
     }
     ws.p = h->d_ws_lat;
   }
@@ -510,7 +506,7 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
     set_error("window decoder with %d sub-blocks is invalid for K=%u", nb, long_cb);
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  auto* h   = new srsran_hip_tdec_batch;
+  std::unique_ptr<srsran_hip_tdec_batch> h(new srsran_hip_tdec_batch);
   h->K      = long_cb;
   h->max_cb = max_nof_cb;
   h->nb     = nb;
@@ -528,7 +524,6 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
     bool         contention = false;
     if (!turbo::xch_fits(long_sb, (uint32_t)nb)) {
       set_error("window decoder with %d sub-blocks of %u steps does not fit the exchange-table entry", nb, long_sb);
-      delete h;
       return SRSRAN_ERROR;
     }
     auto         fill_dir = [&](int dir, void* dst) {
@@ -556,17 +551,15 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
     h->d_inter = static_cast<uint32_t*>(cached_const(ckey(CK_INTER, K, nb, 0), tb, [&](void* d) { fill_dir(1, d); }));
     if (contention) {
       set_error("QPP interleaver of K=%u is not contention free for %d windows", K, nb);
-      delete h;
       return SRSRAN_ERROR;
     }
     if (!h->d_deint || !h->d_inter) {
-      delete h;
       return SRSRAN_ERROR;
     }
     if (!arena) {
       // one slab per wave (64/lpc code blocks); round the block count up to whole waves
       const uint32_t cpw = 64 / lpc;
-      PHY_HIP_CHECK(hipMalloc(&h->d_ws, (size_t)h->ws_stride * ceil_div(max_nof_cb, cpw) * cpw * sizeof(uint32_t)), SRSRAN_ERROR);
+      PHY_HIP_CHECK(grown(h->d_ws.grow((size_t)h->ws_stride * ceil_div(max_nof_cb, cpw) * cpw)), SRSRAN_ERROR);
     }
   } else {
     auto fill16 = [&](int dir, void* dst) {
@@ -577,29 +570,20 @@ static int tdec_batch_create(srsran_hip_tdec_batch_t** hh, uint32_t long_cb, uin
     h->d_inter16   = static_cast<uint16_t*>(cached_const(ckey(CK_INTER16, K, 0, 0), K * sizeof(uint16_t), [&](void* d) { fill16(0, d); }));
     h->d_deinter16 = static_cast<uint16_t*>(cached_const(ckey(CK_DEINTER16, K, 0, 0), K * sizeof(uint16_t), [&](void* d) { fill16(1, d); }));
     if (!h->d_inter16 || !h->d_deinter16) {
-      delete h;
       return SRSRAN_ERROR;
     }
     if (!arena) {
       size_t nwaves = ceil_div(max_nof_cb, 64);
-      PHY_HIP_CHECK(hipMalloc(&h->d_ws_gen, turbo::gen_ws_shorts(K) * nwaves * sizeof(short)), SRSRAN_ERROR);
+      PHY_HIP_CHECK(grown(h->d_ws_gen.grow(turbo::gen_ws_shorts(K) * nwaves)), SRSRAN_ERROR);
     }
   }
-  *hh = h;
+  *hh = h.release();
   return SRSRAN_SUCCESS;
 }
 
 extern "C" void srsran_hip_tdec_batch_free(srsran_hip_tdec_batch_t* h)
 {
-  if (!h) {
-    return;
-  }
-  hipFree(h->d_ws);
-  hipFree(h->d_ws_lat);
-  hipFree(h->d_ws_gen);
-  hipFree(h->d_dec_llr);
-  // (exchange / interleaver tables and CRC multipliers belong to the process-wide cache)
-  delete h;
+  delete h; // (exchange / interleaver tables and CRC multipliers belong to the process-wide cache)
 }
 
 // run half iterations [n_begin, n_end) and take the hard decision for n_iter = n_end.  final_run: the caller has no way to resume this
@@ -639,7 +623,7 @@ static int tdec_batch_run_range(srsran_hip_tdec_batch_t* h, const void* d_input,
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   if (want_llr && !h->d_dec_llr) {
-    PHY_HIP_CHECK(hipMalloc(&h->d_dec_llr, (size_t)h->K * h->max_cb * sizeof(short)), SRSRAN_ERROR);
+    PHY_HIP_CHECK(grown(h->d_dec_llr.grow((size_t)h->K * h->max_cb)), SRSRAN_ERROR);
   }
   const Route     r  = route(h, n_cb, n_begin);
   const Workspace ws = workspace(h, r, n_cb, stream);
@@ -853,14 +837,13 @@ bool phyhip::turbo::prebuild_tables()
 namespace {
 struct TdecCtx {
   DeviceTag   tag;
-  hipStream_t stream = nullptr;
+  StageStream stream;
   // one batch object (max_cb = 1) per (K, nb), created on first use
   std::map<uint64_t, srsran_hip_tdec_batch_t*> dec;
-  int16_t* d_in  = nullptr; // 3*(Kmax+32)+12
-  uint8_t* d_out = nullptr; // Kmax/8
-  int16_t* h_in  = nullptr; // pinned
-  uint8_t* h_out = nullptr; // pinned
-  size_t   in_cap = 0;
+  StageBuf<StageMem::Device, int16_t> d_in;  // 3*(Kmax+32)+12
+  DeviceBuf                           d_out; // Kmax/8
+  StageBuf<StageMem::Pinned, int16_t> h_in;
+  StageBuf<StageMem::Pinned>          h_out;
   bool     dev_state_valid = false; // the handle's own batch object holds the decoder state of the current code block
 };
 
@@ -918,14 +901,18 @@ extern "C" int srsran_tdec_init_manual(srsran_tdec_t* h, uint32_t max_long_cb, s
   } else {
     h->nof_blocks16[0] = dec_type == SRSRAN_TDEC_GENERIC ? 1 : (dec_type == SRSRAN_TDEC_SSE_WINDOW ? 8 : 16);
   }
-  auto* c   = new TdecCtx;
-  c->in_cap = 3 * ((size_t)max_long_cb + 32) + 12;
-  PHY_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipMalloc(&c->d_in, c->in_cap * sizeof(int16_t)), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipMalloc(&c->d_out, max_long_cb / 8 + 8), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipHostMalloc(&c->h_in, c->in_cap * sizeof(int16_t)), SRSRAN_ERROR);
-  PHY_HIP_CHECK(hipHostMalloc(&c->h_out, max_long_cb / 8 + 8), SRSRAN_ERROR);
-  h->dec16_hdlr[0] = c;
+  std::unique_ptr<TdecCtx> c(new TdecCtx);
+  const size_t             in_cap = 3 * ((size_t)max_long_cb + 32) + 12;
+  if (!c->stream.open()) {
+    set_error("srsran_tdec_init: cannot create a stream");
+    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+    return SRSRAN_ERROR;
+  }
+  PHY_HIP_CHECK(grown(c->d_in.grow(in_cap)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(c->d_out.grow(max_long_cb / 8 + 8)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(c->h_in.grow(in_cap)), SRSRAN_ERROR);
+  PHY_HIP_CHECK(grown(c->h_out.grow(max_long_cb / 8 + 8)), SRSRAN_ERROR);
+  h->dec16_hdlr[0] = c.release();
   return SRSRAN_SUCCESS;
 }
 
@@ -935,13 +922,6 @@ extern "C" void srsran_tdec_free(srsran_tdec_t* h)
   if (c) {
     for (auto& kv : c->dec) {
       srsran_hip_tdec_batch_free(kv.second);
-    }
-    hipFree(c->d_in);
-    hipFree(c->d_out);
-    hipHostFree(c->h_in);
-    hipHostFree(c->h_out);
-    if (c->stream) {
-      hipStreamDestroy(c->stream);
     }
     delete c;
   }

@@ -34,6 +34,13 @@ inline int no_device(const char* who) // behind a context's ready() == false
   return failed(who, (std::string(get_error()) + " (there is no CPU fallback)").c_str());
 }
 
+inline int device_failed(const char* who, hipError_t e) // the last-error text is "who: the device's error" and stands on stderr, one line
+{
+  set_error("%s: %s", who, hipGetErrorString(e));
+  fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+  return SRSRAN_ERROR;
+}
+
 // the call's one host wait; the first error of what was enqueued (e) and the wait
 inline hipError_t settle(hipError_t e, hipStream_t st)
 {
@@ -42,7 +49,7 @@ inline hipError_t settle(hipError_t e, hipStream_t st)
 }
 
 // [0, up_bytes) of pin to dev, enqueue(st) -- the call's launches chained, the first error returned --, [down_off, down_off + down_bytes) of dev to pin, settle.
-// false: the last-error text is "who: the device's error" and stands on stderr, one line.
+// false: device_failed(who, the first error).
 template <class Enqueue>
 bool round_trip(const char* who, hipStream_t st, uint8_t* pin, uint8_t* dev, size_t up_bytes, size_t down_off, size_t down_bytes, Enqueue&& enqueue)
 {
@@ -55,8 +62,7 @@ bool round_trip(const char* who, hipStream_t st, uint8_t* pin, uint8_t* dev, siz
   }
   e = settle(e, st);
   if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
-    fprintf(stderr, "[srsran_phy_hip] %s\n", get_error());
+    device_failed(who, e);
   }
   return e == hipSuccess;
 }

@@ -53,14 +53,18 @@ int check_tb(const char* who, uint32_t i, const srsran_hip_nr_tb_t& tb, uint32_t
 }
 
 struct RxCw { // one codeword of a receive call
-  TbCfg    c;
-  uint32_t first_cb;
-  bool     fresh;              // rows are written, not accumulated into, and not uploaded
-  bool     any_flag;
-  int      first, last;        // undecoded blocks on entry
-  size_t   o_sym, o_ce, o_e, o_pay;
-  uint8_t  flags_in[NrTbStage::MAX_CB];
+  TbCfg      c;
+  uint32_t   first_cb;
+  size_t     o_sym, o_ce, o_e, o_pay;
+  SoftStager harq; // its soft buffer, in and out
 };
+
+// the one line of a call that failed behind its first enqueue: the step, and what that step left as the last error
+int failed_at(const char* who, const char* what)
+{
+  fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
+  return SRSRAN_ERROR;
+}
 
 // grids == nullptr: the codewords come as extracted REs (symbols, ce).  Else symbols and ce are not looked at: codeword i is described by grids[i] on the
 // one slot grid sf_symbols, the estimator and the de-mapper (nr_chest_kernels.hip) run in front of the front end and leave its inputs in the device
@@ -127,8 +131,7 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
   }
   NrTbStage& s = tb_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   // ---- layout
   const size_t o_soft = 0, o_data = al256(o_soft + (size_t)n_cb * sb_stride);
@@ -170,8 +173,7 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     NR_CW_REFUSE("%s: %zu bytes of symbols and soft bits in one call", who, o - o_in);
   }
   if (!s.grow(o)) {
-    fprintf(stderr, "[srsran_phy_hip] %s: staging allocation failed\n", who);
-    return SRSRAN_ERROR;
+    return call::failed(who, "staging allocation failed");
   }
   JobList<nrchan::FrontJob> jobs(s.pin, jl.o_jobs, jl.o_tj);
   nrchan::FrontParams       fp;
@@ -179,8 +181,7 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
   {
     modem::Params mp;
     if (!modem::params_for(mp, modem::LLR_I8)) {
-      fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
-      return SRSRAN_ERROR;
+      return call::failed(who, get_error());
     }
     fp.in       = grids ? reinterpret_cast<const float2*>(s.dev + o_in) : reinterpret_cast<const float2*>(s.pin + o_in);
     fp.noise_dev = grids ? reinterpret_cast<const float*>(s.dev + o_noise) : nullptr;
@@ -191,184 +192,138 @@ int nr_cw_decode(uint32_t n, const srsran_hip_nr_cw_rx_t* g, const cf_t* const* 
     fp.n_tiles  = n_tiles;
     fp.x1_bits = mp.x1_bits, fp.x2_cols = mp.x2_cols, fp.k = mp.k;
   }
-  // ---- staging: symbols, estimates, job lists; rows and stored blocks of retransmissions
-  uint8_t flags[NrTbStage::MAX_CB];
+  uint8_t                         flags[NrTbStage::MAX_CB];
   std::vector<srsran_hip_nr_tb_t> tbs(n);
-  for (uint32_t i = 0; i < n; i++) {
-    RxCw&                         w  = cw[i];
-    const TbCfg&                  c  = w.c;
-    const srsran_softbuffer_rx_t* sb = softbuffers[i];
-    const size_t                  nb = (size_t)g[i].nof_re * sizeof(cf_t);
-    const bool                    eq = grids || (ce && ce[i]);
-    if (!grids) {
-      memcpy(s.pin + w.o_sym, symbols[i], nb);
-      if (eq) {
-        memcpy(s.pin + w.o_ce, ce[i], nb);
-      }
-    }
-    const uint32_t nt = modem::tiles_of(g[i].tb.mod, g[i].nof_re);
-    jobs.jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
-                                    (uint32_t)(w.o_e - o_e), g[i].seed, jobs.append(i, nt), nt, g[i].noise_estimate, g[i].noise_estimate > 0.f ? 1u : 0u};
-    const bool new_data = (g[i].tb.rv & SRSRAN_HIP_NR_TB_NEW_DATA) != 0;
-    const uint32_t cb_bytes = (c.Kp - c.L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (sch_nr.c:650-652)
-    bool any_soft = false;
-    w.any_flag = false, w.first = w.last = -1;
-    for (uint32_t r = 0; r < c.C; r++) {
-      const uint8_t f = (!new_data && sb->cb_crc[r]) ? 1 : 0;
-      w.flags_in[r] = flags[w.first_cb + r] = f;
-      if (f) {
-        w.any_flag = true;
-        memcpy(s.pin + o_data + (size_t)(w.first_cb + r) * data_stride, sb->data[r], cb_bytes); // decoded earlier: its packed bits join the assembly
-      } else {
-        any_soft = any_soft || (!new_data && !all_zero(reinterpret_cast<const uint8_t*>(sb->buffer_f[r]), c.N));
-        w.first  = w.first < 0 ? (int)r : w.first;
-        w.last   = (int)r;
-      }
-    }
-    w.fresh = new_data || (!any_soft && !w.any_flag); // rows as srsran_softbuffer_rx_reset left them: written, not accumulated into, and not uploaded
-    if (!w.fresh && w.first >= 0) {
-      const size_t lo = o_soft + (size_t)(w.first_cb + w.first) * sb_stride;
-      for (int r = w.first; r <= w.last; r++) {
-        if (!w.flags_in[r]) {
-          memcpy(s.pin + o_soft + (size_t)(w.first_cb + r) * sb_stride, sb->buffer_f[r], c.N);
+  nr_chest::Record*               rec = reinterpret_cast<nr_chest::Record*>(s.pin + o_rec);
+  // Everything the call enqueues in front of its host wait (the last transport-block pass takes it).  nullptr, or the step that failed, its text the last
+  // error: nothing more is enqueued then, and the ONE exit below waits for what was.
+  auto enqueue = [&]() -> const char* {
+    // ---- staging: symbols, estimates, job lists; rows and stored blocks of retransmissions
+    for (uint32_t i = 0; i < n; i++) {
+      RxCw&        w  = cw[i];
+      const size_t nb = (size_t)g[i].nof_re * sizeof(cf_t);
+      const bool   eq = grids || (ce && ce[i]);
+      if (!grids) {
+        memcpy(s.pin + w.o_sym, symbols[i], nb);
+        if (eq) {
+          memcpy(s.pin + w.o_ce, ce[i], nb);
         }
       }
-      PHY_HIP_CHECK(hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)(w.last - w.first) * sb_stride + c.N, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+      const uint32_t nt = modem::tiles_of(g[i].tb.mod, g[i].nof_re);
+      jobs.jobs[i] = nrchan::FrontJob{g[i].tb.mod, g[i].nof_re, (uint32_t)((w.o_sym - o_in) / sizeof(cf_t)), eq ? (uint32_t)((w.o_ce - o_in) / sizeof(cf_t)) : NR_CHAN_NO_CE,
+                                      (uint32_t)(w.o_e - o_e), g[i].seed, jobs.append(i, nt), nt, g[i].noise_estimate, g[i].noise_estimate > 0.f ? 1u : 0u};
+      const hipError_t e = w.harq.stage_in(s, softbuffers[i], w.c, w.first_cb, o_soft, sb_stride, o_data, data_stride,
+                                           (g[i].tb.rv & SRSRAN_HIP_NR_TB_NEW_DATA) != 0, flags); // (codeword 0: the call's first enqueue on s.st)
+      if (e != hipSuccess) {
+        set_error("%s", hipGetErrorString(e));
+        return "soft buffer";
+      }
+      tbs[i]                = g[i].tb;
+      tbs[i].rv             = (g[i].tb.rv & 3u) | (w.harq.fresh ? SRSRAN_HIP_NR_TB_NEW_DATA : 0u);
+      tbs[i].e_offset       = (uint32_t)(w.o_e - o_e);
+      tbs[i].payload_offset = (uint32_t)(w.o_pay - o_pay);
+      tbs[i].first_cb       = w.first_cb;
     }
-    if (w.any_flag) {
-      const size_t lo = o_data + (size_t)w.first_cb * data_stride;
-      PHY_HIP_CHECK(hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)c.C * data_stride, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
+    // ---- one front-end launch over all codewords, one transport-block pass per (scaling factor, iterations)
+    if (grids) { // the grid is staged once; every codeword has its own table and its own workgroup of the estimator
+      memcpy(s.pin + o_grid, sf_symbols, (size_t)grid_points * sizeof(cf_t));
+      nr_map::Seg*        tab  = reinterpret_cast<nr_map::Seg*>(s.pin + o_tab);
+      uint16_t*           prbs = reinterpret_cast<uint16_t*>(s.pin + o_prbs);
+      nr_chest::EstJob*   ej   = reinterpret_cast<nr_chest::EstJob*>(s.pin + o_ej);
+      nr_chest::DemapJob* dj   = reinterpret_cast<nr_chest::DemapJob*>(s.pin + o_dj);
+      uint32_t            t0 = 0, p0 = 0, max_seg = 0;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ns = nr_map::fill_table(grids[i], tab + t0);
+        nr_chest::fill_job(grids[i], &ej[i], prbs + p0);
+        ej[i].o_prb = p0, ej[i].o_tab = t0, ej[i].n_seg = ns, ej[i].o_ce = (uint32_t)((cw[i].o_ce - o_in) / sizeof(cf_t)), ej[i].nof_re = g[i].nof_re;
+        dj[i]   = nr_chest::DemapJob{t0, ns, (uint32_t)((cw[i].o_sym - o_in) / sizeof(cf_t)), g[i].nof_re};
+        max_seg = std::max(max_seg, ns);
+        t0 += ns, p0 += ej[i].n_prbs;
+      }
+      // one upload of the grid, the tables and the jobs: every codeword's workgroups read them, the estimator's several times
+      hipError_t                e      = hipMemcpyAsync(s.dev + o_grid, s.pin + o_grid, o_rec - o_grid, hipMemcpyHostToDevice, s.st);
+      const float2*             d_grid = reinterpret_cast<const float2*>(s.dev + o_grid);
+      const nr_map::Seg*        d_tab  = reinterpret_cast<const nr_map::Seg*>(s.dev + o_tab);
+      const uint32_t            io_points = (uint32_t)((o_e - o_in) / sizeof(cf_t));
+      nr_chest::DemapParams dp{d_grid, grid_points, reinterpret_cast<const nr_chest::DemapJob*>(s.dev + o_dj), n, max_seg, d_tab, n_seg_total,
+                               reinterpret_cast<float2*>(s.dev + o_in), io_points};
+      nr_chest::EstParams   ep{d_grid, grid_points, reinterpret_cast<const nr_chest::EstJob*>(s.dev + o_ej), reinterpret_cast<const uint16_t*>(s.dev + o_prbs), n_prbs_total,
+                             d_tab, n_seg_total, reinterpret_cast<float2*>(s.dev + o_in), io_points, rec, reinterpret_cast<float*>(s.dev + o_noise), n, max_seg, mp_x1, mp_x2};
+      if (e == hipSuccess) {
+        e = nr_chest::launch_demap(dp, s.st);
+      }
+      if (e == hipSuccess) {
+        e = nr_chest::launch_est(ep, s.st);
+      }
+      if (e != hipSuccess) {
+        set_error("grid upload / nr_demap_kernel / nr_dmrs_est_kernel: %s", hipGetErrorString(e));
+        return "estimator";
+      }
     }
-    tbs[i]                = g[i].tb;
-    tbs[i].rv             = (g[i].tb.rv & 3u) | (w.fresh ? SRSRAN_HIP_NR_TB_NEW_DATA : 0u);
-    tbs[i].e_offset       = (uint32_t)(w.o_e - o_e);
-    tbs[i].payload_offset = (uint32_t)(w.o_pay - o_pay);
-    tbs[i].first_cb       = w.first_cb;
-  }
-  // ---- one front-end launch over all codewords, one transport-block pass per (scaling factor, iterations)
-  auto fail = [&](const char* what) {
-    (void)hipStreamSynchronize(s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
-    fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
-    return SRSRAN_ERROR;
-  };
-  nr_chest::Record* rec = reinterpret_cast<nr_chest::Record*>(s.pin + o_rec);
-  if (grids) { // the grid is staged once; every codeword has its own table and its own workgroup of the estimator
-    memcpy(s.pin + o_grid, sf_symbols, (size_t)grid_points * sizeof(cf_t));
-    nr_map::Seg*        tab  = reinterpret_cast<nr_map::Seg*>(s.pin + o_tab);
-    uint16_t*           prbs = reinterpret_cast<uint16_t*>(s.pin + o_prbs);
-    nr_chest::EstJob*   ej   = reinterpret_cast<nr_chest::EstJob*>(s.pin + o_ej);
-    nr_chest::DemapJob* dj   = reinterpret_cast<nr_chest::DemapJob*>(s.pin + o_dj);
-    uint32_t            t0 = 0, p0 = 0, max_seg = 0;
-    for (uint32_t i = 0; i < n; i++) {
-      const uint32_t ns = nr_map::fill_table(grids[i], tab + t0);
-      nr_chest::fill_job(grids[i], &ej[i], prbs + p0);
-      ej[i].o_prb = p0, ej[i].o_tab = t0, ej[i].n_seg = ns, ej[i].o_ce = (uint32_t)((cw[i].o_ce - o_in) / sizeof(cf_t)), ej[i].nof_re = g[i].nof_re;
-      dj[i]   = nr_chest::DemapJob{t0, ns, (uint32_t)((cw[i].o_sym - o_in) / sizeof(cf_t)), g[i].nof_re};
-      max_seg = std::max(max_seg, ns);
-      t0 += ns, p0 += ej[i].n_prbs;
-    }
-    // one upload of the grid, the tables and the jobs: every codeword's workgroups read them, the estimator's several times
-    PHY_HIP_CHECK(hipMemcpyAsync(s.dev + o_grid, s.pin + o_grid, o_rec - o_grid, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-    const float2*             d_grid = reinterpret_cast<const float2*>(s.dev + o_grid);
-    const nr_map::Seg*        d_tab  = reinterpret_cast<const nr_map::Seg*>(s.dev + o_tab);
-    const uint32_t            io_points = (uint32_t)((o_e - o_in) / sizeof(cf_t));
-    nr_chest::DemapParams dp{d_grid, grid_points, reinterpret_cast<const nr_chest::DemapJob*>(s.dev + o_dj), n, max_seg, d_tab, n_seg_total,
-                             reinterpret_cast<float2*>(s.dev + o_in), io_points};
-    nr_chest::EstParams   ep{d_grid, grid_points, reinterpret_cast<const nr_chest::EstJob*>(s.dev + o_ej), reinterpret_cast<const uint16_t*>(s.dev + o_prbs), n_prbs_total,
-                           d_tab, n_seg_total, reinterpret_cast<float2*>(s.dev + o_in), io_points, rec, reinterpret_cast<float*>(s.dev + o_noise), n, max_seg, mp_x1, mp_x2};
-    hipError_t            e = nr_chest::launch_demap(dp, s.st);
-    if (e == hipSuccess) {
-      e = nr_chest::launch_est(ep, s.st);
-    }
-    if (e != hipSuccess) {
-      set_error("nr_demap_kernel / nr_dmrs_est_kernel: %s", hipGetErrorString(e));
-      return fail("estimator");
-    }
-  }
-  {
-    const hipError_t e = nrchan::launch_front(fp, s.st);
-    if (e != hipSuccess) {
+    if (const hipError_t e = nrchan::launch_front(fp, s.st); e != hipSuccess) {
       set_error("nr_front_kernel: %s", hipGetErrorString(e));
-      return fail("front end");
+      return "front end";
     }
-  }
-  std::vector<uint32_t> order(n);
-  for (uint32_t i = 0; i < n; i++) {
-    order[i] = i;
-  }
-  auto dec_key = [&](uint32_t i) {
-    const float sc = std::isnormal(g[i].scaling_fctr) ? g[i].scaling_fctr : 0.8f; // sch_nr.c:275
-    uint32_t    b;
-    memcpy(&b, &sc, 4);
-    return ((uint64_t)b << 32) | (g[i].max_nof_iter ? g[i].max_nof_iter : 10u);
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) {
+      order[i] = i;
+    }
+    auto dec_key = [&](uint32_t i) {
+      const float sc = std::isnormal(g[i].scaling_fctr) ? g[i].scaling_fctr : 0.8f; // sch_nr.c:275
+      uint32_t    b;
+      memcpy(&b, &sc, 4);
+      return ((uint64_t)b << 32) | (g[i].max_nof_iter ? g[i].max_nof_iter : 10u);
+    };
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return dec_key(a) < dec_key(b); });
+    std::vector<srsran_hip_nr_tb_t>        gtb;
+    std::vector<srsran_hip_nr_tb_result_t> gres;
+    for (uint32_t i = 0; i < n;) {
+      uint32_t e = i;
+      gtb.clear();
+      while (e < n && dec_key(order[e]) == dec_key(order[i])) {
+        gtb.push_back(tbs[order[e]]);
+        e++;
+      }
+      gres.assign(gtb.size(), srsran_hip_nr_tb_result_t{});
+      const uint32_t       i0 = order[i];
+      srsran_hip_sch_nr_t* h  = s.decoder(std::isnormal(g[i0].scaling_fctr) ? g[i0].scaling_fctr : 0.8f, g[i0].max_nof_iter ? g[i0].max_nof_iter : 10u);
+      if (!h) {
+        return "decoder object";
+      }
+      // the last pass carries the downloads in front of its host wait: stored code blocks, payloads, and the soft bits where they are asked for
+      const TailCopy tail[3] = {{s.pin + o_data, s.dev + o_data, (size_t)n_cb * data_stride}, {s.pin + o_pay, s.dev + o_pay, pay_bytes},
+                                {s.pin + o_e, s.dev + o_e, e_out ? e_bytes : 0}};
+      if (sch_nr_decode(h, reinterpret_cast<const int8_t*>(s.dev + o_e), gtb.data(), (uint32_t)gtb.size(), reinterpret_cast<int8_t*>(s.dev + o_soft), sb_stride,
+                        flags, s.dev + o_data, data_stride, s.dev + o_pay, gres.data(), s.st, tail, e == n ? 3 : 0) != SRSRAN_SUCCESS) {
+        return "transport blocks";
+      }
+      for (uint32_t k = i; k < e; k++) {
+        res[order[k]] = gres[k - i];
+      }
+      i = e;
+    }
+    return nullptr;
   };
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return dec_key(a) < dec_key(b); });
-  std::vector<srsran_hip_nr_tb_t>        gtb;
-  std::vector<srsran_hip_nr_tb_result_t> gres;
-  for (uint32_t i = 0; i < n;) {
-    uint32_t e = i;
-    gtb.clear();
-    while (e < n && dec_key(order[e]) == dec_key(order[i])) {
-      gtb.push_back(tbs[order[e]]);
-      e++;
-    }
-    gres.assign(gtb.size(), srsran_hip_nr_tb_result_t{});
-    const uint32_t       i0 = order[i];
-    srsran_hip_sch_nr_t* h  = s.decoder(std::isnormal(g[i0].scaling_fctr) ? g[i0].scaling_fctr : 0.8f, g[i0].max_nof_iter ? g[i0].max_nof_iter : 10u);
-    if (!h) {
-      return fail("decoder object");
-    }
-    // the last pass carries the downloads in front of its host wait: stored code blocks, payloads, and the soft bits where they are asked for
-    const TailCopy tail[3] = {{s.pin + o_data, s.dev + o_data, (size_t)n_cb * data_stride}, {s.pin + o_pay, s.dev + o_pay, pay_bytes},
-                              {s.pin + o_e, s.dev + o_e, e_out ? e_bytes : 0}};
-    if (sch_nr_decode(h, reinterpret_cast<const int8_t*>(s.dev + o_e), gtb.data(), (uint32_t)gtb.size(), reinterpret_cast<int8_t*>(s.dev + o_soft), sb_stride,
-                      flags, s.dev + o_data, data_stride, s.dev + o_pay, gres.data(), s.st, tail, e == n ? 3 : 0) != SRSRAN_SUCCESS) {
-      return fail("transport blocks");
-    }
-    for (uint32_t k = i; k < e; k++) {
-      res[order[k]] = gres[k - i];
-    }
-    i = e;
+  if (const char* what = enqueue()) {
+    (void)call::settle(hipSuccess, s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
+    return failed_at(who, what);
   }
-  // ---- host side effects of sch_nr.c:633-652: flags, the packed bits of the blocks decoded now; rows of the blocks that are still undecoded
-  bool rows_left = false;
-  for (uint32_t i = 0; i < n; i++) {
-    RxCw&                   w  = cw[i];
-    srsran_softbuffer_rx_t* sb = softbuffers[i];
-    const uint32_t          cb_bytes = (w.c.Kp - w.c.L_cb + 7) / 8;
-    w.first = w.last = -1;
-    for (uint32_t r = 0; r < w.c.C; r++) {
-      if (w.flags_in[r]) {
-        continue;
-      }
-      if (flags[w.first_cb + r]) {
-        sb->cb_crc[r] = true;
-        memcpy(sb->data[r], s.pin + o_data + (size_t)(w.first_cb + r) * data_stride, cb_bytes);
-      } else {
-        sb->cb_crc[r] = false;
-        w.first       = w.first < 0 ? (int)r : w.first;
-        w.last        = (int)r;
-      }
-    }
-    if (w.first >= 0) {
-      const size_t lo = o_soft + (size_t)(w.first_cb + w.first) * sb_stride;
-      PHY_HIP_CHECK(hipMemcpyAsync(s.pin + lo, s.dev + lo, (size_t)(w.last - w.first) * sb_stride + w.c.N, hipMemcpyDeviceToHost, s.st), SRSRAN_ERROR);
-      rows_left = true;
-    }
+  // ---- the soft buffers' side of the results; the rows of the blocks that are still undecoded are the one enqueue behind that wait, and take one of their own
+  hipError_t e         = hipSuccess;
+  bool       rows_left = false;
+  for (uint32_t i = 0; i < n && e == hipSuccess; i++) {
+    e         = cw[i].harq.fetch(s, flags);
+    rows_left = rows_left || cw[i].harq.first >= 0;
   }
   if (rows_left) {
-    PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
+    e = call::settle(e, s.st);
+  }
+  if (e != hipSuccess) {
+    return call::device_failed(who, e);
   }
   for (uint32_t i = 0; i < n; i++) {
-    const RxCw&             w  = cw[i];
-    srsran_softbuffer_rx_t* sb = softbuffers[i];
-    // (the circular buffer of a block ends at Ncb = min(N, Nref), ldpc_rm.c:704-705: nothing behind it is ever written or read)
-    const uint32_t n_cb_buf = w.c.N <= w.c.Nref ? w.c.N : w.c.Nref;
-    for (int r = w.first; w.first >= 0 && r <= w.last; r++) {
-      if (!sb->cb_crc[r]) {
-        memcpy(sb->buffer_f[r], s.pin + o_soft + (size_t)(w.first_cb + r) * sb_stride, n_cb_buf);
-      }
-    }
+    const RxCw& w = cw[i];
+    w.harq.finish(s);
     if (res[i].all_decoded) { // sch_nr.c:664-666: otherwise the payload is not touched
       memcpy(payloads[i], s.pin + w.o_pay, w.c.A / 8);
     }
@@ -412,8 +367,7 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
   }
   NrTbStage& s = tb_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s (there is no CPU fallback)\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   srsran_hip_sch_nr_t* h = s.decoder(0.8f, 10); // (the transmit side has no decoder parameters: one object per thread)
   if (!h) {
@@ -444,8 +398,7 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
   modem::Params mp;
   const float2* tab = modem::mod_tables();
   if (!s.grow(o) || !modem::params_for(mp, modem::LLR_I8) || !tab) {
-    fprintf(stderr, "[srsran_phy_hip] %s: %s\n", who, get_error());
-    return SRSRAN_ERROR;
+    return call::failed(who, get_error());
   }
   JobList<nrchan::ModJob>         jobs(s.pin, jl.o_jobs, jl.o_tj);
   std::vector<srsran_hip_nr_tb_t> tbs(n);
@@ -459,24 +412,21 @@ int nr_cw_encode(uint32_t n, const srsran_hip_nr_cw_tx_t* g, const uint8_t* cons
     const float    scale  = (g[i].scaling != 0.f && !std::isnan(g[i].scaling)) ? g[i].scaling : 1.0f;
     jobs.jobs[i] = nrchan::ModJob{g[i].tb.mod, g[i].nof_re, g[i].seed, scale, (uint32_t)(o_e[i] - e0), (uint32_t)((o_sym[i] - s0) / sizeof(cf_t)), jobs.append(i, nt), nt};
   }
-  auto fail = [&](const char* what) {
-    (void)hipStreamSynchronize(s.st);
-    fprintf(stderr, "[srsran_phy_hip] %s: %s: %s\n", who, what, get_error());
-    return SRSRAN_ERROR;
-  };
-  // the coding kernels read the payloads from the pinned image; the rate matcher's bits stay on the device; the modulator writes the pinned image
-  if (srsran_hip_sch_nr_encode(h, s.pin, tbs.data(), n, s.dev + e0, s.st) != SRSRAN_SUCCESS) {
-    return fail("transport blocks");
-  }
   nrchan::ModParams p;
   p.bits = s.dev + e0, p.out = reinterpret_cast<float2*>(s.pin + s0), p.table = tab, p.jobs = jobs.jobs, p.tile_job = jobs.tile_job, p.n_tiles = n_tiles;
   p.x1_bits = mp.x1_bits, p.x2_cols = mp.x2_cols;
-  const hipError_t e = nrchan::launch_mod(p, s.st);
-  if (e != hipSuccess) {
+  // the coding kernels read the payloads from the pinned image; the rate matcher's bits stay on the device; the modulator writes the pinned image
+  const char* what = nullptr; // the step that could not be enqueued, its text the last error
+  if (srsran_hip_sch_nr_encode(h, s.pin, tbs.data(), n, s.dev + e0, s.st) != SRSRAN_SUCCESS) {
+    what = "transport blocks";
+  } else if (const hipError_t e = nrchan::launch_mod(p, s.st); e != hipSuccess) {
     set_error("nr_mod_kernel: %s", hipGetErrorString(e));
-    return fail("modulator");
+    what = "modulator";
   }
-  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
+  const hipError_t w = call::settle(hipSuccess, s.st); // the call's one host wait, whether or not everything was enqueued
+  if (what || w != hipSuccess) {
+    return what ? failed_at(who, what) : call::device_failed(who, w);
+  }
   for (uint32_t i = 0; i < n; i++) {
     memcpy(symbols[i], s.pin + o_sym[i], (size_t)g[i].nof_re * sizeof(cf_t));
   }

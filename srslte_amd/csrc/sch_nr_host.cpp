@@ -486,6 +486,78 @@ NrTbStage& phyhip::nrtb::tb_stage()
   return ref.get();
 }
 
+hipError_t SoftStager::stage_in(NrTbStage& s, srsran_softbuffer_rx_t* softbuffer, const TbCfg& cfg, uint32_t first_code_block, size_t soft_off,
+                                uint32_t soft_stride, size_t data_off, uint32_t row_stride, bool new_data, uint8_t* flags)
+{
+  sb = softbuffer, c = &cfg, first_cb = first_code_block, o_soft = soft_off, sb_stride = soft_stride, o_data = data_off, data_stride = row_stride;
+  const uint32_t cb_bytes = (c->Kp - c->L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (:650-652)
+  bool           any_soft = false;
+  any_flag = false, first = last = -1;
+  for (uint32_t r = 0; r < c->C; r++) {
+    const uint8_t f = (!new_data && sb->cb_crc[r]) ? 1 : 0;
+    flags_in[r] = flags[first_cb + r] = f;
+    if (f) {
+      any_flag = true;
+      memcpy(s.pin + o_data + (size_t)(first_cb + r) * data_stride, sb->data[r], cb_bytes); // decoded earlier: its packed bits join the assembly
+    } else {
+      any_soft = any_soft || (!new_data && !all_zero(reinterpret_cast<const uint8_t*>(sb->buffer_f[r]), c->N));
+      first    = first < 0 ? (int)r : first;
+      last     = (int)r;
+    }
+  }
+  fresh        = new_data || (!any_soft && !any_flag); // rows as srsran_softbuffer_rx_reset left them: written, not accumulated into, and not uploaded
+  hipError_t e = hipSuccess;
+  if (!fresh && first >= 0) { // a retransmission: the rows hold the earlier transmissions' soft bits
+    for (int r = first; r <= last; r++) {
+      if (!flags_in[r]) {
+        memcpy(s.pin + o_soft + (size_t)(first_cb + r) * sb_stride, sb->buffer_f[r], c->N);
+      }
+    }
+    const size_t lo = o_soft + (size_t)(first_cb + first) * sb_stride;
+    e               = hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)(last - first) * sb_stride + c->N, hipMemcpyHostToDevice, s.st);
+  }
+  if (any_flag && e == hipSuccess) {
+    const size_t lo = o_data + (size_t)first_cb * data_stride;
+    e               = hipMemcpyAsync(s.dev + lo, s.pin + lo, (size_t)c->C * data_stride, hipMemcpyHostToDevice, s.st);
+  }
+  return e;
+}
+
+hipError_t SoftStager::fetch(NrTbStage& s, const uint8_t* flags)
+{
+  const uint32_t cb_bytes = (c->Kp - c->L_cb + 7) / 8;
+  first = last = -1;
+  for (uint32_t r = 0; r < c->C; r++) {
+    if (flags_in[r]) {
+      continue;
+    }
+    if (flags[first_cb + r]) {
+      sb->cb_crc[r] = true;
+      memcpy(sb->data[r], s.pin + o_data + (size_t)(first_cb + r) * data_stride, cb_bytes);
+    } else {
+      sb->cb_crc[r] = false;
+      first         = first < 0 ? (int)r : first;
+      last          = (int)r;
+    }
+  }
+  if (first < 0) {
+    return hipSuccess;
+  }
+  const size_t lo = o_soft + (size_t)(first_cb + first) * sb_stride;
+  return hipMemcpyAsync(s.pin + lo, s.dev + lo, (size_t)(last - first) * sb_stride + c->N, hipMemcpyDeviceToHost, s.st);
+}
+
+void SoftStager::finish(NrTbStage& s) const
+{
+  // (the circular buffer of a block ends at Ncb = min(N, Nref), ldpc_rm.c:704-705: nothing behind it is ever written or read)
+  const uint32_t n_cb_buf = c->N <= c->Nref ? c->N : c->Nref;
+  for (int r = first; first >= 0 && r <= last; r++) {
+    if (!sb->cb_crc[r]) {
+      memcpy(sb->buffer_f[r], s.pin + o_soft + (size_t)(first_cb + r) * sb_stride, n_cb_buf);
+    }
+  }
+}
+
 extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_iter, const srsran_hip_nr_tb_t* tb_in, const int8_t* e_bits,
                                            srsran_softbuffer_rx_t* softbuffer, uint8_t* payload, bool* crc, float* avg_iter)
 {
@@ -500,10 +572,10 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
   if (softbuffer->max_cb < c.C || softbuffer->max_cb_size < c.N || c.C > NrTbStage::MAX_CB) { // :556-559
     return SRSRAN_ERROR;
   }
-  NrTbStage& s = tb_stage();
+  static const char* who = "sch_nr decode";
+  NrTbStage&         s   = tb_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] sch_nr decode: %s (there is no CPU fallback)\n", get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   srsran_hip_sch_nr_t* h = s.decoder(scaling_fctr, max_nof_iter);
   if (!h) {
@@ -511,12 +583,9 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
   }
   const uint32_t sb_stride  = (uint32_t)al256(c.N);
   const uint32_t data_stride = (uint32_t)al256((c.Kr + 7) / 8);
-  const uint32_t cb_bytes   = (c.Kp - c.L_cb + 7) / 8; // packed bits of a decoded code block, softbuffer.rx->data[r] (:650-652)
-  uint8_t        flags[NrTbStage::MAX_CB];
   size_t         n_e = 0;
   for (uint32_t r = 0; r < c.C; r++) {
-    flags[r] = softbuffer->cb_crc[r] ? 1 : 0;
-    if (!flags[r]) {
+    if (!softbuffer->cb_crc[r]) {
       n_e += get_E(c, r); // the input holds the soft bits of the still undecoded blocks, back to back (:665)
     }
     if (!softbuffer->buffer_f[r] || !softbuffer->data[r]) {
@@ -526,76 +595,29 @@ extern "C" int srsran_hip_sch_nr_decode_tb(float scaling_fctr, uint32_t max_nof_
   }
   const size_t o_soft = 0, o_data = al256(o_soft + (size_t)c.C * sb_stride), o_e = al256(o_data + (size_t)c.C * data_stride), o_pay = al256(o_e + n_e);
   if (!s.grow(al256(o_pay + c.A / 8 + 8))) {
-    fprintf(stderr, "[srsran_phy_hip] sch_nr decode: staging allocation failed\n");
-    return SRSRAN_ERROR;
+    return call::failed(who, "staging allocation failed");
   }
-  bool any_flag = false, any_soft = false;
-  int  first = -1, last = -1;
-  for (uint32_t r = 0; r < c.C; r++) {
-    if (flags[r]) {
-      any_flag = true;
-      memcpy(s.pin + o_data + (size_t)r * data_stride, softbuffer->data[r], cb_bytes); // decoded earlier: its packed bits join the assembly
-    } else {
-      any_soft = any_soft || !all_zero(reinterpret_cast<const uint8_t*>(softbuffer->buffer_f[r]), c.N);
-      first    = first < 0 ? (int)r : first;
-      last     = (int)r;
-    }
-  }
-  if (any_soft || any_flag) { // a retransmission: the rows hold the earlier transmissions' soft bits
-    for (uint32_t r = 0; r < c.C; r++) {
-      if (!flags[r]) {
-        memcpy(s.pin + o_soft + (size_t)r * sb_stride, softbuffer->buffer_f[r], c.N);
-      }
-    }
-  }
+  memcpy(s.pin + o_e, e_bits, n_e); // (the de-matcher reads them once, coalesced: straight from the pinned image)
+  uint8_t          flags[NrTbStage::MAX_CB];
+  SoftStager       harq;
+  const hipError_t e = harq.stage_in(s, softbuffer, c, 0, o_soft, sb_stride, o_data, data_stride, false, flags); // the call's first enqueue on s.st
   srsran_hip_nr_tb_t tb = *tb_in;
-  tb.rv &= 3u;
+  tb.rv = (tb.rv & 3u) | (harq.fresh ? SRSRAN_HIP_NR_TB_NEW_DATA : 0u);
   tb.e_offset = tb.payload_offset = tb.first_cb = 0;
-  if (first >= 0) {
-    memcpy(s.pin + o_e, e_bits, n_e); // (the de-matcher reads them once, coalesced: straight from the pinned image)
-    if (!any_soft && !any_flag) {
-      tb.rv |= SRSRAN_HIP_NR_TB_NEW_DATA; // rows as srsran_softbuffer_rx_reset left them: written, not accumulated into, and not uploaded
-    } else {
-      PHY_HIP_CHECK(hipMemcpyAsync(s.dev + o_soft + (size_t)first * sb_stride, s.pin + o_soft + (size_t)first * sb_stride,
-                                   (size_t)(last - first) * sb_stride + c.N, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-    }
-  }
-  if (any_flag) {
-    PHY_HIP_CHECK(hipMemcpyAsync(s.dev + o_data, s.pin + o_data, (size_t)c.C * data_stride, hipMemcpyHostToDevice, s.st), SRSRAN_ERROR);
-  }
   srsran_hip_nr_tb_result_t res = {};
   const TailCopy tail[2] = {{s.pin + o_data, s.dev + o_data, (size_t)c.C * data_stride}, {s.pin + o_pay, s.dev + o_pay, c.A / 8}};
-  if (sch_nr_decode(h, reinterpret_cast<const int8_t*>(s.pin + o_e), &tb, 1, reinterpret_cast<int8_t*>(s.dev + o_soft), sb_stride, flags, s.dev + o_data,
-                    data_stride, s.dev + o_pay, &res, s.st, tail, 2) != SRSRAN_SUCCESS) {
-    (void)hipStreamSynchronize(s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
-    fprintf(stderr, "[srsran_phy_hip] sch_nr decode: %s\n", get_error());
-    return SRSRAN_ERROR;
+  if (e != hipSuccess || sch_nr_decode(h, reinterpret_cast<const int8_t*>(s.pin + o_e), &tb, 1, reinterpret_cast<int8_t*>(s.dev + o_soft), sb_stride, flags,
+                                       s.dev + o_data, data_stride, s.dev + o_pay, &res, s.st, tail, 2) != SRSRAN_SUCCESS) {
+    (void)call::settle(e, s.st); // nothing of a failed call may still be in flight when the next one re-uses the images
+    return e != hipSuccess ? call::device_failed(who, e) : call::failed(who, get_error());
   }
-  // host side effects of :633-652: flags, the packed bits of the blocks decoded now; rows of the blocks that are still undecoded
-  int f_first = -1, f_last = -1;
-  for (uint32_t r = 0; r < c.C; r++) {
-    if (softbuffer->cb_crc[r]) {
-      continue;
+  const hipError_t f = harq.fetch(s, flags); // (the transport-block pass took the call's host wait)
+  if (harq.first >= 0) {                     // rows come back: the one enqueue behind that wait, and a wait of its own
+    const hipError_t w = call::settle(f, s.st);
+    if (w != hipSuccess) {
+      return call::device_failed(who, w);
     }
-    if (flags[r]) {
-      softbuffer->cb_crc[r] = true;
-      memcpy(softbuffer->data[r], s.pin + o_data + (size_t)r * data_stride, cb_bytes);
-    } else {
-      f_first = f_first < 0 ? (int)r : f_first;
-      f_last  = (int)r;
-    }
-  }
-  if (f_first >= 0) {
-    PHY_HIP_CHECK(hipMemcpyAsync(s.pin + o_soft + (size_t)f_first * sb_stride, s.dev + o_soft + (size_t)f_first * sb_stride,
-                                 (size_t)(f_last - f_first) * sb_stride + c.N, hipMemcpyDeviceToHost, s.st), SRSRAN_ERROR);
-    PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
-    // (the circular buffer of a block ends at Ncb = min(N, Nref), ldpc_rm.c:704-705: nothing behind it is ever written or read)
-    const uint32_t n_cb_buf = c.N <= c.Nref ? c.N : c.Nref;
-    for (int r = f_first; r <= f_last; r++) {
-      if (!softbuffer->cb_crc[r]) {
-        memcpy(softbuffer->buffer_f[r], s.pin + o_soft + (size_t)r * sb_stride, n_cb_buf);
-      }
-    }
+    harq.finish(s);
   }
   *avg_iter = res.avg_iter; // :657-661
   if (res.all_decoded) {    // :664-666: otherwise neither the payload nor res->crc is touched
@@ -721,10 +743,10 @@ extern "C" int srsran_hip_sch_nr_encode_tb(const srsran_hip_nr_tb_t* tb_in, cons
     fprintf(stderr, "[srsran_phy_hip] sch_nr encode: invalid transport block (tbs %u, mod %u, layers %u)\n", tb_in->tbs, tb_in->mod, tb_in->N_L);
     return SRSRAN_ERROR;
   }
-  NrTbStage& s = tb_stage();
+  static const char* who = "sch_nr encode";
+  NrTbStage&         s   = tb_stage();
   if (!s.ready()) {
-    fprintf(stderr, "[srsran_phy_hip] sch_nr encode: %s (there is no CPU fallback)\n", get_error());
-    return SRSRAN_ERROR;
+    return call::no_device(who);
   }
   srsran_hip_sch_nr_t* h = s.decoder(0.8f, 10); // (the transmit side has no decoder parameters: one object per thread)
   if (!h) {
@@ -736,20 +758,18 @@ extern "C" int srsran_hip_sch_nr_encode_tb(const srsran_hip_nr_tb_t* tb_in, cons
   }
   const size_t o_pay = 0, o_e = al256(o_pay + c.A / 8 + 8);
   if (!s.grow(al256(o_e + n_e))) {
-    fprintf(stderr, "[srsran_phy_hip] sch_nr encode: staging allocation failed\n");
-    return SRSRAN_ERROR;
+    return call::failed(who, "staging allocation failed");
   }
   memcpy(s.pin + o_pay, data, c.A / 8);
   srsran_hip_nr_tb_t tb = *tb_in;
   tb.rv &= 3u;
   tb.e_offset = tb.payload_offset = tb.first_cb = 0;
   // the kernels read the payload from, and the rate matcher writes the bits into, the pinned host image itself (read twice, written once)
-  if (srsran_hip_sch_nr_encode(h, s.pin + o_pay, &tb, 1, s.pin + o_e, s.st) != SRSRAN_SUCCESS) {
-    (void)hipStreamSynchronize(s.st);
-    fprintf(stderr, "[srsran_phy_hip] sch_nr encode: %s\n", get_error());
-    return SRSRAN_ERROR;
+  const int        rc = srsran_hip_sch_nr_encode(h, s.pin + o_pay, &tb, 1, s.pin + o_e, s.st); // (enqueues only)
+  const hipError_t w  = call::settle(hipSuccess, s.st); // the call's one host wait, whether or not everything was enqueued
+  if (rc != SRSRAN_SUCCESS || w != hipSuccess) {
+    return rc != SRSRAN_SUCCESS ? call::failed(who, get_error()) : call::device_failed(who, w);
   }
-  PHY_HIP_CHECK(hipStreamSynchronize(s.st), SRSRAN_ERROR);
   memcpy(e_bits, s.pin + o_e, n_e);
   return SRSRAN_SUCCESS;
 }

@@ -1,9 +1,10 @@
 // sch_nr_internal.h -- what sch_nr_host.cpp shares with the codeword-level entry points (nr_chan_host.cpp): the transport-block parameters of
 // srsran_sch_nr_fill_tb_info, the per-thread transport-block staging context, and the decode loop on soft bits that are already on the device.
 #pragma once
+#include "call_frame.h"
 #include "hip_common.h"
-#include "stage.h"
 #include "srsran_amd/phy_nr_sch_abi.h"
+#include "srsran_amd/phy_sch_abi.h"
 #include <map>
 
 namespace phyhip {
@@ -42,6 +43,25 @@ struct NrTbStage {
   bool                 grow(size_t need) { return dev.grow(need) && pin.grow(need); }
 };
 NrTbStage& tb_stage(); // of the calling thread, on the device it is bound to
+
+// The reference's soft buffer of ONE codeword around a decode call on the stage's images (sch_nr.c:570-588 in, :633-652 out): rows at
+// o_soft + (first_cb + r) * sb_stride, stored code blocks at o_data + (first_cb + r) * data_stride.  stage_in and fetch enqueue on the stage's stream, return
+// the first error of that and wait for nothing.
+struct SoftStager {
+  srsran_softbuffer_rx_t* sb;
+  const TbCfg*            c;
+  uint32_t                first_cb, sb_stride, data_stride;
+  size_t                  o_soft, o_data;
+  uint8_t                 flags_in[NrTbStage::MAX_CB]; // the call's flags on entry
+  bool                    fresh, any_flag;             // fresh: rows are written, not accumulated into, and not uploaded
+  int                     first, last;                 // undecoded blocks: on entry (stage_in), still undecoded (fetch); -1: none
+  // flags[first_cb + r] from cb_crc (none with new_data); stored blocks and, unless fresh, undecoded rows -> pinned image -> device (the rows in one copy)
+  hipError_t stage_in(NrTbStage& s, srsran_softbuffer_rx_t* softbuffer, const TbCfg& cfg, uint32_t first_code_block, size_t soft_off, uint32_t soft_stride,
+                      size_t data_off, uint32_t row_stride, bool new_data, uint8_t* flags);
+  // behind the decode's host wait: cb_crc and data[r] of the blocks decoded now; one download of the rows still undecoded (first >= 0: wait again, then finish)
+  hipError_t fetch(NrTbStage& s, const uint8_t* flags);
+  void       finish(NrTbStage& s) const; // min(N, Nref) bytes of every row still undecoded, back into buffer_f[r]
+};
 
 } // namespace nrtb
 } // namespace phyhip
